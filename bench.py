@@ -10,7 +10,14 @@ the only exchange is one 8-byte RCCL all-reduce(max) per step that elects the be
 A step = one pass of the whole hot path (bin -> integral -> mask -> features+text round trips+scale -> RBF decision
 (fp16 screening pass -> three-pass kernel on its guard band) -> fp64 recheck tiers -> vote/argmax -> pose) over one cloud per rank, inputs already resident in HBM.
 
-  python bench.py --gpus 1 --steps 5 --warmup 1
+A plain run times the headline alone: model seed 42 (the median of the five seeds of a --full run on every box measured), `--warmup`
+untimed and `--steps` timed steps.  --full adds everything else: the workload timed once per seed of --seeds with the median seed as
+headline, label shares, the MFMA rate probe, the other contraction modes, two requests in flight, the hard and the trained model, the CPU
+baselines, the grasp latencies (C2/C3/C4) and the C++-host multi-GPU path (each --no-* option drops one of them).
+--dump-outputs DIR writes what the last timed step returned (roll records and grasp) to DIR/*.npy as float64.
+
+  python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -30,6 +37,8 @@ import numpy as np  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3       # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_F16_MFMA_TFLOPS = 2500.0      # MI355X_MICROARCH.md: BF16/FP16 MFMA, dense
 D_ATTR = 323                       # algorithmic work 2*D*nSV flop per eval, D unpadded
+FULL_SEEDS = "1234,7,11,23,42"
+PLAIN_SEEDS = "42"                 # the median seed of FULL_SEEDS in every --full run recorded (profiles/r0[45]_bench_*_default*.json)
 
 
 def parse():
@@ -37,10 +46,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-seed median, label shares, MFMA probe, other contraction modes, two "
+                         "requests in flight, hard and trained models, CPU baselines, grasp latencies, C++-host multi-GPU path); "
+                         "off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step (the last seed's) returned -- roll records, grasp -- to DIR/<name>.npy as float64")
     ap.add_argument("--nsv", type=int, default=4096, help="support vectors of the seeded random model")
-    ap.add_argument("--seeds", default="1234,7,11,23,42",
+    ap.add_argument("--seeds", default=None,
                     help="seeds of the random model generator (tests/models.py): the workload is timed once per seed (same K steps, "
-                         "same fences each) and `value` is the MEDIAN seed's rate; the per-seed lines are in `seeds`")
+                         "same fences each) and `value` is the MEDIAN seed's rate; the per-seed lines are in `seeds`.  Default: "
+                         "%s with --full, %s without" % (FULL_SEEDS, PLAIN_SEEDS))
     ap.add_argument("--no-label-stats", action="store_true", help="skip the per-seed positive-label share (one untimed debug run per seed)")
     ap.add_argument("--grid", type=int, default=512)
     ap.add_argument("--rolls", type=int, default=36)
@@ -352,6 +368,22 @@ def ranks_block(world, per_rank, shard, use_dist, dist=None, rccl_version=None, 
             "rccl_version": rccl_version}
 
 
+GRASP_FIELDS = ("eval", "grasp_point1", "grasp_point2", "averaged_grasp_point", "approach_vector", "roll", "best_row", "best_col",
+                "best_roll", "best_vote", "rolls_done", "n_evals")
+
+
+def dump_outputs(dirname, records, out):
+    """--dump-outputs: what the caller of the timed path receives from its last step -- the roll records of haf_score_rolls (all rolls
+    of the request) and the grasp of haf_finalize -- one float64 .npy per field (a few hundred bytes in all).  The grasp's n_rechecked
+    is left out: it counts the work of the recheck tiers, not a result."""
+    from haf_grasping_amd import capi
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"roll_" + f: records[f] for f in capi.ROLL_RECORD_DTYPE.names}
+    arrays.update({"grasp_" + k.replace("grasp_", ""): out[k] for k in GRASP_FIELDS})     # grasp_eval, grasp_point1, ...
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.cabi_child:
@@ -378,6 +410,8 @@ def main():
     data = os.path.join(ROOT, "tests", "golden", "data")
     feat, rng_file = os.path.join(data, "Features.txt"), os.path.join(data, "range21062012_allfeatures")
     tmp = tempfile.mkdtemp(prefix="hafbench_%d_" % rank)
+    if args.seeds is None:
+        args.seeds = FULL_SEEDS if args.full else PLAIN_SEEDS
     seeds = [int(t) for t in args.seeds.split(",") if t.strip()]
     if not seeds:
         raise SystemExit("--seeds needs at least one seed")
@@ -403,20 +437,21 @@ def main():
         coll_us = []                                        # host wall-clock of the step's one collective (incl. its sync)
 
         def step():
+            """-> (this rank's roll records, the grasp, the records of all rolls the grasp was finalised from)"""
             if args.shard == "rolls" and collective:
                 first, count = hd.roll_shard(args.rolls, world, rank)
                 local = eng.score_rolls([cloud], [inp], first, count)
                 tc = time.perf_counter()
                 full = hd.gather_roll_records(local, args.rolls, device="cuda")[0]   # one all-gather of 16 B per roll
                 coll_us.append(1e6 * (time.perf_counter() - tc))
-                return local[0], eng.finalize(inp, full)
+                return local[0], eng.finalize(inp, full), full
             rec = eng.score_rolls([cloud], [inp], 0, args.rolls)[0]
             out = eng.finalize(inp, rec)
             if collective:
                 tc = time.perf_counter()
                 hd.best_of_batch(out["best_vote"], tag=rank, device="cuda")   # one 8-byte all-reduce(max) over xGMI (RCCL)
                 coll_us.append(1e6 * (time.perf_counter() - tc))
-            return rec, out
+            return rec, out, rec
         for _ in range(warmup):
             step()
         svm_ms, stage_acc, evals, rechecked, strict, refined, n_i8, n_fp64 = [], {}, 0, 0, 0, 0, 0, 0
@@ -424,7 +459,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
-            rec, out = step()
+            rec, out, records = step()
             evals += int(rec["n_evals"].sum())
             c = eng.last_counts()
             rechecked += c["n_rechecked"]
@@ -441,7 +476,7 @@ def main():
         return dict(low_rank=eng.screen_low_rank(), form=eng.screen_form(),
                     elapsed=time.perf_counter() - t0, coll_us=float(np.median(coll_us)) if coll_us else None, evals=evals, steps=steps, svm_s=float(np.mean(svm_ms)) * 1e-3,
                     stage_ms={k: v / steps for k, v in stage_acc.items()}, rechecked=rechecked / steps,
-                    strict=strict / steps, refined=refined / steps, exact_integer=n_i8 / steps, fp64=n_fp64 / steps, out=out)
+                    strict=strict / steps, refined=refined / steps, exact_integer=n_i8 / steps, fp64=n_fp64 / steps, out=out, records=records)
 
     def positive_share(model_file):
         """share of the evaluations libsvm labels with label[0] (untimed; a debug engine that keeps the label grids)"""
@@ -473,6 +508,9 @@ def main():
     ranked = sorted(runs, key=lambda q: q["total_evals"] / q["elapsed"])
     med = ranked[(len(ranked) - 1) // 2]                    # lower median: never better than half of the seeds
     res, elapsed, total_evals, model_path = med["res"], med["elapsed"], med["total_evals"], med["model"]
+    if args.dump_outputs and rank == 0:
+        # the last timed step of the run: the last seed's (fixed by the arguments, unlike the median seed)
+        dump_outputs(args.dump_outputs, runs[-1]["res"]["records"], runs[-1]["res"]["out"])
 
     def roofline(r, precision, nsv=None, model_key=None):
         """model_key: which profiled run of profiles/index.json this result may be compared with ("seed42", "trained", "hard"; None: none)"""
@@ -550,9 +588,10 @@ def main():
             "dtype": {"f32": "f32", "f16x3": "f16x3", "f16s": "f16"}[args.precision],
             "data": "synthetic",
             # (the driver keeps the first ~100 characters of `workload`: what identifies the model comes first)
-            "config": {"workload": "C5 nSV=%d D=323 gamma=1/323 random RBF model (median of seeds %s: %d); synthetic %dx%d heightmap, %d pts, "
+            "config": {"workload": "C5 nSV=%d D=323 gamma=1/323 random RBF model (%s); synthetic %dx%d heightmap, %d pts, "
                                    "%d rolls x %d deg, %dx%d cm area, one cloud per GPU per step, resident in HBM"
-                                   % (args.nsv, ",".join(str(q) for q in seeds), med["seed"], G, G, xyz.shape[0], args.rolls, args.roll_step, G, G),
+                                   % (args.nsv, ("median of seeds %s: %d" % (",".join(str(q) for q in seeds), med["seed"])) if len(seeds) > 1
+                                      else "seed %d" % med["seed"], G, G, xyz.shape[0], args.rolls, args.roll_step, G, G),
                        "evals_per_cloud": int(res["evals"] / args.steps), "n_sv": args.nsv, "grid": G, "rolls": args.rolls,
                        "contraction": args.precision,
                        "sharding": ("clouds (1 per GPU); all-reduce(max) of an 8-byte best-grasp key per step" if args.shard == "clouds"
@@ -563,7 +602,8 @@ def main():
                                (PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_F16_MFMA_TFLOPS),   # rank 0's GPU against one GPU's peak
             "seeds": {"generator": "tests/models.py write_random_model(nsv, seed, balanced=True): SV values U(-1,1), coef U(0,2) x class sign, "
                                    "sum(coef) = 0, gamma = 1/323, rho 0.01",
-                      "headline": "median seed %d (value, ms_per_step, roofline, stage_ms_per_step are that seed's run)" % med["seed"],
+                      "headline": "%s seed %d (value, ms_per_step, roofline, stage_ms_per_step are that seed's run)"
+                                  % ("median" if len(seeds) > 1 else "the one", med["seed"]),
                       "min_value": ranked[0]["total_evals"] / ranked[0]["elapsed"], "min_seed": ranked[0]["seed"],
                       "max_value": ranked[-1]["total_evals"] / ranked[-1]["elapsed"], "max_seed": ranked[-1]["seed"],
                       "worst_over_median_ms": (ranked[0]["elapsed"] / ranked[0]["res"]["steps"]) / (elapsed / args.steps),
@@ -575,7 +615,8 @@ def main():
                                     "screening_form": q["res"]["form"],
                                     "kernel_ms": q["res"]["svm_s"] * 1e3, "refine_ms": q["res"]["stage_ms"].get("refine"),
                                     "recheck_ms": q["res"]["stage_ms"].get("recheck"),
-                                    "positive_label_share": (positive_share(q["model"]) if (world == 1 and not args.no_label_stats) else None),
+                                    "positive_label_share": (positive_share(q["model"]) if (world == 1 and args.full and not args.no_label_stats)
+                                                             else None),
                                     "best": {"eval": q["res"]["out"]["eval"], "row": q["res"]["out"]["best_row"],
                                              "col": q["res"]["out"]["best_col"], "roll": q["res"]["out"]["best_roll"]}}
                                    for q in runs]},
@@ -595,7 +636,7 @@ def main():
             "best": {"eval": res["out"]["eval"], "row": res["out"]["best_row"], "col": res["out"]["best_col"],
                      "roll": res["out"]["best_roll"]},
         }
-        if args.precision == "f16s":
+        if args.full and args.precision == "f16s":
             # Context for `roofline.frac`: what THIS GPU sustains on a bare loop of the same MFMA instruction (random operands in
             # registers, two 4-wave workgroups per CU, ~20 ms; libhafgrasp_testing.so, testkernels.hip).  The chip runs the matrix
             # pipe at the clock it can hold under the load, and that differs between the boxes of a pool.
@@ -616,7 +657,7 @@ def main():
             except Exception as ex:      # noqa: BLE001 -- context only
                 line["roofline"]["box_bare_mfma_tflops"] = None
                 line["roofline"]["box_note"] = "probe unavailable: %r" % (ex,)
-        if world == 1 and not args.no_f32_side:
+        if world == 1 and args.full and not args.no_f32_side:
             for other in [m for m in ("f16x3", "f32") if m != args.precision]:
                 e2 = make_engine(other)
                 r2 = run(e2, 2, 1, False)
@@ -627,7 +668,7 @@ def main():
                                                            r2["out"]["best_row"] == res["out"]["best_row"] and
                                                            r2["out"]["best_col"] == res["out"]["best_col"] and
                                                            r2["out"]["best_roll"] == res["out"]["best_roll"])}
-        if world == 1 and not args.no_f32_side and args.precision == "f16s":
+        if world == 1 and args.full and not args.no_f32_side and args.precision == "f16s":
             # Two requests in flight on the one GPU (two engines, each its own stream and device state, one host thread each) against
             # one engine serving the same requests one after the other: a request's tail -- the tiers behind the sweep, pre-stages,
             # vote: ~1.4 ms of short lists and small launches -- leaves most of the chip idle, the other request's kernels fill it.
@@ -671,7 +712,7 @@ def main():
                             "throughput of a server that keeps two requests in flight; the headline is one request at a time"}
             except Exception as ex:      # noqa: BLE001 -- a side measurement must never cost the main line
                 line["two_requests_in_flight"] = {"value": None, "note": "unavailable: %r" % (ex,)}
-        if world == 1 and not args.no_hard_side and args.precision == "f16s":
+        if world == 1 and args.full and not args.no_hard_side and args.precision == "f16s":
             # The headline model is benign (seeded random coefficients: decisions spread wide against sum|coef|K).  The only
             # genuinely libsvm-trained model in the repo (tests/golden/surrogate.model, svm-train -c 512: most coefficients at
             # the bound, decisions crowding around zero) is the hard case: replicated to bench size it shows what an
@@ -694,7 +735,7 @@ def main():
                                   "refined_share": rh["refined"] / max(1.0, rh["evals"] / 3), "screening_form": form_h,
                                   "f16x3_ms_per_step": 1e3 * r3["elapsed"],
                                   "same_best_as_f16x3": bool(all(r3["out"][k] == rh["out"][k] for k in ("eval", "best_row", "best_col", "best_roll")))}
-        if world == 1 and not args.no_trained_side and args.precision == "f16s":
+        if world == 1 and args.full and not args.no_trained_side and args.precision == "f16s":
             # The one question the headline cannot answer: a genuinely trained model of "full SV set" size.  The reference's
             # own model is missing from its checkout; this one was trained by the reference's svm-train the way easy.py does it
             # (tools/make_trained_model.py: 24000 feature rows harvested from every data/*.pcd, 7 % label noise, cross-validated
@@ -730,11 +771,11 @@ def main():
                 "same_best_as_f16x3": bool(all(r3["out"][k] == rt["out"][k] for k in ("eval", "best_row", "best_col", "best_roll"))),
                 "best": {"eval": rt["out"]["eval"], "row": rt["out"]["best_row"], "col": rt["out"]["best_col"], "roll": rt["out"]["best_roll"]},
                 "note": "2.19 x the support vectors of the headline model: `value` x n_sv / 4096 is the rate at equal contraction work"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(feat, rng_file, model_path, xyz, args)
         else:
             line["cpu_baseline"] = None
-        if world == 1 and not args.no_latency:
+        if world == 1 and args.full and not args.no_latency:
             tr_lat = None
             if not args.no_trained_side:
                 tr_lat = os.path.join(tmp, "trained.model")
@@ -750,7 +791,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cabi_side:
+        if args.full and not args.no_cabi_side:
             # every rank has let go of its engine; give the other rank processes a moment to exit, then measure the C++-host
             # path (one process driving all the GPUs through the C-ABI) in a child of its own
             del d_xyz

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/final
 rm -rf $O; mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 # (the profiled runs take ONE model seed -- the median seed of the default run above, 42 -- so that the kernel statistics are those
 # of the headline line; the calibration request of haf_create adds one small launch of every kernel to the call counts)
 B="bench.py --steps 3 --warmup 1 --seeds ${SEED:-42} --no-label-stats --no-cpu-baseline --no-latency --no-f32-side --no-hard-side --no-trained-side --no-cabi-side"
