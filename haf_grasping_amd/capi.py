@@ -160,6 +160,7 @@ def _bind(path, testing):
         L.haf_test_poke_flag0_list.argtypes = [E, C.c_int, C.c_int, C.c_int]
         L.haf_test_overflow_stats.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_list.argtypes = [E, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
     return L
 
 

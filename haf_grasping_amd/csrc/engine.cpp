@@ -165,8 +165,8 @@ static int calibrate(haf_engine *e)
             e->screen_active = true;
             rc = score_rolls_impl(e, 1, &cl, &in, 0, R, rec.data());
             if (rc != HAF_OK) break;
-            const double ne = (double)std::max(1, e->last_evals);
-            const double share = e->last_screened ? (double)e->last_flagged0 / ne : 1.0;
+            const double ne = (double)std::max(1, e->last.evals);
+            const double share = e->last.screened ? (double)e->last.flagged0 / ne : 1.0;
             e->variant_share[v] = share;
             if (share < 0.001) break;                    // nothing a later form could win back
         }
@@ -207,20 +207,13 @@ static int calibrate(haf_engine *e)
         e->t1_skip = false;
         rc = score_rolls_impl(e, 1, &cl, &in, 0, R, rec.data());
         e->variant_forced = forced1;
-        if (rc == HAF_OK && e->last_screened && e->last_flagged0 >= 32)
-            e->t1_skip = (double)(e->last_flagged0 - e->last_flagged) < 0.35 * (double)e->last_flagged0;
+        if (rc == HAF_OK && e->last.screened && e->last.flagged0 >= 32)
+            e->t1_skip = (double)(e->last.flagged0 - e->last.flagged) < 0.35 * (double)e->last.flagged0;
         if (fsk) e->t1_skip = atoi(fsk) != 0;
     }
     e->direct_work = keep_direct;
     e->calibrated = true;
-    // (the calibration requests are not a "last scored batch")
-    e->last_B = e->last_R = e->last_roll_first = 0;
-    e->last_evals = e->last_flagged = e->last_flagged2 = e->last_flagged0 = e->last_inexact = e->last_host_resolved = 0;
-    e->last_flaggedi = 0;
-    e->last_bypass = 0;
-    e->last_i8 = false;
-    e->last_screened = false;
-    e->last_inputs.clear();
+    e->last = LastCall{};                                 // (the calibration requests are not a "last scored batch")
     return rc;
 }
 
@@ -393,48 +386,48 @@ int haf_screen_low_rank(const haf_engine *e, int32_t *available, int32_t *rank, 
     if (!e) return HAF_E_ARG;
     if (available) *available = (e->lr_available && e->lr_enabled) ? 1 : 0;
     if (rank) *rank = e->lr_rank;
-    if (last_used) *last_used = e->last_lr ? 1 : 0;
+    if (last_used) *last_used = e->last.lr ? 1 : 0;
     return HAF_OK;
 }
 
 int haf_last_counts(const haf_engine *e, int64_t *n_evals, int64_t *n_rechecked, int64_t *n_strict)
 {
     if (!e) return HAF_E_ARG;
-    if (n_evals) *n_evals = e->last_evals;
-    if (n_rechecked) *n_rechecked = e->last_flagged + (e->last_i8 ? e->last_bypass : 0);   // (the short-list gate's entries skip the exact-integer tier's input list)
-    if (n_strict) *n_strict = e->last_flagged2;
+    if (n_evals) *n_evals = e->last.evals;
+    if (n_rechecked) *n_rechecked = e->last.flagged + (e->last.i8 ? e->last.bypass : 0);   // (the short-list gate's entries skip the exact-integer tier's input list)
+    if (n_strict) *n_strict = e->last.flagged2;
     return HAF_OK;
 }
 
 int haf_last_tiers(const haf_engine *e, int64_t *n_evals, int64_t *n_refined, int64_t *n_rechecked, int64_t *n_strict)
 {
     if (!e) return HAF_E_ARG;
-    if (n_evals) *n_evals = e->last_evals;
-    if (n_refined) *n_refined = e->last_flagged0;
-    if (n_rechecked) *n_rechecked = e->last_flagged + (e->last_i8 ? e->last_bypass : 0);   // (the short-list gate's entries skip the exact-integer tier's input list)
-    if (n_strict) *n_strict = e->last_flagged2;
+    if (n_evals) *n_evals = e->last.evals;
+    if (n_refined) *n_refined = e->last.flagged0;
+    if (n_rechecked) *n_rechecked = e->last.flagged + (e->last.i8 ? e->last.bypass : 0);   // (the short-list gate's entries skip the exact-integer tier's input list)
+    if (n_strict) *n_strict = e->last.flagged2;
     return HAF_OK;
 }
 
 int haf_last_exact_tiers(const haf_engine *e, int64_t *n_integer, int64_t *n_fp64)
 {
     if (!e) return HAF_E_ARG;
-    if (n_integer) *n_integer = e->last_i8 ? e->last_flagged : 0;
-    if (n_fp64) *n_fp64 = e->last_flaggedi;
+    if (n_integer) *n_integer = e->last.i8 ? e->last.flagged : 0;
+    if (n_fp64) *n_fp64 = e->last.flaggedi;
     return HAF_OK;
 }
 
 int haf_last_strict_host(const haf_engine *e, int64_t *n_host)
 {
     if (!e) return HAF_E_ARG;
-    if (n_host) *n_host = e->last_host_resolved;
+    if (n_host) *n_host = e->last.host_resolved;
     return HAF_OK;
 }
 
 int haf_last_prestage(const haf_engine *e, int64_t *n_inexact_grids)
 {
     if (!e) return HAF_E_ARG;
-    if (n_inexact_grids) *n_inexact_grids = e->last_inexact;
+    if (n_inexact_grids) *n_inexact_grids = e->last.inexact;
     return HAF_OK;
 }
 

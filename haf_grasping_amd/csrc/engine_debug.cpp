@@ -7,9 +7,9 @@ extern "C" {
 static int get_roll_grid_impl(haf_engine *e, int32_t cloud, int32_t roll, float *eval_grid, uint8_t *mask)
 {
     if (!e) return HAF_E_ARG;
-    const int rl = roll - e->last_roll_first;
-    if (cloud < 0 || cloud >= e->last_B || rl < 0 || rl >= e->last_R) return fail(e, HAF_E_ARG, "haf_get_roll_grid: (cloud, roll) not in the last scored batch");
-    const size_t HW = (size_t)e->cfg.grid_h * e->cfg.grid_w, base = ((size_t)cloud * e->last_R + rl) * HW;
+    const int rl = roll - e->last.roll_first;
+    if (cloud < 0 || cloud >= e->last.B || rl < 0 || rl >= e->last.R) return fail(e, HAF_E_ARG, "haf_get_roll_grid: (cloud, roll) not in the last scored batch");
+    const size_t HW = (size_t)e->cfg.grid_h * e->cfg.grid_w, base = ((size_t)cloud * e->last.R + rl) * HW;
     if (eval_grid && e->prob_mode) {
         HIPCHK(e, hipMemcpy(eval_grid, e->d_evf.p + base, HW * sizeof(float), hipMemcpyDeviceToHost));
     } else if (eval_grid) {
@@ -26,10 +26,10 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
     if (!e) return HAF_E_ARG;
     if (!dst) return fail(e, HAF_E_ARG, "haf_debug_fetch: null dst");
     if (!(e->cfg.flags & HAF_FLAG_KEEP_DEBUG)) return fail(e, HAF_E_ARG, "haf_debug_fetch: engine was created without HAF_FLAG_KEEP_DEBUG");
-    const int rl = roll - e->last_roll_first;
-    if (cloud < 0 || cloud >= e->last_B || rl < 0 || rl >= e->last_R) return fail(e, HAF_E_ARG, "haf_debug_fetch: (cloud, roll) not in the last scored batch");
+    const int rl = roll - e->last.roll_first;
+    if (cloud < 0 || cloud >= e->last.B || rl < 0 || rl >= e->last.R) return fail(e, HAF_E_ARG, "haf_debug_fetch: (cloud, roll) not in the last scored batch");
     const size_t H = (size_t)e->cfg.grid_h, W = (size_t)e->cfg.grid_w, HW = H * W;
-    const size_t br = (size_t)cloud * e->last_R + rl;
+    const size_t br = (size_t)cloud * e->last.R + rl;
     auto need = [&](size_t n) { return dst_bytes >= n; };
     switch (what) {
         case HAF_DBG_HEIGHTS:
@@ -50,8 +50,8 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             return HAF_OK;
         case HAF_DBG_TRANSFORM: {
             if (!need(16 * 4)) break;
-            NormalisedInput n = normalise(e->last_inputs[(size_t)cloud]);
-            Mat4 m = roll_transform(e->cfg, e->last_inputs[(size_t)cloud], n, roll, true);
+            NormalisedInput n = normalise(e->last.inputs[(size_t)cloud]);
+            Mat4 m = roll_transform(e->cfg, e->last.inputs[(size_t)cloud], n, roll, true);
             memcpy(dst, m.a, 16 * 4);
             return HAF_OK;
         }
@@ -59,13 +59,13 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             if (!need(HW * 8)) break;
             double *g = (double *)dst;
             for (size_t i = 0; i < HW; i++) g[i] = NAN;
-            const size_t ne = (size_t)e->last_evals;
+            const size_t ne = (size_t)e->last.evals;
             if (!ne) return HAF_OK;
             std::vector<int> cell(ne);
             std::vector<float> dec(ne);
             HIPCHK(e, hipMemcpy(cell.data(), e->d_evalcell.p, ne * 4, hipMemcpyDeviceToHost));
             HIPCHK(e, hipMemcpy(dec.data(), e->d_dec.p, ne * 4, hipMemcpyDeviceToHost));
-            const size_t nfl = (size_t)std::min(e->last_flagged, e->list_cap);
+            const size_t nfl = (size_t)std::min(e->last.flagged, e->list_cap);
             std::vector<int> fl(nfl);
             std::vector<double> ex(nfl);
             if (nfl) {
@@ -74,8 +74,8 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             }
             std::vector<double> d64(dec.begin(), dec.end());
             for (size_t k = 0; k < nfl; k++) d64[(size_t)fl[k]] = ex[k];
-            if (e->last_i8) {                              // behind tier 2a the fp64 tier has its own list and values
-                const size_t nfi = (size_t)std::min(e->last_flaggedi, e->list_cap);
+            if (e->last.i8) {                              // behind tier 2a the fp64 tier has its own list and values
+                const size_t nfi = (size_t)std::min(e->last.flaggedi, e->list_cap);
                 if (nfi) {
                     std::vector<int> fli(nfi);
                     std::vector<double> exi(nfi);
@@ -84,7 +84,7 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
                     for (size_t k = 0; k < nfi; k++) d64[(size_t)fli[k]] = exi[k];
                 }
             }
-            const size_t nf2 = (size_t)std::min(e->last_flagged2, e->list_cap);
+            const size_t nf2 = (size_t)std::min(e->last.flagged2, e->list_cap);
             if (nf2) {
                 std::vector<int> fl2(nf2);
                 std::vector<double> ex2(nf2);
@@ -108,7 +108,7 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             if (!need(HW * 16)) break;
             double *g = (double *)dst;
             for (size_t i = 0; i < 2 * HW; i++) g[i] = NAN;
-            const size_t ne = (size_t)e->last_evals;
+            const size_t ne = (size_t)e->last.evals;
             if (!ne) return HAF_OK;
             std::vector<int> cell(ne);
             std::vector<double> pt(2 * ne);
@@ -124,8 +124,8 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             if (!need(HW * 4)) break;
             float *g = (float *)dst;
             for (size_t i = 0; i < HW; i++) g[i] = NAN;
-            const size_t ne = (size_t)e->last_evals;
-            if (!ne || !e->d_margin.p || !e->last_screened) return HAF_OK;
+            const size_t ne = (size_t)e->last.evals;
+            if (!ne || !e->d_margin.p || !e->last.screened) return HAF_OK;
             std::vector<int> cell(ne);
             std::vector<float> mg(ne);
             HIPCHK(e, hipMemcpy(cell.data(), e->d_evalcell.p, ne * 4, hipMemcpyDeviceToHost));
@@ -149,11 +149,11 @@ static int debug_fetch_attr_impl(haf_engine *e, int32_t cloud, int32_t roll, int
     if (!n_cells || max_cells < 0) return fail(e, HAF_E_ARG, "haf_debug_fetch_attr: bad argument");
     if (!(e->cfg.flags & HAF_FLAG_KEEP_DEBUG)) return fail(e, HAF_E_ARG, "haf_debug_fetch_attr: engine was created without HAF_FLAG_KEEP_DEBUG");
     if (!e->d_attr.p) return fail(e, HAF_E_CAPACITY, "haf_debug_fetch_attr: attribute records are kept for engines of up to 2 GiB of them only");
-    const int rl = roll - e->last_roll_first;
-    if (cloud < 0 || cloud >= e->last_B || rl < 0 || rl >= e->last_R) return fail(e, HAF_E_ARG, "haf_debug_fetch_attr: (cloud, roll) not in the last scored batch");
+    const int rl = roll - e->last.roll_first;
+    if (cloud < 0 || cloud >= e->last.B || rl < 0 || rl >= e->last.R) return fail(e, HAF_E_ARG, "haf_debug_fetch_attr: (cloud, roll) not in the last scored batch");
     const size_t H = (size_t)e->cfg.grid_h, W = (size_t)e->cfg.grid_w, HW = H * W;
-    const size_t br = (size_t)cloud * e->last_R + rl;
-    const size_t ne = (size_t)e->last_evals;
+    const size_t br = (size_t)cloud * e->last.R + rl;
+    const size_t ne = (size_t)e->last.evals;
     std::vector<int> cell(ne);
     if (ne) HIPCHK(e, hipMemcpy(cell.data(), e->d_evalcell.p, ne * 4, hipMemcpyDeviceToHost));
     std::vector<int> eval_of(HW, -1);

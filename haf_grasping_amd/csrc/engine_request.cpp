@@ -31,16 +31,37 @@ static double host_kernel_value(const SvmModel &m, const double *xg, int n, int 
     return acc;                                                  // LINEAR
 }
 
+// libsvm's decision value (svm.cpp:2509-2513: both classes' terms in model order) on the HOST from one column of the fp64 image
+static double host_decision(const SvmModel &m, const double *xg, int kx)
+{
+    double sum = 0.0;
+    for (int n = 0; n < m.n_sv; n++) sum += m.coef[(size_t)n] * host_kernel_value(m, xg, n, kx);
+    return sum - m.rho;
+}
+
+// The fp64 attribute image ([group of 16][324][16]) of the entries [off, off + n) of a list -- counters[cnt] entries long -- through
+// the feature kernel, then to the host: column i of x64 (attr_column) holds entry off + i
+static int fetch_attributes64(haf_engine *e, const Dims &d, hipStream_t s, const int *list, int cnt, int off, int n, std::vector<double> &x64)
+{
+    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, reinterpret_cast<float *>(e->d_x64.p), nullptr, d, e->range.lower,
+                    e->range.upper, 0.0f, n, XMODE_F64, ScreenParams{}, list + off, cnt, n, false, n, nullptr, nullptr, s, off);
+    x64.assign(((size_t)n + 15) / 16 * kKP * 16, 0.0);
+    HIPCHK(e, hipMemcpyAsync(x64.data(), e->d_x64.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    return HAF_OK;
+}
+static const double *attr_column(const std::vector<double> &x64, int i) { return x64.data() + (size_t)(i >> 4) * kKP * 16 + (i & 15); }
+
 // The strict tier (k_recheck) restates libsvm's summation order operation for operation, but its exp() is the device's, not
 // glibc's.  Both are within an ulp of the true value, so the two sums differ by at most 2^-52 sum|coef|; a strict-tier decision
 // value closer to zero than host_exp_thr (256 x that) is therefore evaluated once more HERE, on the host, with the C library's
 // exp -- the very function the reference's svm-predict calls (svm.cpp:325-365, 2478-2532) -- from the attributes the device
 // computed (the decimal round trips are bit-pinned to glibc, tests/).  Nothing has come this far in any run; the path exists so
-// that "the labels are libsvm's" has no residual.  Returns the number of evaluations decided here; *changed = a label moved.
-static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool *changed)
+// that "the labels are libsvm's" has no residual.  *resolved = the number of evaluations decided here; *changed = a label moved.
+static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool *changed, int *resolved)
 {
     *changed = false;
-    e->last_host_resolved = 0;
+    *resolved = 0;
     const int n2 = std::min(std::min(e->h_counters[CNT_FLAGGED2], e->list_cap), e->flag_cap);     // (one window of the attribute image)
     if (n2 <= 0 || e->prob_mode) return HAF_OK;
     std::vector<double> dec((size_t)n2);
@@ -51,23 +72,11 @@ static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool
     std::vector<int> cand;
     for (int i = 0; i < n2; i++) if (!(std::fabs(dec[(size_t)i]) > e->host_exp_thr)) cand.push_back(i);
     if (cand.empty()) return HAF_OK;
-    // the fp64 attribute image of the strict tier's list ([group of 16][324][16]) through the feature kernel, then to the host
-    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, reinterpret_cast<float *>(e->d_x64.p), nullptr, d, e->range.lower,
-                    e->range.upper, 0.0f, n2, XMODE_F64, ScreenParams{}, e->d_flag2_list.p, CNT_FLAGGED2, n2, false, n2, nullptr, nullptr, s, 0);
-    const size_t groups = ((size_t)n2 + 15) / 16;
-    std::vector<double> x64(groups * kKP * 16);
-    HIPCHK(e, hipMemcpyAsync(x64.data(), e->d_x64.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    const SvmModel &m = e->model;
-    const int kx = e->kx;
+    std::vector<double> x64;
+    const int rc = fetch_attributes64(e, d, s, e->d_flag2_list.p, CNT_FLAGGED2, 0, n2, x64);
+    if (rc != HAF_OK) return rc;
     for (int i : cand) {
-        const double *xg = x64.data() + (size_t)(i >> 4) * kKP * 16 + (i & 15);
-        double sum = 0.0;
-        for (int n = 0; n < m.n_sv; n++) {                       // svm.cpp:2509-2512: both classes' terms in model order
-            const double kv = host_kernel_value(m, xg, n, kx);
-            sum += m.coef[(size_t)n] * kv;
-        }
-        const double dv = sum - m.rho;                           // 2513
+        const double dv = host_decision(e->model, attr_column(x64, i), e->kx);
         const int8_t lab = (int8_t)(dv > 0.0 ? e->gv0 : e->gv1);
         int cell = 0;
         int8_t old = 0;
@@ -76,7 +85,7 @@ static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool
         if (old != lab) *changed = true;
         HIPCHK(e, hipMemcpy(e->d_labels.p + cell, &lab, 1, hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(e->d_dec_exact2.p + i, &dv, sizeof(double), hipMemcpyHostToDevice));
-        e->last_host_resolved++;
+        (*resolved)++;
     }
     return HAF_OK;
 }
@@ -122,29 +131,21 @@ static int host_probability(double dec, double A, double B, double p[2])
 // move their label or a printed digit; CNT_FLAGGED / d_flag_list) are finished HERE: the libsvm-order decision value with the C
 // library's exp from the device's attributes (as host_resolve_strict does), svm_predict_probability with the C library's exp, the
 // "%g" forms by the host build of decq (pinned to glibc's printf + strtod).  Writes what k_prob_eval writes.
-static int host_resolve_probability(haf_engine *e, const Dims &d, hipStream_t s)
+static int host_resolve_probability(haf_engine *e, const Dims &d, hipStream_t s, int *resolved)
 {
-    e->last_host_resolved = 0;
+    *resolved = 0;
     const int n = std::min(e->h_counters[CNT_FLAGGED], e->list_cap);
     if (n <= 0) return HAF_OK;
-    const SvmModel &m = e->model;
-    const int kx = e->kx;
     std::vector<int> ev((size_t)n);
     HIPCHK(e, hipMemcpyAsync(ev.data(), e->d_flag_list.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
+    std::vector<double> x64;
     for (int off = 0; off < n; off += e->flag_cap) {
         const int nw = std::min(e->flag_cap, n - off);
-        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, reinterpret_cast<float *>(e->d_x64.p), nullptr, d, e->range.lower,
-                        e->range.upper, 0.0f, nw, XMODE_F64, ScreenParams{}, e->d_flag_list.p + off, CNT_FLAGGED, nw, false, nw, nullptr, nullptr, s, off);
-        const size_t groups = ((size_t)nw + 15) / 16;
-        std::vector<double> x64(groups * kKP * 16);
-        HIPCHK(e, hipMemcpyAsync(x64.data(), e->d_x64.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
+        const int rc = fetch_attributes64(e, d, s, e->d_flag_list.p, CNT_FLAGGED, off, nw, x64);
+        if (rc != HAF_OK) return rc;
         for (int i = 0; i < nw; i++) {
-            const double *xg = x64.data() + (size_t)(i >> 4) * kKP * 16 + (i & 15);
-            double sum = 0.0;
-            for (int nn = 0; nn < m.n_sv; nn++) sum += m.coef[(size_t)nn] * host_kernel_value(m, xg, nn, kx);   // svm.cpp:2509-2512
-            const double dv = sum - m.rho;
+            const double dv = host_decision(e->model, attr_column(x64, i), e->kx);
             double p[2];
             const int idx = host_probability(dv, e->prob.A, e->prob.B, p);
             const double q[2] = {hafq::decq(p[0], 6), hafq::decq(p[1], 6)};
@@ -158,28 +159,134 @@ static int host_resolve_probability(haf_engine *e, const Dims &d, hipStream_t s)
             HIPCHK(e, hipMemcpy(e->d_labels.p + cell, &lab, 1, hipMemcpyHostToDevice));
             HIPCHK(e, hipMemcpy(e->d_ptext.p + 2 * (size_t)evi, q, 2 * sizeof(double), hipMemcpyHostToDevice));
             HIPCHK(e, hipMemcpy(e->d_dec_exact2.p + evi, &dv, sizeof(double), hipMemcpyHostToDevice));
-            e->last_host_resolved++;
+            (*resolved)++;
         }
     }
     return HAF_OK;
 }
 
-int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                            int32_t roll_count, haf_roll_record *records)
+// ---- the routing of one decision stage: pure, no device (tests/test_host_cpu.py enumerates it through haf_test_tier_plan) ----
+TierPlan plan_tiers(const TierFacts &f)
 {
-    if (!e) return HAF_E_ARG;
+    TierPlan p;
+    if (f.generic_kernel || f.direct) {
+        // a model whose kernel is not RBF: every evaluation on the strict tier's list, libsvm's own arithmetic for all of them.
+        // A tiny request: exact attributes, fp64 MFMA decision and label of EVERY evaluation in one launch (k_small_direct), what it
+        // leaves on the strict tier's list
+        p.path = f.generic_kernel ? PATH_GENERIC : PATH_DIRECT;
+        p.pass0_out = L_FLAG2;
+        return p;
+    }
+    p.path = f.mode == MODE_SCREEN ? PATH_SCREEN : f.mode == MODE_SPLIT ? PATH_SPLIT : PATH_F32;
+    const int v = f.screen_variant;
+    const bool cr_poly_t1 = p.path == PATH_SCREEN && v == SCREEN_CR_POLY && f.t1_cr_available;
+    // tier 2a in front of the fp64 MFMA tier (exact8.hip): the same evaluations on EXACT integer dot products (int8 digit planes); what
+    // it cannot decide either -- |dec| inside the operands' quantisation, ~1e-7 S -- is the fp64 MFMA tier's list.
+    // (behind the centred-remainder form of tier 1 the exact-integer tier has nothing to add: its band is the quantisation of the
+    // operands relative to sum|coef|K -- 8e-9 S for the trained model, 0.14 -- and tier 1's is relative to S_psi, 0.02: measured,
+    // it decided 8 of 9984 evaluations in 4.6 ms.  What tier 1 leaves goes straight to the fp64 MFMA tier)
+    p.i8 = f.i8_active && !f.small_exact && !cr_poly_t1;
+    if (p.i8) { p.i8_in = L_FLAG; p.i8_out = L_FLAGI; }
+    p.fp64 = f.small_exact ? FP64_SMALL : FP64_MFMA;
+    p.fp64_in = p.i8 ? L_FLAGI : L_FLAG;
+    p.fp64_out = L_FLAG2;
+    p.pass0_out = L_FLAG;
+    if (p.path != PATH_SCREEN) return p;
+
+    // tier 0: single-pass fp16 screening of every evaluation; tier 1: the three-pass kernel on what it could not decide
+    // (the centred-remainder variants have their own operand images: translated attributes, centred support vectors)
+    p.cr = v == SCREEN_CR_EXP || v == SCREEN_CR_POLY;
+    p.reuse = f.reuse_operands;
+    // Low-rank form of the centred-remainder pass (kernels.h: kLrK): whole requests large enough for the thread-per-evaluation
+    // feature kernel on grids that went through the parallel integral image (whose pass records negative heights), when the
+    // centred-remainder form serves the model; the 10-step images go through k_project, the sweep runs on 6-step images.
+    const bool lr_plain = v == SCREEN_PLAIN && f.lr_plain_available;      // the plain epilogue on the projected (centred) operands
+    p.lr = (p.cr || lr_plain) && f.large && f.lr_available && f.lr_enabled && !f.fused_pre && f.hw > 8192 && !f.reuse_operands;
+    p.sp = p.lr && lr_plain ? SP_LRP : p.cr ? SP_CR : SP_PLAIN;
+    // Tier 0b: the centred-remainder form once more on the first pass's list, behind a PLAIN / SUMSQ first pass or a low-rank CR_EXP
+    // one (the waves it cannot bound -- the borders of the grid, waves that are not a run of neighbours -- and what its slightly wider
+    // band leaves).  Round 5: behind a LOW-RANK first pass with the plain epilogue it is the low-rank sweep itself with the
+    // centred-remainder epilogue in its GATHER form -- the first pass's operand images and raw sums by evaluation id, no second
+    // feature kernel.
+    if (f.use_t0b && f.cr_available && !f.small_exact && (!p.cr || (p.lr && v == SCREEN_CR_EXP)))
+        p.t0b = p.sp == SP_LRP && f.lr_fused && !f.t0b_no_gather ? T0B_GATHER : T0B_FEATURES;
+    // A small request with a small model (small_exact): what the screening passes leave goes STRAIGHT to the one-launch exact kernel
+    // (k_small_direct in list mode: exact attributes + fp64 MFMA decision, 9 ns per listed evaluation at 192 SVs) -- the list is
+    // written where that kernel reads it.  Tier 1 in between was a feature kernel and a contraction launch at their latency floors
+    // (C3: 44 + 36 us for 4 072 evaluations, of which it decided nine tenths) in front of the same exact kernel.  The same hand-over
+    // when calibration found tier 1 of little use behind the screening passes (t1_skip).
+    const bool straight = f.small_exact || f.t1_skip;
+    if (p.t0b != T0B_NONE) {
+        p.pass0_out = L_FLAG0;
+        p.t0b_in = L_FLAG0;
+        p.t0b_out = straight ? L_FLAG : L_FLAG0B;
+    } else {
+        p.pass0_out = straight ? L_FLAG : L_FLAG0;
+    }
+    p.t1 = !straight;
+    if (!p.t1) return p;
+    p.t1_in = p.t0b != T0B_NONE ? L_FLAG0B : L_FLAG0;
+    p.t1_cnt = list_counter(p.t1_in);
+    p.t1_out = L_FLAG;
+    // behind the polynomial centred-remainder form (a model whose decisions are 1e-7 of sum|coef|K) tier 1 runs in that form too:
+    // the plain three-pass kernel's band is relative to sum|coef|K and could decide nothing there
+    p.t1cr = cr_poly_t1;
+    // Round 5, the short-list gate: a SMALL request against a BIG model leaves the screening passes a handful of evaluations (C3
+    // against the headline's 4 096-SV model: 31), and tier 1 and the exact-integer tier behind it are then ~120 us of launches and
+    // minimum chains -- feature kernels, sweeps over thousands of SVs by a few workgroups -- for nothing the fp64 tier would
+    // not do in the one pass it makes anyway.  At most kShortListGate entries go straight to its list; tier 1 reads its list's
+    // length from CNT_T1_N (0 then), the exact-integer tier finds an empty input.  Not while the engine calibrates (the
+    // calibration measures what tier 1 decides).
+    p.gate = f.calibrated && f.short_gate && f.n_sv >= kShortGateMinSv && f.evals_cap <= 65536;
+    if (p.gate) {
+        p.gate_in = p.t1_in;
+        p.gate_out = p.fp64_in;
+        p.t1_cnt = CNT_T1_N;
+    }
+    return p;
+}
+
+static int *list_buf(haf_engine *e, int l)
+{
+    int *const buf[] = {e->d_flag0_list.p, e->d_flag0b_list.p, e->d_flag_list.p, e->d_flagi_list.p, e->d_flag2_list.p};
+    return l == L_NONE ? nullptr : buf[l];
+}
+// a pass that writes the exact tiers' input list publishes its length in that list's counter too (screen.hip: also_counter)
+static int handover_counter(int l) { return l == L_FLAG ? CNT_FLAGGED : -1; }
+
+// ---- one request: what its stages share ----
+struct Request {
+    int B = 0, R = 0, max_n = 0;
+    long total_n = 0;
+    bool bucket_ok = true;
+    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R][points of the host clouds]
+    CloudDev *h_clouds = nullptr;
+    const CloudDev *d_clouds = nullptr;
+    const RollGeo *d_geo = nullptr;
+    hipStream_t s = nullptr;
+    Dims d{};
+    float r_row = 0.0f, r_col = 0.0f;
+    long evals_cap = 0, evals_sel = 0;
+    bool direct = false, short_request = false, small_exact = false, large = false, fused_pre = false;
+    // what the last decide() ran, for the adaptive rule and the record of the call
+    bool i8_used = false, t0b_used = false;
+    bool lr_used = false;                // (of the last decide() with a screening pass)
+    int host_resolved = 0;
+};
+
+static int check_request(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
+                         int32_t roll_count, const haf_roll_record *records, Request &q)
+{
     if (!clouds || !in || !records || n_clouds < 1) return fail(e, HAF_E_ARG, "haf_score_rolls: null or empty argument");
     const haf_config &c = e->cfg;
     if (n_clouds > c.max_clouds) return fail(e, HAF_E_CAPACITY, "more clouds than max_clouds");
     if (roll_first < 0 || roll_count < 1 || roll_first + roll_count > c.n_rolls) return fail(e, HAF_E_ARG, "roll range outside [0, n_rolls)");
     if (roll_count > e->max_rolls) return fail(e, HAF_E_CAPACITY, "more rolls in one call than max_rolls_per_call");
     HIPCHK(e, hipSetDevice(c.device));
-    const int B = n_clouds, R = roll_count, H = c.grid_h, W = c.grid_w;
-
-    // ---- host preparation ----
+    q.B = n_clouds;
+    q.R = roll_count;
     size_t host_pts = 0;
-    int max_n = 0;
-    for (int b = 0; b < B; b++) {
+    for (int b = 0; b < q.B; b++) {
         if (clouds[b].n_points && !clouds[b].xyz) return fail(e, HAF_E_ARG, "cloud with null xyz");
         if (clouds[b].stride_floats < 3) return fail(e, HAF_E_ARG, "stride_floats must be >= 3");
         if (clouds[b].n_points > (size_t)INT32_MAX) return fail(e, HAF_E_CAPACITY, "cloud too large");
@@ -191,29 +298,33 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
                 return fail(e, HAF_E_ARG, "on_device = 2 needs a packed xyz cloud inside a buffer registered with haf_register_host_cloud");
         }
         if (clouds[b].on_device != 1) host_pts += clouds[b].n_points;
-        max_n = std::max(max_n, (int)clouds[b].n_points);
+        q.max_n = std::max(q.max_n, (int)clouds[b].n_points);
     }
     if (host_pts > (size_t)c.max_points) return fail(e, HAF_E_CAPACITY, "more host points than max_points");
-    // the request's input block (d_in / h_in): [CloudDev x B][RollGeo x B*R][points of the host clouds], one copy
+    return HAF_OK;
+}
+
+// the request's input block (d_in / h_in): the two header arrays on the host, one copy carries them with the points
+static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp_input *in, int roll_first, Request &q)
+{
+    const haf_config &c = e->cfg;
+    const int B = q.B, R = q.R;
     const size_t geo_off = ((size_t)B * sizeof(CloudDev) + 15) / 16 * 16;
-    const size_t pts_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
-    CloudDev *h_clouds = reinterpret_cast<CloudDev *>(e->h_in);
+    q.pts_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
+    q.h_clouds = reinterpret_cast<CloudDev *>(e->h_in);
     RollGeo *h_geo = reinterpret_cast<RollGeo *>(e->h_in + geo_off);
-    float *h_points = reinterpret_cast<float *>(e->h_in + pts_off);
-    const CloudDev *d_clouds = reinterpret_cast<const CloudDev *>(e->d_in.p);
-    const RollGeo *d_geo = reinterpret_cast<const RollGeo *>(e->d_in.p + geo_off);
-    const float *d_points = reinterpret_cast<const float *>(e->d_in.p + pts_off);
+    q.d_clouds = reinterpret_cast<const CloudDev *>(e->d_in.p);
+    q.d_geo = reinterpret_cast<const RollGeo *>(e->d_in.p + geo_off);
+    const float *d_points = reinterpret_cast<const float *>(e->d_in.p + q.pts_off);
     size_t off = 0;
-    long total_n = 0;
-    bool bucket_ok = true;
     for (int b = 0; b < B; b++) {
         NormalisedInput n = normalise(in[b]);
-        CloudDev &cd = h_clouds[b];
+        CloudDev &cd = q.h_clouds[b];
         for (int r = 0; r < R; r++) fill_roll_geo(c, in[b], n, roll_first + r, h_geo[b * R + r], r == 0 ? cd.m0 : nullptr);
-        if (n.width == 0) bucket_ok = false;             // x-scale 0: every point lands in row H/2, whatever its distance
-        cd.sorted_off = (int)total_n;
+        if (n.width == 0) q.bucket_ok = false;           // x-scale 0: every point lands in row H/2, whatever its distance
+        cd.sorted_off = (int)q.total_n;
         cd.bucket_off = b * e->bkt_ints;
-        total_n += (long)clouds[b].n_points;
+        q.total_n += (long)clouds[b].n_points;
         cd.n = (int)clouds[b].n_points;
         if (clouds[b].on_device == 1) {
             cd.xyz = clouds[b].xyz;
@@ -224,395 +335,508 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
             off += clouds[b].n_points;
         }
     }
-    hipStream_t s = e->stream;
-    mark(e, 0);
-    // Host clouds go through the pinned block in pieces: while the DMA engine moves one piece the host packs the next (a 1.2 MB
-    // cloud -- C3 -- costs ~100 us of host memcpy; its transfer hides behind that).  The first copy carries the two header arrays.
-    {
-        constexpr size_t kPiece = 256 * 1024;                     // bytes of packed points per copy
-        size_t staged = 0, sent = 0;                              // bytes of the points area packed / handed to the DMA engine
-        bool header_sent = false;
-        auto flush = [&](bool last) -> int {
-            if (!header_sent) {
-                HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, pts_off + staged, hipMemcpyHostToDevice, s));
-                header_sent = true;
-            } else if (staged > sent) {
-                HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + sent, e->h_in + pts_off + sent, staged - sent, hipMemcpyHostToDevice, s));
-            }
-            sent = staged;
-            (void)last;
-            return HAF_OK;
-        };
-        for (int b = 0; b < B; b++) {
-            if (clouds[b].on_device == 1 || clouds[b].n_points == 0) continue;
-            if (clouds[b].on_device == 2 && clouds[b].n_points * 12 >= kPiece) {
-                // (a small cloud is cheaper packed into the one staged copy than as a DMA transfer of its own: ~10 us each)
-                // page-locked caller memory: whatever has been packed so far goes out, then the DMA engine takes this cloud from
-                // where it lies (the staging block keeps the same layout, its share of it stays unused)
-                const int rc = flush(false);
-                if (rc != HAF_OK) return rc;
-                const size_t bytes = clouds[b].n_points * 12;
-                HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + staged, clouds[b].xyz, bytes, hipMemcpyHostToDevice, s));
-                staged += bytes;
-                sent = staged;
-                continue;
-            }
-            const float *src = clouds[b].xyz;
-            const size_t st = clouds[b].stride_floats, n = clouds[b].n_points;
-            for (size_t i0 = 0; i0 < n;) {
-                const size_t room = std::max<size_t>(1, (kPiece - (staged - sent)) / 12);
-                const size_t cnt = std::min(n - i0, room);
-                float *dst = reinterpret_cast<float *>(e->h_in + pts_off + staged);
-                if (st == 3) memcpy(dst, src + i0 * 3, cnt * 12);
-                else for (size_t i = 0; i < cnt; i++) { dst[i * 3] = src[(i0 + i) * st]; dst[i * 3 + 1] = src[(i0 + i) * st + 1]; dst[i * 3 + 2] = src[(i0 + i) * st + 2]; }
-                staged += cnt * 12;
-                i0 += cnt;
-                if (staged - sent >= kPiece) { const int rc = flush(false); if (rc != HAF_OK) return rc; }
-            }
-        }
-        const int rc = flush(true);
-        if (rc != HAF_OK) return rc;
-        (void)h_points;
-    }
-    // (the counters were zeroed behind the previous request's copy-out; after an error they may not have been)
-    if (!e->counters_clean) HIPCHK(e, hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), s));
-    e->counters_clean = false;
-    const size_t cells = (size_t)B * R * H * W;
-    if (e->d_attr.p) HIPCHK(e, hipMemsetAsync(e->d_attr.p, 0xFF, e->d_attr.n * sizeof(AttrRecord), s));   // debug: "not computed"
+}
 
-    Dims d;
+// Host clouds go through the pinned block in pieces: while the DMA engine moves one piece the host packs the next (a 1.2 MB
+// cloud -- C3 -- costs ~100 us of host memcpy; its transfer hides behind that).  The first copy carries the two header arrays.
+static int upload_clouds(haf_engine *e, const haf_cloud *clouds, const Request &q)
+{
+    constexpr size_t kPiece = 256 * 1024;                     // bytes of packed points per copy
+    const hipStream_t s = q.s;
+    const size_t pts_off = q.pts_off;
+    size_t staged = 0, sent = 0;                              // bytes of the points area packed / handed to the DMA engine
+    bool header_sent = false;
+    auto flush = [&]() -> int {
+        if (!header_sent) {
+            HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, pts_off + staged, hipMemcpyHostToDevice, s));
+            header_sent = true;
+        } else if (staged > sent) {
+            HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + sent, e->h_in + pts_off + sent, staged - sent, hipMemcpyHostToDevice, s));
+        }
+        sent = staged;
+        return HAF_OK;
+    };
+    for (int b = 0; b < q.B; b++) {
+        if (clouds[b].on_device == 1 || clouds[b].n_points == 0) continue;
+        if (clouds[b].on_device == 2 && clouds[b].n_points * 12 >= kPiece) {
+            // (a small cloud is cheaper packed into the one staged copy than as a DMA transfer of its own: ~10 us each)
+            // page-locked caller memory: whatever has been packed so far goes out, then the DMA engine takes this cloud from
+            // where it lies (the staging block keeps the same layout, its share of it stays unused)
+            const int rc = flush();
+            if (rc != HAF_OK) return rc;
+            const size_t bytes = clouds[b].n_points * 12;
+            HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + staged, clouds[b].xyz, bytes, hipMemcpyHostToDevice, s));
+            staged += bytes;
+            sent = staged;
+            continue;
+        }
+        const float *src = clouds[b].xyz;
+        const size_t st = clouds[b].stride_floats, n = clouds[b].n_points;
+        for (size_t i0 = 0; i0 < n;) {
+            const size_t room = std::max<size_t>(1, (kPiece - (staged - sent)) / 12);
+            const size_t cnt = std::min(n - i0, room);
+            float *dst = reinterpret_cast<float *>(e->h_in + pts_off + staged);
+            if (st == 3) memcpy(dst, src + i0 * 3, cnt * 12);
+            else for (size_t i = 0; i < cnt; i++) { dst[i * 3] = src[(i0 + i) * st]; dst[i * 3 + 1] = src[(i0 + i) * st + 1]; dst[i * 3 + 2] = src[(i0 + i) * st + 2]; }
+            staged += cnt * 12;
+            i0 += cnt;
+            if (staged - sent >= kPiece) { const int rc = flush(); if (rc != HAF_OK) return rc; }
+        }
+    }
+    return flush();
+}
+
+static void classify_request(const haf_engine *e, const haf_grasp_input *in, Request &q)
+{
+    const int B = q.B, R = q.R, H = e->cfg.grid_h, W = e->cfg.grid_w;
+    Dims &d = q.d;
     d.H = H; d.W = W; d.R = R; d.B = B; d.nf = e->nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->n_sv_tiles; d.sv_tile_neg = e->sv_tile_neg;
-    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);   // server.cpp:410-411
-    const long evals_cap = (long)B * R * (H - 14) * (W - 14);
+    q.r_row = (float)((0.5 * (float)H) / 100.0);   // server.cpp:410-411
+    q.r_col = (float)((0.5 * (float)W) / 100.0);
+    q.evals_cap = (long)B * R * (H - 14) * (W - 14);
     // For choosing between the feature kernels only: the masked cells of a roll lie inside the rotated search rectangle of
     // half sizes sx/2 - 7, sy/2 - 7 (pnt_in_box 687-688), at most (a + 2)(b + 2) lattice points for sides a, b -- usually far
     // fewer than the grid could hold (the client's default 32 x 44 area on the 56 x 56 grid: a third).
-    long evals_sel = 0;
     for (int b = 0; b < B; b++) {
         const long a2 = std::max(0, 2 * ((int)in[b].grasp_area_length_x / 2 - 7)) + 2, b2 = std::max(0, 2 * ((int)in[b].grasp_area_length_y / 2 - 7)) + 2;
-        evals_sel += (long)R * std::min<long>((long)(H - 14) * (W - 14), a2 * b2);
+        q.evals_sel += (long)R * std::min<long>((long)(H - 14) * (W - 14), a2 * b2);
     }
+    const long work = q.evals_sel * (long)e->n_sv_pad;
     // A request whose whole SVM work is tiny goes straight to the fp64 MFMA tier (every evaluation enters its list): same
     // labels by construction -- the tier decides outside its own band and hands the rest to the strict tier -- and three
     // launches instead of a feature kernel, a contraction kernel and the rechecks behind them.
-    const bool direct = !e->prob_mode && !e->generic_kernel && e->direct_work > 0 && evals_sel * (long)e->n_sv_pad <= e->direct_work;
-    const bool short_request = evals_sel * (long)e->n_sv_pad <= (1L << 26) && total_n <= (1L << 20);
+    q.direct = !e->prob_mode && !e->generic_kernel && e->direct_work > 0 && work <= e->direct_work;
+    q.short_request = work <= (1L << 26) && q.total_n <= (1L << 20);
     // A small engine with a small model behind one of the fast contractions: what that contraction flags goes through the SAME one-launch
     // kernel in list mode (exact attributes + fp64 MFMA decision, tier 2's arithmetic) instead of tier 2a's three launches and tier 2's
     // three -- at a few thousand evaluations x a few hundred SVs the six launches and two more attribute kernels cost more than the
     // exact work (C3: 81 -> 30 us; the kernel costs ~9 ns per listed evaluation at 192 SVs, so it wins up to ~8 000 of them: a request
     // of up to 2^25 evaluation x SV pairs, of which a trained model flags around a tenth).  Decided from the request's search areas and
     // the model's size, so identical calls take identical paths.
-    const bool small_exact = !direct && !e->prob_mode && e->direct_work > 0 && evals_sel * (long)e->n_sv_pad <= 16 * e->direct_work;
-    // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
-    bool fused_pre = false;
+    q.small_exact = !q.direct && !e->prob_mode && e->direct_work > 0 && work <= 16 * e->direct_work;
+    q.large = q.evals_sel >= e->large_evals;              // enough evaluations to fill the chip with one thread each
+}
+
+static int run_prestages(haf_engine *e, Request &q)
+{
+    const haf_config &c = e->cfg;
+    const hipStream_t s = q.s;
+    const Dims &d = q.d;
+    // (the counters were zeroed behind the previous request's copy-out; after an error they may not have been)
+    if (!e->counters_clean) HIPCHK(e, hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), s));
+    e->counters_clean = false;
+    if (e->d_attr.p) HIPCHK(e, hipMemsetAsync(e->d_attr.p, 0xFF, e->d_attr.n * sizeof(AttrRecord), s));   // debug: "not computed"
     mark(e, HAF_ST_BIN);
+    // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
     if (!e->prob_mode && !e->no_fused_pre)
-        fused_pre = launch_small_pre(d_clouds, d_geo, max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
-                                     e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, direct, d, r_row, r_col, s,
-                                     e->d_brslot.p, ++e->pre_epoch);
-    if (fused_pre) {
+        q.fused_pre = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
+                                       e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
+                                       e->d_brslot.p, ++e->pre_epoch);
+    if (q.fused_pre) {
         mark(e, HAF_ST_INTEGRAL);
         mark(e, HAF_ST_MASK);
-    } else {
-        HIPCHK(e, hipMemsetAsync(e->d_labels.p, 0xFF, cells, s));        // -1: no feature vector for this cell (server.cpp:828-829)
-        BinScratch bs{};
-        bs.sorted = e->d_sorted.p; bs.sorted_cap = e->d_sorted.p ? (long)c.max_points : 0;
-        bs.bkt_count = e->d_bkt.p; bs.bkt_off = e->d_bkt.p ? e->d_bkt.p + (size_t)c.max_clouds * e->bkt_ints : nullptr;
-        bs.bkt_cursor = e->d_bkt.p ? e->d_bkt.p + (size_t)2 * c.max_clouds * e->bkt_ints : nullptr;
-        bs.bkt_cap = e->d_bkt.p ? c.max_clouds * e->bkt_ints : 0;
-        launch_bin(d_clouds, h_clouds, max_n, total_n, d_geo, e->d_heights.p, d, r_row, r_col, bucket_ok && !e->no_bucket_sort, bs, e->d_counters.p, s);
-        mark(e, HAF_ST_INTEGRAL);
-        launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
-        mark(e, HAF_ST_MASK);
-        launch_mask_count(e->d_ii.p, d_geo, e->d_mask.p, e->d_rowcount.p, d, s);
-        launch_scan(e->d_rowcount.p, e->d_rowoff.p, e->d_brcount.p, e->d_counters.p, d, s);
-        launch_compact(e->d_mask.p, e->d_rowcount.p, e->d_rowoff.p, e->d_evalcell.p, d, s);
-        if (direct) launch_prob_list(e->d_counters.p, CNT_FLAGGED, e->d_flag_list.p, e->list_cap, s);
+        return HAF_OK;
     }
-    // features -> decision tiers -> vote -> records on the host, for one contraction mode
-    bool i8_used = false;                                    // the exact-integer tier ran in the last decide()
-    bool t0b_used = false;                                   // tier 0b ran in the last decide()
-    bool lr_used = false;                                    // the screening pass of the last decide() ran in the low-rank form
-    auto decide = [&](int mode, bool reuse_operands) -> int {
-        t0b_used = false;
-        mark(e, HAF_ST_FEATURES);
-        const bool large = evals_sel >= e->large_evals;      // enough evaluations to fill the chip with one thread each
-        if (e->generic_kernel) {
-            // a model whose kernel is not RBF: every evaluation on the strict tier's list, libsvm's own arithmetic for all of them
-            launch_prob_list(e->d_counters.p, CNT_FLAGGED2, e->d_flag2_list.p, e->list_cap, s);
-            launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p, e->list_cap,
-                           e->d_counters.p, CNT_FLAGGED2, e->d_dec_exact2.p, e->d_labels.p, d, s);
-            mark(e, HAF_ST_SVM);
-            mark(e, HAF_ST_REFINE);
-        } else if (direct) {
-            // tiny request: exact attributes, fp64 MFMA decision and label of EVERY evaluation in one launch (k_small_direct: tier 2's
-            // arithmetic); every evaluation counts as rechecked (k_small_pre / k_prob_list have put them on that tier's list)
-            launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, d, std::min<long>(evals_cap, e->list_cap),
-                                e->d_dec_exact.p, e->d_labels.p, e->d_flag2_list.p, e->list_cap, e->d_attr.p, s);
-            mark(e, HAF_ST_SVM);
-            mark(e, HAF_ST_REFINE);
-        } else if (mode == MODE_SCREEN) {
-            // tier 0: single-pass fp16 screening of every evaluation; tier 1: the three-pass kernel on what it could not decide
-            // (the centred-remainder variants have their own operand images: translated attributes, centred support vectors)
-            const bool cr = e->screen_variant == SCREEN_CR_EXP || e->screen_variant == SCREEN_CR_POLY;
-            ScreenParams sp_now = cr ? e->screen_cr : e->screen;
-            sp_now.cr_poly = e->screen_variant == SCREEN_CR_POLY;
-            // Low-rank form of the centred-remainder pass (kernels.h: kLrK): whole requests large enough for the thread-per-evaluation
-            // feature kernel on grids that went through the parallel integral image (whose pass records negative heights), when the
-            // centred-remainder form serves the model; the 10-step images go through k_project, the sweep runs on 6-step images.
-            const bool lr_plain = e->screen_variant == SCREEN_PLAIN && e->lr_plain_available;      // the plain epilogue on the projected (centred) operands
-            const bool lr = (cr || lr_plain) && large && e->lr_available && e->lr_enabled && !fused_pre && (long)H * W > 8192 && !reuse_operands;
-            lr_used = lr;
-            if (lr && lr_plain) sp_now = e->screen_lrp;
-            if (lr) { sp_now.lr = 1; sp_now.lr_negflags = e->d_inexact.p; sp_now.lr_iiabs = e->d_iiabs.p; }
-            if (!reuse_operands)
-                launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
-                                e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, large, evals_sel, nullptr, e->d_ax.p, s);
-            char *y_img = reinterpret_cast<char *>(e->d_X.p) + (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes;   // behind the 10-step images (the buffer holds the 42 KiB three-pass form)
-            mark(e, HAF_ST_SVM);
-            if (lr && !e->lr_fused) launch_project(e->d_X.p, e->d_lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)
-            // A small request with a small model (small_exact): what the screening pass leaves goes STRAIGHT to the one-launch exact kernel
-            // (k_small_direct in list mode: exact attributes + fp64 MFMA decision, 9 ns per listed evaluation at 192 SVs) -- the list
-            // is written where that kernel reads it.  Tier 1 in between was a feature kernel and a contraction launch at their latency
-            // floors (C3: 44 + 36 us for 4 072 evaluations, of which it decided nine tenths) in front of the same exact kernel.
-            // The same hand-over when calibration found tier 1 of little use behind the screening passes (t1_skip).
-            // (behind the low-rank pass the full-rank centred-remainder form runs once more on its list: the waves it cannot bound --
-            // the borders of the grid, waves that are not a run of neighbours -- and what its slightly wider band leaves)
-            const bool t0b = e->use_t0b && e->cr_available && !small_exact && (!cr || (lr && e->screen_variant == SCREEN_CR_EXP));
-            const bool straight = small_exact || (e->t1_skip && !t0b);
-            if (lr)
-                launch_svm_screen_lr(e->lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                                     e->d_flag0_words.p, e->d_flag0_wgcount.p, straight ? e->d_flag_list.p : e->d_flag0_list.p, e->flag0_cap, e->d_counters.p, d,
-                                     evals_cap, e->d_margin.p, e->screen_variant, e->crp, e->lr_band, s, straight ? CNT_FLAGGED : -1,
-                                     e->lr_fused ? e->d_lr_btiles_in.p : nullptr);
-            else
-            launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, cr ? e->d_svt0_cr.p : e->d_svt0.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                              e->d_flag0_words.p, e->d_flag0_wgcount.p, straight ? e->d_flag_list.p : e->d_flag0_list.p, e->flag0_cap, e->d_counters.p, d, evals_cap, e->d_margin.p,
-                              e->screen_variant, e->crp, s, straight ? CNT_FLAGGED : -1, nullptr, CNT_EVALS, CNT_FLAGGED0, e->d_screen_part.p, e->screen_parts);
-            mark(e, HAF_ST_REFINE);
-            const long list_cap = std::min<long>(e->flag0_cap, evals_cap);
-            const int *t1_list = e->d_flag0_list.p;
-            int t1_counter = CNT_FLAGGED0;
-            bool t1_run = !straight;
-            const bool skip1 = e->t1_skip;
-            // round 5: behind a LOW-RANK first pass with the plain epilogue tier 0b is the low-rank sweep itself with the centred-remainder
-            // epilogue in its GATHER form -- the first pass's operand images and raw sums by evaluation id, no second feature kernel
-            const bool t0b_gather = t0b && lr && lr_plain && e->lr_fused && !test_env("HAF_T0B_NO_GATHER");
-            if (t0b_gather) {
-                launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p,
-                                     e->d_labels.p, e->d_flag0_words.p, e->d_flag0_wgcount.p, skip1 ? e->d_flag_list.p : e->d_flag0b_list.p, e->flag0_cap,
-                                     e->d_counters.p, d, list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, e->lr_band, s, skip1 ? CNT_FLAGGED : -1,
-                                     e->d_lr_btiles_in.p, e->d_flag0_list.p, CNT_FLAGGED0, CNT_FLAGGED0B);
-                t1_list = e->d_flag0b_list.p;
-                t1_counter = CNT_FLAGGED0B;
-                t1_run = !skip1;
-                t0b_used = true;
-            } else if (t0b) {
-                // tier 0b: the centred-remainder form on the LIST of the first pass (its own operand images: translated attributes,
-                // centred support vectors; band, common factor and images indexed by list slot)
-                ScreenParams sp_b = e->screen_cr;
-                sp_b.cr_poly = 0;
-                // (the group-parallel feature kernel even for lists of 10^5: one evaluation per lane on SCATTERED cells -- k_features_serial in
-                // list mode -- was measured at 7.7 ns per evaluation against 2.1 ns, its 2 400 corner loads per lane being 64 separate
-                // L1 accesses each)
-                launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_gband.p, d, e->range.lower,
-                                e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SCREEN, sp_b, e->d_flag0_list.p, CNT_FLAGGED0, e->flag0_cap,
-                                false, list_cap, nullptr, e->d_ax.p, s);
-                launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->d_svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                                  e->d_flag0_words.p, e->d_flag0_wgcount.p, skip1 ? e->d_flag_list.p : e->d_flag0b_list.p, e->flag0_cap, e->d_counters.p, d,
-                                  list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, s, skip1 ? CNT_FLAGGED : -1, e->d_flag0_list.p, CNT_FLAGGED0, CNT_FLAGGED0B,
-                                  e->d_screen_part.p, e->screen_parts);
-                t1_list = e->d_flag0b_list.p;
-                t1_counter = CNT_FLAGGED0B;
-                t1_run = !skip1;
-                t0b_used = true;
-            }
-            // Round 5, the short-list gate: a SMALL request against a BIG model leaves the screening passes a handful of evaluations (C3
-            // against the headline's 4 096-SV model: 31), and tier 1 and the exact-integer tier behind it are then ~120 us of launches and
-            // minimum chains -- feature kernels, sweeps over thousands of SVs by a few workgroups -- for nothing the fp64 tier would
-            // not do in the one pass it makes anyway.  At most kShortListGate entries go straight to its list; tier 1 reads its list's
-            // length from CNT_T1_N (0 then), the exact-integer tier finds an empty input.  Not while the engine calibrates (the
-            // calibration measures what tier 1 decides).
-            if (t1_run && e->calibrated && e->short_gate && d.n_sv >= kShortGateMinSv && evals_cap <= 65536 && !e->generic_kernel) {
-                const bool i8_next = e->i8_active && !(e->screen_variant == SCREEN_CR_POLY && e->t1_cr_available);
-                launch_short_list_gate(e->d_counters.p, t1_counter, t1_list, e->flag0_cap, i8_next ? e->d_flagi_list.p : e->d_flag_list.p,
-                                       CNT_FLAGGEDI, i8_next, std::min(kShortListGate, e->flag_cap), s);
-                t1_counter = CNT_T1_N;
-            }
-            if (t1_run) {
-            // (the list is short whenever screening is worth its while: always the group-parallel feature kernel, whose
-            // workgroups beyond the list's end exit at once)
-            // behind the polynomial centred-remainder form (a model whose decisions are 1e-7 of sum|coef|K) tier 1 runs in that form too:
-            // the plain three-pass kernel's band is relative to sum|coef|K and could decide nothing there
-            const bool t1cr = e->screen_variant == SCREEN_CR_POLY && e->t1_cr_available;
-            ScreenParams sp_t1 = e->screen;
-            if (t1cr) { sp_t1.cr_t1_tab = e->d_t1_tab.p; sp_t1.cr_t1_L = e->d_t1_L.p; }
-            launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_ax1.p, d, e->range.lower,
-                            e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SPLIT, sp_t1, t1_list, t1_counter,
-                            e->flag0_cap, false, list_cap, e->d_attr.p, nullptr, s);
-            launch_svm_h(e->d_X1.p, e->d_ax1.p, t1cr ? e->d_svt_h_cr.p : e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                         e->d_flag_list.p, e->list_cap, e->d_counters.p, d, list_cap, t1_list, t1_counter, e->flag0_cap,
-                         e->d_part1.p, e->part1_stride, s, t1cr ? &e->crt1 : nullptr, t1cr ? e->d_t1_L.p : nullptr, e->d_t1_flags.p);
-            }
-        } else if (mode == MODE_SPLIT) {
-            launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
-                            e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SPLIT, e->screen, nullptr, 0, 0, large, evals_sel, e->d_attr.p, nullptr, s);
-            mark(e, HAF_ST_SVM);
-            launch_svm_h(e->d_X.p, e->d_ax.p, e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                         e->d_flag_list.p, e->list_cap, e->d_counters.p, d, evals_cap, nullptr, 0, 0, nullptr, 0, s, nullptr, nullptr, e->d_t1_flags.p);
-            mark(e, HAF_ST_REFINE);
-        } else {
-            launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
-                            e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_F32, e->screen, nullptr, 0, 0, large, evals_sel, e->d_attr.p, nullptr, s);
-            mark(e, HAF_ST_SVM);
-            launch_svm(e->d_X.p, e->d_ax.p, e->d_svt.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
-                       e->d_flag_list.p, e->list_cap, e->d_counters.p, d, evals_cap, s, e->d_t1_flags.p);
-            mark(e, HAF_ST_REFINE);
+    HIPCHK(e, hipMemsetAsync(e->d_labels.p, 0xFF, (size_t)q.B * q.R * d.H * d.W, s));   // -1: no feature vector for this cell (server.cpp:828-829)
+    BinScratch bs{};
+    bs.sorted = e->d_sorted.p; bs.sorted_cap = e->d_sorted.p ? (long)c.max_points : 0;
+    bs.bkt_count = e->d_bkt.p; bs.bkt_off = e->d_bkt.p ? e->d_bkt.p + (size_t)c.max_clouds * e->bkt_ints : nullptr;
+    bs.bkt_cursor = e->d_bkt.p ? e->d_bkt.p + (size_t)2 * c.max_clouds * e->bkt_ints : nullptr;
+    bs.bkt_cap = e->d_bkt.p ? c.max_clouds * e->bkt_ints : 0;
+    launch_bin(q.d_clouds, q.h_clouds, q.max_n, q.total_n, q.d_geo, e->d_heights.p, d, q.r_row, q.r_col, q.bucket_ok && !e->no_bucket_sort, bs,
+               e->d_counters.p, s);
+    mark(e, HAF_ST_INTEGRAL);
+    launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
+    mark(e, HAF_ST_MASK);
+    launch_mask_count(e->d_ii.p, q.d_geo, e->d_mask.p, e->d_rowcount.p, d, s);
+    launch_scan(e->d_rowcount.p, e->d_rowoff.p, e->d_brcount.p, e->d_counters.p, d, s);
+    launch_compact(e->d_mask.p, e->d_rowcount.p, e->d_rowoff.p, e->d_evalcell.p, d, s);
+    if (q.direct) launch_prob_list(e->d_counters.p, CNT_FLAGGED, e->d_flag_list.p, e->list_cap, s);
+    return HAF_OK;
+}
+
+static TierFacts tier_facts(const haf_engine *e, const Request &q, int mode, bool reuse_operands)
+{
+    return TierFacts{e->screen_variant, e->cr_available, e->lr_available, e->lr_enabled, e->lr_plain_available, e->lr_fused,
+                     e->use_t0b, e->t1_skip, e->t1_cr_available, e->i8_active, e->calibrated, e->short_gate, e->generic_kernel,
+                     e->model.n_sv, test_env("HAF_T0B_NO_GATHER") != nullptr, mode, reuse_operands, q.direct, q.small_exact, q.large,
+                     q.fused_pre, (long)q.d.H * q.d.W, q.evals_cap};
+}
+
+// the screening pass (tier 0), tier 0b, the short-list gate and tier 1 of a PATH_SCREEN plan
+static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
+{
+    const hipStream_t s = q.s;
+    const Dims &d = q.d;
+    const long evals_cap = q.evals_cap;
+    ScreenParams sp_now = p.sp == SP_LRP ? e->screen_lrp : p.sp == SP_CR ? e->screen_cr : e->screen;
+    if (p.sp != SP_LRP) sp_now.cr_poly = e->screen_variant == SCREEN_CR_POLY;
+    if (p.lr) { sp_now.lr = 1; sp_now.lr_negflags = e->d_inexact.p; sp_now.lr_iiabs = e->d_iiabs.p; }
+    if (!p.reuse)
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
+                        e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
+    char *y_img = reinterpret_cast<char *>(e->d_X.p) + (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes;   // behind the 10-step images (the buffer holds the 42 KiB three-pass form)
+    mark(e, HAF_ST_SVM);
+    if (p.lr && !e->lr_fused) launch_project(e->d_X.p, e->d_lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)
+    if (p.lr)
+        launch_svm_screen_lr(e->lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                             e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d,
+                             evals_cap, e->d_margin.p, e->screen_variant, e->crp, e->lr_band, s, handover_counter(p.pass0_out),
+                             e->lr_fused ? e->d_lr_btiles_in.p : nullptr);
+    else
+        launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, p.cr ? e->d_svt0_cr.p : e->d_svt0.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                          e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d, evals_cap, e->d_margin.p,
+                          e->screen_variant, e->crp, s, handover_counter(p.pass0_out), nullptr, CNT_EVALS, CNT_FLAGGED0, e->d_screen_part.p, e->screen_parts);
+    mark(e, HAF_ST_REFINE);
+    const long list_cap = std::min<long>(e->flag0_cap, evals_cap);
+    if (p.t0b == T0B_GATHER) {
+        launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p,
+                             e->d_labels.p, e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap,
+                             e->d_counters.p, d, list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, e->lr_band, s, handover_counter(p.t0b_out),
+                             e->d_lr_btiles_in.p, list_buf(e, p.t0b_in), list_counter(p.t0b_in), CNT_FLAGGED0B);
+    } else if (p.t0b == T0B_FEATURES) {
+        // tier 0b: the centred-remainder form on the LIST of the first pass (its own operand images: translated attributes,
+        // centred support vectors; band, common factor and images indexed by list slot)
+        ScreenParams sp_b = e->screen_cr;
+        sp_b.cr_poly = 0;
+        // (the group-parallel feature kernel even for lists of 10^5: one evaluation per lane on SCATTERED cells -- k_features_serial in
+        // list mode -- was measured at 7.7 ns per evaluation against 2.1 ns, its 2 400 corner loads per lane being 64 separate
+        // L1 accesses each)
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_gband.p, d, e->range.lower,
+                        e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SCREEN, sp_b, list_buf(e, p.t0b_in), list_counter(p.t0b_in), e->flag0_cap,
+                        false, list_cap, nullptr, e->d_ax.p, s);
+        launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->d_svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                          e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap, e->d_counters.p, d,
+                          list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, s, handover_counter(p.t0b_out), list_buf(e, p.t0b_in), list_counter(p.t0b_in),
+                          CNT_FLAGGED0B, e->d_screen_part.p, e->screen_parts);
+    }
+    // (the gate's count goes to CNT_FLAGGEDI only when it writes the exact-integer tier's output list)
+    if (p.gate)
+        launch_short_list_gate(e->d_counters.p, list_counter(p.gate_in), list_buf(e, p.gate_in), e->flag0_cap, list_buf(e, p.gate_out),
+                               CNT_FLAGGEDI, p.gate_out == L_FLAGI, std::min(kShortListGate, e->flag_cap), s);
+    if (!p.t1) return;
+    // (the list is short whenever screening is worth its while: always the group-parallel feature kernel, whose
+    // workgroups beyond the list's end exit at once)
+    ScreenParams sp_t1 = e->screen;
+    if (p.t1cr) { sp_t1.cr_t1_tab = e->d_t1_tab.p; sp_t1.cr_t1_L = e->d_t1_L.p; }
+    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_ax1.p, d, e->range.lower,
+                    e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SPLIT, sp_t1, list_buf(e, p.t1_in), p.t1_cnt,
+                    e->flag0_cap, false, list_cap, e->d_attr.p, nullptr, s);
+    launch_svm_h(e->d_X1.p, e->d_ax1.p, p.t1cr ? e->d_svt_h_cr.p : e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                 list_buf(e, p.t1_out), e->list_cap, e->d_counters.p, d, list_cap, list_buf(e, p.t1_in), p.t1_cnt, e->flag0_cap,
+                 e->d_part1.p, e->part1_stride, s, p.t1cr ? &e->crt1 : nullptr, p.t1cr ? e->d_t1_L.p : nullptr, e->d_t1_flags.p);
+}
+
+// the first pass of every other path: the generic / direct tier, or a contraction over every evaluation
+static void launch_first_pass(haf_engine *e, const Request &q, const TierPlan &p)
+{
+    const hipStream_t s = q.s;
+    const Dims &d = q.d;
+    if (p.path == PATH_GENERIC) {
+        launch_prob_list(e->d_counters.p, list_counter(p.pass0_out), list_buf(e, p.pass0_out), e->list_cap, s);
+        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in), e->list_cap,
+                       e->d_counters.p, list_counter(p.strict_in), e->d_dec_exact2.p, e->d_labels.p, d, s);
+        mark(e, HAF_ST_SVM);
+    } else if (p.path == PATH_DIRECT) {
+        // every evaluation counts as rechecked (k_small_pre / k_prob_list have put them on the exact tier's list)
+        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, d, std::min<long>(q.evals_cap, e->list_cap),
+                            e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.pass0_out), e->list_cap, e->d_attr.p, s);
+        mark(e, HAF_ST_SVM);
+    } else if (p.path == PATH_SPLIT) {
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
+                        e->range.upper, e->svm.neg_gamma2, q.evals_cap, XMODE_SPLIT, e->screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
+        mark(e, HAF_ST_SVM);
+        launch_svm_h(e->d_X.p, e->d_ax.p, e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                     list_buf(e, p.pass0_out), e->list_cap, e->d_counters.p, d, q.evals_cap, nullptr, 0, 0, nullptr, 0, s, nullptr, nullptr, e->d_t1_flags.p);
+    } else {
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
+                        e->range.upper, e->svm.neg_gamma2, q.evals_cap, XMODE_F32, e->screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
+        mark(e, HAF_ST_SVM);
+        launch_svm(e->d_X.p, e->d_ax.p, e->d_svt.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+                   list_buf(e, p.pass0_out), e->list_cap, e->d_counters.p, d, q.evals_cap, s, e->d_t1_flags.p);
+    }
+    mark(e, HAF_ST_REFINE);
+}
+
+// One window [off, off + flag_cap) of the exact tiers' input lists.  Tier 2: fp64 MFMA (GEMM form) for the guard band of the fast
+// contraction; tier 2a in front of it: the exact-integer tier (plan_tiers)
+static void fp64_window(haf_engine *e, const Request &q, const TierPlan &p, int off)
+{
+    if (p.fp64 == FP64_SMALL)
+        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, q.d, e->flag_cap, e->d_dec_exact.p,
+                            e->d_labels.p, list_buf(e, p.fp64_out), e->list_cap, nullptr, q.s, list_buf(e, p.fp64_in), list_counter(p.fp64_in), off);
+    else
+        launch_recheck_mfma(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->exact, list_buf(e, p.fp64_in), e->flag_cap, off, e->d_counters.p,
+                            e->d_x64.p, e->d_part64.p, p.i8 ? e->d_dec_exacti.p : e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.fp64_out), e->list_cap,
+                            q.d, q.s, nullptr, false, list_counter(p.fp64_in), e->d_tier_words.p);
+}
+static void i8_window(haf_engine *e, const Request &q, const TierPlan &p, int off)
+{
+    launch_recheck_i8(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv_i8.p, e->i8, e->range.lower, e->range.upper, list_buf(e, p.i8_in), e->flag_cap,
+                      off, e->d_counters.p, e->d_x64.p, e->d_part64.p, e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.i8_out), e->list_cap, q.d, q.s,
+                      e->d_tier_words.p);
+}
+
+// the vote, then the counters and the roll records to the host (one copy), and the wait for them
+static int vote_and_wait(haf_engine *e, const Request &q)
+{
+    const hipStream_t s = q.s;
+    mark(e, HAF_ST_VOTE);
+    launch_vote(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, q.d, s);
+    mark(e, HAF_ST_DOWNLOAD);
+    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));   // counters + records
+    mark(e, HAF_ST_COUNT);
+    // a short request (tens to hundreds of microseconds on the device) is waited for by polling: the wake-up of a
+    // blocked host thread costs more than the request's last kernels
+    if (q.short_request) {
+        hipError_t r;
+        while ((r = hipStreamQuery(s)) == hipErrorNotReady) __builtin_ia32_pause();   // (spin politely: the sibling hyper-thread may be the driver's)
+        HIPCHK(e, r);
+    } else {
+        HIPCHK(e, hipStreamSynchronize(s));
+    }
+    HIPCHK(e, hipGetLastError());
+    return HAF_OK;
+}
+
+// What the counters that came back with the roll records ask for: the exact tiers' further windows, the strict tier, the host
+static int finish_exact_tiers(haf_engine *e, Request &q, const TierPlan &p)
+{
+    const hipStream_t s = q.s;
+    int rc = HAF_OK;
+    bool strict_ran = false;
+    q.host_resolved = 0;
+    const int flagged = e->h_counters[CNT_FLAGGED];
+    const bool lists_valid = p.fp64 != FP64_NONE && !(p.path == PATH_SCREEN && e->h_counters[CNT_FLAGGED0] > e->flag0_cap);
+    const bool more_i8 = lists_valid && p.i8 && flagged > e->flag_cap;
+    const bool more_fp64 = lists_valid && e->h_counters[list_counter(p.fp64_in)] > e->flag_cap;
+    if (more_i8 || more_fp64) {
+        // More evaluations inside a guard band than one window of an exact tier holds (an ill-conditioned model): the
+        // reference never fails a goal on this path (server.cpp:778-796), so neither does the engine -- the remaining
+        // windows of the lists go through the same kernels one after the other, then the strict tier over its whole list,
+        // then the vote again.  Slower, same labels.
+        int done_fp64 = e->flag_cap;                  // entries of its list the fp64 tier has seen (window 0)
+        if (more_i8) {
+            for (int off = e->flag_cap; off < flagged; off += e->flag_cap) { i8_window(e, q, p, off); e->stat_extra_windows++; }
+            // the fp64 tier's list has grown behind its first window: all of it again from the start (its results and the
+            // strict tier's list are rebuilt; both are idempotent)
+            HIPCHK(e, hipMemsetAsync(e->d_counters.p + list_counter(p.fp64_out), 0, sizeof(int), s));
+            HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
+            HIPCHK(e, hipStreamSynchronize(s));
+            done_fp64 = 0;
         }
-        mark(e, HAF_ST_RECHECK);
-        // tier 2: fp64 MFMA (GEMM form) for the guard band of the fast contraction; tier 3: libsvm's strict order for what
-        // is still within 2^-40 of zero (practically nothing).  Window 0 of the tier-2 list goes with every request; the
-        // strict tier is launched only when the counters that come back with the roll records say it has work (never so far).
-        // tier 2a in front of it (exact8.hip): the same evaluations on EXACT integer dot products (int8 digit planes); what it
-        // cannot decide either -- |dec| inside the operands' quantisation, ~1e-7 S -- is the fp64 MFMA tier's list
-        // (behind the centred-remainder form of tier 1 the exact-integer tier has nothing to add: its band is the quantisation of the
-        // operands relative to sum|coef|K -- 8e-9 S for the trained model, 0.14 -- and tier 1's is relative to S_psi, 0.02: measured,
-        // it decided 8 of 9984 evaluations in 4.6 ms.  What tier 1 leaves goes straight to the fp64 MFMA tier)
-        const bool i8 = e->i8_active && !direct && !small_exact && !(mode == MODE_SCREEN && e->screen_variant == SCREEN_CR_POLY && e->t1_cr_available);
-        i8_used = i8;
-        auto fp64_window = [&](int off) {
-            if (small_exact)
-                launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, d, e->flag_cap, e->d_dec_exact.p,
-                                    e->d_labels.p, e->d_flag2_list.p, e->list_cap, nullptr, s, e->d_flag_list.p, CNT_FLAGGED, off);
-            else if (i8)
-                launch_recheck_mfma(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->exact, e->d_flagi_list.p, e->flag_cap, off, e->d_counters.p,
-                                    e->d_x64.p, e->d_part64.p, e->d_dec_exacti.p, e->d_labels.p, e->d_flag2_list.p, e->list_cap, d, s, nullptr, false,
-                                    CNT_FLAGGEDI, e->d_tier_words.p);
-            else
-                launch_recheck_mfma(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->exact, e->d_flag_list.p, e->flag_cap, off, e->d_counters.p,
-                                    e->d_x64.p, e->d_part64.p, e->d_dec_exact.p, e->d_labels.p, e->d_flag2_list.p, e->list_cap, d, s, nullptr, false,
-                                    CNT_FLAGGED, e->d_tier_words.p);
-        };
-        auto i8_window = [&](int off) {
-            launch_recheck_i8(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv_i8.p, e->i8, e->range.lower, e->range.upper, e->d_flag_list.p, e->flag_cap,
-                              off, e->d_counters.p, e->d_x64.p, e->d_part64.p, e->d_dec_exact.p, e->d_labels.p, e->d_flagi_list.p, e->list_cap, d, s,
-                              e->d_tier_words.p);
-        };
-        if (!direct && !e->generic_kernel) {
-            if (i8) i8_window(0);
-            fp64_window(0);
-        }
-        // the counters come back with the roll records: a second window costs nothing unless it is needed
-        auto vote = [&]() -> int {
-            mark(e, HAF_ST_VOTE);
-            launch_vote(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, d, s);
-            mark(e, HAF_ST_DOWNLOAD);
-            HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)B * R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));   // counters + records
-            mark(e, HAF_ST_COUNT);
-            // a short request (tens to hundreds of microseconds on the device) is waited for by polling: the wake-up of a
-            // blocked host thread costs more than the request's last kernels
-            if (short_request) {
-                hipError_t q;
-                while ((q = hipStreamQuery(s)) == hipErrorNotReady) __builtin_ia32_pause();   // (spin politely: the sibling hyper-thread may be the driver's)
-                HIPCHK(e, q);
-            } else {
-                HIPCHK(e, hipStreamSynchronize(s));
-            }
-            HIPCHK(e, hipGetLastError());
-            return HAF_OK;
-        };
-        int rc = vote();
+        const int n_fp64 = e->h_counters[list_counter(p.fp64_in)];
+        for (int off = done_fp64; off < n_fp64; off += e->flag_cap) { fp64_window(e, q, p, off); e->stat_extra_windows++; }
+        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in), e->list_cap,
+                       e->d_counters.p, list_counter(p.strict_in), e->d_dec_exact2.p, e->d_labels.p, q.d, s);
+        if ((rc = vote_and_wait(e, q)) != HAF_OK) return rc;
+        strict_ran = e->h_counters[list_counter(p.strict_in)] > 0;
+    } else if (p.path == PATH_GENERIC) {
+        strict_ran = true;                            // (it has run, on everything; what is left is the C library's tanh near zero)
+    } else if (e->h_counters[list_counter(p.strict_in)] > 0) {
+        // (the host knows the list's length here: the spread form of the tier, recheck.hip)
+        launch_recheck_known(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in),
+                             std::min(e->h_counters[list_counter(p.strict_in)], e->list_cap), e->d_strict_terms.p, kStrictSlots, e->d_dec_exact2.p,
+                             e->d_labels.p, q.d, s);
+        if ((rc = vote_and_wait(e, q)) != HAF_OK) return rc;
+        strict_ran = true;
+    }
+    if (strict_ran) {
+        // what the strict tier left within a last-bit exp error of zero: glibc's exp on the host, then the vote once more
+        bool changed = false;
+        if ((rc = host_resolve_strict(e, q.d, s, &changed, &q.host_resolved)) != HAF_OK) return rc;
+        if (changed && (rc = vote_and_wait(e, q)) != HAF_OK) return rc;
+    }
+    return HAF_OK;
+}
+
+// features -> decision tiers -> vote -> records on the host, for one contraction mode
+static int decide(haf_engine *e, Request &q, int mode, bool reuse_operands)
+{
+    mark(e, HAF_ST_FEATURES);
+    const TierPlan p = plan_tiers(tier_facts(e, q, mode, reuse_operands));
+    if (p.path == PATH_SCREEN) {
+        q.lr_used = p.lr;
+        launch_screening(e, q, p);
+    } else {
+        launch_first_pass(e, q, p);
+    }
+    q.t0b_used = p.t0b != T0B_NONE;
+    q.i8_used = p.i8;
+    mark(e, HAF_ST_RECHECK);
+    // Window 0 of the exact tiers' lists goes with every request; the strict tier (libsvm's order, for what is still within 2^-40 of
+    // zero: practically nothing) is launched only when the counters that come back with the roll records say it has work
+    if (p.fp64 != FP64_NONE) {
+        if (p.i8) i8_window(e, q, p, 0);
+        fp64_window(e, q, p, 0);
+    }
+    const int rc = vote_and_wait(e, q);
+    if (rc != HAF_OK) return rc;
+    return finish_exact_tiers(e, q, p);
+}
+
+// probability-output mode: every evaluation through the strict tier (libsvm's own order), then svm_predict_probability,
+// the output lines as show_predicted_gps reads them, the fp32 vote (prob.hip)
+static int decide_probability(haf_engine *e, Request &q)
+{
+    const hipStream_t s = q.s;
+    const Dims &d = q.d;
+    mark(e, HAF_ST_FEATURES); mark(e, HAF_ST_SVM); mark(e, HAF_ST_REFINE); mark(e, HAF_ST_RECHECK);
+    launch_prob_list(e->d_counters.p, CNT_FLAGGED2, e->d_flag2_list.p, e->list_cap, s);
+    launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p, e->list_cap,
+                   e->d_counters.p, CNT_FLAGGED2, e->d_dec_exact2.p, e->d_labels.p, d, s);
+    // the estimates; those a last-bit exp difference could move come back as a list and are finished on the host (round 4)
+    launch_probability_eval(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_own.p, e->d_ptext.p,
+                            e->d_flag_list.p, e->list_cap, e->d_counters.p, q.evals_cap, s);
+    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    const int rc = host_resolve_probability(e, d, s, &q.host_resolved);
+    if (rc != HAF_OK) return rc;
+    mark(e, HAF_ST_VOTE);
+    launch_probability(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_mask.p, e->d_rowcount.p,
+                       e->d_brcount.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_own.p, e->d_ptext.p, e->d_gridf.p,
+                       e->d_evf.p, e->d_rec.p, q.evals_cap, d, s);
+    mark(e, HAF_ST_DOWNLOAD);
+    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));
+    mark(e, HAF_ST_COUNT);
+    HIPCHK(e, hipStreamSynchronize(s));
+    HIPCHK(e, hipGetLastError());
+    return HAF_OK;
+}
+
+// the next form of the screening pass to try when the one in use leaves too much undecided: PLAIN -> SUMSQ (the same operand
+// images: only the decision stage is redone) -> CR_EXP -> CR_POLY (their own images) -> none
+static int next_variant(const haf_engine *e, int v)
+{
+    if (v == SCREEN_PLAIN) return SCREEN_SUMSQ;
+    if (v == SCREEN_SUMSQ && e->cr_available) return SCREEN_CR_EXP;
+    if (v == SCREEN_CR_EXP) return SCREEN_CR_POLY;
+    return -1;
+}
+
+// The adaptive choice of the screening form, behind a request that ran the screening pass (*mode: MODE_SPLIT when this request's
+// labels came from the three-pass fallback)
+static int adapt_screen_form(haf_engine *e, Request &q, int *mode, bool reprobe)
+{
+    auto undecided = [&]() { return e->h_counters[CNT_FLAGGED0]; };
+    const int ne = e->h_counters[CNT_EVALS];
+    // More undecided evaluations than the refinement list holds: this pass's labels are incomplete.  Remedy: the next form, and
+    // stay with it; when none is left (or the variant is pinned by a test), the three-pass kernel for every evaluation of
+    // this call (same labels by construction) -- and, unless pinned, no screening pass for this model from now on.
+    if (undecided() > e->flag0_cap) e->stat_flag0_overflows++;
+    while (undecided() > e->flag0_cap && !e->variant_forced && next_variant(e, e->screen_variant) >= 0) {
+        const bool reuse = e->screen_variant == SCREEN_PLAIN && !q.t0b_used && !q.lr_used;     // (tier 0b writes its bands where the first pass's were; the low-rank form's images are the centred ones)
+        e->screen_variant = next_variant(e, e->screen_variant);
+        HIPCHK(e, hipMemsetAsync(e->d_counters.p + 1, 0, (CNT_COUNT - 1) * sizeof(int), q.s));
+        const int rc = decide(e, q, MODE_SCREEN, reuse);
         if (rc != HAF_OK) return rc;
-        bool strict_ran = false;
-        e->last_host_resolved = 0;
-        const int flagged = e->h_counters[CNT_FLAGGED];
-        const bool lists_valid = !direct && !(mode == MODE_SCREEN && e->h_counters[CNT_FLAGGED0] > e->flag0_cap);
-        const bool more_i8 = lists_valid && i8 && flagged > e->flag_cap;
-        const bool more_fp64 = lists_valid && (i8 ? e->h_counters[CNT_FLAGGEDI] > e->flag_cap : flagged > e->flag_cap);
-        if (more_i8 || more_fp64) {
-            // More evaluations inside a guard band than one window of an exact tier holds (an ill-conditioned model): the
-            // reference never fails a goal on this path (server.cpp:778-796), so neither does the engine -- the remaining
-            // windows of the lists go through the same kernels one after the other, then the strict tier over its whole list,
-            // then the vote again.  Slower, same labels.
-            int done_fp64 = e->flag_cap;                  // entries of its list the fp64 tier has seen (window 0)
-            if (more_i8) {
-                for (int off = e->flag_cap; off < flagged; off += e->flag_cap) { i8_window(off); e->stat_extra_windows++; }
-                // the fp64 tier's list has grown behind its first window: all of it again from the start (its results and the
-                // strict tier's list are rebuilt; both are idempotent)
-                HIPCHK(e, hipMemsetAsync(e->d_counters.p + CNT_FLAGGED2, 0, sizeof(int), s));
-                HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
-                HIPCHK(e, hipStreamSynchronize(s));
-                done_fp64 = 0;
+    }
+    if (undecided() > e->flag0_cap) {
+        if (!e->variant_forced) e->screen_active = false;
+        *mode = MODE_SPLIT;
+        HIPCHK(e, hipMemsetAsync(e->d_counters.p + 1, 0, (CNT_COUNT - 1) * sizeof(int), q.s));
+        return decide(e, q, MODE_SPLIT, false);
+    }
+    if (reprobe) {
+        const double share = ne > 0 ? (double)undecided() / (double)ne : 1.0;
+        e->variant_share[e->screen_variant] = share;
+        if (ne >= 256 && share <= 0.6) e->screen_active = true;
+    } else if (ne >= 256 && !e->variant_forced && !e->variant_settled) {
+        // Adaptive rule on real requests (an engine that was not calibrated, or whose calibration scene misjudged the model): a form
+        // that leaves more than a quarter undecided makes room for the next untried one; when all have been seen the engine
+        // settles on the one with the lowest cost -- or on none, if even that one leaves more than 60 %.
+        const double share = (double)undecided() / (double)ne;
+        e->variant_share[e->screen_variant] = share;
+        if (share > 0.25) {
+            int nv = next_variant(e, e->screen_variant);
+            while (nv >= 0 && e->variant_share[nv] >= 0.0) nv = next_variant(e, nv);       // (already seen: at calibration or on a request)
+            if (nv >= 0) {
+                e->screen_variant = nv;
+            } else {
+                int best = e->screen_variant;
+                double best_cost = 1e30;
+                for (int v = 0; v < SCREEN_VARIANTS; v++) {
+                    if (e->variant_share[v] < 0.0) continue;
+                    const double cost = variant_cost(e, v) + kUndecidedCost * e->variant_share[v];
+                    if (cost < best_cost) { best_cost = cost; best = v; }
+                }
+                e->screen_variant = best;
+                e->variant_settled = true;
+                if (e->variant_share[best] > 0.6) e->screen_active = false;
             }
-            const int n_fp64 = i8 ? e->h_counters[CNT_FLAGGEDI] : flagged;
-            for (int off = done_fp64; off < n_fp64; off += e->flag_cap) { fp64_window(off); e->stat_extra_windows++; }
-            launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p, e->list_cap,
-                           e->d_counters.p, CNT_FLAGGED2, e->d_dec_exact2.p, e->d_labels.p, d, s);
-            rc = vote();
-            if (rc != HAF_OK) return rc;
-            strict_ran = e->h_counters[CNT_FLAGGED2] > 0;
-        } else if (e->generic_kernel) {
-            strict_ran = true;                            // (it has run, on everything; what is left is the C library's tanh near zero)
-        } else if (e->h_counters[CNT_FLAGGED2] > 0) {
-            // (the host knows the list's length here: the spread form of the tier, recheck.hip)
-            launch_recheck_known(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p,
-                                 std::min(e->h_counters[CNT_FLAGGED2], e->list_cap), e->d_strict_terms.p, kStrictSlots, e->d_dec_exact2.p, e->d_labels.p, d, s);
-            rc = vote();
-            if (rc != HAF_OK) return rc;
-            strict_ran = true;
         }
-        if (strict_ran) {
-            // what the strict tier left within a last-bit exp error of zero: glibc's exp on the host, then the vote once more
-            bool changed = false;
-            rc = host_resolve_strict(e, d, s, &changed);
-            if (rc != HAF_OK) return rc;
-            if (changed) { rc = vote(); if (rc != HAF_OK) return rc; }
-        }
-        return HAF_OK;
-    };
-    // probability-output mode: every evaluation through the strict tier (libsvm's own order), then svm_predict_probability,
-    // the output lines as show_predicted_gps reads them, the fp32 vote (prob.hip)
-    auto decide_probability = [&]() -> int {
-        mark(e, HAF_ST_FEATURES); mark(e, HAF_ST_SVM); mark(e, HAF_ST_REFINE); mark(e, HAF_ST_RECHECK);
-        launch_prob_list(e->d_counters.p, CNT_FLAGGED2, e->d_flag2_list.p, e->list_cap, s);
-        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p, e->list_cap,
-                       e->d_counters.p, CNT_FLAGGED2, e->d_dec_exact2.p, e->d_labels.p, d, s);
-        // the estimates; those a last-bit exp difference could move come back as a list and are finished on the host (round 4)
-        launch_probability_eval(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_own.p, e->d_ptext.p,
-                                e->d_flag_list.p, e->list_cap, e->d_counters.p, evals_cap, s);
-        HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-        if (e->h_counters[CNT_FLAGGED] > 0) {
-            const int rc = host_resolve_probability(e, d, s);
-            if (rc != HAF_OK) return rc;
-        } else {
-            e->last_host_resolved = 0;
-        }
-        mark(e, HAF_ST_VOTE);
-        launch_probability(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_mask.p, e->d_rowcount.p,
-                           e->d_brcount.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_own.p, e->d_ptext.p, e->d_gridf.p,
-                           e->d_evf.p, e->d_rec.p, evals_cap, d, s);
-        mark(e, HAF_ST_DOWNLOAD);
-        HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)B * R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));
-        mark(e, HAF_ST_COUNT);
-        HIPCHK(e, hipStreamSynchronize(s));
-        HIPCHK(e, hipGetLastError());
-        return HAF_OK;
-    };
-    int mode = contraction_mode(c);
+    }
+    return HAF_OK;
+}
+
+static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact_grids, int roll_first, const haf_grasp_input *in,
+                          haf_roll_record *records)
+{
+    if (e->cfg.flags & HAF_FLAG_PROFILE)
+        for (int i = 0; i < HAF_ST_COUNT; i++) (void)hipEventElapsedTime(&e->stage_ms[i], e->ev[i], e->ev[i + 1]);
+    const int *h = e->h_counters;
+    LastCall &l = e->last;
+    l.B = q.B; l.R = q.R; l.roll_first = roll_first;
+    l.evals = h[CNT_EVALS];
+    l.flagged = e->prob_mode ? 0 : h[CNT_FLAGGED];      // (probability mode: the counter holds the estimates the host finished)
+    l.flagged2 = h[CNT_FLAGGED2];
+    l.lr = q.lr_used;
+    l.flagged0 = q.t0b_used ? std::min(h[CNT_FLAGGED0B], h[CNT_FLAGGED0]) : h[CNT_FLAGGED0];   // what leaves the screening passes
+    l.flaggedi = q.i8_used ? h[CNT_FLAGGEDI] : h[CNT_FLAGGED];
+    l.bypass = h[CNT_BYPASS];                            // (the short-list gate: entries that went around tier 1 and the exact-integer tier)
+    l.inexact = inexact_grids;
+    l.screened = (mode == MODE_SCREEN) && !e->prob_mode && !q.direct && h[CNT_FLAGGED0] <= e->flag0_cap;
+    l.host_resolved = q.host_resolved;
+    l.i8 = q.i8_used;
+    l.inputs.assign(in, in + q.B);
+    // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
+    if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), q.s) == hipSuccess) e->counters_clean = true;
+    // (the tier lists hold every evaluation of a request: list_cap >= last.evals >= last.flagged >= last.flagged2)
+    if (l.flagged > e->list_cap || l.flagged2 > e->list_cap || l.flaggedi > e->list_cap) return fail(e, HAF_E_INTERNAL, "recheck list counters exceed the number of evaluations");
+#ifdef HAF_TESTING
+    // testing build, HAF_CANARY_CHECK set (opt-in: engine_state.h): the guard zones around every device buffer after EVERY request
+    if (test_env("HAF_CANARY_CHECK")) {
+        std::string rep;
+        const int bad = canary_check(&rep);
+        if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
+    }
+#endif
+    for (int i = 0; i < q.B * q.R; i++) {
+        records[i].vote = e->h_rec[i].vote;
+        records[i].row = e->h_rec[i].row;
+        records[i].col = e->h_rec[i].col;
+        records[i].h_locmax = e->h_rec[i].h_locmax;
+        records[i].n_evals = e->h_rec[i].n_evals;
+    }
+    return HAF_OK;
+}
+
+int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
+                     int32_t roll_count, haf_roll_record *records)
+{
+    if (!e) return HAF_E_ARG;
+    Request q;
+    int rc = check_request(e, n_clouds, clouds, in, roll_first, roll_count, records, q);
+    if (rc != HAF_OK) return rc;
+    pack_headers(e, clouds, in, roll_first, q);
+    q.s = e->stream;
+    mark(e, 0);
+    if ((rc = upload_clouds(e, clouds, q)) != HAF_OK) return rc;
+    classify_request(e, in, q);
+    if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
+    int mode = contraction_mode(e->cfg);
     bool reprobe = false;
     if (mode == MODE_SCREEN && !e->screen_active) {
         // (the switch-off used to be for the engine's lifetime) every reprobe_every-th request that is large enough to judge by
         // runs the screening pass again; it costs that request one wasted pass at worst
-        if (!e->variant_forced && !e->prob_mode && !direct && evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
+        if (!e->variant_forced && !e->prob_mode && !q.direct && q.evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
             e->inactive_calls = 0;
             reprobe = true;
         } else {
             mode = MODE_SPLIT;
         }
     }
-    int rc = e->prob_mode ? decide_probability() : decide(mode, false);
+    rc = e->prob_mode ? decide_probability(e, q) : decide(e, q, mode, false);
     if (rc != HAF_OK) return rc;
     if (e->h_counters[CNT_ERROR] != 0 && !e->no_bucket_sort) {
         // a tile of k_bin_tiles had more candidate buckets than its list holds (never observed; the bound is geometric): the
@@ -622,101 +846,8 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
-    if (mode == MODE_SCREEN && !e->prob_mode && !direct) {
-        auto undecided = [&]() { return e->h_counters[CNT_FLAGGED0]; };
-        const int ne = e->h_counters[CNT_EVALS];
-        // the next form of the screening pass to try when the one in use leaves too much undecided: PLAIN -> SUMSQ (the same operand
-        // images: only the decision stage is redone) -> CR_EXP -> CR_POLY (their own images) -> none
-        auto next_variant = [&](int v) {
-            if (v == SCREEN_PLAIN) return (int)SCREEN_SUMSQ;
-            if (v == SCREEN_SUMSQ && e->cr_available) return (int)SCREEN_CR_EXP;
-            if (v == SCREEN_CR_EXP) return (int)SCREEN_CR_POLY;
-            return -1;
-        };
-        // More undecided evaluations than the refinement list holds: this pass's labels are incomplete.  Remedy: the next form, and
-        // stay with it; when none is left (or the variant is pinned by a test), the three-pass kernel for every evaluation of
-        // this call (same labels by construction) -- and, unless pinned, no screening pass for this model from now on.
-        if (undecided() > e->flag0_cap) e->stat_flag0_overflows++;
-        while (undecided() > e->flag0_cap && !e->variant_forced && next_variant(e->screen_variant) >= 0) {
-            const bool reuse = e->screen_variant == SCREEN_PLAIN && !t0b_used && !lr_used;     // (tier 0b writes its bands where the first pass's were; the low-rank form's images are the centred ones)
-            t0b_used = false;
-            e->screen_variant = next_variant(e->screen_variant);
-            HIPCHK(e, hipMemsetAsync(e->d_counters.p + 1, 0, (CNT_COUNT - 1) * sizeof(int), s));
-            rc = decide(MODE_SCREEN, reuse);
-            if (rc != HAF_OK) return rc;
-        }
-        if (undecided() > e->flag0_cap) {
-            if (!e->variant_forced) e->screen_active = false;
-            mode = MODE_SPLIT;
-            HIPCHK(e, hipMemsetAsync(e->d_counters.p + 1, 0, (CNT_COUNT - 1) * sizeof(int), s));
-            rc = decide(MODE_SPLIT, false);
-            if (rc != HAF_OK) return rc;
-        } else if (reprobe) {
-            const double share = ne > 0 ? (double)undecided() / (double)ne : 1.0;
-            e->variant_share[e->screen_variant] = share;
-            if (ne >= 256 && share <= 0.6) e->screen_active = true;
-        } else if (ne >= 256 && !e->variant_forced && !e->variant_settled) {
-            // Adaptive rule on real requests (an engine that was not calibrated, or whose calibration scene misjudged the model): a form
-            // that leaves more than a quarter undecided makes room for the next untried one; when all have been seen the engine
-            // settles on the one with the lowest cost -- or on none, if even that one leaves more than 60 %.
-            const double share = (double)undecided() / (double)ne;
-            e->variant_share[e->screen_variant] = share;
-            if (share > 0.25) {
-                int nv = next_variant(e->screen_variant);
-                while (nv >= 0 && e->variant_share[nv] >= 0.0) nv = next_variant(nv);       // (already seen: at calibration or on a request)
-                if (nv >= 0) {
-                    e->screen_variant = nv;
-                } else {
-                    int best = e->screen_variant;
-                    double best_cost = 1e30;
-                    for (int v = 0; v < SCREEN_VARIANTS; v++) {
-                        if (e->variant_share[v] < 0.0) continue;
-                        const double cost = variant_cost(e, v) + kUndecidedCost * e->variant_share[v];
-                        if (cost < best_cost) { best_cost = cost; best = v; }
-                    }
-                    e->screen_variant = best;
-                    e->variant_settled = true;
-                    if (e->variant_share[best] > 0.6) e->screen_active = false;
-                }
-            }
-        }
-    }
-
-    if (c.flags & HAF_FLAG_PROFILE)
-        for (int i = 0; i < HAF_ST_COUNT; i++) (void)hipEventElapsedTime(&e->stage_ms[i], e->ev[i], e->ev[i + 1]);
-
-    e->last_B = B; e->last_R = R; e->last_roll_first = roll_first;
-    e->last_evals = e->h_counters[CNT_EVALS];
-    e->last_flagged = e->prob_mode ? 0 : e->h_counters[CNT_FLAGGED];      // (probability mode: the counter holds the estimates the host finished)
-    e->last_flagged2 = e->h_counters[CNT_FLAGGED2];
-    e->last_lr = lr_used;
-    e->last_flagged0 = t0b_used ? std::min(e->h_counters[CNT_FLAGGED0B], e->h_counters[CNT_FLAGGED0]) : e->h_counters[CNT_FLAGGED0];   // what leaves the screening passes
-    e->last_flaggedi = i8_used ? e->h_counters[CNT_FLAGGEDI] : e->h_counters[CNT_FLAGGED];
-    e->last_bypass = e->h_counters[CNT_BYPASS];                            // (the short-list gate: entries that went around tier 1 and the exact-integer tier)
-    e->last_inexact = inexact_grids;
-    e->last_screened = (mode == MODE_SCREEN) && !e->prob_mode && !direct && e->h_counters[CNT_FLAGGED0] <= e->flag0_cap;
-    // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
-    if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), s) == hipSuccess) e->counters_clean = true;
-    e->last_inputs.assign(in, in + B);
-    // (the tier lists hold every evaluation of a request: list_cap >= last_evals >= last_flagged >= last_flagged2)
-    if (e->last_flagged > e->list_cap || e->last_flagged2 > e->list_cap || e->last_flaggedi > e->list_cap) return fail(e, HAF_E_INTERNAL, "recheck list counters exceed the number of evaluations");
-    e->last_i8 = i8_used;
-#ifdef HAF_TESTING
-    // testing build, HAF_CANARY_CHECK set (tests/conftest.py): the guard zones around every device buffer after EVERY request
-    if (test_env("HAF_CANARY_CHECK")) {
-        std::string rep;
-        const int bad = canary_check(&rep);
-        if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
-    }
-#endif
-    for (int i = 0; i < B * R; i++) {
-        records[i].vote = e->h_rec[i].vote;
-        records[i].row = e->h_rec[i].row;
-        records[i].col = e->h_rec[i].col;
-        records[i].h_locmax = e->h_rec[i].h_locmax;
-        records[i].n_evals = e->h_rec[i].n_evals;
-    }
-    return HAF_OK;
+    if (mode == MODE_SCREEN && !e->prob_mode && !q.direct && (rc = adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
+    return record_outcome(e, q, mode, inexact_grids, roll_first, in, records);
 }
 
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out)
@@ -729,21 +860,17 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     bool none_runs = in != nullptr && clouds != nullptr && n_clouds >= 1 && n_clouds <= e->cfg.max_clouds;
     for (int b = 0; none_runs && b < n_clouds; b++) none_runs = (int)in[b].max_calculation_time < 0;
     int rc = HAF_OK;
-    if (none_runs) {
-        e->last_B = e->last_R = e->last_roll_first = 0;
-        e->last_evals = e->last_flagged = e->last_flagged2 = e->last_flagged0 = e->last_flaggedi = e->last_inexact = e->last_host_resolved = 0;
-        e->last_bypass = 0;
-        e->last_i8 = e->last_screened = false;
-    } else {
+    if (none_runs)
+        e->last = LastCall{};
+    else
         rc = haf_score_rolls(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data());
-    }
     if (rc != HAF_OK) return rc;
     for (int b = 0; b < n_clouds; b++) {
         rc = haf_finalize(e, &in[b], rec.data() + (size_t)b * e->cfg.n_rolls, &out[b]);
         if (rc != HAF_OK) return rc;
     }
     // rechecks are counted per batch; attribute them to the first cloud's output and leave the others at 0
-    out[0].n_rechecked = e->last_flagged + (e->last_i8 ? e->last_bypass : 0);
+    out[0].n_rechecked = e->last.flagged + (e->last.i8 ? e->last.bypass : 0);
     return HAF_OK;
 }
 

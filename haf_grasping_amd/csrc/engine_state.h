@@ -66,7 +66,8 @@ bool invert(const Mat4 &m, Mat4 &inv);
 // the buffer's last byte to the next multiple of kCanaryGuard plus kCanaryGuard behind -- and is registered with the source line that
 // allocated it (engine_testing.cpp: canary_check).  A kernel that writes one element past a list, an operand image or a flag-word
 // array changes a guard byte; read as a list entry the pattern is a NEGATIVE evaluation id (0xA5A5A5A5), which no consumer may follow.
-// The tests check the zones after every request (HAF_CANARY_CHECK=1 in tests/conftest.py; haf_test_check_canaries).  The product
+// The check is opt-in: with HAF_CANARY_CHECK set the engine checks the zones after every request (the tests that drive the lists into
+// their capacities set it; `HAF_CANARY_CHECK=1 pytest -m gpu` runs the whole suite so), haf_test_check_canaries on demand.  The product
 // library allocates exactly what is asked for.
 #ifdef HAF_TESTING
 constexpr size_t kCanaryGuard = 256;
@@ -109,6 +110,24 @@ template <typename T> struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 #endif
+};
+
+// What the last scored call leaves for the getters (engine.cpp) and the debug reads (engine_debug.cpp, engine_testing.cpp).  A call
+// that scores nothing the caller asked for (the calibration requests, a batch whose every budget is negative) resets it: e->last = {}.
+struct LastCall {
+    int B = 0, R = 0, roll_first = 0;
+    int evals = 0;
+    int flagged0 = 0;            // what left the screening passes
+    int flagged = 0;             // what entered the exact tiers (the exact-integer tier's input list when i8)
+    int flaggedi = 0;            // evaluations that entered the fp64 MFMA tier
+    int bypass = 0;              // ... of them through the short-list gate (engine_request.cpp), around tier 1 and the exact-integer tier
+    int flagged2 = 0;            // the strict tier's list
+    int host_resolved = 0;       // strict-tier decisions made on the host with the C library's exp
+    int inexact = 0;             // (cloud, roll) grids whose integral image needed the sequential order
+    bool screened = false;       // the labels came through the screening tier (not its three-pass fallback)
+    bool lr = false;             // the screening pass ran in the low-rank form
+    bool i8 = false;             // tier 2a ran (then d_dec_exact holds ITS values and d_dec_exacti the fp64 tier's)
+    std::vector<haf_grasp_input> inputs;
 };
 
 }  // namespace haf_host
@@ -219,7 +238,6 @@ struct haf_engine {
     bool lr_fused = true;            // testing build: HAF_LR_UNFUSED = k_project + sweep as two launches
     DevBuf<unsigned long long> d_iiabs;   // per (cloud, roll): sum of |height| in units of 2^-20 m (k_integral_totals)
     LrBand lr_band{};
-    bool last_lr = false;            // the last request's screening pass ran in the low-rank form
     DevBuf<FeatDesc> d_fd_slot_cr;
     DevBuf<ScrDesc> d_sd_cr;
     DevBuf<ScrDesc3> d_sd3_cr;
@@ -238,10 +256,7 @@ struct haf_engine {
     DevBuf<double> d_dec_exacti;
     I8Params i8{};
     bool i8_active = false;
-    int last_flaggedi = 0;          // evaluations that entered the fp64 MFMA tier in the last call
-    int last_bypass = 0;            // ... of them through the short-list gate (engine_request.cpp), around tier 1 and the exact-integer tier
     bool short_gate = true;         // testing build: HAF_NO_SHORT_GATE switches the gate off
-    bool last_i8 = false;           // the last call ran tier 2a (then d_dec_exact holds ITS values and d_dec_exacti the fp64 tier's)
     DevBuf<short> d_ev16;
     DevBuf<float> d_margin;         // HAF_FLAG_KEEP_DEBUG, default mode: |dec^| / band of every evaluation the screening tier decided
     DevBuf<AttrRecord> d_attr;      // HAF_FLAG_KEEP_DEBUG: [max_evals][kKP] attribute records of the exact-form feature kernels
@@ -274,7 +289,6 @@ struct haf_engine {
     // strict tier: an evaluation whose libsvm-order decision value is within this of zero is decided on the HOST with glibc's exp
     // (the device's exp may differ from it in the last bit: 2^-52 per kernel value, i.e. at most 2^-52 sum|coef| in the sum)
     double host_exp_thr = 0.0;
-    int last_host_resolved = 0;
     bool calibrated = false;        // the screening variant was chosen at creation (calibrate())
     double mfma_kappa = 12.0;       // error of one v_mfma_f32_16x16x32_f16 in units of 2^-24 (|c| + sum|a b|): max(12, 1.5 x probe_mfma_rounding())
     double mfma_kappa16 = 12.0;     // the same for v_mfma_f32_16x16x16f16 (the K tail of the three-pass kernel)
@@ -287,11 +301,7 @@ struct haf_engine {
     // how often a request met a list smaller than what it had to hold (the overflow campaigns read them: haf_test_overflow_stats)
     long stat_flag0_overflows = 0;  // the screening passes left more undecided than their list holds: decision stage redone
     long stat_extra_windows = 0;    // windows of the exact tiers' lists beyond the first
-    // last call
-    int last_B = 0, last_R = 0, last_roll_first = 0;
-    int last_evals = 0, last_flagged = 0, last_flagged2 = 0, last_flagged0 = 0, last_inexact = 0;
-    bool last_screened = false;     // the last call's labels came through the screening tier (not its three-pass fallback)
-    std::vector<haf_grasp_input> last_inputs;
+    LastCall last;
 };
 
 namespace haf_host {
@@ -343,6 +353,52 @@ inline int contraction_mode(const haf_config &c)
     if (c.flags & HAF_FLAG_SPLIT_F16) return MODE_SPLIT;
     return MODE_SCREEN;
 }
+
+// ---- the routing of one decision stage (engine_request.cpp: plan_tiers) ----
+// The tier lists by name; each list's length lives in its own counter (list_counter), CNT_T1_N being the one re-count (what tier 1
+// reads as its list's length behind the short-list gate).  engine_request.cpp: list_buf maps a name to the engine's buffer.
+enum ListId { L_NONE = -1, L_FLAG0 = 0, L_FLAG0B, L_FLAG, L_FLAGI, L_FLAG2 };
+inline int list_counter(int l)
+{
+    static const int cnt[] = {CNT_FLAGGED0, CNT_FLAGGED0B, CNT_FLAGGED, CNT_FLAGGEDI, CNT_FLAGGED2};
+    return l == L_NONE ? -1 : cnt[l];
+}
+// what the routing depends on: the engine's state and the request's classification (tier_facts and haf_test_tier_plan fill it in
+// declaration order)
+struct TierFacts {
+    int screen_variant = SCREEN_PLAIN;
+    bool cr_available = false, lr_available = false, lr_enabled = false, lr_plain_available = false, lr_fused = false;
+    bool use_t0b = false, t1_skip = false, t1_cr_available = false, i8_active = false, calibrated = false, short_gate = false;
+    bool generic_kernel = false;
+    int n_sv = 0;
+    bool t0b_no_gather = false;      // testing build: HAF_T0B_NO_GATHER
+    int mode = MODE_SCREEN;
+    bool reuse_operands = false, direct = false, small_exact = false, large = false, fused_pre = false;
+    long hw = 0, evals_cap = 0;
+};
+enum { PATH_GENERIC, PATH_DIRECT, PATH_SCREEN, PATH_SPLIT, PATH_F32 };
+enum { SP_PLAIN, SP_CR, SP_LRP };               // ScreenParams set of the screening pass: screen / screen_cr / screen_lrp
+enum { T0B_NONE, T0B_GATHER, T0B_FEATURES };    // tier 0b: not run / the low-rank sweep's gather form / feature kernel + sweep
+enum { FP64_NONE, FP64_SMALL, FP64_MFMA };      // window 0 of the fp64 tier: none / k_small_direct in list mode / k_recheck_mfma
+// Which tiers run in which form, and for every producer the list it writes, for every consumer the list (and counter) it reads.
+// The stages run in this order: first pass, tier 0b, gate, tier 1, exact-integer tier, fp64 MFMA tier, strict tier.
+struct TierPlan {
+    int path = PATH_SCREEN;
+    int sp = SP_PLAIN;
+    bool cr = false, lr = false;     // the screening pass: centred-remainder form, low-rank form
+    bool reuse = false;              // ... on the previous pass's operand images (no feature kernel)
+    int pass0_out = L_NONE;          // the first pass: the screening pass, the contraction over every evaluation, the generic / direct tier
+    int t0b = T0B_NONE, t0b_in = L_NONE, t0b_out = L_NONE;
+    bool gate = false;
+    int gate_in = L_NONE, gate_out = L_NONE;
+    bool t1 = false, t1cr = false;
+    int t1_in = L_NONE, t1_cnt = -1, t1_out = L_NONE;
+    bool i8 = false;
+    int i8_in = L_NONE, i8_out = L_NONE;
+    int fp64 = FP64_NONE, fp64_in = L_NONE, fp64_out = L_NONE;
+    int strict_in = L_FLAG2;
+};
+TierPlan plan_tiers(const TierFacts &f);
 
 inline int fail(haf_engine *e, int code, const std::string &msg)
 {

@@ -86,11 +86,11 @@ int haf_test_fetch_list(haf_engine *e, int which, int *out, int cap, int *n)
     const int *src = nullptr;
     int cnt = 0;
     switch (which) {
-        case 0: src = e->d_evalcell.p; cnt = e->last_evals; break;
-        case 1: src = e->d_flag_list.p; cnt = std::min(e->last_flagged, e->list_cap); break;
-        case 2: src = e->d_flagi_list.p; cnt = e->last_i8 ? std::min(e->last_flaggedi, e->list_cap) : 0; break;
-        case 3: src = e->d_flag2_list.p; cnt = std::min(e->last_flagged2, e->list_cap); break;
-        case 4: src = e->d_flag0_list.p; cnt = std::min(e->last_flagged0, e->flag0_cap); break;
+        case 0: src = e->d_evalcell.p; cnt = e->last.evals; break;
+        case 1: src = e->d_flag_list.p; cnt = std::min(e->last.flagged, e->list_cap); break;
+        case 2: src = e->d_flagi_list.p; cnt = e->last.i8 ? std::min(e->last.flaggedi, e->list_cap) : 0; break;
+        case 3: src = e->d_flag2_list.p; cnt = std::min(e->last.flagged2, e->list_cap); break;
+        case 4: src = e->d_flag0_list.p; cnt = std::min(e->last.flagged0, e->flag0_cap); break;
         default: return HAF_E_ARG;
     }
     *n = cnt;
@@ -327,9 +327,34 @@ int haf_test_i8_mfma(const signed char *a, const signed char *b, int *c)
 int haf_test_screen_state(haf_engine *e, int *variant, int *active, double *shares /* [4] */)
 {
     if (!e) return HAF_E_ARG;
-    if (variant) *variant = e->screen_variant | (e->use_t0b ? 16 : 0) | (e->t1_skip ? 32 : 0) | (e->last_lr ? 64 : 0);
+    if (variant) *variant = e->screen_variant | (e->use_t0b ? 16 : 0) | (e->t1_skip ? 32 : 0) | (e->last.lr ? 64 : 0);
     if (active) *active = e->screen_active ? 1 : 0;
     if (shares) for (int i = 0; i < SCREEN_VARIANTS; i++) shares[i] = e->variant_share[i];
+    return HAF_OK;
+}
+
+// plan_tiers over `rows` sets of facts, each given as 23 integers (TierFacts in declaration order) -> each plan as 24 integers
+// (TierPlan in declaration order, booleans as 0 / 1); n_facts / n_plan: the row widths the caller assumes.  No device.
+int haf_test_tier_plan(const long long *facts, int n_facts, int *plan, int n_plan, int rows)
+{
+    if (!facts || !plan || n_facts != 23 || n_plan != 24 || rows < 0) return HAF_E_ARG;
+    for (int r = 0; r < rows; r++) {
+        const long long *x = facts + (size_t)r * 23;
+        TierFacts f;
+        f.screen_variant = (int)*x++;
+        for (bool *b : {&f.cr_available, &f.lr_available, &f.lr_enabled, &f.lr_plain_available, &f.lr_fused, &f.use_t0b, &f.t1_skip,
+                        &f.t1_cr_available, &f.i8_active, &f.calibrated, &f.short_gate, &f.generic_kernel}) *b = *x++ != 0;
+        f.n_sv = (int)*x++;
+        f.t0b_no_gather = *x++ != 0;
+        f.mode = (int)*x++;
+        for (bool *b : {&f.reuse_operands, &f.direct, &f.small_exact, &f.large, &f.fused_pre}) *b = *x++ != 0;
+        f.hw = (long)*x++;
+        f.evals_cap = (long)*x++;
+        const TierPlan p = plan_tiers(f);
+        const int out[24] = {p.path, p.sp, p.cr, p.lr, p.reuse, p.pass0_out, p.t0b, p.t0b_in, p.t0b_out, p.gate, p.gate_in, p.gate_out,
+                             p.t1, p.t1cr, p.t1_in, p.t1_cnt, p.t1_out, p.i8, p.i8_in, p.i8_out, p.fp64, p.fp64_in, p.fp64_out, p.strict_in};
+        memcpy(plan + (size_t)r * 24, out, sizeof out);
+    }
     return HAF_OK;
 }
 

@@ -623,3 +623,138 @@ def test_haf_attributes_span_158_dimensions(data_dir):
     sv = np.linalg.svd(A, compute_uv=False)
     assert int((sv > 1e-9 * sv[0]).sum()) == 158
     assert sv[157] / sv[0] > 1e-4 and sv[158] / sv[0] < 1e-12
+
+
+# ---- the routing of the decision tiers (csrc/engine_request.cpp: plan_tiers) ----
+PLAN_FACTS = ("screen_variant", "cr_available", "lr_available", "lr_enabled", "lr_plain_available", "lr_fused", "use_t0b", "t1_skip",
+              "t1_cr_available", "i8_active", "calibrated", "short_gate", "generic_kernel", "n_sv", "t0b_no_gather", "mode",
+              "reuse_operands", "direct", "small_exact", "large", "fused_pre", "hw", "evals_cap")
+PLAN_FIELDS = ("path", "sp", "cr", "lr", "reuse", "pass0_out", "t0b", "t0b_in", "t0b_out", "gate", "gate_in", "gate_out", "t1", "t1cr",
+               "t1_in", "t1_cnt", "t1_out", "i8", "i8_in", "i8_out", "fp64", "fp64_in", "fp64_out", "strict_in")
+PLAN_BOOLS = ("cr_available", "lr_available", "lr_enabled", "lr_plain_available", "lr_fused", "use_t0b", "t1_skip", "t1_cr_available",
+              "i8_active", "calibrated", "short_gate", "generic_kernel", "t0b_no_gather", "reuse_operands", "direct", "small_exact",
+              "large", "fused_pre")
+NONE, FLAG0, FLAG0B, FLAG, FLAGI, FLAG2 = -1, 0, 1, 2, 3, 4                   # ListId
+GENERIC, DIRECT, SCREEN, SPLIT, F32 = range(5)                                 # PATH_*
+SP_PLAIN, SP_CR, SP_LRP = range(3)
+T0B_NONE, T0B_GATHER, T0B_FEATURES = range(3)
+FP64_NONE, FP64_SMALL, FP64_MFMA = range(3)
+
+
+def _counters():
+    with open(os.path.join(ROOT, "haf_grasping_amd", "csrc", "kernels.h")) as f:
+        return {k: int(v) for k, v in re.findall(r"\b(CNT_[A-Z0-9_]+) = (\d+)", f.read())}
+
+
+def _plans(facts):
+    """facts: int64 [rows, 23] -> int32 [rows, 24] through haf_test_tier_plan"""
+    facts = np.ascontiguousarray(facts, dtype=np.int64)
+    out = np.zeros((facts.shape[0], len(PLAN_FIELDS)), np.int32)
+    assert capi.testlib().haf_test_tier_plan(facts.ctypes.data, len(PLAN_FACTS), out.ctypes.data, len(PLAN_FIELDS), facts.shape[0]) == 0
+    return out
+
+
+def _plan(**kw):
+    row = np.array([[kw[k] for k in PLAN_FACTS]], np.int64)
+    return dict(zip(PLAN_FIELDS, (int(v) for v in _plans(row)[0])))
+
+
+def test_tier_plan_wiring_over_the_fact_space():
+    """Every boolean fact exhaustively, with every screening form, every contraction mode and representative sizes: every list a planned
+    stage writes is read by a later planned stage, every list a planned stage reads was written by an earlier one (tier 1's count
+    included: its list's counter, or CNT_T1_N behind the short-list gate), and the gate writes the list the exact tiers read."""
+    cnt = _counters()
+    list_cnt = np.array([cnt["CNT_FLAGGED0"], cnt["CNT_FLAGGED0B"], cnt["CNT_FLAGGED"], cnt["CNT_FLAGGEDI"], cnt["CNT_FLAGGED2"]])
+    bits = np.arange(1 << len(PLAN_BOOLS), dtype=np.int64)
+    base = {k: (bits >> i) & 1 for i, k in enumerate(PLAN_BOOLS)}
+    rows = 0
+    for variant in range(4):
+        for mode in range(3):
+            for n_sv, hw, evals_cap in ((172, 56 * 56, 20 * 42 * 42), (4096, 56 * 56, 20 * 42 * 42), (8964, 512 * 512, 36 * 498 * 498),
+                                        (4096, 100 * 100, 65536), (2048, 96 * 96, 65537)):
+                cols = dict(base, screen_variant=variant, mode=mode, n_sv=n_sv, hw=hw, evals_cap=evals_cap)
+                f = np.stack([np.broadcast_to(np.asarray(cols[k], np.int64), bits.shape) for k in PLAN_FACTS], axis=1)
+                plans = _plans(f)
+                P = {k: plans[:, i] for i, k in enumerate(PLAN_FIELDS)}
+                rows += len(bits)
+                # the stages in launch order: (runs, list read, counter read, list written)
+                stages = [(np.ones_like(P["path"], bool), None, None, P["pass0_out"]),
+                          (P["t0b"] != T0B_NONE, P["t0b_in"], None, P["t0b_out"]),
+                          (P["gate"] == 1, P["gate_in"], None, P["gate_out"]),
+                          (P["t1"] == 1, P["t1_in"], P["t1_cnt"], P["t1_out"]),
+                          (P["i8"] == 1, P["i8_in"], None, P["i8_out"]),
+                          (P["fp64"] != FP64_NONE, P["fp64_in"], None, P["fp64_out"]),
+                          (np.ones_like(P["path"], bool), P["strict_in"], None, None)]
+                for j, (runs, rd, _, wr) in enumerate(stages):
+                    if wr is not None:
+                        assert ((wr >= FLAG0) | ~runs).all(), ("a running stage writes no list", j)
+                        read_later = np.zeros_like(runs)
+                        for runs2, rd2, _, _ in stages[j + 1:]:
+                            if rd2 is not None:
+                                read_later |= runs2 & (rd2 == wr)
+                        assert (read_later | ~runs).all(), ("nothing reads what stage %d writes" % j, f[~(read_later | ~runs)][:3])
+                    if rd is not None:
+                        assert ((rd >= FLAG0) | ~runs).all(), ("a running stage reads no list", j)
+                        written = np.zeros_like(runs)
+                        for runs0, _, _, wr0 in stages[:j]:
+                            if wr0 is not None:
+                                written |= runs0 & (wr0 == rd)
+                        assert (written | ~runs).all(), ("stage %d reads a list nothing wrote" % j, f[~(written | ~runs)][:3])
+                t1 = P["t1"] == 1
+                want_cnt = np.where(P["gate"] == 1, cnt["CNT_T1_N"], list_cnt[np.clip(P["t1_in"], 0, 4)])
+                assert (~t1 | (P["t1_cnt"] == want_cnt)).all()
+                assert ((P["gate"] == 0) | t1).all(), "the gate sits in front of tier 1"
+                # the gate's destination is the exact tiers' input: the exact-integer tier's output when it runs
+                g = P["gate"] == 1
+                assert (~g | (P["gate_out"] == P["fp64_in"])).all()
+                assert (~g | ((P["gate_out"] == FLAGI) == (P["i8"] == 1))).all()
+                fp = P["fp64"] != FP64_NONE
+                assert (~fp | (P["fp64_in"] == np.where(P["i8"] == 1, FLAGI, FLAG))).all()
+                # the generic and direct paths run no screening, tier or window of the exact tiers; every other path has window 0
+                gd = (cols["generic_kernel"] == 1) | (cols["direct"] == 1)
+                assert (P["path"][gd] <= DIRECT).all() and (P["fp64"][gd] == FP64_NONE).all() and (P["i8"][gd] == 0).all()
+                assert (P["fp64"][~gd] != FP64_NONE).all()
+    assert rows == 4 * 3 * 5 * (1 << len(PLAN_BOOLS))
+
+
+def test_tier_plan_pinned_cases():
+    """Concrete engines and requests with their whole plan, as the decision stage routes them."""
+    cnt = _counters()
+    eng = dict(cr_available=1, lr_available=1, lr_enabled=1, lr_plain_available=1, lr_fused=1, use_t0b=0, t1_skip=0, t1_cr_available=1,
+               i8_active=1, calibrated=1, short_gate=1, generic_kernel=0, t0b_no_gather=0, reuse_operands=0, direct=0, small_exact=0)
+    c5 = dict(eng, mode=0, large=1, fused_pre=0, hw=512 * 512, evals_cap=36 * 498 * 498)
+    c3 = dict(eng, mode=0, large=0, fused_pre=1, hw=56 * 56, evals_cap=20 * 42 * 42)
+    empty = dict(sp=SP_PLAIN, cr=0, lr=0, reuse=0, t0b=T0B_NONE, t0b_in=NONE, t0b_out=NONE, gate=0, gate_in=NONE, gate_out=NONE, t1=0, t1cr=0,
+                 t1_in=NONE, t1_cnt=-1, t1_out=NONE, i8=0, i8_in=NONE, i8_out=NONE, fp64=FP64_NONE, fp64_in=NONE, fp64_out=NONE, strict_in=FLAG2)
+    exact_i8 = dict(i8=1, i8_in=FLAG, i8_out=FLAGI, fp64=FP64_MFMA, fp64_in=FLAGI, fp64_out=FLAG2)
+    cases = {
+        # C5, the headline's seed-42 model as calibration leaves it: low-rank form with the plain epilogue, tier 0b in its gather form
+        # writing the exact tiers' list (tier 1 skipped), the exact-integer tier
+        "c5_seed42": (dict(c5, screen_variant=0, use_t0b=1, t1_skip=1, n_sv=4096),
+                      dict(empty, path=SCREEN, sp=SP_LRP, lr=1, pass0_out=FLAG0, t0b=T0B_GATHER, t0b_in=FLAG0, t0b_out=FLAG, **exact_i8)),
+        # ... with tier 1 kept (HAF_T1_SKIP=0): tier 0b hands its own list to tier 1
+        "c5_seed42_tier1": (dict(c5, screen_variant=0, use_t0b=1, n_sv=4096),
+                            dict(empty, path=SCREEN, sp=SP_LRP, lr=1, pass0_out=FLAG0, t0b=T0B_GATHER, t0b_in=FLAG0, t0b_out=FLAG0B,
+                                 t1=1, t1_in=FLAG0B, t1_cnt=cnt["CNT_FLAGGED0B"], t1_out=FLAG, **exact_i8)),
+        # the trained model: centred-remainder/poly (low-rank), tier 1 in the centred-remainder form, no exact-integer tier
+        "c5_trained": (dict(c5, screen_variant=3, n_sv=8964),
+                       dict(empty, path=SCREEN, sp=SP_CR, cr=1, lr=1, pass0_out=FLAG0, t1=1, t1cr=1, t1_in=FLAG0, t1_cnt=cnt["CNT_FLAGGED0"],
+                            t1_out=FLAG, fp64=FP64_MFMA, fp64_in=FLAG, fp64_out=FLAG2)),
+        # C3 against the 4 096-SV model: full-rank plain pass, tier 0b through the feature kernel, the short-list gate into the
+        # exact-integer tier's output list, tier 1 counting CNT_T1_N
+        "c3_4096": (dict(c3, screen_variant=0, use_t0b=1, n_sv=4096),
+                    dict(empty, path=SCREEN, sp=SP_PLAIN, pass0_out=FLAG0, t0b=T0B_FEATURES, t0b_in=FLAG0, t0b_out=FLAG0B,
+                         gate=1, gate_in=FLAG0B, gate_out=FLAGI, t1=1, t1_in=FLAG0B, t1_cnt=cnt["CNT_T1_N"], t1_out=FLAG, **exact_i8)),
+        # C3 against the surrogate (172 SVs): small_exact -- the screening pass writes the one-launch exact kernel's list
+        "c3_surrogate": (dict(c3, screen_variant=2, use_t0b=0, n_sv=172, small_exact=1),
+                         dict(empty, path=SCREEN, sp=SP_CR, cr=1, pass0_out=FLAG, fp64=FP64_SMALL, fp64_in=FLAG, fp64_out=FLAG2)),
+        # C2: the direct path
+        "c2": (dict(c3, screen_variant=2, n_sv=172, direct=1, evals_cap=12 * 42 * 42), dict(empty, path=DIRECT, pass0_out=FLAG2)),
+        # a model whose kernel is not RBF: libsvm's order for everything
+        "non_rbf": (dict(c5, screen_variant=0, n_sv=4096, generic_kernel=1, i8_active=0), dict(empty, path=GENERIC, pass0_out=FLAG2)),
+        # the split-fp16 mode on the same engine: the contraction over every evaluation writes the exact tiers' list
+        "c5_split": (dict(c5, screen_variant=0, use_t0b=1, n_sv=4096, mode=1),
+                     dict(empty, path=SPLIT, pass0_out=FLAG, **exact_i8)),
+    }
+    for name, (facts, want) in cases.items():
+        assert _plan(**facts) == want, name
