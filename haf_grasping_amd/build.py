@@ -19,9 +19,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhafgrasp.so")
 LIB_TESTING = os.path.join(HERE, "libhafgrasp_testing.so")
 # the engine's host side: every one of these is compiled twice, without and with -DHAF_TESTING (csrc/engine_state.h: test_env)
-ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp"]
+ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp"]
 TESTING_ONLY = ["engine_testing.cpp", "testkernels.hip"]         # libhafgrasp_testing.so only
-SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip"] + \
+SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip"] + \
           ENGINE_SOURCES + ["parsers.cpp", "multi.cpp"]
 # per-file extra flags (screen.hip: see its header)
 EXTRA = {"screen.hip": ["-fno-slp-vectorize"]}

@@ -46,6 +46,16 @@ class RollRecord(C.Structure):
                 ("n_evals", C.c_int32)]
 
 
+class TopParams(C.Structure):
+    """haf_top_params: ranked top-K candidates of the last scored batch (haf_top_grasps)"""
+    _fields_ = [("k", C.c_int32), ("min_vote", C.c_int32), ("cell_radius", C.c_int32), ("roll_window", C.c_int32),
+                ("min_dist_m", C.c_double)]
+
+
+class GraspCandidate(C.Structure):
+    _fields_ = [("grasp", GraspOutput), ("run_length", C.c_int32), ("h_locmax", C.c_float)]
+
+
 class Cloud(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("n_points", C.c_size_t), ("stride_floats", C.c_size_t), ("on_device", C.c_int32)]
 
@@ -91,6 +101,9 @@ def _bind(path, testing):
     L.haf_debug_fetch.argtypes = [E, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]
     L.haf_debug_fetch_attr.argtypes = [E, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_int32)]
+    L.haf_top_params_default.argtypes = [E, C.POINTER(TopParams)]
+    L.haf_top_params_default.restype = None
+    L.haf_top_grasps.argtypes = [E, C.POINTER(TopParams), C.c_void_p, C.c_void_p]
     L.haf_set_stream.argtypes = [E, C.c_void_p]
     L.haf_get_stream.restype = C.c_void_p
     L.haf_get_stream.argtypes = [E]
@@ -161,6 +174,8 @@ def _bind(path, testing):
         L.haf_test_overflow_stats.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_list.argtypes = [E, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.haf_test_top_merge.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int] + [C.c_void_p] * 5 + \
+            [C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return L
 
 
@@ -228,6 +243,23 @@ def output_to_dict(o):
                 averaged_grasp_point=tuple(o.averaged_grasp_point), approach_vector=tuple(o.approach_vector),
                 roll=o.roll, best_row=o.best_row, best_col=o.best_col, best_roll=o.best_roll, best_vote=o.best_vote,
                 rolls_done=o.rolls_done, n_evals=o.n_evals, n_rechecked=o.n_rechecked)
+
+
+def top_params(engine_handle=None, **kw):
+    """haf_top_params_default (min_vote from the engine's graspval_th; haf_config_default's without an engine) with kw overrides"""
+    p = TopParams()
+    lib().haf_top_params_default(engine_handle, C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_top_params field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def candidate_to_dict(c):
+    d = output_to_dict(c.grasp)
+    d.update(run_length=c.run_length, h_locmax=c.h_locmax)
+    return d
 
 
 def load_pcd(path):
@@ -378,6 +410,16 @@ class Engine:
         out, pub = GraspOutput(), C.c_int32()
         self._check(self._L.haf_roll_pose(self._h, C.byref(grasp_input), rec.ctypes.data, roll, C.byref(out), C.byref(pub)))
         return output_to_dict(out), bool(pub.value)
+
+    def top_grasps(self, **params):
+        """haf_top_grasps: ranked, suppressed candidates of the last scored batch -> one list of candidate dicts per cloud
+        (output_to_dict fields + run_length, h_locmax).  params: k, min_vote, cell_radius, roll_window, min_dist_m."""
+        p = top_params(self._h, **params)
+        cap = max(1, self.cfg.max_clouds)
+        out = (GraspCandidate * (cap * min(1024, max(1, p.k))))()
+        n = (C.c_int32 * cap)(*([-1] * cap))          # the call fills one entry per cloud of the last batch
+        self._check(self._L.haf_top_grasps(self._h, C.byref(p), out, n))
+        return [[candidate_to_dict(out[b * p.k + i]) for i in range(n[b])] for b in range(cap) if n[b] >= 0]
 
     def debug_attr(self, cloud, roll):
         """Attribute records of the masked cells of (cloud, roll): cells [n, 2], records [n, 324], computed [n]."""

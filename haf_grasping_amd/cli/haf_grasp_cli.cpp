@@ -16,6 +16,8 @@
 //   --shards-per-gpu K                K shards on every GPU (they share its RCCL rank)
 //   --probability                     svm_with_probability: "svm-predict -b 1" output as show_predicted_gps reads it (model with probA/probB)
 //   --hypotheses                      also print the per-roll hypotheses the server publishes when show_only_best is off
+//   --top-k N                         after the normal output, "top <rank> <hypothesis>" for the N best distinct candidates of the
+//                                     goal (haf_top_grasps); --top-radius cells, --top-rolls steps, --top-dist metres set its suppression
 //                                     (server.cpp:962-969), in its string format
 #include "../../include/hafgrasp.h"
 
@@ -86,6 +88,7 @@ static void usage()
             "usage: haf_grasp_cli --features F --range R --model M [options] cloud.pcd [cloud2.pcd ...]\n"
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
+            "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -97,6 +100,8 @@ int main(int argc, char **argv)
     haf_grasp_input_default(&in);
     double sx = 18, sy = 30;                       // launch defaults (launch/haf_grasping_all.launch:25-65)
     bool per_roll = false, hypotheses = false;
+    int top_k = 0, top_radius = -1, top_rolls = -1;       // --top-k: ranked candidates (haf_top_grasps); -1: the library's default
+    double top_dist = -1.0;
     std::string grid_out;                          // --grid-out FILE: the per-roll grasp grid the shim's callback delivers (979-1016)
     int gpus = 0, shards_per_gpu = 1;
     std::string shard = "rolls";
@@ -121,6 +126,10 @@ int main(int argc, char **argv)
         else if (a == "--per-roll") per_roll = true;
         else if (a == "--hypotheses") hypotheses = true;
         else if (a == "--grid-out") { need(1); grid_out = argv[++i]; }
+        else if (a == "--top-k") { need(1); top_k = atoi(argv[++i]); }
+        else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
+        else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }
+        else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
         else if (a == "--probability") cfg.flags |= HAF_FLAG_PROBABILITY;     // svm_with_probability (server.cpp:383, 791, 831-841)
         else if (a == "--gpus") { need(1); gpus = atoi(argv[++i]); }
         else if (a == "--shard") { need(1); shard = argv[++i]; }
@@ -178,6 +187,20 @@ int main(int argc, char **argv)
             if (hypotheses) printf("hypothesis %s\n", lines[l].c_str());
         printf("%s\n", lines.back().c_str());
         (void)res;
+        if (top_k > 0) {
+            haf_top_params tp;
+            haf_top_params_default(eng, &tp);
+            tp.k = top_k;
+            if (top_radius >= 0) tp.cell_radius = top_radius;
+            if (top_rolls >= 0) tp.roll_window = top_rolls;
+            if (top_dist >= 0.0) tp.min_dist_m = top_dist;
+            std::vector<std::string> top;
+            if (hafshim::top_hypotheses(eng, cfg, tp, &top, &serr) != HAF_OK) {
+                fprintf(stderr, "%s: %s\n", argv[i], serr.c_str());
+                rc = 1;
+            }
+            for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
+        }
         fprintf(stderr, "%s: %zu points, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", argv[i], n,
                 (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
         if (per_roll) {

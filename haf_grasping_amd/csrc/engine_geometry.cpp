@@ -209,4 +209,17 @@ int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_rol
     return pose_impl(c, in, r, roll, roll, out, error);
 }
 
+// one ranked candidate of haf_top_grasps (engine_topgrasps.cpp): the pose haf_roll_pose computes for the candidate's record at its roll,
+// with eval = vote - 20 (server.cpp:390) instead of the per-roll hypothesis's clamped value
+int candidate_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record &r, int roll, haf_grasp_output *out,
+                        std::string &error)
+{
+    memset(out, 0, sizeof *out);
+    out->eval = r.vote - 20;
+    out->best_row = r.row; out->best_col = r.col; out->best_roll = roll; out->best_vote = r.vote;
+    out->rolls_done = roll + 1;
+    out->n_evals = r.n_evals;
+    return pose_impl(c, in, r, roll, roll, out, error);
+}
+
 }  // namespace haf_host

@@ -4,6 +4,7 @@
 //   engine_request.cpp   one request: stage launches, decision tiers, host resolution of the residual cases, the batch wrapper
 //   engine_geometry.cpp  per-roll transforms, the rotated-rectangle scalars, the final grasp pose (host fp32, glibc)
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
+//   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every translation unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
@@ -302,6 +303,12 @@ struct haf_engine {
     long stat_flag0_overflows = 0;  // the screening passes left more undecided than their list holds: decision stage redone
     long stat_extra_windows = 0;    // windows of the exact tiers' lists beyond the first
     LastCall last;
+    // haf_top_grasps (engine_topgrasps.cpp), allocated on its first call: run-list scratch of its slots, the output block
+    // [hdr: 4 ints per (cloud, roll)][TopCandDev x depth per (cloud, roll)] and its pinned host copy
+    DevBuf<unsigned long long> d_top_scratch;
+    DevBuf<char> d_top_out;
+    char *h_top_out = nullptr;
+    size_t h_top_cap = 0;
 };
 
 namespace haf_host {
@@ -440,5 +447,17 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,
                    int32_t *published, std::string &error);
+int candidate_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record &r, int roll, haf_grasp_output *out,
+                        std::string &error);
+// engine_topgrasps.cpp: steps 4-6 of haf_top_grasps over one cloud's per-roll greedy sequences (lists in ascending roll order)
+struct TopList {
+    int roll = 0;                     // global roll index
+    int n = 0;                        // entries of the sequence present
+    bool more = false;                // the sequence may go on beyond them
+    const haf_roll_record *rec = nullptr;   // n records {vote, row, col, h_locmax, n_evals of the roll}
+    const int32_t *len = nullptr;     // n run lengths
+};
+int top_merge(const haf_config &c, const haf_grasp_input *in, const std::vector<TopList> &lists, int k, int roll_window, double min_dist_m,
+              haf_grasp_candidate *out, int32_t *n_found, bool *need_more, std::string &error);
 
 }  // namespace haf_host

@@ -191,6 +191,31 @@ int haf_test_roll_pose(const haf_config *cfg, const haf_grasp_input *in, const h
     return roll_pose_impl(*cfg, in, rec, roll, out, published, err);
 }
 
+// steps 4-6 of haf_top_grasps without a device: n_lists per-roll greedy sequences (ascending roll order), list i holding n_cand[i]
+// records (concatenated in rec / run_len) of global roll roll[i], more[i] = its sequence may go on.  *need_more = 1: a list ran out while
+// its sequence may go on (haf_top_grasps redoes its device pass with a larger depth then; out is not final).
+int haf_test_top_merge(const haf_config *cfg, const haf_grasp_input *in, int n_lists, const int32_t *roll, const int32_t *n_cand,
+                       const int32_t *more, const haf_roll_record *rec, const int32_t *run_len, int k, int roll_window, double min_dist_m,
+                       haf_grasp_candidate *out, int32_t *n_found, int32_t *need_more)
+{
+    if (!cfg || !in || n_lists < 0 || k < 1 || !out || !n_found || !need_more) return HAF_E_ARG;
+    std::vector<TopList> lists((size_t)n_lists);
+    size_t at = 0;
+    for (int i = 0; i < n_lists; i++) {
+        lists[(size_t)i].roll = roll[i];
+        lists[(size_t)i].n = n_cand[i];
+        lists[(size_t)i].more = more[i] != 0;
+        lists[(size_t)i].rec = rec + at;
+        lists[(size_t)i].len = run_len + at;
+        at += (size_t)n_cand[i];
+    }
+    std::string err;
+    bool nm = false;
+    const int rc = top_merge(*cfg, in, lists, k, roll_window, min_dist_m, out, n_found, &nm, err);
+    *need_more = nm ? 1 : 0;
+    return rc;
+}
+
 // ---- test hooks (host and device builds of the decimal round-trip arithmetic; see tests/) ----
 double haf_test_decq_host(double x, int digits) { return digits == 40 ? hafq::decq4_float((float)x) : hafq::decq(x, digits); }
 double haf_test_scale_host(double q4, double fmin, double fmax, double lower, double upper)

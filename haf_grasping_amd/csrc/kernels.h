@@ -472,6 +472,12 @@ void launch_recheck_mfma(const float *ii, const int *evalcell, const FeatDesc *f
 constexpr int kRecheckPartRows = 2 * 8 + 1;       // part64: [2 * kMSplit + 1][flag_cap] doubles (partial sums + |x|^2)
 void launch_vote(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
                  int *rowmax, RollRecordDev *rec, Dims d, hipStream_t s);
+// ranked grasp candidates (topgrasps.hip, haf_top_grasps): per (cloud, roll) hdr[4] = {kept, the greedy sequence may go on, the roll's
+// n_evals, its top vote} and cand[D] = the first D entries of the roll's in-roll greedy sequence.  scratch: n_slots x 2 x slot_words
+// 64-bit words (slot_words >= H*W), one slot per workgroup
+struct TopCandDev { int vote; short row, col; int len; float h_locmax; };
+void launch_top_grasps(const short *ev16, const float *heights, const RollRecordDev *rec, unsigned long long *scratch, size_t slot_words,
+                       int n_slots, int *hdr, TopCandDev *cand, int D, int min_vote, int radius, Dims d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

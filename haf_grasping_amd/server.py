@@ -77,5 +77,15 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
+    def top_grasps(self, k=None, **params):
+        """Ranked top-k grasp candidates of the last execute() (haf_top_grasps: in-roll and cross-roll suppression, rank 1 = the
+        result execute() returned when show_only_best_grasp is off) as GraspOutputMsgs, best first.  params: min_vote, cell_radius,
+        roll_window, min_dist_m (haf_top_params)."""
+        if k is not None:
+            params["k"] = k
+        cands = self.engine.top_grasps(**params)[0]
+        return [GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                               c["approach_vector"], c["roll"]) for c in cands]
+
     def close(self):
         self.engine.close()

@@ -169,6 +169,42 @@ int haf_finalize(haf_engine *e, const haf_grasp_input *in, const haf_roll_record
 int haf_roll_pose(haf_engine *e, const haf_grasp_input *in, const haf_roll_record *records, int32_t roll,
                   haf_grasp_output *out, int32_t *published);
 
+/* Ranked top-K grasp candidates of the LAST scored batch, for a planner whose best grasp fails IK or a collision check.  Defined on the
+ * vote and height grids that batch left on the device (no new request; records, roll grids, debug data and counters stay as they were):
+ *  1. runs: in every (cloud, roll) each maximal horizontal run of equal vote v >= min_vote; its cell is (row, end - len/2), the
+ *     reference's centring (server.cpp:904-932);
+ *  2. order: vote desc, roll asc, len desc, row asc, col asc.  A roll's first candidate is its record; the overall first is
+ *     haf_finalize's best when show_only_best_grasp is off (strict '>' keeps the lowest roll, 362-365, 953-960);
+ *  3. in-roll suppression: walking a roll's candidates in order, one within Chebyshev distance <= cell_radius cells of a kept candidate
+ *     of the SAME roll is dropped (0: none);
+ *  4. pose: the candidate's record {vote, row, col, h_locmax of the 9x8 window, n_evals of its roll} through haf_roll_pose's pose, then
+ *     eval = vote - 20 (390): rank 1 equals haf_score's output in every pose and identity field;
+ *  5. cross-roll suppression: merging the rolls in key order, a candidate is dropped when a kept candidate of a DIFFERENT roll lies
+ *     1..roll_window roll steps away (circularly when n_rolls * roll_step_deg == 180) and its averaged_grasp_point within min_dist_m
+ *     (squared distance in double, <=).  roll_window = 0 or min_dist_m = 0 switches it off.  The two stages are separate: a candidate
+ *     dropped in its roll stays dropped even when the one that dropped it is removed across rolls;
+ *  6. stop at k kept candidates or when none is left.
+ * Every roll the last call scored counts (global roll indices [roll_first, roll_first + roll_count) of a haf_score_rolls call): the
+ * ranking does NOT apply show_only_best_grasp's early exit.  A cloud whose budget truncates to a negative value gets 0 candidates.
+ * HAF_E_ARG: no scored batch, an engine created with HAF_FLAG_PROBABILITY, a parameter out of range or min_dist_m NaN. */
+typedef struct haf_top_params {
+    int32_t k;            /* 1..1024 candidates per cloud; default 8                                                    */
+    int32_t min_vote;     /* >= 1; default graspval_th + 1 (the hypothesis threshold, 960-962)                         */
+    int32_t cell_radius;  /* >= 0; in-roll Chebyshev suppression radius in cells; default 7                           */
+    int32_t roll_window;  /* >= 0; cross-roll suppression window in roll steps; default 1                             */
+    double  min_dist_m;   /* >= 0; cross-roll suppression distance in metres; default 0.02                            */
+} haf_top_params;
+typedef struct haf_grasp_candidate {
+    haf_grasp_output grasp;   /* pose + best_row/col/roll/vote of the candidate, eval = vote - 20, rolls_done = roll + 1,
+                                 n_evals of its roll, n_rechecked 0                                                             */
+    int32_t run_length;
+    float   h_locmax;
+} haf_grasp_candidate;
+/* e may be NULL: min_vote then comes from haf_config_default's graspval_th */
+void haf_top_params_default(const haf_engine *e, haf_top_params *p);
+/* every cloud c of the last scored batch: out[c * p->k + i] for i < n_found[c] */
+int  haf_top_grasps(haf_engine *e, const haf_top_params *p, haf_grasp_candidate *out, int32_t *n_found);
+
 /* ---- several GPUs of one node in ONE process (csrc/multi.cpp) ---------------------------------------------------------
  * For a C++ host such as the action server: one engine, one host thread and one HIP stream per entry of devices[], one RCCL
  * communicator over the distinct devices (ncclCommInitAll), collectives over xGMI.  What is sharded is what the reference

@@ -163,5 +163,24 @@ inline int run_goal(haf_engine *engine, const haf_config &cfg, const GoalFields 
     return HAF_OK;
 }
 
+// The ranked top-k candidates of the engine's last scored goal (haf_top_grasps; run_goal scores one cloud per call) as hypothesis
+// strings, best first -- the next-best DISTINCT grasps for a planner whose first choice fails IK or a collision check.  An adapter
+// would publish them after the goal's own result, or hand them back in a service reply.  Returns the engine's status; on failure
+// *err carries haf_last_error().
+inline int top_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_top_params &p, std::vector<std::string> *lines,
+                          std::string *err)
+{
+    const size_t clouds = (size_t)(cfg.max_clouds > 0 ? cfg.max_clouds : 1), k = (size_t)(p.k > 0 ? p.k : 1);
+    std::vector<haf_grasp_candidate> cand(clouds * k);
+    std::vector<int32_t> n(clouds, 0);
+    const int rc = haf_top_grasps(engine, &p, cand.data(), n.data());
+    if (rc != HAF_OK) {
+        if (err) *err = haf_last_error(engine);
+        return rc;
+    }
+    for (int32_t i = 0; i < n[0]; i++) lines->push_back(hypothesis_string(cand[(size_t)i].grasp, cfg.roll_step_deg));
+    return HAF_OK;
+}
+
 }  // namespace hafshim
 #endif  // HAF_SHIM_CORE_H_
