@@ -191,6 +191,157 @@ def check_descriptor_loads(lib=None, verbose=False):
     if bad:
         raise RuntimeError("build check failed: the group-parallel feature kernels fetch descriptor words by vector loads again "
                            "(> %d global/buffer loads): %r" % (MAX_VECTOR_LOADS, bad))
+    check_slot_loop(lib, verbose=verbose)           # (the feature kernels' other ISA check: below)
+    return rep
+
+
+# Round 6: the slot loop of the screening feature kernel k_features_serial<2, true> (csrc/feature_device.h: screen_group) reads every
+# corner of a region with ds_read_addtid_b32, whose LDS address comes from M0 -- so every read drags scalar instructions along: the M0
+# write, its wait state, and the waits and scalar loads around the reads.  Two things are checked in the disassembly.
+SLOT_LOOP_KERNEL = "k_features_serialILi2ELb1"
+SLOT_LOOP_AUDITED = ["k_features_serialILi2ELb1", "k_features_serialILi2ELb0"]
+# (SALU + s_nop + s_waitcnt) per ds_read_addtid_b32 in the block with the most such reads (the loop body of a fast group on path A):
+# 4.52 before round 6 ((144 + 116 + 29) / 64), 3.05 as built since ((98 + 76 + 21) / 64); the build allows one instruction per read more
+MAX_SLOT_LOOP_OVERHEAD = 4.05
+
+
+def _device_disassembly(lib, extra=()):
+    import glob
+    import shutil
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="haf_isa_")
+    try:
+        shutil.copy(lib, os.path.join(tmp, "lib.so"))
+        subprocess.check_call([OBJDUMP, "--offloading", "lib.so"], cwd=tmp, stdout=subprocess.DEVNULL)
+        text = ""
+        for co in sorted(glob.glob(os.path.join(tmp, "*gfx950*"))):
+            text += subprocess.check_output([OBJDUMP, "-d"] + list(extra) + [co]).decode(errors="replace")
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return text
+
+
+def _all_regs(text):
+    out = set()
+    for m in re.finditer(r"\b([sv])\[(\d+):(\d+)\]|\b([sv])(\d+)\b", text):
+        if m.group(1):
+            out |= {(m.group(1), i) for i in range(int(m.group(2)), int(m.group(3)) + 1)}
+        else:
+            out.add((m.group(4), int(m.group(5))))
+    return out
+
+
+def inflight_violations(code):
+    """Instructions of a straight listing that touch a register which an LDS read or a scalar load still has IN FLIGHT.  The corner reads
+    and the descriptor loads of the slot loop are issued from inline asm, which hipcc does not model: a copy, a spill or an early use of
+    such a register between the load and the s_waitcnt that covers it would be silent garbage.  LDS reads return in order (lgkmcnt(N)
+    retires all but the N youngest), scalar loads only at lgkmcnt(0); a branch ends the search (nothing is tracked across it).
+    -> (loads seen, [(index, instruction, registers)])"""
+    queue, bad, loads = [], [], 0
+    for i, ins in enumerate(code):
+        op, _, rest = ins.partition(" ")
+        if op.startswith(("s_branch", "s_cbranch", "s_endpgm", "s_setpc")):
+            queue = []
+            continue
+        if op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", ins)
+            if m:
+                n = int(m.group(1))
+                lds = [k for k, e in enumerate(queue) if e[0] == "lds"]
+                keep = set(lds[-n:]) if n else set()
+                queue = [e for k, e in enumerate(queue) if (n and e[0] == "smem") or k in keep]
+            continue
+        flying = set().union(*[e[1] for e in queue]) if queue else set()
+        hit = _all_regs(rest) & flying
+        if hit:
+            bad.append((i, ins, sorted(hit)))
+        if op.startswith(("s_load", "s_buffer_load")):
+            queue.append(("smem", _all_regs(rest.split(",")[0])))
+            loads += 1
+        elif op.startswith(("ds_read", "ds_load")):
+            queue.append(("lds", _all_regs(rest.split(",")[0])))
+            loads += 1
+    return loads, bad
+
+
+def slot_loop_report(lib=None):
+    """{"block": {class: count} of the block of k_features_serial<2, true> with the most ds_read_addtid_b32, "reads": their number,
+    "overhead": (SALU + s_nop + s_waitcnt) / reads, "inflight": {kernel: (loads, violations)}} from the disassembly (blocks as
+    llvm-objdump --symbolize-operands labels them)."""
+    text = _device_disassembly(lib or LIB, ["--symbolize-operands"])
+    kernels, cur, blk = {}, None, None
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
+        if m:
+            if re.fullmatch(r"L\d+", m.group(1)):
+                if cur:
+                    blk = []
+                    kernels[cur].append(blk)
+            else:
+                cur = m.group(1) if any(k in m.group(1) for k in SLOT_LOOP_AUDITED) and not m.group(1).endswith(".kd") else None
+                if cur:
+                    blk = []
+                    kernels[cur] = [blk]
+            continue
+        ins = line.split("//")[0].strip()
+        if cur and ins and not ins.endswith(":"):
+            blk.append(ins)
+
+    def cls(op):
+        if op.startswith("s_nop"):
+            return "nop"
+        if op.startswith("s_waitcnt"):
+            return "wait"
+        if op.startswith(("s_load", "s_buffer_load")):
+            return "smem"
+        if op.startswith(("s_branch", "s_cbranch")):
+            return "branch"
+        if op.startswith("s_"):
+            return "salu"
+        if op.startswith("ds_read_addtid"):
+            return "addtid"
+        if op.startswith("ds_"):
+            return "lds"
+        if op.startswith("v_"):
+            return "valu"
+        return "other"
+
+    rep = {"block": {}, "reads": 0, "overhead": None, "inflight": {}}
+    for name, blocks in kernels.items():
+        rep["inflight"][name] = inflight_violations([i for b in blocks for i in b])
+        if SLOT_LOOP_KERNEL not in name:
+            continue
+        for b in blocks:
+            c = {}
+            for ins in b:
+                k = cls(ins.split()[0])
+                c[k] = c.get(k, 0) + 1
+            if c.get("addtid", 0) > rep["reads"]:
+                rep["block"], rep["reads"] = c, c["addtid"]
+    if rep["reads"]:
+        c = rep["block"]
+        rep["overhead"] = (c.get("salu", 0) + c.get("nop", 0) + c.get("wait", 0)) / float(rep["reads"])
+    return rep
+
+
+def check_slot_loop(lib=None, verbose=False):
+    """Fails the build when the scalar-side overhead per corner read of k_features_serial<2, true>'s slot loop -- (SALU + s_nop + s_waitcnt)
+    / ds_read_addtid_b32 in the block with the most such reads -- exceeds MAX_SLOT_LOOP_OVERHEAD = 4.05: the loop as built reaches 3.05,
+    the loop before round 6 stood at 4.52 (one instruction per read of slack over what is reached); and when any instruction of the two
+    screening instances touches a register of a load still in flight (inflight_violations)."""
+    rep = slot_loop_report(lib)
+    if verbose:
+        print("  slot-loop check: %d corner reads, %r -> overhead %s per read" % (rep["reads"], rep["block"], rep["overhead"]))
+        for k, (n, bad) in sorted(rep["inflight"].items()):
+            print("  slot-loop check: %-40s %4d LDS reads / scalar loads, %d touched in flight" % (k[:40], n, len(bad)))
+    if not rep["reads"] or len(rep["inflight"]) != len(SLOT_LOOP_AUDITED):
+        raise RuntimeError("check_slot_loop: %s or its ds_read_addtid_b32 loop not found in %s (kernel renamed?)" % (SLOT_LOOP_KERNEL, lib or LIB))
+    if rep["overhead"] > MAX_SLOT_LOOP_OVERHEAD:
+        raise RuntimeError("build check failed: %.2f scalar-side instructions per corner read in the slot loop of %s (> %.2f): %r"
+                           % (rep["overhead"], SLOT_LOOP_KERNEL, MAX_SLOT_LOOP_OVERHEAD, rep["block"]))
+    bad = {k: v[1][:4] for k, v in rep["inflight"].items() if v[1]}
+    if bad:
+        raise RuntimeError("build check failed: a register of an LDS read or scalar load in flight is touched before its s_waitcnt: %r" % bad)
     return rep
 
 

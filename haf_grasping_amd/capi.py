@@ -173,6 +173,8 @@ def _bind(path, testing):
         L.haf_test_poke_flag0_list.argtypes = [E, C.c_int, C.c_int, C.c_int]
         L.haf_test_overflow_stats.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_list.argtypes = [E, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.haf_test_snapshot_screen.argtypes = [E, C.c_int]
+        L.haf_test_fetch_snapshot.argtypes = [E, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
         L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.haf_test_top_merge.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int] + [C.c_void_p] * 5 + \
             [C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -347,6 +349,22 @@ class Engine:
         n = C.c_int()
         self._check(self._L.haf_test_fetch_list(self._h, which, buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return buf[:min(n.value, cap)].copy()
+
+    def snapshot_screen(self, on=True):
+        """Testing build: from now on every request keeps a copy of what its screening feature pass wrote (fetch_snapshot)."""
+        self._check(self._L.haf_test_snapshot_screen(self._h, 1 if on else 0))
+
+    def fetch_snapshot(self, which, offset=0, nbytes=None):
+        """Testing build: bytes of the last request's snapshot as uint8 -- which = 0 the fp16 operand images (20 KiB per tile of 32
+        evaluations), 1 the 8 band floats per evaluation (the raw sums in the low-rank form), 2 a_x."""
+        avail = C.c_longlong()
+        self._check(self._L.haf_test_fetch_snapshot(self._h, which, 0, None, 0, C.byref(avail)))
+        if nbytes is None:
+            nbytes = avail.value - offset
+        buf = np.empty(max(0, nbytes), dtype=np.uint8)
+        if nbytes > 0:
+            self._check(self._L.haf_test_fetch_snapshot(self._h, which, offset, buf.ctypes.data_as(C.c_void_p), nbytes, C.byref(avail)))
+        return buf
 
     def overflow_stats(self):
         """Testing build: how often this engine's requests met a list smaller than what it had to hold."""

@@ -68,6 +68,7 @@ void haf_destroy(haf_engine *e)
     e->d_ii.release(); e->d_mask.release(); e->d_rowcount.release(); e->d_rowoff.release(); e->d_brcount.release();
     e->d_evalcell.release(); e->d_flag_list.release(); e->d_X.release(); e->d_ax.release();
     e->d_dec.release(); e->d_svt.release(); e->d_svt_h.release(); e->d_labels.release(); e->d_dec_exact.release(); e->d_strict_terms.release(); e->d_part64.release(); e->d_dec_exact2.release(); e->d_flag2_list.release(); e->d_x64.release(); e->d_sv64.release();
+    e->snap_X.release(); e->snap_gband.release(); e->snap_ax.release();
     e->d_svt0.release(); e->d_X1.release(); e->d_ax1.release(); e->d_gband.release(); e->d_flag0_list.release(); e->d_flag0_words.release(); e->d_flag0_wgcount.release();
     e->d_own.release(); e->d_gridf.release(); e->d_evf.release(); e->d_ptext.release();
     e->d_sv_i8.release(); e->d_flagi_list.release(); e->d_dec_exacti.release();

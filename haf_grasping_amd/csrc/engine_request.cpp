@@ -475,6 +475,13 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     if (!p.reuse)
         launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
                         e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
+    if (e->snap_on && !p.reuse) {        // (testing library only: haf_test_snapshot_screen)
+        const long cap = std::min<long>(evals_cap, e->max_evals_pad);
+        e->snap_cap = cap;
+        (void)hipMemcpyAsync(e->snap_X.p, e->d_X.p, (size_t)((cap + kTile - 1) / kTile) * (size_t)kS0MatBytes, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(e->snap_gband.p, e->d_gband.p, (size_t)cap * kBandFloats * sizeof(float), hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(e->snap_ax.p, e->d_ax.p, (size_t)cap * sizeof(float), hipMemcpyDeviceToDevice, s);
+    }
     char *y_img = reinterpret_cast<char *>(e->d_X.p) + (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes;   // behind the 10-step images (the buffer holds the 42 KiB three-pass form)
     mark(e, HAF_ST_SVM);
     if (p.lr && !e->lr_fused) launch_project(e->d_X.p, e->d_lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)

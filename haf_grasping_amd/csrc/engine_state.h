@@ -303,6 +303,12 @@ struct haf_engine {
     long stat_flag0_overflows = 0;  // the screening passes left more undecided than their list holds: decision stage redone
     long stat_extra_windows = 0;    // windows of the exact tiers' lists beyond the first
     LastCall last;
+    // testing library (engine_testing.cpp: haf_test_snapshot_screen): copies of what the screening feature pass of a request left --
+    // the operand images, the raw band sums and a_x -- taken right behind its launch, before the sweep and the later tiers reuse the buffers
+    bool snap_on = false;
+    long snap_cap = 0;              // evaluation slots the last snapshot covers
+    DevBuf<char> snap_X;
+    DevBuf<float> snap_gband, snap_ax;
     // haf_top_grasps (engine_topgrasps.cpp), allocated on its first call: run-list scratch of its slots, the output block
     // [hdr: 4 ints per (cloud, roll)][TopCandDev x depth per (cloud, roll)] and its pinned host copy
     DevBuf<unsigned long long> d_top_scratch;

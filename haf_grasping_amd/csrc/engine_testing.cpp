@@ -104,6 +104,35 @@ int haf_test_overflow_stats(haf_engine *e, long long *out2)
     out2[0] = e->stat_flag0_overflows; out2[1] = e->stat_extra_windows;
     return HAF_OK;
 }
+// Snapshot of the screening feature pass: with on != 0 every later request whose screening tier runs its feature kernel copies what that
+// kernel wrote -- the fp16 operand images (20 KiB per tile of 32 evaluations), the 8 band floats per evaluation (the RAW sums in the
+// low-rank form) and a_x -- aside before the sweep, the projection and the later tiers reuse the buffers.  Sized for the engine's
+// largest request.
+int haf_test_snapshot_screen(haf_engine *e, int on)
+{
+    if (!e) return HAF_E_ARG;
+    if (on && !e->snap_X.p) {
+        if (e->snap_X.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes) != hipSuccess ||
+            e->snap_gband.alloc((size_t)e->max_evals_pad * kBandFloats) != hipSuccess || e->snap_ax.alloc((size_t)e->max_evals_pad) != hipSuccess)
+            return HAF_E_DEVICE;
+    }
+    e->snap_on = on != 0;
+    if (!on) e->snap_cap = 0;
+    return HAF_OK;
+}
+// bytes [offset, offset + bytes) of the last snapshot: which = 0 operand images, 1 band floats, 2 a_x; *avail = bytes the snapshot holds
+int haf_test_fetch_snapshot(haf_engine *e, int which, long long offset, void *out, long long bytes, long long *avail)
+{
+    if (!e || !avail || offset < 0 || bytes < 0 || which < 0 || which > 2) return HAF_E_ARG;
+    const char *src = which == 0 ? e->snap_X.p : which == 1 ? reinterpret_cast<const char *>(e->snap_gband.p) : reinterpret_cast<const char *>(e->snap_ax.p);
+    const long long have = which == 0 ? (long long)((e->snap_cap + kTile - 1) / kTile) * kS0MatBytes
+                                      : (long long)e->snap_cap * (which == 1 ? kBandFloats : 1) * (long long)sizeof(float);
+    *avail = src ? have : 0;
+    if (!bytes) return HAF_OK;
+    if (!src || !out || offset + bytes > have) return HAF_E_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return HAF_E_DEVICE;
+    return hipMemcpy(out, src + offset, (size_t)bytes, hipMemcpyDeviceToHost) == hipSuccess ? HAF_OK : HAF_E_DEVICE;
+}
 // writes `count` ints of value `v` at int offset `at` relative to the END of the d_flag0_list buffer (at >= 0) of this engine -- the
 // canary test's own "bug": what a producer that ignores its capacity does
 int haf_test_poke_flag0_list(haf_engine *e, int at, int count, int v)

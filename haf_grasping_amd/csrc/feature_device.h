@@ -222,10 +222,10 @@ __device__ __forceinline__ float screen_attribute_lr(const Src &src, const FeatD
 constexpr int kBandRows = 15;
 constexpr int kBandFloats4 = kBandRows * kBandPitch;  // per wave
 
-// Four attribute slots of a "fast" group (ScreenParams::fast_groups: plain HAF features of at most two regions): the 32
-// corner reads go out back to back before anything waits on them, and nothing branches.  An inactive region has weight 0
-// and its corners at the window origin: it adds 0.0f * 0.0f, which leaves the sum of fv.cpp:164 as it is.
-// hipcc does not know that the asm reads are asynchronous: the registers are handed on only through the s_waitcnt statement.
+// The eight attribute slots of a "fast" group (ScreenParams::fast_groups: plain HAF features of at most two regions), two slots
+// at a time (screen_group below), and nothing branches.  An inactive region has weight 0 and its corners at the window origin: it adds
+// 0.0f * 0.0f, which leaves the sum of fv.cpp:164 as it is.
+// hipcc does not know that the asm reads are asynchronous: the registers are handed on only through the s_waitcnt statements.
 // The descriptors are read through the constant address space: the memory clobbers around the band would otherwise make
 // hipcc fetch every wave-uniform descriptor word with a vector load.
 typedef const ScrDesc __attribute__((address_space(4))) *ScrDescK;
@@ -237,62 +237,140 @@ __device__ __forceinline__ ScrDescK constant_ptr(const ScrDesc *p) { return (Scr
 // per wave), times |scr_mul| (ScrDesc::pad, rounded up; 0 for a SHAF slot, which is passed through as it is).
 // u = 2^-24: 3 u (1 + 1e-3) and 4 u (1 + 1e-3), rounded up (the fp32 roundings of the bound's own three operations included)
 constexpr float kNbRound = 1.80e-7f, kNbRound3 = 2.40e-7f;
-template <int NB>
-__device__ __forceinline__ void screen_quad(unsigned band, ScrDescK sd, const hafq::ScrTabs &st, float *ud, float &nu2, float &rmin)
+// The wait state between an SALU write of M0 and the add-TID read that uses it (a read issued directly behind the write would use the
+// previous M0 and return wrong corners silently).  HAF_SLOT_PAD2: a timing probe that doubles every pad (build.py --variant).
+#ifdef HAF_SLOT_PAD2
+#define HAF_SLOT_PAD "s_nop 0\n\ts_nop 0\n\t"
+#else
+#define HAF_SLOT_PAD "s_nop 0\n\t"
+#endif
+#define HAF_CORNER_READ(dst, off, band) "s_add_i32 m0, %" #off ", %" #band "\n\t" HAF_SLOT_PAD "ds_read_addtid_b32 %" #dst "\n\t"
+// The eight corner reads of one slot in ONE statement: M0 = band + corner offset is written by the add itself (no temporary, no move),
+// and hipcc puts nothing between the reads (between two statements that clobber M0 it pads a wait state of its own).
+template <class OffK>
+__device__ __forceinline__ void corner_reads8(unsigned band, OffK off, float *c)
 {
-    float c[4][8];
-    unsigned adr[4][8];                               // all descriptor words first: a volatile asm pins what follows it
+    asm volatile(HAF_CORNER_READ(0, 8, 16) HAF_CORNER_READ(1, 9, 16) HAF_CORNER_READ(2, 10, 16) HAF_CORNER_READ(3, 11, 16)
+                 HAF_CORNER_READ(4, 12, 16) HAF_CORNER_READ(5, 13, 16) HAF_CORNER_READ(6, 14, 16) HAF_CORNER_READ(7, 15, 16)
+                 : "=v"(c[0]), "=v"(c[1]), "=v"(c[2]), "=v"(c[3]), "=v"(c[4]), "=v"(c[5]), "=v"(c[6]), "=v"(c[7])
+                 : "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]), "s"(off[4]), "s"(off[5]), "s"(off[6]), "s"(off[7]), "s"(band)
+                 : "m0", "scc");
+}
+template <class OffK>
+__device__ __forceinline__ void corner_reads4(unsigned band, OffK off, float *c)
+{
+    asm volatile(HAF_CORNER_READ(0, 4, 8) HAF_CORNER_READ(1, 5, 8) HAF_CORNER_READ(2, 6, 8) HAF_CORNER_READ(3, 7, 8)
+                 : "=v"(c[0]), "=v"(c[1]), "=v"(c[2]), "=v"(c[3])
+                 : "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]), "s"(band)
+                 : "m0", "scc");
+}
+// ---- a fast group of eight slots as four PAIRS, software-pipelined three deep -------------------------------------------------------
+// pair p + 2: its descriptor words are on their way (scalar loads issued by hand, so that nothing waits for them where they are issued);
+// pair p + 1: its sixteen corner reads are in flight; pair p: its sums, products, "%.4g" lookups and bounds execute.  The one full wait
+// of a pair (pair_wait) stands where everything older has long been drained by the lookups of the pair before, and the two lookups of a
+// pair's slots are formed side by side, so that they share their two LDS round trips.  Round 6, at C5, A/B on one box: 3.19-3.21 -> 2.99-3.03 ms
+// (profiles/r06_slot_loop_ab.txt).  What did NOT matter is the length of the instruction stream: doubling every pad of the old loop
+// (64 more s_nop per group) cost 0.02 ms; one slot at a time with a counted wait (lgkmcnt(8)) for the slot in front reached 3.07 ms;
+// six waves per SIMD 3.12 ms.  No operation on a value changed: tests/test_slot_loop_gpu.py holds the kernel to the bits it wrote before.
+typedef int s_int8 __attribute__((ext_vector_type(8)));
+typedef float s_float4 __attribute__((ext_vector_type(4)));
+struct PairDesc { s_int8 off0, off1; s_float4 k0, k1; float pad0, pad1; };      // per slot: off[8], {w[0], w[1], scr_mul, scr_add}, pad
+static_assert(offsetof(ScrDesc, off) == 0 && offsetof(ScrDesc, w) == 0x20 && offsetof(ScrDesc, scr_mul) == 0x28 && offsetof(ScrDesc, scr_add) == 0x2c &&
+              offsetof(ScrDesc, pad) == 0x34 && sizeof(ScrDesc) == 0x40, "pair_desc_load reads ScrDesc by byte offsets");
+// hipcc does not know that these loads are asynchronous: the registers are handed on only through pair_wait / desc_wait
+__device__ __forceinline__ void pair_desc_load(ScrDescK sd, PairDesc &d)
+{
+    asm volatile("s_load_dwordx8 %0, %6, 0x0\n\ts_load_dwordx4 %2, %6, 0x20\n\ts_load_dword %4, %6, 0x34\n\t"
+                 "s_load_dwordx8 %1, %6, 0x40\n\ts_load_dwordx4 %3, %6, 0x60\n\ts_load_dword %5, %6, 0x74"
+                 : "=&s"(d.off0), "=&s"(d.off1), "=&s"(d.k0), "=&s"(d.k1), "=&s"(d.pad0), "=&s"(d.pad1) : "s"(sd));
+}
+__device__ __forceinline__ void desc_wait(PairDesc &d)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d.off0), "+s"(d.off1), "+s"(d.k0), "+s"(d.k1), "+s"(d.pad0), "+s"(d.pad1));
+}
+// everything in flight has to be back: pair p's sixteen corners (c) and pair p + 1's descriptor words (d)
+__device__ __forceinline__ void pair_wait(float *c, PairDesc &d)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]),
+                                          "+s"(d.off0), "+s"(d.off1), "+s"(d.k0), "+s"(d.k1), "+s"(d.pad0), "+s"(d.pad1));
+    asm volatile("" : "+v"(c[8]), "+v"(c[9]), "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]));
+}
+__device__ __forceinline__ void pair_wait(float *c)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]));
+    asm volatile("" : "+v"(c[8]), "+v"(c[9]), "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]));
+}
+struct VecOff { s_int8 v; __device__ __forceinline__ int operator[](int j) const { return v[j]; } };
+__device__ __forceinline__ void pair_reads(unsigned band, const PairDesc &d, float *c)
+{
+    corner_reads8(band, VecOff{d.off0}, c);
+    corner_reads8(band, VecOff{d.off1}, c + 8);
+}
+template <int NB>
+__device__ __forceinline__ void pair_math(const float *c, const PairDesc &d, const hafq::ScrTabs &st, float *ud, float &nu2, float &rmin)
+{
+    float ar[2] = {0.0f, 0.0f}, q4f[2];
+    // the two slots side by side in the halves of packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32: the same IEEE operation per half)
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f w0 = {d.k0[0], d.k1[0]}, w1 = {d.k0[1], d.k1[1]};
+    const v2f c0 = {c[0], c[8]}, c1 = {c[1], c[9]}, c2 = {c[2], c[10]}, c3 = {c[3], c[11]}, c4 = {c[4], c[12]}, c5 = {c[5], c[13]}, c6 = {c[6], c[14]},
+              c7 = {c[7], c[15]};
+    const v2f s10 = c0 - c1, s20 = s10 - c2, s11 = c4 - c5, s21 = s11 - c6;
+    const v2f R0 = s20 + c3, R1 = s21 + c7;
+    const v2f r0 = w0 * R0, r1 = w1 * R1;
+    const v2f v = r0 + r1;                  // 0.0f + r0 first (fv.cpp:164) only turns a -0 into +0: same decimal, same u'
+    if (NB == 2)                            // a wave that did not pass the exactness test as a whole (features.hip)
 #pragma unroll
-    for (int q = 0; q < 4; q++)
+        for (int i = 0; i < 2; i++)
+            ar[i] = fabsf(w0[i]) * region_round_bound(c0[i], c1[i], c2[i], c3[i], s10[i], s20[i], R0[i]) +
+                    fabsf(w1[i]) * region_round_bound(c4[i], c5[i], c6[i], c7[i], s11[i], s21[i], R1[i]);
 #pragma unroll
-        for (int j = 0; j < 8; j++) adr[q][j] = band + (unsigned)sd[q].off[j];
+    for (int i = 0; i < 2; i++) q4f[i] = (float)hafq::decq4_float_scr(v[i], st);
 #pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const unsigned a = adr[q][j];
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(c[q][j]) : "s"(a) : "m0");
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(c[0][0]), "+v"(c[0][1]), "+v"(c[0][2]), "+v"(c[0][3]), "+v"(c[0][4]), "+v"(c[0][5]), "+v"(c[0][6]), "+v"(c[0][7]));
-#pragma unroll
-    for (int q = 1; q < 4; q++)
-        asm volatile("" : "+v"(c[q][0]), "+v"(c[q][1]), "+v"(c[q][2]), "+v"(c[q][3]), "+v"(c[q][4]), "+v"(c[q][5]), "+v"(c[q][6]),
-                          "+v"(c[q][7]));
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float s10 = __fsub_rn(c[q][0], c[q][1]), s20 = __fsub_rn(s10, c[q][2]), s11 = __fsub_rn(c[q][4], c[q][5]), s21 = __fsub_rn(s11, c[q][6]);
-        const float R0 = __fadd_rn(s20, c[q][3]);
-        const float R1 = __fadd_rn(s21, c[q][7]);
-        const float r0 = __fmul_rn(sd[q].w[0], R0);
-        const float r1 = __fmul_rn(sd[q].w[1], R1);
-        const float v = __fadd_rn(r0, r1);      // 0.0f + r0 first (fv.cpp:164) only turns a -0 into +0: same decimal, same u'
-        const float q4f = (float)hafq::decq4_float_scr(v, st);
-        ud[q] = fmaf(q4f, sd[q].scr_mul, sd[q].scr_add);
+    for (int i = 0; i < 2; i++) {
+        const s_float4 k = i ? d.k1 : d.k0;
+        ud[i] = fmaf(q4f[i], k[2], k[3]);
         if (NB) {
             // round 5: the fp32 roundings BOUNDED instead of measured -- two products (u |r_k| each), their sum (u |v|) and the cast of q4
             // (u |q4| <= 1.0005 u |v|), |v| <= (1 + u)(|r0| + |r1|): at most kNbRound (|r0| + |r1|), a thousandth of the "%.4g" term beside
             // it (|q4 - v| ~ 1e-4 |v|).  Six vector instructions per slot instead of eleven.
-            float ar = 0.0f;                               // NB == 2: a wave that did not pass the exactness test as a whole (features.hip)
-            if (NB == 2)
-                ar = fabsf(sd[q].w[0]) * region_round_bound(c[q][0], c[q][1], c[q][2], c[q][3], s10, s20, R0) +
-                     fabsf(sd[q].w[1]) * region_round_bound(c[q][4], c[q][5], c[q][6], c[q][7], s11, s21, R1);
-            float nbq = fmaf(kNbRound, fabsf(r0) + fabsf(r1), fabsf(q4f - v));
-            if (NB == 2) nbq += ar;
+            float nbq = fmaf(kNbRound, fabsf(r0[i]) + fabsf(r1[i]), fabsf(q4f[i] - v[i]));
+            if (NB == 2) nbq += ar[i];
             // path A (NB == 1, the wave passed the exactness test as a whole): that test takes R >= 0 from the monotone integral image, which
             // holds for the TRUE sums; the fp32-rounded corners can leave a near-empty region at -1..-3 ulp(d), and then (a - b) - c may have
             // rounded.  The smallest computed R of the evaluation rides along (one v_min3 per slot); a negative one voids the
             // evaluation's screening pass (features.hip)
-            if (NB == 1) rmin = fminf(fminf(R0, R1), rmin);
-            nbq *= sd[q].pad;
+            if (NB == 1) rmin = fminf(fminf(R0[i], R1[i]), rmin);
+            nbq *= i ? d.pad1 : d.pad0;
             nu2 = fmaf(nbq, nbq, nu2);
-            // (the sum is tied to the sequence of the volatile LDS reads: left to float, the temporaries of eight slots stay alive until
-            // the sums are finally formed -- 45 registers, two waves of occupancy)
-            asm volatile("" : "+v"(nu2));
         }
     }
+    // (the sum is tied to the sequence of the volatile LDS reads: left to float, the temporaries of eight slots stay alive until the sums
+    // are finally formed)
+    if (NB) asm volatile("" : "+v"(nu2));
 }
-__device__ __forceinline__ void screen_quad(unsigned band, ScrDescK sd, const hafq::ScrTabs &st, float *ud) { float dummy = 0.0f, dmin = 0.0f; screen_quad<0>(band, sd, st, ud, dummy, dmin); }
+template <int NB>
+__device__ __forceinline__ void screen_group(unsigned band, ScrDescK sd, const hafq::ScrTabs &st, float *ud, float &nu2, float &rmin)
+{
+    PairDesc d[3];
+    float c[2][16];
+    pair_desc_load(sd, d[0]);
+    desc_wait(d[0]);
+    pair_reads(band, d[0], c[0]);
+    pair_desc_load(sd + 2, d[1]);
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        if (p < 3) {
+            pair_wait(c[p & 1], d[(p + 1) % 3]);
+            pair_reads(band, d[(p + 1) % 3], c[(p + 1) & 1]);
+        } else {
+            pair_wait(c[p & 1]);
+        }
+        if (p < 2) pair_desc_load(sd + 2 * (p + 2), d[(p + 2) % 3]);
+        pair_math<NB>(c[p & 1], d[p % 3], st, ud + 2 * p, nu2, rmin);
+    }
+}
+__device__ __forceinline__ void screen_group(unsigned band, ScrDescK sd, const hafq::ScrTabs &st, float *ud) { float dummy = 0.0f, dmin = 0.0f; screen_group<0>(band, sd, st, ud, dummy, dmin); }
 
 // Two attribute slots of any other group, from the band: three regions each, the HAF sum or the SHAF rule (feature_value).
 // A slot of a dropped or absent attribute has scr_mul = scr_add = 0: its u' is 0 (NaN if its feature value left the decimal
@@ -306,18 +384,11 @@ template <int NB, int NQ>
 __device__ __forceinline__ void screen_pair3(unsigned band, ScrDesc3K sd, const hafq::ScrTabs &st, float *ud, float &nu2, float &rmin)
 {
     float c[NQ][12];
-    unsigned adr[NQ][12];
 #pragma unroll
-    for (int q = 0; q < NQ; q++)
-#pragma unroll
-        for (int j = 0; j < 12; j++) adr[q][j] = band + (unsigned)sd[q].off[j];
-#pragma unroll
-    for (int q = 0; q < NQ; q++)
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const unsigned a = adr[q][j];
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(c[q][j]) : "s"(a) : "m0");
-        }
+    for (int q = 0; q < NQ; q++) {
+        corner_reads8(band, sd[q].off, c[q]);
+        corner_reads4(band, sd[q].off + 8, c[q] + 8);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(c[0][0]), "+v"(c[0][1]), "+v"(c[0][2]), "+v"(c[0][3]), "+v"(c[0][4]), "+v"(c[0][5]), "+v"(c[0][6]), "+v"(c[0][7]),
                    "+v"(c[0][8]), "+v"(c[0][9]), "+v"(c[0][10]), "+v"(c[0][11]));
@@ -351,7 +422,7 @@ __device__ __forceinline__ void screen_pair3(unsigned band, ScrDesc3K sd, const 
             // at most 4 u (|r0| + |r1| + |r2|) <= kNbRound3 of it)
             const float nbq = sd[q].pad[0] * (fmaf(kNbRound3, (fabsf(r[0]) + fabsf(r[1])) + fabsf(r[2]), fabsf(q4f - v)) + ar);
             nu2 = fmaf(nbq, nbq, nu2);
-            if (NB == 1 && !sd[q].shaf) rmin = fminf(fminf(Rk[0], Rk[1]), fminf(Rk[2], rmin));   // (as in screen_quad; a SHAF slot is passed through, not bounded)
+            if (NB == 1 && !sd[q].shaf) rmin = fminf(fminf(Rk[0], Rk[1]), fminf(Rk[2], rmin));   // (as in screen_group; a SHAF slot is passed through, not bounded)
             asm volatile("" : "+v"(nu2));
         }
     }

@@ -40,7 +40,7 @@ __device__ __forceinline__ void store_group_h(char *xtile, int r, int g, half8 h
     store_group_img(xtile + kHMatBytes, r, g, lo);
 }
 
-// screening operand of one attribute: u' in fp64 (screen_attribute / screen_quad), u^ = fp16(fl32(u')); accumulates |fl32(u')|^2 and |u^ - fl32(u')|^2 in fp32, the two norms the guard band of the screening pass is made of
+// screening operand of one attribute: u' in fp64 (screen_attribute / screen_group), u^ = fp16(fl32(u')); accumulates |fl32(u')|^2 and |u^ - fl32(u')|^2 in fp32, the two norms the guard band of the screening pass is made of
 // Centred form of the band (kernels.h: ScreenParams): three more fp32 sums over the slots -- cr = (u^ - u').G + u'.Hd, the first-order
 // error of the evaluation-independent part of the coefficient-weighted kernel vector, which the contraction kernel SUBTRACTS, and
 // ub = u'.ubar for |u' - ubar|.  (u^ - u' is exact in fp32, so the first dot product does not cancel.)
@@ -312,7 +312,7 @@ __device__ __forceinline__ void i8_store(float *X, long e, int g, const unsigned
 // LR (screening form only; kernels.h: kLrK, ScreenParams::lr): the wave also sums nu2 >= |p' - p_lin|^2 over the HAF slots and the
 // kernel leaves the RAW sums {su2, sd2, sx2, L, nu2} where the finished band would go (k_project adds |y^ - y32|^2, the sweep's tail
 // finishes the band: screen_band.h).  Per slot the bound is the "%.4g" rounding as it happened plus the fp32 roundings of the products
-// and their sum, bounded (round 5; the fast paths measured them until then) (feature_device.h: screen_quad / screen_pair3 / screen_attribute_lr), plus, for a region whose sum is not
+// and their sum, bounded (round 5; the fast paths measured them until then) (feature_device.h: screen_group / screen_pair3 / screen_attribute_lr), plus, for a region whose sum is not
 // provably EXACT in the reference's own order ((a - b) - c) + d (fv.cpp:161-162), the three roundings of that order.  Three paths,
 // wave-uniform: (A) a run of 64 neighbours whose windows pass the exactness test AS A WHOLE -- no negative height in the grid (integral
 // image monotone), bottom row of the band <= 2 x its top row in each of the lane's 15 columns (a - b exact by Sterbenz), the window's
@@ -418,28 +418,25 @@ const float *__restrict__ ii, const int *__restrict__ evalcell,
         float sx = 0.0f;
         const bool lr_nb = LR && fastwave && lr_exact;    // wave-uniform: every region sum of the wave is exact
         float nu2 = 0.0f;
-        float rmin = 0.0f;                                // path A: the smallest computed region sum of this evaluation (feature_device.h: screen_quad)
+        float rmin = 0.0f;                                // path A: the smallest computed region sum of this evaluation (feature_device.h: pair_math)
         for (int g = 0; g < kS0Groups; g++) {             // 40 groups of 8 SLOTS (kernels.h)
             float ud[8];
             if (lr_nb) {
                 if ((sp.fast_groups >> g) & 1) {
-                    screen_quad<1>(band, constant_ptr(sp.sd) + g * 8, st, ud, nu2, rmin);
-                    screen_quad<1>(band, constant_ptr(sp.sd) + g * 8 + 4, st, ud + 4, nu2, rmin);
+                    screen_group<1>(band, constant_ptr(sp.sd) + g * 8, st, ud, nu2, rmin);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 8; q++) screen_pair3<1, 1>(band, constant_ptr(sp.sd3) + g * 8 + q, st, ud + q, nu2, rmin);
                 }
             } else if (LR && fastwave) {                  // a wave with regions that may round: bounded region by region
                 if ((sp.fast_groups >> g) & 1) {
-                    screen_quad<2>(band, constant_ptr(sp.sd) + g * 8, st, ud, nu2, rmin);
-                    screen_quad<2>(band, constant_ptr(sp.sd) + g * 8 + 4, st, ud + 4, nu2, rmin);
+                    screen_group<2>(band, constant_ptr(sp.sd) + g * 8, st, ud, nu2, rmin);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 8; q++) screen_pair3<2, 1>(band, constant_ptr(sp.sd3) + g * 8 + q, st, ud + q, nu2, rmin);
                 }
             } else if (fastwave && ((sp.fast_groups >> g) & 1)) {   // wave-uniform
-                screen_quad(band, constant_ptr(sp.sd) + g * 8, st, ud);
-                screen_quad(band, constant_ptr(sp.sd) + g * 8 + 4, st, ud + 4);
+                screen_group(band, constant_ptr(sp.sd) + g * 8, st, ud);
             } else if (fastwave) {
 #pragma unroll
                 for (int q = 0; q < 8; q += 2) screen_pair3(band, constant_ptr(sp.sd3) + g * 8 + q, st, ud + q);

@@ -205,7 +205,7 @@ enum { SCREEN_PLAIN = 0, SCREEN_SUMSQ = 1, SCREEN_CR_EXP = 2, SCREEN_CR_POLY = 3
 // feature (beyond the feature file, norm slots) is all zero and evaluates to exactly 0.
 struct ScrDesc {
     int    off[8];                // BYTE offsets of the corners of regions 0 and 1 (A-B-C+D each) from the window origin, in
-                                  // the LDS band of a wave (kBandPitch floats per row, features.hip: screen_quad)
+                                  // the LDS band of a wave (kBandPitch floats per row, feature_device.h: screen_group)
     float  w[2];                  // region weights (0: region inactive, its corners point at the window origin)
     // round 5: the scaling runs in fp32 -- u' = fmaf(fl32(q4), scr_mul, scr_add) -- with the fp64 constants of FeatDesc rounded once
     // (what that costs, 3 u (|u'| + |scr_add|) per slot, is part of eta: kScreenEtaRel, ScreenParams::eta_abs)
