@@ -15,6 +15,7 @@ HAF_OK, HAF_E_ARG, HAF_E_IO, HAF_E_DEVICE, HAF_E_CAPACITY, HAF_E_BUDGET, HAF_E_I
 FLAG_KEEP_DEBUG, FLAG_PROFILE, FLAG_FP32_MFMA, FLAG_SPLIT_F16, FLAG_PROBABILITY, FLAG_FULL_RANK = 1, 2, 4, 8, 16, 32
 DBG_HEIGHTS, DBG_INTEGRAL, DBG_MASK, DBG_LABELS, DBG_DECISION, DBG_TRANSFORM, DBG_SCREEN_MARGIN, DBG_PROBABILITY, DBG_GRASPSGRID = range(9)
 SHARD_ROLLS, SHARD_CLOUDS = 0, 1
+FRAME_DEPTH_U16, FRAME_DEPTH_F32, FRAME_XYZ_F32 = 0, 1, 2
 STAGES = ["upload", "bin", "integral", "mask", "features", "svm", "refine", "recheck", "vote", "download"]
 
 
@@ -58,6 +59,14 @@ class GraspCandidate(C.Structure):
 
 class Cloud(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("n_points", C.c_size_t), ("stride_floats", C.c_size_t), ("on_device", C.c_int32)]
+
+
+class Frame(C.Structure):
+    """haf_frame: a depth image with its camera's intrinsics, or an organised sensor-frame cloud, plus the sensor-to-base transform"""
+    _fields_ = [("data", C.c_void_p), ("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("on_device", C.c_int32),
+                ("row_stride_bytes", C.c_size_t), ("point_stride_bytes", C.c_size_t),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("sensor_to_base", C.c_float * 12)]
 
 
 ATTR_RECORD_DTYPE = np.dtype([("feature", np.float32), ("pad", np.float32), ("q4", np.float64), ("scaled", np.float64)])
@@ -123,6 +132,13 @@ def _bind(path, testing):
     L.haf_pcd_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t), C.c_char_p,
                                C.c_size_t]
     L.haf_free.argtypes = [C.c_void_p]
+    L.haf_frame_default.argtypes = [C.POINTER(Frame)]
+    L.haf_frame_default.restype = None
+    L.haf_frame_points.argtypes = [C.POINTER(Frame), C.c_void_p]
+    L.haf_score_frames.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
+    L.haf_debug_fetch_points.argtypes = [E, C.c_int32, C.c_void_p, C.c_size_t]
+    L.haf_pgm16_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p,
+                                 C.c_size_t]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -278,6 +294,88 @@ def load_pcd(path):
         lib().haf_free(p)
 
 
+def load_pgm16(path):
+    """16-bit binary PGM -> uint16 [height, width] through the library's own reader (haf_pgm16_load)."""
+    p = C.POINTER(C.c_uint16)()
+    w, h = C.c_int32(), C.c_int32()
+    err = C.create_string_buffer(256)
+    rc = lib().haf_pgm16_load(path.encode(), C.byref(p), C.byref(w), C.byref(h), err, 256)
+    if rc != HAF_OK:
+        raise HafError(rc, err.value.decode())
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value)).copy()
+    finally:
+        lib().haf_free(p)
+
+
+def default_frame(**kw):
+    f = Frame()
+    lib().haf_frame_default(C.byref(f))
+    for k, v in kw.items():
+        if not hasattr(f, k):
+            raise TypeError("unknown haf_frame field %r" % k)
+        if k == "sensor_to_base":
+            v = (C.c_float * 12)(*np.asarray(v, dtype=np.float32).reshape(-1)[:12])
+        setattr(f, k, v)
+    return f
+
+
+def _frame_of(kind, data, width, height, on_device, row_stride_bytes, point_stride_bytes, keep, **kw):
+    f = default_frame(data=data, kind=kind, width=width, height=height, on_device=on_device, row_stride_bytes=row_stride_bytes,
+                      point_stride_bytes=point_stride_bytes, **kw)
+    f._keep = keep                  # the array must outlive the frame
+    return f
+
+
+def depth_frame(array, fx, fy, cx, cy, depth_scale=None, min_depth=0.0, max_depth=0.0, sensor_to_base=None, width=None, height=None,
+                row_stride_bytes=None, dtype=None):
+    """haf_frame of a depth image: a numpy uint16 / float32 [height, width] array (host; its last axis contiguous, rows may be padded:
+    a view into a wider array), or a device pointer (int) with width, height and dtype given.  depth_scale defaults to 0.001 for uint16
+    and 1 for float32; sensor_to_base is a 3x4 or 4x4 matrix (default: identity)."""
+    if isinstance(array, np.ndarray):
+        assert array.ndim == 2 and array.dtype in (np.uint16, np.float32) and array.strides[1] == array.itemsize
+        dt, on_dev, ptr = array.dtype, 0, array.ctypes.data
+        height, width = array.shape
+        row_stride_bytes = array.strides[0] if height > 1 else (row_stride_bytes or width * array.itemsize)
+    else:
+        dt, on_dev, ptr = np.dtype(dtype), 1, int(array)
+        assert dt in (np.uint16, np.float32) and width and height
+        row_stride_bytes = row_stride_bytes or width * dt.itemsize
+    kind = FRAME_DEPTH_U16 if dt == np.uint16 else FRAME_DEPTH_F32
+    if depth_scale is None:
+        depth_scale = 0.001 if kind == FRAME_DEPTH_U16 else 1.0
+    kw = dict(fx=fx, fy=fy, cx=cx, cy=cy, depth_scale=depth_scale, min_depth=min_depth, max_depth=max_depth)
+    if sensor_to_base is not None:
+        kw["sensor_to_base"] = sensor_to_base
+    return _frame_of(kind, ptr, width, height, on_dev, row_stride_bytes, 0, array, **kw)
+
+
+def xyz_frame(array, sensor_to_base=None, width=None, height=None, row_stride_bytes=None, point_stride_bytes=None):
+    """haf_frame of an organised sensor-frame cloud: numpy float32 [height, width, >= 3] (host) or a device pointer with width, height
+    and the strides given."""
+    if isinstance(array, np.ndarray):
+        assert array.ndim == 3 and array.dtype == np.float32 and array.shape[2] >= 3 and array.strides[2] == 4
+        height, width = array.shape[:2]
+        on_dev, ptr = 0, array.ctypes.data
+        point_stride_bytes = array.strides[1] if width > 1 else (point_stride_bytes or array.shape[2] * 4)
+        row_stride_bytes = array.strides[0] if height > 1 else (row_stride_bytes or width * point_stride_bytes)
+    else:
+        on_dev, ptr = 1, int(array)
+        point_stride_bytes = point_stride_bytes or 12
+        row_stride_bytes = row_stride_bytes or width * point_stride_bytes
+    kw = {} if sensor_to_base is None else dict(sensor_to_base=sensor_to_base)
+    return _frame_of(FRAME_XYZ_F32, ptr, width, height, on_dev, row_stride_bytes, point_stride_bytes, array, **kw)
+
+
+def frame_points(frame):
+    """haf_frame_points: the host definition of record -> float32 [height * width, 3]"""
+    out = np.empty((max(0, frame.width) * max(0, frame.height), 3), np.float32)
+    rc = lib().haf_frame_points(C.byref(frame), out.ctypes.data)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_frame_points refused the frame")
+    return out
+
+
 class Engine:
     """Owns one haf_engine handle (one GPU)."""
 
@@ -400,7 +498,27 @@ class Engine:
         gi = (GraspInput * n)(*inputs)
         out = (GraspOutput * n)()
         self._check(self._L.haf_score_batch(self._h, n, arr, gi, out))
+        self._last_points = [int(c.n_points) for c in arr]
         return [output_to_dict(o) for o in out]
+
+    def score_frames(self, frames, inputs):
+        """haf_score_frames: one Frame (depth_frame / xyz_frame) and one GraspInput per request of the batch"""
+        n = len(frames)
+        arr = (Frame * n)(*frames)
+        gi = (GraspInput * n)(*inputs)
+        out = (GraspOutput * n)()
+        self._check(self._L.haf_score_frames(self._h, n, arr, gi, out))
+        self._last_points = [f.width * f.height for f in frames]
+        return [output_to_dict(o) for o in out]
+
+    def debug_points(self, cloud, n_points=None):
+        """haf_debug_fetch_points: cloud `cloud` of the last batch as the kernels read it -> float32 [n_points, 3] (KEEP_DEBUG).
+        n_points defaults to the cloud's size in the last score_frames / score_batch call made through this object."""
+        if n_points is None:
+            n_points = getattr(self, "_last_points", [])[cloud]
+        out = np.empty((n_points, 3), np.float32)
+        self._check(self._L.haf_debug_fetch_points(self._h, cloud, out.ctypes.data, n_points))
+        return out
 
     def score_rolls(self, clouds, inputs, roll_first, roll_count):
         n = len(clouds)

@@ -19,12 +19,19 @@
 //   --top-k N                         after the normal output, "top <rank> <hypothesis>" for the N best distinct candidates of the
 //                                     goal (haf_top_grasps); --top-radius cells, --top-rolls steps, --top-dist metres set its suppression
 //                                     (server.cpp:962-969), in its string format
+//   --depth FILE.pgm --intrinsics fx fy cx cy   in place of the .pcd arguments: a 16-bit depth image (binary PGM) as the sensor
+//                                     delivers it, deprojected and transformed on the device (haf_score_frames); optional
+//                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
+//                                     --sensor-pose with the 12 floats of rows 0..2 of the sensor-to-base matrix (default identity).
+//                                     --hypotheses and --top-k work with it (the per-roll hypotheses are then read from the ranked
+//                                     candidates of haf_top_grasps, one per roll: the same records through the same pose)
 #include "../../include/hafgrasp.h"
 
 #include "shim_core.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -86,10 +93,76 @@ static void usage()
 {
     fprintf(stderr,
             "usage: haf_grasp_cli --features F --range R --model M [options] cloud.pcd [cloud2.pcd ...]\n"
+            "       haf_grasp_cli --features F --range R --model M [options] --depth FILE.pgm --intrinsics fx fy cx cy\n"
+            "                     [--depth-scale S] [--depth-range MIN MAX] [--sensor-pose m00 m01 ... m23]\n"
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
+}
+
+static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, int top_k, int top_radius, int top_rolls, double top_dist, int *rc)
+{
+    haf_top_params tp;
+    haf_top_params_default(eng, &tp);
+    tp.k = top_k;
+    if (top_radius >= 0) tp.cell_radius = top_radius;
+    if (top_rolls >= 0) tp.roll_window = top_rolls;
+    if (top_dist >= 0.0) tp.min_dist_m = top_dist;
+    std::vector<std::string> top;
+    std::string serr;
+    if (hafshim::top_hypotheses(eng, cfg, tp, &top, &serr) != HAF_OK) {
+        fprintf(stderr, "%s: %s\n", what, serr.c_str());
+        *rc = 1;
+    }
+    for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
+}
+
+// --depth: one goal whose cloud is a depth image, deprojected on the device.  stdout as for a .pcd: with --hypotheses every roll's own
+// hypothesis first (server.cpp:962-969: !show_only_best, vote > graspval_th, the rolls the sequential loop would have executed), then
+// the overall best.  A roll's hypothesis is its record through haf_roll_pose's pose; haf_score_frames keeps the records on the
+// device, and haf_top_grasps hands them back: with an in-roll radius of the whole grid and no cross-roll suppression its candidates
+// are exactly one per roll whose vote exceeds graspval_th, eval = vote - 20 (> 10, so the reference's clamp never acts).
+static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::string &path, haf_frame frame,
+                     bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist)
+{
+    uint16_t *depth = nullptr;
+    char err[256];
+    if (haf_pgm16_load(path.c_str(), &depth, &frame.width, &frame.height, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", path.c_str(), err); return 1; }
+    frame.kind = HAF_FRAME_DEPTH_U16;
+    frame.data = depth;
+    frame.row_stride_bytes = (size_t)frame.width * 2;
+    int rc = 0;
+    haf_grasp_output out;
+    if (haf_score_frames(eng, 1, &frame, &in, &out) != HAF_OK) {
+        fprintf(stderr, "%s: %s\n", path.c_str(), haf_last_error(eng));
+        haf_free(depth);
+        return 1;
+    }
+    if (hypotheses && !in.show_only_best_grasp) {
+        haf_top_params tp;
+        haf_top_params_default(eng, &tp);
+        tp.k = std::min(cfg.n_rolls, 1024);
+        tp.min_vote = cfg.graspval_th + 1;
+        tp.cell_radius = cfg.grid_h;
+        tp.roll_window = 0;
+        std::vector<haf_grasp_candidate> cand((size_t)tp.k);
+        int32_t n = 0;
+        if (cfg.n_rolls > 1024 || haf_top_grasps(eng, &tp, cand.data(), &n) != HAF_OK) {
+            fprintf(stderr, "%s: --hypotheses: %s\n", path.c_str(), cfg.n_rolls > 1024 ? "more than 1024 rolls" : haf_last_error(eng));
+            rc = 1;
+            n = 0;
+        }
+        std::sort(cand.begin(), cand.begin() + n, [](const haf_grasp_candidate &a, const haf_grasp_candidate &b) { return a.grasp.best_roll < b.grasp.best_roll; });
+        for (int32_t i = 0; i < n; i++)
+            if (cand[(size_t)i].grasp.best_roll < out.rolls_done) printf("hypothesis %s\n", hafshim::hypothesis_string(cand[(size_t)i].grasp, cfg.roll_step_deg).c_str());
+    }
+    printf("%s\n", hafshim::hypothesis_string(out, cfg.roll_step_deg).c_str());
+    if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc);
+    fprintf(stderr, "%s: %d x %d pixels, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", path.c_str(),
+            frame.width, frame.height, (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
+    haf_free(depth);
+    return rc;
 }
 
 int main(int argc, char **argv)
@@ -106,6 +179,10 @@ int main(int argc, char **argv)
     int gpus = 0, shards_per_gpu = 1;
     std::string shard = "rolls";
     std::string features, range, model;
+    std::string depth_file;                        // --depth: a 16-bit PGM in place of the .pcd arguments
+    bool have_intrinsics = false;
+    haf_frame frame;
+    haf_frame_default(&frame);
     int first_cloud = argc;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -130,6 +207,11 @@ int main(int argc, char **argv)
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }
         else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
+        else if (a == "--depth") { need(1); depth_file = argv[++i]; }
+        else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
+        else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
+        else if (a == "--depth-range") { need(2); frame.min_depth = (float)atof(argv[++i]); frame.max_depth = (float)atof(argv[++i]); }
+        else if (a == "--sensor-pose") { need(12); for (int k = 0; k < 12; k++) frame.sensor_to_base[k] = (float)atof(argv[++i]); }
         else if (a == "--probability") cfg.flags |= HAF_FLAG_PROBABILITY;     // svm_with_probability (server.cpp:383, 791, 831-841)
         else if (a == "--gpus") { need(1); gpus = atoi(argv[++i]); }
         else if (a == "--shard") { need(1); shard = argv[++i]; }
@@ -137,7 +219,8 @@ int main(int argc, char **argv)
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { first_cloud = i; break; }
     }
-    if (features.empty() || range.empty() || model.empty() || first_cloud >= argc) { usage(); return 2; }
+    const bool from_depth = !depth_file.empty();
+    if (features.empty() || range.empty() || model.empty() || (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);
     cfg.feature_file = features.c_str();
@@ -150,6 +233,20 @@ int main(int argc, char **argv)
     haf_engine *eng = nullptr;
     if (haf_create(&cfg, &eng) != HAF_OK) { fprintf(stderr, "haf_create: %s\n", haf_last_error(nullptr)); return 1; }
     int rc = 0;
+    if (from_depth) {
+        // (the goal goes through the adapter's fields like every other: goal_to_input rounds the duration through float, 277)
+        hafshim::GoalFields goal;
+        for (int k = 0; k < 3; k++) { goal.center[k] = in.grasp_area_center[k]; goal.approach_vector[k] = in.approach_vector[k]; }
+        goal.length_x = in.grasp_area_length_x; goal.length_y = in.grasp_area_length_y;
+        goal.max_calculation_time = in.max_calculation_time;
+        goal.show_only_best_grasp = in.show_only_best_grasp != 0;
+        goal.gripper_opening_width = in.gripper_opening_width;
+        haf_grasp_input gin;
+        hafshim::goal_to_input(goal, &gin);
+        rc = run_depth(eng, cfg, gin, depth_file, frame, hypotheses, top_k, top_radius, top_rolls, top_dist);
+        haf_destroy(eng);
+        return rc;
+    }
     for (int i = first_cloud; i < argc; i++) {
         float *xyz = nullptr;
         size_t n = 0;
@@ -187,20 +284,7 @@ int main(int argc, char **argv)
             if (hypotheses) printf("hypothesis %s\n", lines[l].c_str());
         printf("%s\n", lines.back().c_str());
         (void)res;
-        if (top_k > 0) {
-            haf_top_params tp;
-            haf_top_params_default(eng, &tp);
-            tp.k = top_k;
-            if (top_radius >= 0) tp.cell_radius = top_radius;
-            if (top_rolls >= 0) tp.roll_window = top_rolls;
-            if (top_dist >= 0.0) tp.min_dist_m = top_dist;
-            std::vector<std::string> top;
-            if (hafshim::top_hypotheses(eng, cfg, tp, &top, &serr) != HAF_OK) {
-                fprintf(stderr, "%s: %s\n", argv[i], serr.c_str());
-                rc = 1;
-            }
-            for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
-        }
+        if (top_k > 0) print_top(eng, cfg, argv[i], top_k, top_radius, top_rolls, top_dist, &rc);
         fprintf(stderr, "%s: %zu points, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", argv[i], n,
                 (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
         if (per_roll) {

@@ -179,6 +179,26 @@ static int debug_fetch_attr_impl(haf_engine *e, int32_t cloud, int32_t roll, int
     return HAF_OK;
 }
 
+// cloud `cloud` of the last batch as the kernels read it: the points area of the input block holds it until the next request
+static int debug_fetch_points_impl(haf_engine *e, int32_t cloud, float *xyz, size_t n_points)
+{
+    if (!e) return HAF_E_ARG;
+    if (!xyz) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: null xyz");
+    if (!(e->cfg.flags & HAF_FLAG_KEEP_DEBUG)) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: engine was created without HAF_FLAG_KEEP_DEBUG");
+    if (cloud < 0 || cloud >= e->last.B || (size_t)cloud >= e->last.clouds.size()) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: cloud not in the last scored batch");
+    const LastCall::CloudSrc &c = e->last.clouds[(size_t)cloud];
+    if (!c.staged) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: a device-resident xyz cloud lies in the caller's memory, the engine holds no copy");
+    if (n_points < c.n) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: xyz holds fewer points than the cloud has");
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    if (c.n) HIPCHK(e, hipMemcpy(xyz, reinterpret_cast<const float *>(e->d_in.p) + c.float_off, c.n * 12, hipMemcpyDeviceToHost));
+    return HAF_OK;
+}
+
+int haf_debug_fetch_points(haf_engine *e, int32_t cloud, float *xyz, size_t n_points)
+{
+    return guarded(e ? &e->error : nullptr, [&] { return debug_fetch_points_impl(e, cloud, xyz, n_points); });
+}
+
 int haf_debug_fetch_attr(haf_engine *e, int32_t cloud, int32_t roll, int32_t max_cells, int32_t *cells, haf_attr_record *attr,
                          uint8_t *computed, int32_t *n_cells)
 {

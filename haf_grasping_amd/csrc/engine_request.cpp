@@ -259,7 +259,11 @@ struct Request {
     int B = 0, R = 0, max_n = 0;
     long total_n = 0;
     bool bucket_ok = true;
-    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R][points of the host clouds]
+    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x B])[points of the host clouds]
+    const haf_frame *frames = nullptr;   // haf_score_frames: cloud b's points are frame b's, written by k_frame_points
+    FrameDev *h_frames = nullptr;
+    const FrameDev *d_frames = nullptr;
+    std::vector<LastCall::CloudSrc> src; // where every cloud's points lie (LastCall::clouds)
     CloudDev *h_clouds = nullptr;
     const CloudDev *d_clouds = nullptr;
     const RollGeo *d_geo = nullptr;
@@ -310,7 +314,11 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     const haf_config &c = e->cfg;
     const int B = q.B, R = q.R;
     const size_t geo_off = ((size_t)B * sizeof(CloudDev) + 15) / 16 * 16;
-    q.pts_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
+    const size_t frames_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
+    q.pts_off = frames_off + (q.frames ? ((size_t)B * sizeof(FrameDev) + 15) / 16 * 16 : 0);
+    q.h_frames = reinterpret_cast<FrameDev *>(e->h_in + frames_off);
+    q.d_frames = reinterpret_cast<const FrameDev *>(e->d_in.p + frames_off);
+    q.src.assign((size_t)B, LastCall::CloudSrc{});
     q.h_clouds = reinterpret_cast<CloudDev *>(e->h_in);
     RollGeo *h_geo = reinterpret_cast<RollGeo *>(e->h_in + geo_off);
     q.d_clouds = reinterpret_cast<const CloudDev *>(e->d_in.p);
@@ -330,11 +338,69 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
             cd.xyz = clouds[b].xyz;
             cd.stride = (int)clouds[b].stride_floats;
         } else {
+            if (q.frames) off = (off + 3) / 4 * 4;       // a frame's points start 16-byte aligned: k_frame_points stores whole dwordx4
             cd.xyz = d_points + off * 3;
             cd.stride = 3;
+            q.src[(size_t)b] = LastCall::CloudSrc{q.pts_off / sizeof(float) + off * 3, clouds[b].n_points, true};
             off += clouds[b].n_points;
         }
     }
+    // the frames' descriptors: device-resident frames are read where they lie; a host XYZ frame is packed where its points go and
+    // transformed in place; a host depth frame's pixels go through the raw area, every frame at a multiple of 16 bytes
+    size_t raw = 0;
+    for (int b = 0; q.frames && b < B; b++) {
+        const haf_frame &f = q.frames[b];
+        FrameDev &fd = q.h_frames[b];
+        fd.dst = const_cast<float *>(q.h_clouds[b].xyz);
+        fd.width = f.width;
+        fd.n = q.h_clouds[b].n;
+        fd.kind = f.kind;
+        fd.m = frame_math(f);
+        const size_t px = frame_pixel_bytes(f.kind);
+        if (f.on_device == 1) {
+            fd.src = f.data;
+            fd.row_stride = f.row_stride_bytes;
+            fd.point_stride = (unsigned)frame_elem_bytes(f);
+        } else {
+            fd.src = f.kind == HAF_FRAME_XYZ_F32 ? reinterpret_cast<const char *>(fd.dst) : e->d_raw.p + raw;
+            fd.row_stride = (unsigned long long)f.width * px;
+            fd.point_stride = (unsigned)px;
+            if (f.kind != HAF_FRAME_XYZ_F32) raw += ((size_t)fd.n * px + 15) / 16 * 16;
+        }
+    }
+}
+
+// Host frames go to the device as upload_clouds sends host clouds: in pieces of 256 KB, the DMA engine moving one while the host
+// copies the rows of the next -- only the width elements of a row, not its padding, and of an XYZ frame only the three floats of a
+// point.  Then ONE launch per kind writes the points of every frame of the batch (frames.hip).
+static int upload_frames(haf_engine *e, const Request &q)
+{
+    constexpr size_t kPiece = 256 * 1024;
+    const hipStream_t s = q.s;
+    HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, q.pts_off, hipMemcpyHostToDevice, s));      // the three header arrays
+    for (int b = 0; b < q.B; b++) {
+        const haf_frame &f = q.frames[b];
+        if (f.on_device == 1) continue;
+        const FrameDev &fd = q.h_frames[b];
+        const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
+        char *const dev = xyz ? e->d_in.p : e->d_raw.p, *const host = xyz ? e->h_in : e->h_raw;
+        const size_t at = (size_t)(static_cast<const char *>(fd.src) - dev);      // the frame's place in its block, device and pinned alike
+        const size_t row_bytes = (size_t)f.width * frame_pixel_bytes(f.kind);
+        size_t staged = 0, sent = 0;
+        for (int v = 0; v < f.height; v++) {
+            const char *row = static_cast<const char *>(f.data) + (size_t)v * f.row_stride_bytes;
+            char *dst = host + at + staged;
+            if (!xyz || f.point_stride_bytes == 12) memcpy(dst, row, row_bytes);
+            else for (int u = 0; u < f.width; u++) memcpy(dst + (size_t)u * 12, row + (size_t)u * f.point_stride_bytes, 12);
+            staged += row_bytes;
+            if (staged - sent >= kPiece || v + 1 == f.height) {
+                HIPCHK(e, hipMemcpyAsync(dev + at + sent, host + at + sent, staged - sent, hipMemcpyHostToDevice, s));
+                sent = staged;
+            }
+        }
+    }
+    launch_frame_points(q.d_frames, q.h_frames, q.B, s);
+    return HAF_OK;
 }
 
 // Host clouds go through the pinned block in pieces: while the DMA engine moves one piece the host packs the next (a 1.2 MB
@@ -796,6 +862,7 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
     l.host_resolved = q.host_resolved;
     l.i8 = q.i8_used;
     l.inputs.assign(in, in + q.B);
+    l.clouds = q.src;
     // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
     if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), q.s) == hipSuccess) e->counters_clean = true;
     // (the tier lists hold every evaluation of a request: list_cap >= last.evals >= last.flagged >= last.flagged2)
@@ -819,16 +886,17 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
 }
 
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records)
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames)
 {
     if (!e) return HAF_E_ARG;
     Request q;
+    q.frames = frames;
     int rc = check_request(e, n_clouds, clouds, in, roll_first, roll_count, records, q);
     if (rc != HAF_OK) return rc;
     pack_headers(e, clouds, in, roll_first, q);
     q.s = e->stream;
     mark(e, 0);
-    if ((rc = upload_clouds(e, clouds, q)) != HAF_OK) return rc;
+    if ((rc = frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
     classify_request(e, in, q);
     if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
     int mode = contraction_mode(e->cfg);
@@ -850,14 +918,15 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         // height grids of this call may miss points.  Serve the request -- and this engine from now on -- with k_bin instead.
         e->no_bucket_sort = true;
         e->counters_clean = false;
-        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records);
+        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
     if (mode == MODE_SCREEN && !e->prob_mode && !q.direct && (rc = adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
     return record_outcome(e, q, mode, inexact_grids, roll_first, in, records);
 }
 
-int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out)
+int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
+                     const haf_frame *frames)
 {
     if (!e) return HAF_E_ARG;
     if (!out) return fail(e, HAF_E_ARG, "haf_score_batch: null output");
@@ -869,6 +938,8 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     int rc = HAF_OK;
     if (none_runs)
         e->last = LastCall{};
+    else if (frames)
+        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames);
     else
         rc = haf_score_rolls(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data());
     if (rc != HAF_OK) return rc;
@@ -879,6 +950,27 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     // rechecks are counted per batch; attribute them to the first cloud's output and leave the others at 0
     out[0].n_rechecked = e->last.flagged + (e->last.i8 ? e->last.bypass : 0);
     return HAF_OK;
+}
+
+// haf_score_frames: every refusal before any device work, then the batch path with frame b as the source of cloud b's points
+int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out)
+{
+    if (!e) return HAF_E_ARG;
+    if (!frames || !in || !out || n < 1) return fail(e, HAF_E_ARG, "haf_score_frames: null or empty argument");
+    if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, "haf_score_frames: more frames than max_clouds");
+    int64_t total = 0;
+    std::vector<haf_cloud> clouds((size_t)n);
+    for (int b = 0; b < n; b++) {
+        std::string msg;
+        const int rc = check_frame(frames[b], msg);
+        if (rc != HAF_OK) return fail(e, rc, "haf_score_frames: frame " + std::to_string(b) + ": " + msg);
+        const size_t px = (size_t)frames[b].width * (size_t)frames[b].height;
+        total += (int64_t)px;
+        if (total > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, "haf_score_frames: more pixels than max_points");
+        // (xyz is never read on this path: the points area of the input block is the cloud; on_device = 0 reserves its place there)
+        clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[b].data), px, 3, 0};
+    }
+    return score_batch_impl(e, n, clouds.data(), in, out, frames);
 }
 
 }  // namespace haf_host

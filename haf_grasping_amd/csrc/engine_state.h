@@ -12,6 +12,7 @@
 #include "../../include/hafgrasp.h"
 #include "kernels.h"
 #include "parsers.h"
+#include "frames.h"
 #include "decq.h"
 #include "engine_internal.h"
 
@@ -129,6 +130,10 @@ struct LastCall {
     bool lr = false;             // the screening pass ran in the low-rank form
     bool i8 = false;             // tier 2a ran (then d_dec_exact holds ITS values and d_dec_exacti the fp64 tier's)
     std::vector<haf_grasp_input> inputs;
+    // where the kernels read every cloud of the batch (haf_debug_fetch_points): its first float inside the points area of d_in and its
+    // point count; staged = false for a device-resident xyz cloud, which lies in the caller's memory
+    struct CloudSrc { size_t float_off = 0; size_t n = 0; bool staged = false; };
+    std::vector<CloudSrc> clouds;
 };
 
 }  // namespace haf_host
@@ -202,7 +207,12 @@ struct haf_engine {
     // pinned staging block h_in has the same layout
     DevBuf<char> d_in;
     char *h_in = nullptr;
-    size_t in_hdr_cap = 0;          // bytes reserved for the two header arrays
+    size_t in_hdr_cap = 0;          // bytes reserved for the header arrays (CloudDev, RollGeo, FrameDev)
+    // haf_score_frames: the raw pixels of host depth frames, 2 or 4 bytes each, go through their own pinned block and device area
+    // (4 bytes x max_points, every frame at a multiple of 16 bytes); k_frame_points writes their points into the points area of d_in.
+    // Never converted inside the points area itself: a point's 12-byte slot overlaps raw pixels other lanes have not read yet
+    DevBuf<char> d_raw;
+    char *h_raw = nullptr;
     // ONE output block: [counters][roll records], fetched with a single device-to-host copy (d_counters / d_rec point into it)
     DevBuf<char> d_out;
     char *h_out = nullptr;
@@ -446,9 +456,12 @@ double sigma_upper_bound(const double *M, int n, int d);
 int build_tables(haf_engine *e);
 int alloc_buffers(haf_engine *e);
 // engine_request.cpp
+// (frames != nullptr: cloud b's points are frame b's, deprojected on the device; clouds[b] then only carries its point count)
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records);
-int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out);
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr);
+int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
+                     const haf_frame *frames = nullptr);
+int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

@@ -1,0 +1,21 @@
+// frames.h -- what the host units share about sensor frames (haf_frame, include/hafgrasp.h): the argument checks every entry point
+// applies to a frame's own fields, and the per-frame constants of the arithmetic (frame_points.h).  frames_host.cpp defines them and
+// needs neither HIP nor an engine.
+#pragma once
+#include "../../include/hafgrasp.h"
+#include "frame_points.h"
+
+#include <string>
+
+namespace haf {
+
+// bytes between two pixels of a row: 2 / 4 for the depth kinds, point_stride_bytes for XYZ; 0 for an unknown kind
+size_t frame_elem_bytes(const haf_frame &f);
+// bytes of a pixel the engine moves: 2 / 4 / 12
+size_t frame_pixel_bytes(int kind);
+// HAF_OK, HAF_E_ARG or HAF_E_CAPACITY with a message: every refusal of a frame that needs no engine
+int check_frame(const haf_frame &f, std::string &err);
+// ifx = 1.0f / fx, ify = 1.0f / fy: formed once per frame, here
+haf_frame_math::FrameMath frame_math(const haf_frame &f);
+
+}  // namespace haf

@@ -1,0 +1,133 @@
+// frames.hip -- k_frame_points<KIND>: the pixels of the sensor frames of a haf_score_frames batch -> packed base-frame xyz in the points
+// area of the request's input block, where a staged host cloud would lie (engine_request.cpp: upload_frames).  The arithmetic is
+// frame_points.h's, the same source haf_frame_points runs on the host: the two agree bit for bit (tests/test_frames_gpu.py).
+//
+// A streaming kernel, 2-4 bytes in and 12 out per pixel.  A lane owns a GROUP of consecutive points by flat index v * width + u: eight
+// of a U16 frame, four of an F32 or XYZ frame -- 16 bytes of pixels, 96 or 48 bytes of points.
+//   * loads: a group that lies inside one row at a 16-byte aligned address is ONE global_load_dwordx4 (neighbouring lanes read
+//     neighbouring 16 bytes); any other group -- a row's head or tail where the width is not a multiple of the group, a base or row stride
+//     that is not 16-byte aligned, the last group of the frame -- reads its pixels one by one, each from its own (row, column).  A 640-wide
+//     frame at an aligned base has no such group.  A packed XYZ frame (12-byte points, no row padding) is three dwordx4 loads per group
+//     whatever its width;
+//   * stores: a frame's points start at a multiple of four points from a 16-byte aligned base, so a whole group is 6 (3) aligned
+//     global_store_dwordx4; only the frame's last, partial group stores words.
+// A staged host XYZ frame is transformed IN PLACE (src == dst): a lane reads all of its own points before it writes any, and no lane
+// touches another's.  One launch per kind present in the batch covers every frame of the batch (grid.y); a block whose frame is of
+// another kind or ends before it returns at once.  The per-frame constants are wave-uniform: scalar loads.
+#include "device_common.h"
+#include "../../include/hafgrasp.h"
+
+namespace haf {
+
+using namespace haf_frame_math;
+
+constexpr int kFrameThreads = 256;
+// the frame's two pointers come out of the descriptor, where the compiler cannot see their address space: said here, so that the
+// accesses are global_load / global_store and not flat ones
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <class T> using global_ptr = __attribute__((address_space(1))) T *;
+template <class T> __device__ __forceinline__ global_ptr<T> as_global(const void *p) { return (global_ptr<T>)(uintptr_t)p; }
+template <int KIND> constexpr unsigned frame_group() { return KIND == HAF_FRAME_DEPTH_U16 ? 8u : 4u; }
+
+template <int KIND>
+__global__ __launch_bounds__(kFrameThreads) void k_frame_points(const FrameDev *__restrict__ frames)
+{
+    constexpr unsigned G = frame_group<KIND>();
+    const FrameDev &f = frames[blockIdx.y];
+    if (f.kind != KIND) return;
+    const unsigned n = (unsigned)f.n, W = (unsigned)f.width;
+    const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;      // (n < 2^31 and at most 2^11 points of slack: no wrap)
+    if (i0 >= n) return;
+    const unsigned v0 = i0 / W, u0 = i0 - v0 * W;
+    const bool whole = i0 + G <= n;
+    const char *src = static_cast<const char *>(f.src);
+    const unsigned long long rs = f.row_stride;
+    // the group's raw words first -- one wide load, or pixel by pixel from each one's own (row, column) -- then ONE pass of arithmetic
+    // over them; a pixel beyond the frame's end keeps a zero word and its point is never stored
+    constexpr unsigned RAW = KIND == HAF_FRAME_XYZ_F32 ? 3 * G : G;      // 32-bit words (a U16 sample per word)
+    unsigned raw[RAW] = {};
+    if constexpr (KIND == HAF_FRAME_XYZ_F32) {
+        const char *a = src + (size_t)i0 * 12;
+        if (whole && f.point_stride == 12u && rs == (unsigned long long)W * 12ull && (reinterpret_cast<uintptr_t>(a) & 15u) == 0) {
+            const global_ptr<const v4u> q = as_global<const v4u>(a);
+            const v4u w0 = q[0], w1 = q[1], w2 = q[2];
+            raw[0] = w0.x; raw[1] = w0.y; raw[2] = w0.z; raw[3] = w0.w; raw[4] = w1.x; raw[5] = w1.y; raw[6] = w1.z; raw[7] = w1.w;
+            raw[8] = w2.x; raw[9] = w2.y; raw[10] = w2.z; raw[11] = w2.w;
+        } else {
+            unsigned u = u0, v = v0;
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) {
+                if (i0 + k < n) {
+                    const global_ptr<const unsigned> s = as_global<const unsigned>(src + (size_t)v * rs + (size_t)u * f.point_stride);
+                    raw[3 * k] = s[0]; raw[3 * k + 1] = s[1]; raw[3 * k + 2] = s[2];
+                }
+                if (++u == W) { u = 0; v++; }
+            }
+        }
+    } else {
+        constexpr unsigned E = KIND == HAF_FRAME_DEPTH_U16 ? 2u : 4u;
+        const char *a = src + (size_t)v0 * rs + (size_t)u0 * E;
+        if (whole && u0 + G <= W && (reinterpret_cast<uintptr_t>(a) & 15u) == 0) {
+            const v4u w4 = *as_global<const v4u>(a);
+            const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) raw[k] = KIND == HAF_FRAME_DEPTH_U16 ? (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu : w[k];
+        } else {
+            unsigned u = u0, v = v0;
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) {
+                if (i0 + k < n) {
+                    const char *s = src + (size_t)v * rs + (size_t)u * E;
+                    if constexpr (KIND == HAF_FRAME_DEPTH_U16) raw[k] = *as_global<const uint16_t>(s);
+                    else raw[k] = *as_global<const unsigned>(s);
+                }
+                if (++u == W) { u = 0; v++; }
+            }
+        }
+    }
+    float p[G * 3];
+    {
+        unsigned u = u0, v = v0;
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) {
+            if constexpr (KIND == HAF_FRAME_DEPTH_U16) point_u16(f.m, u, v, (uint16_t)raw[k], p + 3 * k);
+            else if constexpr (KIND == HAF_FRAME_DEPTH_F32) point_f32(f.m, u, v, __uint_as_float(raw[k]), p + 3 * k);
+            else point_xyz(f.m, __uint_as_float(raw[3 * k]), __uint_as_float(raw[3 * k + 1]), __uint_as_float(raw[3 * k + 2]), p + 3 * k);
+            if (++u == W) { u = 0; v++; }
+        }
+    }
+
+    const global_ptr<float> dst = as_global<float>(f.dst + (size_t)i0 * 3);
+    if (whole) {
+        const global_ptr<v4f> o = as_global<v4f>(f.dst + (size_t)i0 * 3);
+#pragma unroll
+        for (unsigned j = 0; j < G * 3 / 4; j++) o[j] = v4f{p[4 * j], p[4 * j + 1], p[4 * j + 2], p[4 * j + 3]};
+    } else {
+#pragma unroll
+        for (unsigned k = 0; k < G; k++)
+            if (i0 + k < n) { dst[3 * k] = p[3 * k]; dst[3 * k + 1] = p[3 * k + 1]; dst[3 * k + 2] = p[3 * k + 2]; }
+    }
+}
+
+template <int KIND> static void launch_kind(const FrameDev *frames_dev, const FrameDev *frames_host, int n_frames, hipStream_t s)
+{
+    constexpr unsigned G = frame_group<KIND>();
+    unsigned groups = 0;
+    for (int b = 0; b < n_frames; b++)
+        if (frames_host[b].kind == KIND) groups = std::max(groups, ((unsigned)frames_host[b].n + G - 1) / G);
+    if (!groups) return;
+    for (int b0 = 0; b0 < n_frames; b0 += 65535) {            // (grid.y holds 65535 frames)
+        const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads, (unsigned)std::min(65535, n_frames - b0));
+        hipLaunchKernelGGL(k_frame_points<KIND>, grid, dim3(kFrameThreads), 0, s, frames_dev + b0);
+    }
+}
+
+void launch_frame_points(const FrameDev *frames_dev, const FrameDev *frames_host, int n_frames, hipStream_t s)
+{
+    launch_kind<HAF_FRAME_DEPTH_U16>(frames_dev, frames_host, n_frames, s);
+    launch_kind<HAF_FRAME_DEPTH_F32>(frames_dev, frames_host, n_frames, s);
+    launch_kind<HAF_FRAME_XYZ_F32>(frames_dev, frames_host, n_frames, s);
+}
+
+}  // namespace haf

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "frame_points.h"
 
 namespace haf {
 
@@ -249,6 +250,18 @@ struct CloudDev {
     int bucket_off;
 };
 
+// per sensor frame of a haf_score_frames batch (frames.hip): where its pixels lie and where its points go.  The array rides in the
+// request's header block behind the RollGeo array.  dst is 16-byte aligned (the points of a frame start at a multiple of four points)
+struct FrameDev {
+    const void *src;                 // first pixel: the raw area (staged host depth frames), dst itself (staged host XYZ frames: in place), or the caller's device memory
+    float *dst;                      // packed xyz, width * height points: CloudDev::xyz of the same index
+    unsigned long long row_stride;   // bytes between rows of src
+    unsigned point_stride;           // bytes between pixels of a row
+    int width, n;                    // n = width * height
+    int kind;                        // HAF_FRAME_*
+    haf_frame_math::FrameMath m;
+};
+
 // per (cloud, roll): rows 0..2 of the fp32 transform (server.cpp:483) and the rotated-rectangle scalars of
 // pnt_in_box (server.cpp:679-696), all computed on the host with the reference's float/double mix
 struct RollGeo {
@@ -472,6 +485,9 @@ void launch_recheck_mfma(const float *ii, const int *evalcell, const FeatDesc *f
 constexpr int kRecheckPartRows = 2 * 8 + 1;       // part64: [2 * kMSplit + 1][flag_cap] doubles (partial sums + |x|^2)
 void launch_vote(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
                  int *rowmax, RollRecordDev *rec, Dims d, hipStream_t s);
+// sensor frames -> base-frame points (frames.hip): one launch per kind present in the batch, every frame of that kind in it
+void launch_frame_points(const FrameDev *frames_dev, const FrameDev *frames_host, int n_frames, hipStream_t s);
+
 // ranked grasp candidates (topgrasps.hip, haf_top_grasps): per (cloud, roll) hdr[4] = {kept, the greedy sequence may go on, the roll's
 // n_evals, its top vote} and cand[D] = the first D entries of the roll's in-roll greedy sequence.  scratch: n_slots x 2 x slot_words
 // 64-bit words (slot_words >= H*W), one slot per workgroup

@@ -351,4 +351,48 @@ bool load_pcd(const std::string &path, std::vector<float> &xyz, std::string &err
     return false;
 }
 
+bool load_pgm16(const std::string &path, std::vector<unsigned short> &depth, int &width, int &height, std::string &err)
+{
+    std::ifstream in(path.c_str(), std::ios::binary);
+    if (!in) { err = "cannot open " + path; return false; }
+    std::stringstream ss;
+    ss << in.rdbuf();
+    const std::string raw = ss.str();
+    if (raw.size() < 2 || raw[0] != 'P' || raw[1] != '5') { err = "PGM: not a binary PGM (P5) file: " + path; return false; }
+    // width, height, maxval: decimal tokens separated by white space, '#' starts a comment that runs to the end of its line; ONE
+    // white-space character ends the header
+    size_t pos = 2;
+    long val[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++) {
+        for (;;) {
+            while (pos < raw.size() && isspace((unsigned char)raw[pos])) pos++;
+            if (pos < raw.size() && raw[pos] == '#') { while (pos < raw.size() && raw[pos] != '\n' && raw[pos] != '\r') pos++; continue; }
+            break;
+        }
+        const size_t start = pos;
+        long v = 0;
+        while (pos < raw.size() && raw[pos] >= '0' && raw[pos] <= '9') {
+            if (pos - start >= 9) { err = "PGM: header number out of range in " + path; return false; }      // (< 10^9: no overflow)
+            v = v * 10 + (raw[pos++] - '0');
+        }
+        if (pos == start) { err = "PGM: truncated or malformed header in " + path; return false; }
+        val[k] = v;
+    }
+    if (pos >= raw.size() || !isspace((unsigned char)raw[pos])) { err = "PGM: truncated or malformed header in " + path; return false; }
+    pos++;
+    if (val[0] < 1 || val[1] < 1 || val[0] > kMaxPgmPixels || val[1] > kMaxPgmPixels || val[0] * val[1] > kMaxPgmPixels) {
+        err = "PGM: dimensions " + std::to_string(val[0]) + " x " + std::to_string(val[1]) + " out of range in " + path; return false;
+    }
+    if (val[2] < 256 || val[2] > 65535) { err = "PGM: maxval " + std::to_string(val[2]) + " is not that of 16-bit samples (256..65535)"; return false; }
+    const size_t n = (size_t)val[0] * (size_t)val[1], remain = raw.size() - pos;
+    if (remain < n * 2) { err = "PGM: truncated (" + std::to_string(remain) + " bytes of samples, " + std::to_string(n * 2) + " expected)"; return false; }
+    if (remain > n * 2) { err = "PGM: " + std::to_string(remain - n * 2) + " bytes behind the last sample"; return false; }
+    depth.resize(n);
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(raw.data()) + pos;
+    for (size_t i = 0; i < n; i++) depth[i] = (unsigned short)((p[2 * i] << 8) | p[2 * i + 1]);
+    width = (int)val[0];
+    height = (int)val[1];
+    return true;
+}
+
 }  // namespace haf

@@ -48,4 +48,8 @@ bool load_model(const std::string &path, SvmModel &m, std::string &err);
 // PCD v0.7: ascii, binary, binary_compressed (LZF, SoA); x, y, z must be 4-byte floats
 bool load_pcd(const std::string &path, std::vector<float> &xyz, std::string &err);
 
+// Binary PGM ("P5") with 16-bit big-endian samples, maxval 256..65535: a 16UC1 depth image as a file (haf_pgm16_load)
+constexpr long kMaxPgmPixels = 1L << 28;
+bool load_pgm16(const std::string &path, std::vector<unsigned short> &depth, int &width, int &height, std::string &err);
+
 }  // namespace haf

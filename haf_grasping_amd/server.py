@@ -77,6 +77,17 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
+    def execute_frame(self, goal: GraspInputMsg, frame) -> GraspOutputMsg:
+        """execute() for a goal whose cloud is still what the sensor delivered: `frame` is a capi.depth_frame (a 16UC1 / 32FC1 depth
+        image with the camera's K and the sensor-to-base transform) or a capi.xyz_frame (an organised cloud in the sensor frame);
+        goal.input_pc is not read.  The engine deprojects and transforms on the device (haf_score_frames): the step the reference does
+        with pcl_ros::transformPointCloud before the hot path (server.cpp:307-316).  top_grasps() works afterwards as after execute()."""
+        if goal.goal_frame_id:
+            self.base_frame_id = goal.goal_frame_id
+        out = self.engine.score_frames([frame], [goal.to_c()])[0]
+        return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
+                              out["averaged_grasp_point"], out["approach_vector"], out["roll"])
+
     def top_grasps(self, k=None, **params):
         """Ranked top-k grasp candidates of the last execute() (haf_top_grasps: in-roll and cross-roll suppression, rank 1 = the
         result execute() returned when show_only_best_grasp is off) as GraspOutputMsgs, best first.  params: min_vote, cell_radius,

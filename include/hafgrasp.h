@@ -78,7 +78,7 @@ typedef struct haf_config {
                                       * measurements and for a deployment that prefers the ten-step kernels it has run so far          */
 
 /* GraspInput (reference msg/GraspInput.msg:3-15) minus the cloud and the frame id: the cloud is passed
- * separately, already in the base frame (server.cpp:316). */
+ * separately, already in the base frame (server.cpp:316) -- or as a sensor frame the engine puts there (haf_frame, below). */
 typedef struct haf_grasp_input {
     double  grasp_area_center[3];        /* geometry_msgs/Point, metres (258-260)                         */
     float   grasp_area_length_x;         /* "in m" in the .msg, used as integer cm incl. the +14 border    */
@@ -325,6 +325,60 @@ int haf_screen_low_rank(const haf_engine *e, int32_t *available, int32_t *rank, 
  * Returns a malloc'ed packed xyz array (free with haf_free) and the point count. */
 int  haf_pcd_load(const char *path, float **xyz, size_t *n_points, char *err, size_t err_cap);
 void haf_free(void *p);
+
+/* ---- sensor frames: what a driver hands over, deprojected and put into the base frame ON THE DEVICE (csrc/frames.hip) ---------
+ * haf_score / haf_score_batch take packed xyz already in the base frame, i.e. the cloud AFTER read_pc_cb's
+ * pcl_ros::transformPointCloud (server.cpp:307-316).  A haf_frame is the step before: a 16-bit or float depth image with the pinhole
+ * intrinsics of its camera, or an organised sensor-frame cloud, plus the sensor-to-base transform (rows 0..2 of the TF matrix).  The
+ * engine uploads the raw pixels (2 or 4 bytes each instead of 12) and one kernel writes the base-frame points where a staged host
+ * cloud would lie; everything downstream is the cloud path, unchanged.
+ *
+ * The arithmetic, per pixel (u, v) -- point index v * width + u -- every step ONE correctly rounded fp32 operation, in this order,
+ * never a fused multiply-add (csrc/frame_points.h, compiled for host and device):
+ *   U16:   invalid when d == 0; else z = (float)d * depth_scale
+ *   F32:   invalid when d is not finite or d <= 0; else z = d * depth_scale
+ *   both:  invalid when z is not finite, z < min_depth (if min_depth > 0) or z > max_depth (if max_depth > 0)
+ *          xc = (((float)u - cx) * ifx) * z,  yc = (((float)v - cy) * ify) * z,  ifx = 1.0f / fx and ify = 1.0f / fy once per frame
+ *   XYZ:   (xc, yc, z) = the three floats at the pixel; invalid when any is not finite; intrinsics, scale and limits are ignored
+ *   base:  p[r] = ((t[r][0] * xc + t[r][1] * yc) + t[r][2] * z) + t[r][3], left to right, t = sensor_to_base
+ *   an invalid pixel is the point (NaN, NaN, NaN), all three words 0x7FC00000; so is any component whose result is a NaN.
+ * An invalid pixel still yields a point (NaN never passes the binning comparisons), so order and count are those of the pixels:
+ * the engine bins width * height points per frame, it does not compact them.  With HAF_FRAME_XYZ_F32 the transform takes the place of
+ * pcl_ros::transformPointCloud; PCL's own operation order is not pinned here, the order above is the definition.  No lens distortion. */
+enum { HAF_FRAME_DEPTH_U16 = 0, HAF_FRAME_DEPTH_F32 = 1, HAF_FRAME_XYZ_F32 = 2 };
+typedef struct haf_frame {
+    const void *data;
+    int32_t kind, width, height;
+    int32_t on_device;           /* 0 host, 1 device-resident (caller has synchronised its writer); 2 is HAF_E_ARG */
+    size_t  row_stride_bytes;    /* >= width * element size, a multiple of the element size */
+    size_t  point_stride_bytes;  /* XYZ only: >= 12, multiple of 4 (16 = pcl::PointXYZ, 32 = PointXYZRGB) */
+    float   fx, fy, cx, cy;      /* pinhole intrinsics in pixels; depth kinds only */
+    float   depth_scale;         /* metres per unit: 0.001 for the usual 16UC1 millimetres, 1 for 32FC1 metres */
+    float   min_depth, max_depth;/* metres; 0 = no limit on that side; depth kinds only */
+    float   sensor_to_base[12];  /* rows 0..2 of the 4x4, row-major: the TF step of server.cpp:316 */
+} haf_frame;
+/* (element size: 2 / 4 bytes for the depth kinds, point_stride_bytes for XYZ, whose data must be 4-byte aligned) */
+
+void haf_frame_default(haf_frame *f);                       /* identity pose, scale 0.001, no limits, zeros elsewhere */
+/* The HOST definition of record of the arithmetic above: width * height * 3 floats from a host frame (on_device = 0).  No device, no
+ * engine; HAF_E_ARG for a frame haf_score_frames would refuse for its own fields. */
+int  haf_frame_points(const haf_frame *f, float *xyz);
+/* haf_score_batch with frames in place of clouds: in[b] and out[b] per frame, the same last-batch state afterwards (haf_top_grasps,
+ * haf_get_roll_grid, haf_debug_fetch*, haf_last_*, haf_get_stage_ms; the deprojection kernel counts as HAF_ST_UPLOAD).  Checked before
+ * any device work -- HAF_E_ARG: a null argument, n < 1, a null data pointer, an unknown kind, on_device not 0 or 1, a non-positive
+ * dimension, a stride too small or misaligned, data not aligned to its element, for the depth kinds fx or fy zero or not finite, a cx,
+ * cy, limit or matrix entry that is not finite, depth_scale not finite or not positive; HAF_E_CAPACITY: a frame of more than INT32_MAX
+ * pixels, sum of width * height > max_points, n > max_clouds.  A refused call leaves the engine as it was.  An engine created with
+ * HAF_FLAG_PROBABILITY takes frames like any other (only the source of the cloud differs).  Not through haf_score_rolls or the sharded
+ * multi-GPU calls. */
+int  haf_score_frames(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out);
+/* Cloud `cloud` of the last scored batch as the device kernels read it: n_points >= its point count, packed xyz (HAF_FLAG_KEEP_DEBUG).
+ * Frames and staged host clouds; HAF_E_ARG for a device-resident xyz cloud, which the engine never copies. */
+int  haf_debug_fetch_points(haf_engine *e, int32_t cloud, float *xyz, size_t n_points);
+/* Binary PGM ("P5") with 16-bit samples, the usual file form of a 16UC1 depth image: maxval 256..65535, big-endian samples, '#' comments
+ * in the header.  Returns a malloc'ed width * height array in host byte order (free with haf_free); HAF_E_IO and a message for anything
+ * else, a truncated or over-long file included. */
+int  haf_pgm16_load(const char *path, uint16_t **depth, int32_t *width, int32_t *height, char *err, size_t err_cap);
 
 int haf_abi_version(void);
 
