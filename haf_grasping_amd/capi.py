@@ -137,6 +137,9 @@ def _bind(path, testing):
     L.haf_frame_points.argtypes = [C.POINTER(Frame), C.c_void_p]
     L.haf_score_frames.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
     L.haf_debug_fetch_points.argtypes = [E, C.c_int32, C.c_void_p, C.c_size_t]
+    L.haf_view_points.argtypes = [C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.haf_score_views.argtypes = [E, C.c_int32, C.POINTER(C.c_int32), C.POINTER(Frame), C.POINTER(GraspInput), C.POINTER(GraspOutput),
+                                  C.POINTER(C.c_int64)]
     L.haf_pgm16_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p,
                                  C.c_size_t]
     # several GPUs in one process (csrc/multi.cpp)
@@ -376,6 +379,24 @@ def frame_points(frame):
     return out
 
 
+MAX_VIEWS = 16
+
+
+def view_points(frames):
+    """haf_view_points: the host definition of record of a request's fused cloud -- the valid points of `frames` (host Frames), frame
+    after frame in pixel order -> float32 [n_valid, 3]"""
+    L, n = lib(), len(frames)
+    arr = (Frame * max(1, n))(*frames)
+    cnt = C.c_size_t()
+    rc = L.haf_view_points(arr, n, None, 0, C.byref(cnt))
+    if rc == HAF_OK:
+        out = np.empty((cnt.value, 3), np.float32)
+        rc = L.haf_view_points(arr, n, out.ctypes.data, cnt.value, C.byref(cnt))
+    if rc != HAF_OK:
+        raise HafError(rc, (L.haf_last_error(None) or b"").decode())
+    return out
+
+
 class Engine:
     """Owns one haf_engine handle (one GPU)."""
 
@@ -510,6 +531,26 @@ class Engine:
         self._check(self._L.haf_score_frames(self._h, n, arr, gi, out))
         self._last_points = [f.width * f.height for f in frames]
         return [output_to_dict(o) for o in out]
+
+    def score_views(self, view_sets, inputs):
+        """haf_score_views: per request a list of Frames (its views, fused on the device into one cloud of their valid points) and one
+        GraspInput -> (outputs, valid points per request)"""
+        n = len(view_sets)
+        flat = [f for vs in view_sets for f in vs]
+        arr = (Frame * max(1, len(flat)))(*flat)
+        per = (C.c_int32 * max(1, n))(*[len(vs) for vs in view_sets])
+        gi = (GraspInput * max(1, n))(*inputs)
+        out = (GraspOutput * max(1, n))()
+        cnt = (C.c_int64 * max(1, n))()
+        self._check(self._L.haf_score_views(self._h, n, per, arr, gi, out, cnt))
+        counts = [int(c) for c in cnt[:n]]
+        self._last_points = [max(0, c) for c in counts]
+        return [output_to_dict(o) for o in out[:n]], counts
+
+    def fetch_points(self, cloud, n_points=None):
+        """debug_points under the name of the C function: after score_views the request's fused cloud, its valid points in the order
+        the device compacted them (unspecified; sort the rows to compare)"""
+        return self.debug_points(cloud, n_points)
 
     def debug_points(self, cloud, n_points=None):
         """haf_debug_fetch_points: cloud `cloud` of the last batch as the kernels read it -> float32 [n_points, 3] (KEEP_DEBUG).

@@ -24,7 +24,12 @@
 //                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
 //                                     --sensor-pose with the 12 floats of rows 0..2 of the sensor-to-base matrix (default identity).
 //                                     --hypotheses and --top-k work with it (the per-roll hypotheses are then read from the ranked
-//                                     candidates of haf_top_grasps, one per roll: the same records through the same pose)
+//                                     candidates of haf_top_grasps, one per roll: the same records through the same pose).
+//                                     A repeated --depth opens a further VIEW of the one request (a second camera, or a second pose):
+//                                     the valid points of all views are fused into one cloud on the device (haf_score_views).
+//                                     --intrinsics, --depth-scale, --depth-range and --sensor-pose apply to the view opened last; a view
+//                                     inherits the previous view's values until it overrides them; given before the first --depth
+//                                     they apply to the first view
 #include "../../include/hafgrasp.h"
 
 #include "shim_core.h"
@@ -95,6 +100,7 @@ static void usage()
             "usage: haf_grasp_cli --features F --range R --model M [options] cloud.pcd [cloud2.pcd ...]\n"
             "       haf_grasp_cli --features F --range R --model M [options] --depth FILE.pgm --intrinsics fx fy cx cy\n"
             "                     [--depth-scale S] [--depth-range MIN MAX] [--sensor-pose m00 m01 ... m23]\n"
+            "                     [--depth FILE2.pgm [its --intrinsics, --depth-scale, --depth-range, --sensor-pose] ...]\n"
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
@@ -123,20 +129,38 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 // the overall best.  A roll's hypothesis is its record through haf_roll_pose's pose; haf_score_frames keeps the records on the
 // device, and haf_top_grasps hands them back: with an in-roll radius of the whole grid and no cross-roll suppression its candidates
 // are exactly one per roll whose vote exceeds graspval_th, eval = vote - 20 (> 10, so the reference's clamp never acts).
-static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::string &path, haf_frame frame,
+// Several --depth: the views of the one goal, fused on the device (haf_score_views); one --depth is haf_score_frames as ever.
+struct DepthView { std::string path; haf_frame frame; };
+static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::vector<DepthView> &views,
                      bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist)
 {
-    uint16_t *depth = nullptr;
+    std::vector<uint16_t *> images;
+    std::vector<haf_frame> frames;
+    auto release = [&]() { for (uint16_t *p : images) haf_free(p); };
     char err[256];
-    if (haf_pgm16_load(path.c_str(), &depth, &frame.width, &frame.height, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", path.c_str(), err); return 1; }
-    frame.kind = HAF_FRAME_DEPTH_U16;
-    frame.data = depth;
-    frame.row_stride_bytes = (size_t)frame.width * 2;
+    for (const DepthView &v : views) {
+        haf_frame f = v.frame;
+        uint16_t *depth = nullptr;
+        if (haf_pgm16_load(v.path.c_str(), &depth, &f.width, &f.height, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", v.path.c_str(), err); release(); return 1; }
+        images.push_back(depth);
+        f.kind = HAF_FRAME_DEPTH_U16;
+        f.data = depth;
+        f.row_stride_bytes = (size_t)f.width * 2;
+        frames.push_back(f);
+    }
+    // what the messages below are about: the file of a single view; every file of a fused request ("a.pgm + b.pgm"), in view order, so
+    // that the library's "request 0 view V" finds its file
+    std::string path = views[0].path;
+    for (size_t v = 1; v < views.size(); v++) path += " + " + views[v].path;
+    long long pixels = 0;
+    for (const haf_frame &f : frames) pixels += (long long)f.width * f.height;
     int rc = 0;
     haf_grasp_output out;
-    if (haf_score_frames(eng, 1, &frame, &in, &out) != HAF_OK) {
+    const int32_t n_views = (int32_t)frames.size();
+    int64_t n_points = 0;
+    if ((n_views == 1 ? haf_score_frames(eng, 1, frames.data(), &in, &out) : haf_score_views(eng, 1, &n_views, frames.data(), &in, &out, &n_points)) != HAF_OK) {
         fprintf(stderr, "%s: %s\n", path.c_str(), haf_last_error(eng));
-        haf_free(depth);
+        release();
         return 1;
     }
     if (hypotheses && !in.show_only_best_grasp) {
@@ -159,9 +183,13 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     }
     printf("%s\n", hafshim::hypothesis_string(out, cfg.roll_step_deg).c_str());
     if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc);
-    fprintf(stderr, "%s: %d x %d pixels, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", path.c_str(),
-            frame.width, frame.height, (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
-    haf_free(depth);
+    char size[96];
+    if (n_views == 1) snprintf(size, sizeof size, "%d x %d pixels", frames[0].width, frames[0].height);
+    else snprintf(size, sizeof size, "%lld pixels in %d views", pixels, n_views);
+    fprintf(stderr, "%s: %s, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", path.c_str(), size,
+            (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
+    if (n_views > 1) fprintf(stderr, "%d views fused: %lld valid points\n", n_views, (long long)n_points);
+    release();
     return rc;
 }
 
@@ -179,9 +207,9 @@ int main(int argc, char **argv)
     int gpus = 0, shards_per_gpu = 1;
     std::string shard = "rolls";
     std::string features, range, model;
-    std::string depth_file;                        // --depth: a 16-bit PGM in place of the .pcd arguments
+    std::vector<DepthView> views;                  // --depth: 16-bit PGMs in place of the .pcd arguments, the views of one request
     bool have_intrinsics = false;
-    haf_frame frame;
+    haf_frame frame;                               // the sensor options as they stand: what the next view opened inherits
     haf_frame_default(&frame);
     int first_cloud = argc;
     for (int i = 1; i < argc; i++) {
@@ -207,7 +235,7 @@ int main(int argc, char **argv)
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }
         else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
-        else if (a == "--depth") { need(1); depth_file = argv[++i]; }
+        else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
         else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
         else if (a == "--depth-range") { need(2); frame.min_depth = (float)atof(argv[++i]); frame.max_depth = (float)atof(argv[++i]); }
@@ -218,9 +246,10 @@ int main(int argc, char **argv)
         else if (a == "--shards-per-gpu") { need(1); shards_per_gpu = atoi(argv[++i]); if (shards_per_gpu < 1) shards_per_gpu = 1; }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { first_cloud = i; break; }
+        if (!views.empty()) views.back().frame = frame;       // (a sensor option applies to the view opened last)
     }
-    const bool from_depth = !depth_file.empty();
-    if (features.empty() || range.empty() || model.empty() || (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0) : first_cloud >= argc)) { usage(); return 2; }
+    const bool from_depth = !views.empty();
+    if (features.empty() || range.empty() || model.empty() || (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);
     cfg.feature_file = features.c_str();
@@ -243,7 +272,7 @@ int main(int argc, char **argv)
         goal.gripper_opening_width = in.gripper_opening_width;
         haf_grasp_input gin;
         hafshim::goal_to_input(goal, &gin);
-        rc = run_depth(eng, cfg, gin, depth_file, frame, hypotheses, top_k, top_radius, top_rolls, top_dist);
+        rc = run_depth(eng, cfg, gin, views, hypotheses, top_k, top_radius, top_rolls, top_dist);
         haf_destroy(eng);
         return rc;
     }

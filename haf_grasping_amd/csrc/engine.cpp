@@ -64,7 +64,7 @@ void haf_destroy(haf_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &r : e->host_regs) (void)hipHostUnregister((void *)r.first);
     e->host_regs.clear();
-    e->d_in.release(); e->d_raw.release(); e->d_out.release(); e->d_sorted.release(); e->d_bkt.release(); e->d_heights.release(); e->d_rowsum.release(); e->d_inexact.release();
+    e->d_in.release(); e->d_raw.release(); e->d_raw_xyz.release(); e->d_out.release(); e->d_sorted.release(); e->d_bkt.release(); e->d_heights.release(); e->d_rowsum.release(); e->d_inexact.release();
     e->d_ii.release(); e->d_mask.release(); e->d_rowcount.release(); e->d_rowoff.release(); e->d_brcount.release();
     e->d_evalcell.release(); e->d_flag_list.release(); e->d_X.release(); e->d_ax.release();
     e->d_dec.release(); e->d_svt.release(); e->d_svt_h.release(); e->d_labels.release(); e->d_dec_exact.release(); e->d_strict_terms.release(); e->d_part64.release(); e->d_dec_exact2.release(); e->d_flag2_list.release(); e->d_x64.release(); e->d_sv64.release();
@@ -81,6 +81,7 @@ void haf_destroy(haf_engine *e)
     e->d_brslot.release(); e->d_tier_words.release(); e->d_t1_flags.release(); e->d_lr_btiles.release(); e->d_svt_lr.release(); e->d_lr_btiles_in.release(); e->d_corr_lrp.release(); e->d_iiabs.release();
     if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_raw) (void)hipHostFree(e->h_raw);
+    if (e->h_raw_xyz) (void)hipHostFree(e->h_raw_xyz);
     if (e->h_out) (void)hipHostFree(e->h_out);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -503,6 +504,18 @@ int haf_score_batch(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, co
 int haf_score_frames(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out)
 {
     return guarded(e ? &e->error : nullptr, [&] { return score_frames_impl(e, n, frames, in, out); });
+}
+
+int haf_score_views(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
+                    haf_grasp_output *out, int64_t *n_points)
+{
+    return guarded(e ? &e->error : nullptr, [&] { return score_views_impl(e, n, views_per_request, frames, in, out, n_points); });
+}
+
+// (no engine to carry the message: it goes where haf_create's does, haf_last_error(NULL))
+int haf_view_points(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid)
+{
+    return guarded(&g_create_error, [&] { return view_points_impl(frames, n_views, xyz, cap_points, n_valid, g_create_error); });
 }
 
 int haf_score(haf_engine *e, const haf_cloud *cloud, const haf_grasp_input *in, haf_grasp_output *out)

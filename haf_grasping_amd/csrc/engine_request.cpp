@@ -259,8 +259,12 @@ struct Request {
     int B = 0, R = 0, max_n = 0;
     long total_n = 0;
     bool bucket_ok = true;
-    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x B])[points of the host clouds]
+    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x n_frames])[points of the host clouds]
     const haf_frame *frames = nullptr;   // haf_score_frames: cloud b's points are frame b's, written by k_frame_points
+    // haf_score_views: cloud b's points are the valid points of views[b] consecutive frames, compacted by k_view_points; the host then
+    // sizes everything by the UPPER bound clouds[b].n_points = the pixels of those views, the live count is CloudDev::n on the device
+    const int32_t *views = nullptr;
+    int n_frames = 0;                    // entries of frames / h_frames: B, or the sum of views
     FrameDev *h_frames = nullptr;
     const FrameDev *d_frames = nullptr;
     std::vector<LastCall::CloudSrc> src; // where every cloud's points lie (LastCall::clouds)
@@ -315,7 +319,9 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     const int B = q.B, R = q.R;
     const size_t geo_off = ((size_t)B * sizeof(CloudDev) + 15) / 16 * 16;
     const size_t frames_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
-    q.pts_off = frames_off + (q.frames ? ((size_t)B * sizeof(FrameDev) + 15) / 16 * 16 : 0);
+    q.n_frames = 0;
+    for (int b = 0; q.frames && b < B; b++) q.n_frames += q.views ? q.views[b] : 1;
+    q.pts_off = frames_off + ((size_t)q.n_frames * sizeof(FrameDev) + 15) / 16 * 16;
     q.h_frames = reinterpret_cast<FrameDev *>(e->h_in + frames_off);
     q.d_frames = reinterpret_cast<const FrameDev *>(e->d_in.p + frames_off);
     q.src.assign((size_t)B, LastCall::CloudSrc{});
@@ -333,7 +339,7 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
         cd.sorted_off = (int)q.total_n;
         cd.bucket_off = b * e->bkt_ints;
         q.total_n += (long)clouds[b].n_points;
-        cd.n = (int)clouds[b].n_points;
+        cd.n = q.views ? 0 : (int)clouds[b].n_points;    // (views: the kernels count the valid points)
         if (clouds[b].on_device == 1) {
             cd.xyz = clouds[b].xyz;
             cd.stride = (int)clouds[b].stride_floats;
@@ -346,26 +352,32 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
         }
     }
     // the frames' descriptors: device-resident frames are read where they lie; a host XYZ frame is packed where its points go and
-    // transformed in place; a host depth frame's pixels go through the raw area, every frame at a multiple of 16 bytes
-    size_t raw = 0;
-    for (int b = 0; q.frames && b < B; b++) {
-        const haf_frame &f = q.frames[b];
-        FrameDev &fd = q.h_frames[b];
-        fd.dst = const_cast<float *>(q.h_clouds[b].xyz);
-        fd.width = f.width;
-        fd.n = q.h_clouds[b].n;
-        fd.kind = f.kind;
-        fd.m = frame_math(f);
-        const size_t px = frame_pixel_bytes(f.kind);
-        if (f.on_device == 1) {
-            fd.src = f.data;
-            fd.row_stride = f.row_stride_bytes;
-            fd.point_stride = (unsigned)frame_elem_bytes(f);
-        } else {
-            fd.src = f.kind == HAF_FRAME_XYZ_F32 ? reinterpret_cast<const char *>(fd.dst) : e->d_raw.p + raw;
-            fd.row_stride = (unsigned long long)f.width * px;
-            fd.point_stride = (unsigned)px;
-            if (f.kind != HAF_FRAME_XYZ_F32) raw += ((size_t)fd.n * px + 15) / 16 * 16;
+    // transformed in place; a host depth frame's pixels go through the raw area, every frame at a multiple of 16 bytes.
+    // Views: compaction writes where other lanes have not read yet, so a host XYZ view is NOT staged in the points area but in a raw
+    // area of its own (d_raw_xyz); the views of a request share its region and its counter
+    size_t raw = 0, raw_xyz = 0;
+    for (int b = 0, k = 0; q.frames && b < B; b++) {
+        for (int v = 0; v < (q.views ? q.views[b] : 1); v++, k++) {
+            const haf_frame &f = q.frames[k];
+            FrameDev &fd = q.h_frames[k];
+            fd.dst = const_cast<float *>(q.h_clouds[b].xyz);
+            fd.count = q.views ? const_cast<int *>(&q.d_clouds[b].n) : nullptr;
+            fd.width = f.width;
+            fd.n = f.width * f.height;
+            fd.kind = f.kind;
+            fd.m = frame_math(f);
+            const size_t px = frame_pixel_bytes(f.kind);
+            if (f.on_device == 1) {
+                fd.src = f.data;
+                fd.row_stride = f.row_stride_bytes;
+                fd.point_stride = (unsigned)frame_elem_bytes(f);
+            } else {
+                const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
+                fd.src = !xyz ? e->d_raw.p + raw : q.views ? e->d_raw_xyz.p + raw_xyz : reinterpret_cast<const char *>(fd.dst);
+                fd.row_stride = (unsigned long long)f.width * px;
+                fd.point_stride = (unsigned)px;
+                (xyz ? raw_xyz : raw) += ((size_t)fd.n * px + 15) / 16 * 16;
+            }
         }
     }
 }
@@ -378,12 +390,12 @@ static int upload_frames(haf_engine *e, const Request &q)
     constexpr size_t kPiece = 256 * 1024;
     const hipStream_t s = q.s;
     HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, q.pts_off, hipMemcpyHostToDevice, s));      // the three header arrays
-    for (int b = 0; b < q.B; b++) {
+    for (int b = 0; b < q.n_frames; b++) {
         const haf_frame &f = q.frames[b];
         if (f.on_device == 1) continue;
         const FrameDev &fd = q.h_frames[b];
         const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
-        char *const dev = xyz ? e->d_in.p : e->d_raw.p, *const host = xyz ? e->h_in : e->h_raw;
+        char *const dev = !xyz ? e->d_raw.p : q.views ? e->d_raw_xyz.p : e->d_in.p, *const host = !xyz ? e->h_raw : q.views ? e->h_raw_xyz : e->h_in;
         const size_t at = (size_t)(static_cast<const char *>(fd.src) - dev);      // the frame's place in its block, device and pinned alike
         const size_t row_bytes = (size_t)f.width * frame_pixel_bytes(f.kind);
         size_t staged = 0, sent = 0;
@@ -399,7 +411,14 @@ static int upload_frames(haf_engine *e, const Request &q)
             }
         }
     }
-    launch_frame_points(q.d_frames, q.h_frames, q.B, s);
+    if (!q.views) {
+        launch_frame_points(q.d_frames, q.h_frames, q.B, s);
+        return HAF_OK;
+    }
+    launch_view_points(q.d_frames, q.h_frames, q.n_frames, s);
+    // the live counts, for n_points and the debug fetch: the CloudDev array back into the pinned header, where the host's copy of
+    // CloudDev::n lies.  The call's own synchronisation (vote_and_wait) completes it: no wait here
+    HIPCHK(e, hipMemcpyAsync(e->h_in, e->d_in.p, (size_t)q.B * sizeof(CloudDev), hipMemcpyDeviceToHost, s));
     return HAF_OK;
 }
 
@@ -863,6 +882,7 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
     l.i8 = q.i8_used;
     l.inputs.assign(in, in + q.B);
     l.clouds = q.src;
+    for (int b = 0; q.views && b < q.B; b++) l.clouds[(size_t)b].n = (size_t)q.h_clouds[b].n;      // (upload_frames: the live counts)
     // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
     if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), q.s) == hipSuccess) e->counters_clean = true;
     // (the tier lists hold every evaluation of a request: list_cap >= last.evals >= last.flagged >= last.flagged2)
@@ -886,11 +906,12 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
 }
 
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames)
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames, const int32_t *views)
 {
     if (!e) return HAF_E_ARG;
     Request q;
     q.frames = frames;
+    q.views = views;
     int rc = check_request(e, n_clouds, clouds, in, roll_first, roll_count, records, q);
     if (rc != HAF_OK) return rc;
     pack_headers(e, clouds, in, roll_first, q);
@@ -918,7 +939,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         // height grids of this call may miss points.  Serve the request -- and this engine from now on -- with k_bin instead.
         e->no_bucket_sort = true;
         e->counters_clean = false;
-        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames);
+        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames, views);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
     if (mode == MODE_SCREEN && !e->prob_mode && !q.direct && (rc = adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
@@ -926,7 +947,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
 }
 
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames)
+                     const haf_frame *frames, const int32_t *views)
 {
     if (!e) return HAF_E_ARG;
     if (!out) return fail(e, HAF_E_ARG, "haf_score_batch: null output");
@@ -939,7 +960,7 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     if (none_runs)
         e->last = LastCall{};
     else if (frames)
-        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames);
+        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames, views);
     else
         rc = haf_score_rolls(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data());
     if (rc != HAF_OK) return rc;
@@ -971,6 +992,55 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
         clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[b].data), px, 3, 0};
     }
     return score_batch_impl(e, n, clouds.data(), in, out, frames);
+}
+
+// haf_score_views: every refusal before any device work, then the batch path with the views of request b as the source of cloud b's
+// points.  clouds[b].n_points is the UPPER bound, the pixels of the request's views: it sizes the request's region, sorted_off, max_n,
+// total_n and every launch grid; the kernels stop at the live count on the device
+int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
+                     haf_grasp_output *out, int64_t *n_points)
+{
+    if (!e) return HAF_E_ARG;
+    if (!views_per_request || !frames || !in || !out || n < 1) return fail(e, HAF_E_ARG, "haf_score_views: null or empty argument");
+    if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, "haf_score_views: more requests than max_clouds");
+    for (int b = 0; b < n; b++)
+        if (views_per_request[b] < 1 || views_per_request[b] > HAF_MAX_VIEWS)
+            return fail(e, HAF_E_ARG, "haf_score_views: request " + std::to_string(b) + ": view count outside [1, HAF_MAX_VIEWS]");
+    int64_t total = 0;
+    bool host_xyz = false;
+    std::vector<haf_cloud> clouds((size_t)n);
+    for (int b = 0, k = 0; b < n; b++) {
+        size_t upper = 0;
+        for (int v = 0; v < views_per_request[b]; v++, k++) {
+            std::string msg;
+            const int rc = check_frame(frames[k], msg);
+            if (rc != HAF_OK) return fail(e, rc, "haf_score_views: request " + std::to_string(b) + " view " + std::to_string(v) + ": " + msg);
+            const size_t px = (size_t)frames[k].width * (size_t)frames[k].height;
+            total += (int64_t)px;
+            if (total > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, "haf_score_views: more pixels than max_points");
+            upper += px;
+            host_xyz = host_xyz || (frames[k].kind == HAF_FRAME_XYZ_F32 && frames[k].on_device == 0);
+        }
+        // (xyz is never read on this path, as in score_frames_impl)
+        clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[k - 1].data), upper, 3, 0};
+    }
+    if (host_xyz && !e->d_raw_xyz.p) {
+        // the raw area of staged host XYZ views (12 bytes x max_points, every view at a multiple of 16 bytes) and its pinned twin: an
+        // engine that never sees such a view never pays for them
+        HIPCHK(e, hipSetDevice(e->cfg.device));
+        const size_t bytes = (size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16;
+        HIPCHK(e, e->d_raw_xyz.alloc(bytes));
+        if (hipHostMalloc((void **)&e->h_raw_xyz, bytes) != hipSuccess) {
+            e->d_raw_xyz.release();
+            e->h_raw_xyz = nullptr;
+            return fail(e, HAF_E_DEVICE, "haf_score_views: no pinned memory for the raw area of host XYZ views");
+        }
+    }
+    const int rc = score_batch_impl(e, n, clouds.data(), in, out, frames, views_per_request);
+    if (rc != HAF_OK) return rc;
+    // (a batch whose every budget is negative runs nothing, on the device either: no count exists)
+    for (int b = 0; n_points && b < n; b++) n_points[b] = (size_t)b < e->last.clouds.size() ? (int64_t)e->last.clouds[(size_t)b].n : -1;
+    return HAF_OK;
 }
 
 }  // namespace haf_host

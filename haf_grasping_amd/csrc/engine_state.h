@@ -213,6 +213,10 @@ struct haf_engine {
     // Never converted inside the points area itself: a point's 12-byte slot overlaps raw pixels other lanes have not read yet
     DevBuf<char> d_raw;
     char *h_raw = nullptr;
+    // haf_score_views: the raw area of staged host XYZ views, 12 bytes x max_points, allocated by the first call that has one.  Such a
+    // view cannot be converted in place as haf_score_frames does: compaction writes where other lanes have not read yet
+    DevBuf<char> d_raw_xyz;
+    char *h_raw_xyz = nullptr;
     // ONE output block: [counters][roll records], fetched with a single device-to-host copy (d_counters / d_rec point into it)
     DevBuf<char> d_out;
     char *h_out = nullptr;
@@ -458,10 +462,13 @@ int alloc_buffers(haf_engine *e);
 // engine_request.cpp
 // (frames != nullptr: cloud b's points are frame b's, deprojected on the device; clouds[b] then only carries its point count)
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr);
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr, const int32_t *views = nullptr);
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames = nullptr);
+                     const haf_frame *frames = nullptr, const int32_t *views = nullptr);
 int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out);
+// (views != nullptr: cloud b's points are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count)
+int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
+                     haf_grasp_output *out, int64_t *n_points);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

@@ -1114,10 +1114,10 @@ int alloc_buffers(haf_engine *e)
     // and their window-by-window consumers rely on exactly that (a counter never exceeds the list).
     if (const char *v = test_env("HAF_FLAG0_CAP")) e->flag0_cap = mode == MODE_SCREEN ? (int)std::min<long>(e->list_cap, std::max(256, atoi(v) / 256 * 256)) : 0;
     bool ok = true;
-    e->in_hdr_cap = (B * sizeof(CloudDev) + 15) / 16 * 16 + (B * R * sizeof(RollGeo) + 15) / 16 * 16 + (B * sizeof(FrameDev) + 15) / 16 * 16;
+    e->in_hdr_cap = (B * sizeof(CloudDev) + 15) / 16 * 16 + (B * R * sizeof(RollGeo) + 15) / 16 * 16 + (B * HAF_MAX_VIEWS * sizeof(FrameDev) + 15) / 16 * 16;     // (haf_score_views: up to HAF_MAX_VIEWS descriptors per request)
     // (+ 48 bytes per cloud: the points of a frame start at a multiple of four points, pack_headers)
     ok &= hipSuccess == e->d_in.alloc(e->in_hdr_cap + (size_t)c.max_points * 3 * sizeof(float) + B * 48);
-    ok &= hipSuccess == e->d_raw.alloc((size_t)c.max_points * 4 + B * 16);
+    ok &= hipSuccess == e->d_raw.alloc((size_t)c.max_points * 4 + B * HAF_MAX_VIEWS * 16);
     ok &= hipSuccess == e->d_out.alloc(kCntBytes + B * R * sizeof(RollRecordDev));
     if (ok) {
         e->d_counters.p = reinterpret_cast<int *>(e->d_out.p);

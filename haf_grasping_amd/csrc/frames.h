@@ -17,5 +17,7 @@ size_t frame_pixel_bytes(int kind);
 int check_frame(const haf_frame &f, std::string &err);
 // ifx = 1.0f / fx, ify = 1.0f / fy: formed once per frame, here
 haf_frame_math::FrameMath frame_math(const haf_frame &f);
+// haf_view_points (include/hafgrasp.h) with its refusal's text: the valid points of host frames, in order
+int view_points_impl(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid, std::string &err);
 
 }  // namespace haf

@@ -102,6 +102,52 @@ static int frame_points_impl(const haf_frame *f, float *xyz)
     return HAF_OK;
 }
 
+// haf_view_points: frame after frame, pixel after pixel as frame_points_impl walks them, the points whose three words are finite kept
+// in that order.  Every view is checked before the first point is written
+int view_points_impl(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid, std::string &err)
+{
+    if (!frames || !n_valid) { err = "haf_view_points: null argument"; return HAF_E_ARG; }
+    if (n_views < 1 || n_views > HAF_MAX_VIEWS) { err = "haf_view_points: view count outside [1, HAF_MAX_VIEWS]"; return HAF_E_ARG; }
+    for (int v = 0; v < n_views; v++) {
+        std::string msg;
+        int rc = check_frame(frames[v], msg);
+        if (rc == HAF_OK && frames[v].on_device != 0) { rc = HAF_E_ARG; msg = "haf_frame: host memory only"; }
+        if (rc != HAF_OK) { err = "haf_view_points: view " + std::to_string(v) + ": " + msg; return rc; }
+    }
+    using haf_frame_math::f_finite;
+    size_t n = 0;
+    for (int v = 0; v < n_views; v++) {
+        const haf_frame &f = frames[v];
+        const FrameMath m = frame_math(f);
+        for (uint32_t r = 0; r < (uint32_t)f.height; r++) {
+            const char *src = static_cast<const char *>(f.data) + (size_t)r * f.row_stride_bytes;
+            for (uint32_t u = 0; u < (uint32_t)f.width; u++) {
+                float p[3], dst[3];
+                if (f.kind == HAF_FRAME_DEPTH_U16) {
+                    uint16_t d;
+                    memcpy(&d, src + (size_t)u * 2, 2);
+                    haf_frame_math::point_u16(m, u, r, d, dst);
+                } else if (f.kind == HAF_FRAME_DEPTH_F32) {
+                    float d;
+                    memcpy(&d, src + (size_t)u * 4, 4);
+                    haf_frame_math::point_f32(m, u, r, d, dst);
+                } else {
+                    memcpy(p, src + (size_t)u * f.point_stride_bytes, 12);
+                    haf_frame_math::point_xyz(m, p[0], p[1], p[2], dst);
+                }
+                if (!(f_finite(dst[0]) && f_finite(dst[1]) && f_finite(dst[2]))) continue;
+                if (xyz) {
+                    if (n >= cap_points) { err = "haf_view_points: xyz holds fewer points than the views have valid ones"; return HAF_E_CAPACITY; }
+                    memcpy(xyz + n * 3, dst, 12);
+                }
+                n++;
+            }
+        }
+    }
+    *n_valid = n;
+    return HAF_OK;
+}
+
 static int pgm16_load_impl(const char *path, uint16_t **depth, int32_t *width, int32_t *height, char *err, size_t err_cap)
 {
     if (!path || !depth || !width || !height) return HAF_E_ARG;

@@ -251,10 +251,13 @@ struct CloudDev {
 };
 
 // per sensor frame of a haf_score_frames batch (frames.hip): where its pixels lie and where its points go.  The array rides in the
-// request's header block behind the RollGeo array.  dst is 16-byte aligned (the points of a frame start at a multiple of four points)
+// request's header block behind the RollGeo array.  dst is 16-byte aligned (the points of a frame start at a multiple of four points).
+// haf_score_views: one entry per VIEW; dst is the start of the request's region (all its views share it) and count the request's live
+// point counter on the device, CloudDev::n, which k_view_points advances (null on the haf_score_frames path)
 struct FrameDev {
     const void *src;                 // first pixel: the raw area (staged host depth frames), dst itself (staged host XYZ frames: in place), or the caller's device memory
     float *dst;                      // packed xyz, width * height points: CloudDev::xyz of the same index
+    int *count;                      // views only: CloudDev::n of the request
     unsigned long long row_stride;   // bytes between rows of src
     unsigned point_stride;           // bytes between pixels of a row
     int width, n;                    // n = width * height
@@ -487,6 +490,9 @@ void launch_vote(const int8_t *labels, const float *heights, const int *brcount,
                  int *rowmax, RollRecordDev *rec, Dims d, hipStream_t s);
 // sensor frames -> base-frame points (frames.hip): one launch per kind present in the batch, every frame of that kind in it
 void launch_frame_points(const FrameDev *frames_dev, const FrameDev *frames_host, int n_frames, hipStream_t s);
+// the views of a haf_score_views batch -> the VALID base-frame points of every request, compacted from the start of its region; the
+// request's CloudDev::n (uploaded as 0) counts them.  One launch per kind present, every view of that kind in it
+void launch_view_points(const FrameDev *views_dev, const FrameDev *views_host, int n_views, hipStream_t s);
 
 // ranked grasp candidates (topgrasps.hip, haf_top_grasps): per (cloud, roll) hdr[4] = {kept, the greedy sequence may go on, the roll's
 // n_evals, its top vote} and cand[D] = the first D entries of the roll's in-roll greedy sequence.  scratch: n_slots x 2 x slot_words

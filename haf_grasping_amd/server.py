@@ -88,6 +88,17 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
+    def execute_views(self, goal: GraspInputMsg, frames) -> GraspOutputMsg:
+        """execute_frame() for a goal seen by several sensors, or by one sensor from several poses: `frames` is a list of up to
+        capi.MAX_VIEWS capi.depth_frame / capi.xyz_frame, each with its own intrinsics and sensor-to-base transform.  The engine fuses
+        the valid points of all of them into one cloud on the device (haf_score_views); the result is execute()'s on
+        capi.view_points(frames)."""
+        if goal.goal_frame_id:
+            self.base_frame_id = goal.goal_frame_id
+        out = self.engine.score_views([list(frames)], [goal.to_c()])[0][0]
+        return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
+                              out["averaged_grasp_point"], out["approach_vector"], out["roll"])
+
     def top_grasps(self, k=None, **params):
         """Ranked top-k grasp candidates of the last execute() (haf_top_grasps: in-roll and cross-roll suppression, rank 1 = the
         result execute() returned when show_only_best_grasp is off) as GraspOutputMsgs, best first.  params: min_vote, cell_radius,

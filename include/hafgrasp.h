@@ -375,6 +375,33 @@ int  haf_score_frames(haf_engine *e, int32_t n, const haf_frame *frames, const h
 /* Cloud `cloud` of the last scored batch as the device kernels read it: n_points >= its point count, packed xyz (HAF_FLAG_KEEP_DEBUG).
  * Frames and staged host clouds; HAF_E_ARG for a device-resident xyz cloud, which the engine never copies. */
 int  haf_debug_fetch_points(haf_engine *e, int32_t cloud, float *xyz, size_t n_points);
+/* ---- several views of one scene as ONE cloud (csrc/frames.hip: k_view_points) ------------------------------------------------
+ * A second camera, or a second pose of the same one, fills the holes one view leaves behind every object.  The fused cloud of a
+ * request is the set of VALID points of its views, formed on the device: the points are compacted as they are deprojected, so the
+ * later stages read only them (haf_score_frames keeps width * height points per frame, invalid ones included).
+ *
+ * Host definition of record: the VALID points of frames[0..n_views) -- frame after frame, pixel order inside a frame, each point
+ * exactly haf_frame_points' words -- packed into xyz (capacity cap_points; NULL = count only); *n_valid = their number.
+ * A pixel is dropped when haf_frame_points gives it any component that is not finite (the all-NaN invalid pixel included).
+ * Why that rule changes no result: in every binning kernel and in the bucket sort (k_bin, k_bin_lds, k_bin_tiles, k_small_pre,
+ * point_bucket) a point with a NaN or infinite component makes the transformed px or py NaN or infinite, and every range test on
+ * them fails; such a point can never reach a height grid.
+ * Host frames only (on_device = 0).  HAF_E_ARG: a null frames or n_valid, n_views < 1 or > HAF_MAX_VIEWS, a frame haf_frame_points
+ * would refuse; HAF_E_CAPACITY: a frame of more than INT32_MAX pixels, more valid points than cap_points (nothing is written past
+ * it).  Every view is checked before a point is written; the message, which names the view, is haf_last_error(NULL)'s. */
+#define HAF_MAX_VIEWS 16
+int  haf_view_points(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid);
+/* n requests; request b fuses frames[first_b .. first_b + views_per_request[b]), first_b = sum of the counts before it.
+ * Identical in every output and in all last-batch state to haf_score_batch on the clouds haf_view_points defines, except that the
+ * ORDER of the points haf_debug_fetch_points returns is unspecified (their multiset and their count are exact).
+ * n_points (may be NULL): valid points per request (-1 when every budget of the batch is negative: no roll runs, nothing is counted).
+ * The views of one request may mix kinds, host and device residence, sizes, intrinsics and poses.  Checked before any device work,
+ * a refused call leaves the engine as it was -- per frame as haf_score_frames checks it, the message naming the request and the
+ * view; HAF_E_ARG: a null argument (n_points excepted), n < 1, a view count < 1 or > HAF_MAX_VIEWS; HAF_E_CAPACITY: n > max_clouds,
+ * the sum of all pixels > max_points.  HAF_FLAG_PROBABILITY engines take views like any other.  Not through haf_score_rolls or the
+ * sharded multi-GPU calls.  The first call with a host XYZ view allocates that kind's raw area (12 bytes x max_points). */
+int  haf_score_views(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames,
+                     const haf_grasp_input *in, haf_grasp_output *out, int64_t *n_points);
 /* Binary PGM ("P5") with 16-bit samples, the usual file form of a 16UC1 depth image: maxval 256..65535, big-endian samples, '#' comments
  * in the header.  Returns a malloc'ed width * height array in host byte order (free with haf_free); HAF_E_IO and a message for anything
  * else, a truncated or over-long file included. */

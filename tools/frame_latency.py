@@ -26,6 +26,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=200)
@@ -39,27 +40,13 @@ if a.baseline_lib:
     os.environ["HAF_LIB"] = os.path.abspath(a.baseline_lib)
 
 import pcdio  # noqa: E402
+from render import render_depth  # noqa: E402  (tools/render.py)
 from haf_grasping_amd import capi  # noqa: E402
 
 D = os.path.join(ROOT, "tests", "golden", "data")
 FEAT, RNG, MODEL = os.path.join(D, "Features.txt"), os.path.join(D, "range21062012_allfeatures"), os.path.join(ROOT, "tests", "golden", "surrogate.model")
 W, H, FX, FY, CX, CY = 640, 480, 525.0, 525.0, 319.5, 239.5
 S2B = np.array([1, 0, 0, 0.13, 0, -1, 0, 0.2, 0, 0, -1, 0.9], np.float32)
-
-
-def render_depth(xyz):
-    """nearest depth per pixel, millimetres as uint16, of a pinhole camera at S2B"""
-    m = S2B.astype(np.float64).reshape(3, 4)
-    pc = (np.asarray(xyz, np.float64) - m[:, 3]) @ m[:, :3]
-    pc = pc[np.isfinite(pc).all(axis=1) & (pc[:, 2] > 0.05)]
-    u = np.rint(FX * pc[:, 0] / pc[:, 2] + CX).astype(np.int64)
-    v = np.rint(FY * pc[:, 1] / pc[:, 2] + CY).astype(np.int64)
-    mm = np.rint(pc[:, 2] * 1000.0).astype(np.int64)
-    ok = (u >= 0) & (u < W) & (v >= 0) & (v < H) & (mm > 0) & (mm < 65536)
-    img = np.full(W * H, 65536, np.int64)
-    np.minimum.at(img, v[ok] * W + u[ok], mm[ok])
-    img[img == 65536] = 0
-    return img.astype(np.uint16).reshape(H, W)
 
 
 def host_points(depth):
@@ -97,7 +84,7 @@ def stats(ns):
 
 
 xyz = pcdio.load_pcd(os.path.join(D, "table1_mult_obj_rcs_1428580506606673.pcd"))
-depth = render_depth(xyz)
+depth = render_depth(xyz, S2B, W, H, FX, FY, CX, CY)
 organised = host_points(depth)
 valid = np.ascontiguousarray(organised[np.isfinite(organised).all(axis=1)])
 metres = depth.astype(np.float32) * np.float32(0.001)
