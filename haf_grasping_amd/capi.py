@@ -16,6 +16,7 @@ FLAG_KEEP_DEBUG, FLAG_PROFILE, FLAG_FP32_MFMA, FLAG_SPLIT_F16, FLAG_PROBABILITY,
 DBG_HEIGHTS, DBG_INTEGRAL, DBG_MASK, DBG_LABELS, DBG_DECISION, DBG_TRANSFORM, DBG_SCREEN_MARGIN, DBG_PROBABILITY, DBG_GRASPSGRID = range(9)
 SHARD_ROLLS, SHARD_CLOUDS = 0, 1
 FRAME_DEPTH_U16, FRAME_DEPTH_F32, FRAME_XYZ_F32 = 0, 1, 2
+MAP_NO_CELL = -32768                 # HAF_MAP_NO_CELL: a grasp-map pixel no roll has a cell for
 STAGES = ["upload", "bin", "integral", "mask", "features", "svm", "refine", "recheck", "vote", "download"]
 
 
@@ -142,6 +143,13 @@ def _bind(path, testing):
                                   C.POINTER(C.c_int64)]
     L.haf_pgm16_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p,
                                  C.c_size_t]
+    L.haf_point_cells.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.haf_grasp_map_ref.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Frame), C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+    L.haf_grasp_map.argtypes = [E, C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.haf_cell_pose.argtypes = [E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GraspCandidate)]
+    L.haf_grasp_map_best.argtypes = [E, C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(GraspCandidate),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -397,6 +405,33 @@ def view_points(frames):
     return out
 
 
+def point_cells(cfg, grasp_input, roll, xyz):
+    """haf_point_cells: the cell row * grid_w + col of every point of float32 [N, >= 3] `xyz` under roll `roll` (global index) of
+    `grasp_input` on the grids of Config `cfg`, or -1 -> int32 [N].  Host definition of record: no device, no engine."""
+    a = np.ascontiguousarray(xyz, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[1] >= 3
+    out = np.empty(a.shape[0], np.int32)
+    rc = lib().haf_point_cells(C.byref(cfg), C.byref(grasp_input), roll, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_point_cells refused its arguments")
+    return out
+
+
+def grasp_map_ref(cfg, grasp_input, roll_first, eval_grids, frame, want=("vote", "roll", "cell")):
+    """haf_grasp_map_ref: the host definition of record of a grasp map.  eval_grids: float32 [roll_count, grid_h, grid_w] as
+    Engine.roll_grid returns them for the rolls roll_first .. of one request; frame: a host Frame
+    -> dict(vote int16 [height, width], roll int16, cell int32), only the images named in `want`."""
+    g = np.ascontiguousarray(eval_grids, dtype=np.float32).reshape(-1, cfg.grid_h, cfg.grid_w)
+    shape = (max(0, frame.height), max(0, frame.width))
+    out = {k: np.empty(shape, np.int32 if k == "cell" else np.int16) for k in want}
+    ptr = lambda k: out[k].ctypes.data if k in out else None
+    rc = lib().haf_grasp_map_ref(C.byref(cfg), C.byref(grasp_input), roll_first, g.shape[0], g.ctypes.data if g.size else None, C.byref(frame),
+                                 ptr("vote"), ptr("roll"), ptr("cell"))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_grasp_map_ref refused its arguments")
+    return out
+
+
 class Engine:
     """Owns one haf_engine handle (one GPU)."""
 
@@ -597,6 +632,42 @@ class Engine:
         n = (C.c_int32 * cap)(*([-1] * cap))          # the call fills one entry per cloud of the last batch
         self._check(self._L.haf_top_grasps(self._h, C.byref(p), out, n))
         return [[candidate_to_dict(out[b * p.k + i]) for i in range(n[b])] for b in range(cap) if n[b] >= 0]
+
+    def grasp_map(self, request, frame, want=("vote", "roll", "cell"), device_out=None):
+        """haf_grasp_map: the last batch's votes in the pixels of `frame` (a Frame, host or device-resident, scored or not)
+        -> dict(vote int16 [height, width], roll int16 (global roll index, -1 without a cell), cell int32 (row * grid_w + col, or -1)),
+        only the images named in `want`; a pixel without a cell has vote MAP_NO_CELL.  device_out: dict name -> device pointer of a
+        packed width * height image; the images are then written there and None is returned."""
+        if device_out is not None:
+            self._check(self._L.haf_grasp_map(self._h, request, C.byref(frame), device_out.get("vote"), device_out.get("roll"),
+                                              device_out.get("cell"), 1))
+            return None
+        shape = (max(0, frame.height), max(0, frame.width))
+        out = {k: np.empty(shape, np.int32 if k == "cell" else np.int16) for k in want}
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._L.haf_grasp_map(self._h, request, C.byref(frame), ptr("vote"), ptr("roll"), ptr("cell"), 0))
+        return out
+
+    def cell_pose(self, request, roll, row, col):
+        """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""
+        c = GraspCandidate()
+        self._check(self._L.haf_cell_pose(self._h, request, roll, row, col, C.byref(c)))
+        return candidate_to_dict(c)
+
+    def best_in_mask(self, request, frame, mask=None, min_vote=1):
+        """haf_grasp_map_best: the best pixel of grasp_map(request, frame) among those `mask` (uint8 [height, width], None: all) selects
+        and whose vote is >= min_vote -- vote descending, roll, v, u ascending -> (candidate dict, u, v), or None when none qualifies"""
+        ptr, stride, keep = None, 0, None
+        if mask is not None:
+            keep = np.asarray(mask)
+            assert keep.dtype == np.uint8 and keep.shape == (frame.height, frame.width) and (keep.shape[1] == 1 or keep.strides[1] == 1)
+            if keep.shape[0] > 1 and keep.strides[0] < keep.shape[1]:
+                keep = np.ascontiguousarray(keep)
+            ptr, stride = keep.ctypes.data, (keep.strides[0] if keep.shape[0] > 1 else keep.shape[1])
+        c, u, v, found = GraspCandidate(), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        self._check(self._L.haf_grasp_map_best(self._h, request, C.byref(frame), ptr, stride, min_vote, C.byref(c), C.byref(u), C.byref(v),
+                                               C.byref(found)))
+        return (candidate_to_dict(c), u.value, v.value) if found.value else None
 
     def debug_attr(self, cloud, roll):
         """Attribute records of the masked cells of (cloud, roll): cells [n, 2], records [n, 324], computed [n]."""

@@ -19,6 +19,12 @@
 //   --top-k N                         after the normal output, "top <rank> <hypothesis>" for the N best distinct candidates of the
 //                                     goal (haf_top_grasps); --top-radius cells, --top-rolls steps, --top-dist metres set its suppression
 //                                     (server.cpp:962-969), in its string format
+//   --map-out PREFIX                  with --depth: the goal's votes in the pixels of the (first) depth image (haf_grasp_map), written as
+//                                     PREFIX.vote.pgm and PREFIX.roll.pgm: 16-bit binary PGMs of the image's size, sample = value + 32768
+//                                     (a pixel without a cell: vote -32768 -> 0, roll -1 -> 32767)
+//   --mask FILE.pgm                   with --depth: an 8-bit binary PGM of the image's size; after the normal output one line
+//                                     "mask <u> <v> <hypothesis>" for the best pixel under its non-zero samples whose vote is at
+//                                     least --mask-min-vote (default 1), or "mask none" (haf_grasp_map_best)
 //   --depth FILE.pgm --intrinsics fx fy cx cy   in place of the .pcd arguments: a 16-bit depth image (binary PGM) as the sensor
 //                                     delivers it, deprojected and transformed on the device (haf_score_frames); optional
 //                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
@@ -104,6 +110,7 @@ static void usage()
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
+            "  --map-out PREFIX  --mask FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -131,8 +138,86 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 // are exactly one per roll whose vote exceeds graspval_th, eval = vote - 20 (> 10, so the reference's clamp never acts).
 // Several --depth: the views of the one goal, fused on the device (haf_score_views); one --depth is haf_score_frames as ever.
 struct DepthView { std::string path; haf_frame frame; };
+// --map-out / --mask: the goal's votes in the pixels of the FIRST view (haf_grasp_map, haf_grasp_map_best)
+struct MapOptions { std::string out_prefix, mask_path; int min_vote = 1; };
+
+static bool write_pgm16(const std::string &path, const int16_t *img, int w, int h)
+{
+    FILE *fp = fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    fprintf(fp, "P5\n%d %d\n65535\n", w, h);
+    std::vector<unsigned char> row((size_t)w * 2);
+    bool ok = true;
+    for (int v = 0; v < h && ok; v++) {
+        for (int u = 0; u < w; u++) {
+            const unsigned x = (unsigned)((int)img[(size_t)v * w + u] + 32768);
+            row[2 * (size_t)u] = (unsigned char)(x >> 8);
+            row[2 * (size_t)u + 1] = (unsigned char)(x & 255u);
+        }
+        ok = fwrite(row.data(), 1, row.size(), fp) == row.size();
+    }
+    return fclose(fp) == 0 && ok;
+}
+
+// binary PGM with 8-bit samples (maxval <= 255), '#' comments in the header
+static bool read_pgm8(const std::string &path, std::vector<uint8_t> &img, int &w, int &h)
+{
+    FILE *fp = fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    auto token = [&](long &val) {
+        int c = fgetc(fp);
+        for (;;) {
+            while (c == ' ' || c == '\t' || c == '\n' || c == '\r') c = fgetc(fp);
+            if (c != '#') break;
+            while (c != '\n' && c != EOF) c = fgetc(fp);
+        }
+        if (c < '0' || c > '9') return false;
+        val = 0;
+        while (c >= '0' && c <= '9' && val < (1L << 30)) { val = val * 10 + (c - '0'); c = fgetc(fp); }
+        return c == ' ' || c == '\t' || c == '\n' || c == '\r';
+    };
+    long W = 0, H = 0, maxval = 0;
+    bool ok = fgetc(fp) == 'P' && fgetc(fp) == '5' && token(W) && token(H) && token(maxval) && W >= 1 && H >= 1 && maxval >= 1 && maxval <= 255 &&
+              W * H <= (1L << 30);
+    if (ok) {
+        img.resize((size_t)(W * H));
+        ok = fread(img.data(), 1, img.size(), fp) == img.size();
+        w = (int)W; h = (int)H;
+    }
+    fclose(fp);
+    return ok;
+}
+
+static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, const MapOptions &mo)
+{
+    const size_t n = (size_t)f.width * (size_t)f.height;
+    if (!mo.out_prefix.empty()) {
+        std::vector<int16_t> vote(n), roll(n);
+        if (haf_grasp_map(eng, 0, &f, vote.data(), roll.data(), nullptr, 0) != HAF_OK) { fprintf(stderr, "--map-out: %s\n", haf_last_error(eng)); return 1; }
+        if (!write_pgm16(mo.out_prefix + ".vote.pgm", vote.data(), f.width, f.height) || !write_pgm16(mo.out_prefix + ".roll.pgm", roll.data(), f.width, f.height)) {
+            fprintf(stderr, "--map-out: cannot write %s.vote.pgm / .roll.pgm\n", mo.out_prefix.c_str());
+            return 1;
+        }
+    }
+    if (!mo.mask_path.empty()) {
+        std::vector<uint8_t> mask;
+        int w = 0, h = 0;
+        if (!read_pgm8(mo.mask_path, mask, w, h)) { fprintf(stderr, "%s: not a binary 8-bit PGM\n", mo.mask_path.c_str()); return 1; }
+        if (w != f.width || h != f.height) { fprintf(stderr, "%s: %d x %d, the depth image has %d x %d\n", mo.mask_path.c_str(), w, h, f.width, f.height); return 1; }
+        haf_grasp_candidate best;
+        int32_t u = -1, v = -1, found = 0;
+        if (haf_grasp_map_best(eng, 0, &f, mask.data(), (size_t)w, mo.min_vote, &best, &u, &v, &found) != HAF_OK) {
+            fprintf(stderr, "--mask: %s\n", haf_last_error(eng));
+            return 1;
+        }
+        if (found) printf("mask %d %d %s\n", u, v, hafshim::hypothesis_string(best.grasp, cfg.roll_step_deg).c_str());
+        else printf("mask none\n");
+    }
+    return 0;
+}
+
 static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::vector<DepthView> &views,
-                     bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist)
+                     bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist, const MapOptions &mo)
 {
     std::vector<uint16_t *> images;
     std::vector<haf_frame> frames;
@@ -183,6 +268,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     }
     printf("%s\n", hafshim::hypothesis_string(out, cfg.roll_step_deg).c_str());
     if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc);
+    if (run_map(eng, cfg, frames[0], mo) != 0) rc = 1;
     char size[96];
     if (n_views == 1) snprintf(size, sizeof size, "%d x %d pixels", frames[0].width, frames[0].height);
     else snprintf(size, sizeof size, "%lld pixels in %d views", pixels, n_views);
@@ -209,6 +295,7 @@ int main(int argc, char **argv)
     std::string features, range, model;
     std::vector<DepthView> views;                  // --depth: 16-bit PGMs in place of the .pcd arguments, the views of one request
     bool have_intrinsics = false;
+    MapOptions map_opt;
     haf_frame frame;                               // the sensor options as they stand: what the next view opened inherits
     haf_frame_default(&frame);
     int first_cloud = argc;
@@ -235,6 +322,9 @@ int main(int argc, char **argv)
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }
         else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
+        else if (a == "--map-out") { need(1); map_opt.out_prefix = argv[++i]; }
+        else if (a == "--mask") { need(1); map_opt.mask_path = argv[++i]; }
+        else if (a == "--mask-min-vote") { need(1); map_opt.min_vote = atoi(argv[++i]); }
         else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
         else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
@@ -249,7 +339,8 @@ int main(int argc, char **argv)
         if (!views.empty()) views.back().frame = frame;       // (a sensor option applies to the view opened last)
     }
     const bool from_depth = !views.empty();
-    if (features.empty() || range.empty() || model.empty() || (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
+    if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty())) ||
+        (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);
     cfg.feature_file = features.c_str();
@@ -272,7 +363,7 @@ int main(int argc, char **argv)
         goal.gripper_opening_width = in.gripper_opening_width;
         haf_grasp_input gin;
         hafshim::goal_to_input(goal, &gin);
-        rc = run_depth(eng, cfg, gin, views, hypotheses, top_k, top_radius, top_rolls, top_dist);
+        rc = run_depth(eng, cfg, gin, views, hypotheses, top_k, top_radius, top_rolls, top_dist, map_opt);
         haf_destroy(eng);
         return rc;
     }

@@ -78,6 +78,8 @@ void haf_destroy(haf_engine *e)
     e->d_svt0_cr.release(); e->d_fd_slot_cr.release(); e->d_sd_cr.release(); e->d_sd3_cr.release(); e->d_corr_cr.release();
     e->d_top_scratch.release(); e->d_top_out.release();
     if (e->h_top_out) (void)hipHostFree(e->h_top_out);
+    e->d_map.release();
+    if (e->h_map) (void)hipHostFree(e->h_map);
     e->d_brslot.release(); e->d_tier_words.release(); e->d_t1_flags.release(); e->d_lr_btiles.release(); e->d_svt_lr.release(); e->d_lr_btiles_in.release(); e->d_corr_lrp.release(); e->d_iiabs.release();
     if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_raw) (void)hipHostFree(e->h_raw);

@@ -1,0 +1,279 @@
+// engine_graspmap.cpp -- haf_grasp_map, haf_cell_pose and haf_grasp_map_best: the votes of the last scored batch in the pixels of a
+// sensor frame (include/hafgrasp.h).  The device pass (graspmap.hip) reads the vote grids that batch left on the device and, for
+// haf_cell_pose, its height grids and records; nothing here writes to any of them, to the request's input block or to the raw areas
+// of haf_score_frames / haf_score_views: the frame's pixels, the roll transforms, the images and the mask live in one block of their
+// own (haf_engine::d_map).  The roll transforms are recomputed from the inputs the batch was scored with (LastCall::inputs) through
+// fill_roll_geo: the header of the request's input block may have been overwritten since.  Built with -ffp-contract=off.
+#include "engine_state.h"
+
+namespace haf_host {
+
+using haf_cell_math::CellGeo;
+
+namespace {
+
+constexpr size_t kMapHdr = 64;            // [0] the best key of k_map_best, [16] the record of k_cell_record
+constexpr size_t kMapRecOff = 16;
+
+size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+
+struct MapLayout {
+    size_t geo = 0, vote = 0, roll = 0, cell = 0, mask = 0, raw = 0, total = 0;
+};
+
+// the block for images of n_img pixels, a mask of n_mask bytes and raw_bytes of a staged host frame's pixels (each may be 0)
+MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t raw_bytes)
+{
+    MapLayout l;
+    l.geo = kMapHdr;
+    l.vote = l.geo + (size_t)std::max(1, e->max_rolls) * sizeof(CellGeo);
+    l.roll = l.vote + up16(n_img * 2);
+    l.cell = l.roll + up16(n_img * 2);
+    l.mask = l.cell + up16(n_img * 4);
+    l.raw = l.mask + up16(n_mask);
+    l.total = l.raw + up16(raw_bytes);
+    return l;
+}
+
+int ensure_map(haf_engine *e, size_t bytes)
+{
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    if (e->d_map.n >= bytes && e->h_map_cap >= bytes) return HAF_OK;
+    e->d_map.release();
+    if (e->h_map) (void)hipHostFree(e->h_map);
+    e->h_map = nullptr;
+    e->h_map_cap = 0;
+    HIPCHK(e, e->d_map.alloc(bytes));
+    HIPCHK(e, hipHostMalloc((void **)&e->h_map, bytes, hipHostMallocDefault));
+    e->h_map_cap = bytes;
+    return HAF_OK;
+}
+
+// what every entry point here asks of the last batch; *rolls = the rolls that ran for the request (0: its budget was negative)
+int check_last(haf_engine *e, const char *who, int32_t request, int *rolls)
+{
+    const std::string name(who);
+    if (e->prob_mode) return fail(e, HAF_E_ARG, name + ": not available with HAF_FLAG_PROBABILITY (fp32 votes)");
+    const LastCall &last = e->last;
+    if (last.B < 1 || last.R < 1 || (int)last.inputs.size() < last.B) return fail(e, HAF_E_ARG, name + ": no scored batch");
+    if (request < 0 || request >= last.B) return fail(e, HAF_E_ARG, name + ": request not in the last scored batch");
+    *rolls = (int)last.inputs[(size_t)request].max_calculation_time < 0 ? 0 : last.R;      // the reference scores none of its rolls
+    return HAF_OK;
+}
+
+int check_map_frame(haf_engine *e, const char *who, const haf_frame *f)
+{
+    const std::string name(who);
+    if (!f) return fail(e, HAF_E_ARG, name + ": null frame");
+    std::string msg;
+    const int rc = check_frame(*f, msg);
+    if (rc != HAF_OK) return fail(e, rc, name + ": " + msg);
+    if ((int64_t)f->width * (int64_t)f->height > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, name + ": more pixels than max_points");
+    return HAF_OK;
+}
+
+#ifdef HAF_TESTING
+int check_guards(haf_engine *e)
+{
+    if (!test_env("HAF_CANARY_CHECK")) return HAF_OK;
+    std::string rep;
+    const int bad = canary_check(&rep);
+    if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
+    return HAF_OK;
+}
+#else
+int check_guards(haf_engine *) { return HAF_OK; }
+#endif
+
+// The device pass for one checked frame: stages a host frame's pixels as upload_frames does (in pieces of 256 KB, only the width
+// elements of a row, of an XYZ frame only the three floats of a point), uploads the roll transforms and launches k_grasp_map on the
+// engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
+int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll, int *d_cell)
+{
+    constexpr size_t kPiece = 256 * 1024;
+    const haf_config &c = e->cfg;
+    const LastCall &last = e->last;
+    const hipStream_t s = e->stream;
+    memset(e->h_map, 0, kMapHdr);
+    fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->h_map + l.geo));
+    HIPCHK(e, hipMemcpyAsync(e->d_map.p, e->h_map, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
+    FrameDev fd;
+    memset(&fd, 0, sizeof fd);
+    fd.width = f.width;
+    fd.n = f.width * f.height;
+    fd.kind = f.kind;
+    fd.m = frame_math(f);
+    const size_t px = frame_pixel_bytes(f.kind);
+    if (f.on_device == 1) {
+        fd.src = f.data;
+        fd.row_stride = f.row_stride_bytes;
+        fd.point_stride = (unsigned)frame_elem_bytes(f);
+    } else {
+        fd.src = e->d_map.p + l.raw;
+        fd.row_stride = (unsigned long long)f.width * px;
+        fd.point_stride = (unsigned)px;
+        const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
+        const size_t row_bytes = (size_t)f.width * px;
+        size_t staged = 0, sent = 0;
+        for (int v = 0; v < f.height; v++) {
+            const char *row = static_cast<const char *>(f.data) + (size_t)v * f.row_stride_bytes;
+            char *dst = e->h_map + l.raw + staged;
+            if (!xyz || f.point_stride_bytes == 12) memcpy(dst, row, row_bytes);
+            else for (int u = 0; u < f.width; u++) memcpy(dst + (size_t)u * 12, row + (size_t)u * f.point_stride_bytes, 12);
+            staged += row_bytes;
+            if (staged - sent >= kPiece || v + 1 == f.height) {
+                HIPCHK(e, hipMemcpyAsync(e->d_map.p + l.raw + sent, e->h_map + l.raw + sent, staged - sent, hipMemcpyHostToDevice, s));
+                sent = staged;
+            }
+        }
+    }
+    const int H = c.grid_h, W = c.grid_w;
+    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    const short *ev = e->d_ev16.p + (size_t)request * last.R * (size_t)H * W;
+    launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(e->d_map.p + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll,
+                     d_cell, s);
+    HIPCHK(e, hipGetLastError());
+    return HAF_OK;
+}
+
+int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *vote, int16_t *roll, int32_t *cell, int32_t out_on_device)
+{
+    int rolls = 0, rc;
+    if ((rc = check_last(e, "haf_grasp_map", request, &rolls)) != HAF_OK) return rc;
+    if (out_on_device != 0 && out_on_device != 1) return fail(e, HAF_E_ARG, "haf_grasp_map: out_on_device must be 0 (host) or 1 (device)");
+    if ((rc = check_map_frame(e, "haf_grasp_map", f)) != HAF_OK) return rc;
+    const size_t n = (size_t)f->width * (size_t)f->height;
+    // (device outputs: the images are the caller's, the block only holds the header, the transforms and a host frame's pixels)
+    const MapLayout use = map_layout(e, out_on_device ? 0 : n, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
+    if ((rc = ensure_map(e, use.total)) != HAF_OK) return rc;
+    char *d = e->d_map.p;
+    short *dv = !vote ? nullptr : out_on_device ? vote : reinterpret_cast<short *>(d + use.vote);
+    short *dr = !roll ? nullptr : out_on_device ? roll : reinterpret_cast<short *>(d + use.roll);
+    int *dc = !cell ? nullptr : out_on_device ? cell : reinterpret_cast<int *>(d + use.cell);
+    if ((rc = launch_map(e, request, rolls, *f, use, dv, dr, dc)) != HAF_OK) return rc;
+    if (!out_on_device) {
+        if (vote) HIPCHK(e, hipMemcpyAsync(e->h_map + use.vote, d + use.vote, n * 2, hipMemcpyDeviceToHost, e->stream));
+        if (roll) HIPCHK(e, hipMemcpyAsync(e->h_map + use.roll, d + use.roll, n * 2, hipMemcpyDeviceToHost, e->stream));
+        if (cell) HIPCHK(e, hipMemcpyAsync(e->h_map + use.cell, d + use.cell, n * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if (!out_on_device) {
+        if (vote) memcpy(vote, e->h_map + use.vote, n * 2);
+        if (roll) memcpy(roll, e->h_map + use.roll, n * 2);
+        if (cell) memcpy(cell, e->h_map + use.cell, n * 4);
+    }
+    return HAF_OK;
+}
+
+int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, haf_grasp_candidate *out)
+{
+    const haf_config &c = e->cfg;
+    const LastCall &last = e->last;
+    int rc;
+    if (e->d_map.n < kMapHdr && (rc = ensure_map(e, map_layout(e, 0, 0, 0).total)) != HAF_OK) return rc;
+    HIPCHK(e, hipSetDevice(c.device));
+    const int br = request * last.R + (roll - last.roll_first);
+    RollRecordDev *d_rec = reinterpret_cast<RollRecordDev *>(e->d_map.p + kMapRecOff);
+    launch_cell_record(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, br, row, col, c.grid_h, c.grid_w, d_rec, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_map + kMapRecOff, d_rec, sizeof(RollRecordDev), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    RollRecordDev q;
+    memcpy(&q, e->h_map + kMapRecOff, sizeof q);
+    haf_roll_record rec;
+    rec.vote = q.vote; rec.row = q.row; rec.col = q.col; rec.h_locmax = q.h_locmax; rec.n_evals = q.n_evals;
+    haf_grasp_candidate cand;
+    memset(&cand, 0, sizeof cand);
+    rc = candidate_pose_impl(c, &last.inputs[(size_t)request], rec, roll, &cand.grasp, e->error);
+    if (rc != HAF_OK) return rc;
+    cand.run_length = 0;
+    cand.h_locmax = rec.h_locmax;
+    *out = cand;
+    return HAF_OK;
+}
+
+int cell_pose_impl(haf_engine *e, int32_t request, int32_t roll, int32_t row, int32_t col, haf_grasp_candidate *out)
+{
+    int rolls = 0, rc;
+    if (!out) return fail(e, HAF_E_ARG, "haf_cell_pose: null argument");
+    if ((rc = check_last(e, "haf_cell_pose", request, &rolls)) != HAF_OK) return rc;
+    if (rolls == 0) return fail(e, HAF_E_ARG, "haf_cell_pose: no roll ran for this request (negative budget)");
+    if (roll < e->last.roll_first || roll >= e->last.roll_first + e->last.R) return fail(e, HAF_E_ARG, "haf_cell_pose: roll not in the last scored batch");
+    if (row < 0 || row >= e->cfg.grid_h || col < 0 || col >= e->cfg.grid_w) return fail(e, HAF_E_ARG, "haf_cell_pose: cell outside the grid");
+    return cell_pose_checked(e, request, roll, row, col, out);
+}
+
+int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint8_t *mask, size_t mask_row_stride, int32_t min_vote,
+                  haf_grasp_candidate *out, int32_t *u, int32_t *v, int32_t *found)
+{
+    int rolls = 0, rc;
+    if (!out || !found) return fail(e, HAF_E_ARG, "haf_grasp_map_best: null argument");
+    if ((rc = check_last(e, "haf_grasp_map_best", request, &rolls)) != HAF_OK) return rc;
+    if ((rc = check_map_frame(e, "haf_grasp_map_best", f)) != HAF_OK) return rc;
+    if (mask && mask_row_stride < (size_t)f->width) return fail(e, HAF_E_ARG, "haf_grasp_map_best: mask_row_stride smaller than a row");
+    const size_t n = (size_t)f->width * (size_t)f->height;
+    const MapLayout l = map_layout(e, n, mask ? n : 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
+    if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
+    char *d = e->d_map.p;
+    short *dv = reinterpret_cast<short *>(d + l.vote), *dr = reinterpret_cast<short *>(d + l.roll);
+    int *dc = reinterpret_cast<int *>(d + l.cell);
+    if ((rc = launch_map(e, request, rolls, *f, l, dv, dr, dc)) != HAF_OK) return rc;
+    if (mask) {
+        for (int r = 0; r < f->height; r++) memcpy(e->h_map + l.mask + (size_t)r * f->width, mask + (size_t)r * mask_row_stride, (size_t)f->width);
+        HIPCHK(e, hipMemcpyAsync(d + l.mask, e->h_map + l.mask, n, hipMemcpyHostToDevice, e->stream));
+    }
+    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d);      // (zeroed by launch_map's header copy)
+    launch_map_best(dv, dr, mask ? reinterpret_cast<const unsigned char *>(d + l.mask) : nullptr, (unsigned)n, min_vote, d_key, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_map, d_key, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    unsigned long long key;
+    memcpy(&key, e->h_map, 8);
+    if (key == 0ull) { *found = 0; return HAF_OK; }
+    const size_t i = (size_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull);
+    if (i >= n || roll < e->last.roll_first || roll >= e->last.roll_first + e->last.R) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed key");
+    int32_t ci = -1;
+    HIPCHK(e, hipMemcpyAsync(e->h_map + 8, dc + i, 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    memcpy(&ci, e->h_map + 8, 4);
+    const int W = e->cfg.grid_w;
+    if (ci < 0 || ci >= e->cfg.grid_h * W) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed cell");
+    haf_grasp_candidate cand;
+    if ((rc = cell_pose_checked(e, request, roll, ci / W, ci % W, &cand)) != HAF_OK) return rc;
+    *out = cand;
+    if (u) *u = (int32_t)(i % (size_t)f->width);
+    if (v) *v = (int32_t)(i / (size_t)f->width);
+    *found = 1;
+    return HAF_OK;
+}
+
+}  // namespace
+
+}  // namespace haf_host
+
+extern "C" {
+
+int haf_grasp_map(haf_engine *e, int32_t request, const haf_frame *frame, int16_t *vote, int16_t *roll, int32_t *cell, int32_t out_on_device)
+{
+    if (!e) return HAF_E_ARG;
+    return guarded(&e->error, [&] { return grasp_map_impl(e, request, frame, vote, roll, cell, out_on_device); });
+}
+
+int haf_cell_pose(haf_engine *e, int32_t request, int32_t roll, int32_t row, int32_t col, haf_grasp_candidate *out)
+{
+    if (!e) return HAF_E_ARG;
+    return guarded(&e->error, [&] { return cell_pose_impl(e, request, roll, row, col, out); });
+}
+
+int haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, const uint8_t *mask, size_t mask_row_stride, int32_t min_vote,
+                       haf_grasp_candidate *out, int32_t *u, int32_t *v, int32_t *found)
+{
+    if (!e) return HAF_E_ARG;
+    return guarded(&e->error, [&] { return map_best_impl(e, request, frame, mask, mask_row_stride, min_vote, out, u, v, found); });
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //   engine_geometry.cpp  per-roll transforms, the rotated-rectangle scalars, the final grasp pose (host fp32, glibc)
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
 //   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
+//   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every translation unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
@@ -63,6 +64,8 @@ Mat4 roll_transform(const haf_config &cfg, const haf_grasp_input &in, const Norm
                     Mat4 *pre_roll = nullptr, float *roll_cs = nullptr);
 void fill_roll_geo(const haf_config &cfg, const haf_grasp_input &in, const NormalisedInput &n, int roll, RollGeo &g, float *m0 = nullptr);
 bool invert(const Mat4 &m, Mat4 &inv);
+// graspmap_host.cpp: rows 0..2 of the transforms of rolls roll_first .. roll_first + roll_count - 1 (fill_roll_geo's), 64 bytes each
+void fill_cell_geo(const haf_config &cfg, const haf_grasp_input &in, int roll_first, int roll_count, haf_cell_math::CellGeo *geo);
 
 // Testing build: every device buffer lies between two guard zones filled with kCanaryByte -- kCanaryGuard bytes in front, and from
 // the buffer's last byte to the next multiple of kCanaryGuard plus kCanaryGuard behind -- and is registered with the source line that
@@ -329,6 +332,11 @@ struct haf_engine {
     DevBuf<char> d_top_out;
     char *h_top_out = nullptr;
     size_t h_top_cap = 0;
+    // haf_grasp_map (engine_graspmap.cpp), allocated on its first call and grown to the largest frame seen: the device block
+    // [best key + cell record: 64 bytes][R x CellGeo][vote | roll | cell images][mask bytes] and its pinned host copy
+    DevBuf<char> d_map;
+    char *h_map = nullptr;
+    size_t h_map_cap = 0;
 };
 
 namespace haf_host {

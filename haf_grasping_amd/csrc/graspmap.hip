@@ -1,0 +1,192 @@
+// graspmap.hip -- k_grasp_map<KIND>: the per-pixel grasp map of haf_grasp_map (engine_graspmap.cpp) -- for every pixel of a sensor frame
+// the best vote any roll of a request of the last scored batch gives the cell the pixel's point falls into, that roll and that cell.
+// The definition is haf_grasp_map_ref's (graspmap_host.cpp), compiled from the same two headers: frame_points.h (pixel -> base-frame
+// point) and grasp_cells.h (point -> cell of a roll).  The two agree in every pixel (tests/test_grasp_map_gpu.py).
+//
+// A streaming kernel with R gathers per pixel.  A lane owns a GROUP of consecutive pixels exactly as in k_frame_points (frame_group.h):
+// eight of a U16 frame, four of an F32 or XYZ frame, one global_load_dwordx4 where the group is aligned.
+//   * the frame's constants arrive as a kernel argument and the R roll transforms (64 bytes each) are read by a wave-uniform index:
+//     both are scalar loads, a roll costs a lane no vector load but its gathers;
+//   * per roll the lane computes its G cells, then issues its G gathers from the request's vote grids (2 bytes each; R grids of H*W
+//     shorts -- 125 KB at 56 x 56 x 20, 18 MB at 512 x 512 x 36 -- which neighbouring pixels share: they mostly hit L2), then keeps the
+//     larger vote with a strict '>' (rolls ascend: the lowest roll wins a tie);
+//   * the three images are packed width * height arrays and a group starts at a multiple of G pixels, so a whole group is ONE
+//     global_store_dwordx4 (dwordx2 for G = 4) per 16-bit image and two (one) dwordx4 for the cells when the caller's base is aligned
+//     accordingly; a misaligned base or the frame's last, partial group stores element by element.
+// Floor per pixel: 2-12 bytes read, 8 written, R two-byte gathers.  It reads the vote grids and nothing else of the request.
+//
+// k_map_best: the masked best pixel of haf_grasp_map_best -- a wave-level maximum of a packed 64-bit key over the pixels whose mask
+// byte is not zero and whose vote is >= min_vote, then one 64-bit atomicMax per wave.  Key, most significant first: vote + 32768
+// (16 bits), 65535 - roll (16), 2^32 - 1 - pixel index (32): its maximum is vote descending, roll ascending, then v, then u ascending.
+// k_cell_record: the record of one arbitrary cell for haf_cell_pose, with the 9 x 8 z window of k_top_grasps.
+#include "frame_group.h"
+#include "grasp_cells.h"
+
+namespace haf {
+
+using haf_cell_math::CellGeo;
+
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+template <int KIND>
+__global__ __launch_bounds__(kFrameThreads) void k_grasp_map(const FrameDev f, const CellGeo *__restrict__ geo, int R, int roll_first,
+                                                             const short *__restrict__ ev16, int H, int W, float r_row, float r_col,
+                                                             short *__restrict__ vote, short *__restrict__ roll, int *__restrict__ cell)
+{
+    constexpr unsigned G = frame_group<KIND>();
+    const unsigned n = (unsigned)f.n;
+    const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;      // (n < 2^31 and at most 2^11 points of slack: no wrap)
+    if (i0 >= n) return;
+    const bool whole = i0 + G <= n;
+    float p[G * 3];
+    group_points<KIND>(f, i0, n, p);
+
+    bool usable[G];
+    int best[G], best_roll[G], best_cell[G];
+#pragma unroll
+    for (unsigned k = 0; k < G; k++) {
+        usable[k] = i0 + k < n && haf_cell_math::point_usable(p + 3 * k);
+        best[k] = haf_cell_math::kNoCellVote; best_roll[k] = -1; best_cell[k] = -1;
+    }
+    const size_t HW = (size_t)H * (size_t)W;
+    for (int r = 0; r < R; r++) {
+        const CellGeo &g = geo[r];                        // (r is wave-uniform: sixteen scalar registers)
+        const global_ptr<const short> grid = as_global<const short>(ev16 + (size_t)r * HW);
+        int ci[G], val[G];
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) {
+            const int c = haf_cell_math::point_cell(g.m, p[3 * k], p[3 * k + 1], p[3 * k + 2], r_row, r_col, H, W);
+            ci[k] = usable[k] ? c : -1;
+        }
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) val[k] = ci[k] >= 0 ? (int)grid[ci[k]] : 0;      // (0 <= ci < H * W: inside roll r's grid)
+#pragma unroll
+        for (unsigned k = 0; k < G; k++)
+            if (ci[k] >= 0 && (best_roll[k] < 0 || val[k] > best[k])) { best[k] = val[k]; best_roll[k] = roll_first + r; best_cell[k] = ci[k]; }
+    }
+
+    // a 16-bit image's group is 2 G bytes, the cells' 4 G: vector stores where the caller's base makes the group's address a multiple of that
+    unsigned pv[G / 2], pr[G / 2];
+#pragma unroll
+    for (unsigned k = 0; k < G / 2; k++) {
+        pv[k] = ((unsigned)best[2 * k] & 0xFFFFu) | ((unsigned)best[2 * k + 1] << 16);
+        pr[k] = ((unsigned)best_roll[2 * k] & 0xFFFFu) | ((unsigned)best_roll[2 * k + 1] << 16);
+    }
+    auto store16 = [&](short *img, const unsigned (&w)[G / 2], const int (&e)[G]) {
+        if (!img) return;
+        short *at = img + i0;
+        if (whole && (reinterpret_cast<uintptr_t>(at) & (2u * G - 1u)) == 0) {
+            if constexpr (G == 8) *as_global<v4u>(at) = v4u{w[0], w[1], w[2], w[3]};
+            else *as_global<v2u>(at) = v2u{w[0], w[1]};
+        } else {
+            const global_ptr<short> o = as_global<short>(at);
+#pragma unroll
+            for (unsigned k = 0; k < G; k++)
+                if (i0 + k < n) o[k] = (short)e[k];
+        }
+    };
+    store16(vote, pv, best);
+    store16(roll, pr, best_roll);
+    if (cell) {
+        int *at = cell + i0;
+        if (whole && (reinterpret_cast<uintptr_t>(at) & 15u) == 0) {
+            const global_ptr<v4u> o = as_global<v4u>(at);
+#pragma unroll
+            for (unsigned j = 0; j < G / 4; j++)
+                o[j] = v4u{(unsigned)best_cell[4 * j], (unsigned)best_cell[4 * j + 1], (unsigned)best_cell[4 * j + 2], (unsigned)best_cell[4 * j + 3]};
+        } else {
+            const global_ptr<int> o = as_global<int>(at);
+#pragma unroll
+            for (unsigned k = 0; k < G; k++)
+                if (i0 + k < n) o[k] = best_cell[k];
+        }
+    }
+}
+
+void launch_grasp_map(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row, float r_col,
+                      short *vote, short *roll, int *cell, hipStream_t s)
+{
+    const unsigned G = f.kind == HAF_FRAME_DEPTH_U16 ? 8u : 4u;
+    const unsigned groups = ((unsigned)f.n + G - 1) / G;
+    if (!groups) return;
+    const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
+    if (f.kind == HAF_FRAME_DEPTH_U16)
+        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_DEPTH_U16>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
+    else if (f.kind == HAF_FRAME_DEPTH_F32)
+        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_DEPTH_F32>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
+    else
+        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_XYZ_F32>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
+}
+
+// ---- the masked best pixel ----
+constexpr int kBestThreads = 256;
+
+__device__ __forceinline__ unsigned long long map_key(int vote, int roll, unsigned i)
+{
+    return ((unsigned long long)(unsigned)(vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - roll) << 32) | (unsigned long long)(0xFFFFFFFFu - i);
+}
+
+// mask: n packed bytes (the host's rows without their padding), or null for every pixel.  *best starts as 0, which no pixel's key is
+// (a pixel with a roll has a vote above HAF_MAP_NO_CELL: its top 16 bits are not zero)
+__global__ __launch_bounds__(kBestThreads) void k_map_best(const short *__restrict__ vote, const short *__restrict__ roll,
+                                                           const unsigned char *__restrict__ mask, unsigned n, int min_vote,
+                                                           unsigned long long *__restrict__ best)
+{
+    unsigned long long key = 0ull;
+    for (unsigned i = blockIdx.x * (unsigned)kBestThreads + threadIdx.x; i < n; i += gridDim.x * (unsigned)kBestThreads) {
+        const int r = roll[i], v = vote[i];
+        if (r >= 0 && v >= min_vote && v > haf_cell_math::kNoCellVote && (!mask || mask[i] != 0)) {
+            const unsigned long long k = map_key(v, r, i);
+            key = k > key ? k : key;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, 64);
+        key = other > key ? other : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key != 0ull) atomicMax(best, key);
+}
+
+void launch_map_best(const short *vote, const short *roll, const unsigned char *mask, unsigned n, int min_vote, unsigned long long *best,
+                     hipStream_t s)
+{
+    const unsigned blocks = std::max(1u, std::min(1024u, (n + kBestThreads - 1) / kBestThreads));
+    hipLaunchKernelGGL(k_map_best, dim3(blocks), dim3(kBestThreads), 0, s, vote, roll, mask, n, min_vote, best);
+}
+
+// ---- the record of one cell ----
+// rec[br] as k_top_grasps reads it (the roll's n_evals); out = {vote at the cell, row, col, max height of rows row-4..row+4, cols
+// col-4..col+3 as an ordered-key maximum above -10 (k_vote_record; server.cpp:1342-1351), n_evals}.  One wave.
+__global__ __launch_bounds__(64) void k_cell_record(const short *__restrict__ ev16, const float *__restrict__ heights,
+                                                    const RollRecordDev *__restrict__ rec, int br, int row, int col, int H, int W,
+                                                    RollRecordDev *__restrict__ out)
+{
+    const size_t HW = (size_t)H * W;
+    int zk = f2key(-10.0f);
+    for (int q = threadIdx.x; q < 72; q += 64) {
+        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
+        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
+            const float h = heights[(size_t)br * HW + (size_t)rr * W + cc];
+            if (-10.0f < h) zk = max(zk, f2key(h));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) zk = max(zk, __shfl_xor(zk, o, 64));
+    if (threadIdx.x == 0) {
+        RollRecordDev q;
+        q.vote = ev16[(size_t)br * HW + (size_t)row * W + col];
+        q.row = (short)row; q.col = (short)col;
+        q.h_locmax = key2f(zk);
+        q.n_evals = rec[br].n_evals;
+        *out = q;
+    }
+}
+
+void launch_cell_record(const short *ev16, const float *heights, const RollRecordDev *rec, int br, int row, int col, int H, int W,
+                        RollRecordDev *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cell_record, dim3(1), dim3(64), 0, s, ev16, heights, rec, br, row, col, H, W, out);
+}
+
+}  // namespace haf

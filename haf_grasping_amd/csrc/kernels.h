@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "frame_points.h"
+#include "grasp_cells.h"
 
 namespace haf {
 
@@ -500,6 +501,17 @@ void launch_view_points(const FrameDev *views_dev, const FrameDev *views_host, i
 struct TopCandDev { int vote; short row, col; int len; float h_locmax; };
 void launch_top_grasps(const short *ev16, const float *heights, const RollRecordDev *rec, unsigned long long *scratch, size_t slot_words,
                        int n_slots, int *hdr, TopCandDev *cand, int D, int min_vote, int radius, Dims d, hipStream_t s);
+// per-pixel grasp maps (graspmap.hip, haf_grasp_map): one frame, the R cell transforms of one request of the last batch and that request's
+// vote grids (ev16 = its first grid) -> packed width * height images, any of them null; f.dst and f.count are not read
+void launch_grasp_map(const FrameDev &f, const haf_cell_math::CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row,
+                      float r_col, short *vote, short *roll, int *cell, hipStream_t s);
+// *best (zeroed by the caller) = the largest key of the n pixels whose mask byte (null: all) is not zero and whose vote is >= min_vote:
+// (vote + 32768) << 48 | (65535 - roll) << 32 | (2^32 - 1 - pixel index); still 0 when none qualifies
+void launch_map_best(const short *vote, const short *roll, const unsigned char *mask, unsigned n, int min_vote, unsigned long long *best,
+                     hipStream_t s);
+// the record of cell (row, col) of (cloud, roll) br of the last batch: its vote, the 9x8 z window of k_top_grasps, the roll's n_evals
+void launch_cell_record(const short *ev16, const float *heights, const RollRecordDev *rec, int br, int row, int col, int H, int W,
+                        RollRecordDev *out, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

@@ -109,5 +109,22 @@ class CalcGraspPointsServer:
         return [GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
                                c["approach_vector"], c["roll"]) for c in cands]
 
+    def grasp_map(self, frame, want=("vote", "roll")):
+        """The last execute*()'s votes in the pixels of `frame` (haf_grasp_map): any capi.depth_frame / capi.xyz_frame -- the scored
+        view, another camera, the registered RGB view -- -> dict of [height, width] images: vote int16 (capi.MAP_NO_CELL where no roll
+        has a cell for the pixel), roll int16 (the winning roll, -1), cell int32 when asked for."""
+        return self.engine.grasp_map(0, frame, want=want)
+
+    def best_in_mask(self, frame, mask=None, min_vote=1):
+        """The best grasp of the last execute*() inside an image-space mask (uint8 [height, width], e.g. a segmenter's instance mask
+        synchronised with the depth topic; None: the whole image) -> (GraspOutputMsg, u, v) of the best pixel, or None when no pixel
+        under the mask has a vote >= min_vote (haf_grasp_map_best)."""
+        hit = self.engine.best_in_mask(0, frame, mask, min_vote)
+        if hit is None:
+            return None
+        c, u, v = hit
+        return GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                              c["approach_vector"], c["roll"]), u, v
+
     def close(self):
         self.engine.close()

@@ -407,6 +407,54 @@ int  haf_score_views(haf_engine *e, int32_t n, const int32_t *views_per_request,
  * else, a truncated or over-long file included. */
 int  haf_pgm16_load(const char *path, uint16_t **depth, int32_t *width, int32_t *height, char *err, size_t err_cap);
 
+/* ---- per-pixel grasp maps: the votes and rolls of the last scored batch in a sensor frame's image space (csrc/graspmap.hip) ------
+ * Every result above lives in the rotated 1 cm grids of the rolls.  A grasp map answers in the caller's pixels: for pixel (u, v) of any
+ * haf_frame -- the scored one, another camera, the registered RGB view -- the best vote any roll gives the cell the pixel's point falls
+ * into, that roll, and that cell.
+ *
+ * Host definitions of record (no device, no engine):
+ * haf_point_cells: cell[i] = row * grid_w + col of point i (xyz + i * stride_floats) under roll `roll` (global index) of request input
+ * `in`, or -1.  The arithmetic is the binning kernel's (server.cpp:488, 510-514), csrc/grasp_cells.h: the roll's fp32 transform,
+ * p[r] = ((m[r][0] x + m[r][1] y) + m[r][2] z) + m[r][3] left to right, every step one correctly rounded fp32 operation and never a
+ * fused multiply-add; a cell only when -r_row < p[0] < r_row, -r_col < p[1] < r_col (strict; r_row = (float)((0.5 * (float)grid_h) / 100.0))
+ * and p[2] is not a NaN; row = (int)floorf(100 * (p[0] + r_row)), col likewise, both inside the grid.
+ * HAF_E_ARG: a null argument, grid_h / grid_w / n_rolls < 1, roll outside [0, n_rolls), stride_floats < 3; HAF_E_CAPACITY: n > INT32_MAX.
+ *
+ * haf_grasp_map_ref: eval_grids = roll_count x grid_h x grid_w floats as haf_get_roll_grid returns them for the rolls roll_first ..
+ * roll_first + roll_count - 1 of one request.  For pixel (u, v) of the host frame -- index v * width + u -- the point is
+ * haf_frame_points' words; the rolls are walked in ascending order, wherever the point has a cell the vote is (int)eval_grid[cell]
+ * (votes are signed), and the largest vote is kept with a strict '>': the lowest roll wins a tie.  vote / roll / cell = that vote, its
+ * GLOBAL roll index and its cell.  A pixel gets HAF_MAP_NO_CELL, roll -1 and cell -1 when it is invalid or its point has a component
+ * that is not finite (the rule of haf_view_points), or when it has no cell in any roll.  Any output pointer may be NULL.
+ * HAF_E_ARG: a null cfg, in or frame, null eval_grids with roll_count > 0, a roll range outside [0, n_rolls] (roll_count = 0 is the
+ * request no roll ran for), a frame haf_frame_points would refuse; HAF_E_CAPACITY: a frame of more than INT32_MAX pixels. */
+#define HAF_MAP_NO_CELL (-32768)
+int  haf_point_cells(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const float *xyz, size_t n, size_t stride_floats,
+                     int32_t *cell);
+int  haf_grasp_map_ref(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                       const haf_frame *frame, int16_t *vote, int16_t *roll, int32_t *cell);
+/* The map of request `request` of the LAST scored batch for `frame` (host or device-resident, any kind), computed on the device from
+ * the vote grids that batch left there: equal to haf_grasp_map_ref on the request's haf_get_roll_grid grids in every pixel.  vote, roll,
+ * cell: width * height packed images in host memory, or in device memory when out_on_device = 1 (written on the engine's stream and
+ * complete when the call returns); any of them may be NULL.  A request whose budget was negative (no roll ran) yields HAF_MAP_NO_CELL
+ * everywhere.  Leaves all last-batch state as it was (records, grids, counters, debug data), like haf_top_grasps.
+ * HAF_E_ARG: a null frame, no scored batch, request out of range, out_on_device not 0 or 1, an engine created with
+ * HAF_FLAG_PROBABILITY (fp32 votes), a frame haf_score_frames would refuse; HAF_E_CAPACITY: width * height > max_points. */
+int  haf_grasp_map(haf_engine *e, int32_t request, const haf_frame *frame, int16_t *vote, int16_t *roll, int32_t *cell,
+                   int32_t out_on_device);
+/* The pose of an arbitrary cell of the last scored batch: the record {vote at the cell, row, col, h_locmax of the 9x8 window as
+ * haf_top_grasps computes it, n_evals of the roll} through haf_top_grasps' pose with eval = vote - 20 and run_length 0.  roll is the
+ * global roll index.  HAF_E_ARG: no scored batch, HAF_FLAG_PROBABILITY, request / roll / row / col outside the last batch or the grid,
+ * a request no roll ran for. */
+int  haf_cell_pose(haf_engine *e, int32_t request, int32_t roll, int32_t row, int32_t col, haf_grasp_candidate *out);
+/* The best pixel of haf_grasp_map(request, frame) under a host mask (mask[v * mask_row_stride + u] != 0 selects pixel (u, v); NULL:
+ * every pixel; mask_row_stride in bytes, >= width) among the pixels whose vote is >= min_vote: vote descending, then roll ascending,
+ * then v ascending, then u ascending.  *found = 1 and *out = haf_cell_pose of that pixel's (roll, cell), *u / *v its position (either
+ * may be NULL); *found = 0 when no pixel qualifies (out, u, v untouched).  Refusals as haf_grasp_map, plus a null out or found and a
+ * mask_row_stride < width with a mask. */
+int  haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, const uint8_t *mask, size_t mask_row_stride,
+                        int32_t min_vote, haf_grasp_candidate *out, int32_t *u, int32_t *v, int32_t *found);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
