@@ -19,10 +19,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhafgrasp.so")
 LIB_TESTING = os.path.join(HERE, "libhafgrasp_testing.so")
 # the engine's host side: every one of these is compiled twice, without and with -DHAF_TESTING (csrc/engine_state.h: test_env)
-ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp", "engine_graspmap.cpp"]
+ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp", "engine_graspmap.cpp", "engine_roi.cpp"]
 TESTING_ONLY = ["engine_testing.cpp", "testkernels.hip"]         # libhafgrasp_testing.so only
-SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip", "frames.hip", "graspmap.hip"] + \
-          ENGINE_SOURCES + ["parsers.cpp", "frames_host.cpp", "graspmap_host.cpp", "multi.cpp"]
+SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip", "frames.hip", "graspmap.hip", "roi.hip"] + \
+          ENGINE_SOURCES + ["parsers.cpp", "frames_host.cpp", "graspmap_host.cpp", "roi_host.cpp", "multi.cpp"]
 # per-file extra flags (screen.hip: see its header)
 EXTRA = {"screen.hip": ["-fno-slp-vectorize"]}
 HEADERS = ["kernels.h", "device_common.h", "feature_device.h", "screen_band.h", "parsers.h", "decq.h", "engine_internal.h", "engine_state.h", "frame_points.h", "frames.h", "frame_group.h", "grasp_cells.h"] + TESTING_ONLY + [ os.path.join("..", "..", "include", "hafgrasp.h"),

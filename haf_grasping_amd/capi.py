@@ -70,6 +70,11 @@ class Frame(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("sensor_to_base", C.c_float * 12)]
 
 
+class Roi(C.Structure):
+    """haf_roi: the pixel mask of one request of haf_score_frames_roi"""
+    _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
+
+
 ATTR_RECORD_DTYPE = np.dtype([("feature", np.float32), ("pad", np.float32), ("q4", np.float64), ("scaled", np.float64)])
 assert ATTR_RECORD_DTYPE.itemsize == 24
 
@@ -150,6 +155,9 @@ def _bind(path, testing):
     L.haf_cell_pose.argtypes = [E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GraspCandidate)]
     L.haf_grasp_map_best.argtypes = [E, C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(GraspCandidate),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.haf_roi_cells.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_void_p,
+                                C.c_void_p]
+    L.haf_score_frames_roi.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -432,6 +440,28 @@ def grasp_map_ref(cfg, grasp_input, roll_first, eval_grids, frame, want=("vote",
     return out
 
 
+def _host_mask(mask, frame):
+    """uint8 [height, width] with contiguous rows (they may be padded: a view into a wider array) -> (array to keep, pointer, row stride)"""
+    keep = np.asarray(mask)
+    assert keep.dtype == np.uint8 and keep.shape == (frame.height, frame.width) and (keep.shape[1] == 1 or keep.strides[1] == 1)
+    if keep.shape[0] > 1 and keep.strides[0] < keep.shape[1]:
+        keep = np.ascontiguousarray(keep)
+    return keep, keep.ctypes.data, (keep.strides[0] if keep.shape[0] > 1 else keep.shape[1])
+
+
+def roi_cells(cfg, grasp_input, roll, frame, mask, want=("roi", "eval")):
+    """haf_roi_cells: the host definition of record of haf_score_frames_roi's cell sets for roll `roll` (global index) -- roi: the cells
+    of the masked pixels' points, eval: their dilation by the vote's 29-tap footprint (before the test of the search area)
+    -> dict of uint8 [grid_h, grid_w], only the grids named in `want`.  frame: a host Frame; mask: uint8 [height, width]."""
+    keep, ptr, stride = _host_mask(mask, frame)
+    out = {k: np.empty((cfg.grid_h, cfg.grid_w), np.uint8) for k in want}
+    p = lambda k: out[k].ctypes.data if k in out else None
+    rc = lib().haf_roi_cells(C.byref(cfg), C.byref(grasp_input), roll, C.byref(frame), ptr, stride, p("roi"), p("eval"))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_roi_cells refused its arguments")
+    return out
+
+
 class Engine:
     """Owns one haf_engine handle (one GPU)."""
 
@@ -567,6 +597,26 @@ class Engine:
         self._last_points = [f.width * f.height for f in frames]
         return [output_to_dict(o) for o in out]
 
+    def score_frames_roi(self, frames, masks, inputs):
+        """haf_score_frames_roi: score_frames with, per request, a pixel mask over its frame -- only the cells near the cells of the
+        masked pixels are evaluated.  masks[b]: uint8 [height, width] (host; rows may be padded), or (device_ptr, row_stride_bytes)."""
+        n = len(frames)
+        arr = (Frame * max(1, n))(*frames)
+        rois = (Roi * max(1, n))()
+        keep = []
+        for b, m in enumerate(masks):
+            if isinstance(m, tuple):
+                rois[b] = Roi(int(m[0]), int(m[1]), 1)
+            else:
+                k, ptr, stride = _host_mask(m, frames[b])
+                keep.append(k)
+                rois[b] = Roi(ptr, stride, 0)
+        gi = (GraspInput * max(1, n))(*inputs)
+        out = (GraspOutput * max(1, n))()
+        self._check(self._L.haf_score_frames_roi(self._h, n, arr, rois, gi, out))
+        self._last_points = [f.width * f.height for f in frames]
+        return [output_to_dict(o) for o in out[:n]]
+
     def score_views(self, view_sets, inputs):
         """haf_score_views: per request a list of Frames (its views, fused on the device into one cloud of their valid points) and one
         GraspInput -> (outputs, valid points per request)"""
@@ -659,11 +709,7 @@ class Engine:
         and whose vote is >= min_vote -- vote descending, roll, v, u ascending -> (candidate dict, u, v), or None when none qualifies"""
         ptr, stride, keep = None, 0, None
         if mask is not None:
-            keep = np.asarray(mask)
-            assert keep.dtype == np.uint8 and keep.shape == (frame.height, frame.width) and (keep.shape[1] == 1 or keep.strides[1] == 1)
-            if keep.shape[0] > 1 and keep.strides[0] < keep.shape[1]:
-                keep = np.ascontiguousarray(keep)
-            ptr, stride = keep.ctypes.data, (keep.strides[0] if keep.shape[0] > 1 else keep.shape[1])
+            keep, ptr, stride = _host_mask(mask, frame)
         c, u, v, found = GraspCandidate(), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
         self._check(self._L.haf_grasp_map_best(self._h, request, C.byref(frame), ptr, stride, min_vote, C.byref(c), C.byref(u), C.byref(v),
                                                C.byref(found)))

@@ -25,6 +25,9 @@
 //   --mask FILE.pgm                   with --depth: an 8-bit binary PGM of the image's size; after the normal output one line
 //                                     "mask <u> <v> <hypothesis>" for the best pixel under its non-zero samples whose vote is at
 //                                     least --mask-min-vote (default 1), or "mask none" (haf_grasp_map_best)
+//   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
+//                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
+//                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
 //   --depth FILE.pgm --intrinsics fx fy cx cy   in place of the .pcd arguments: a 16-bit depth image (binary PGM) as the sensor
 //                                     delivers it, deprojected and transformed on the device (haf_score_frames); optional
 //                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
@@ -111,6 +114,7 @@ static void usage()
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
             "  --map-out PREFIX  --mask FILE.pgm [--mask-min-vote N]      (with --depth)\n"
+            "  --roi-mask FILE.pgm                                         (with one --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -139,7 +143,8 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 // Several --depth: the views of the one goal, fused on the device (haf_score_views); one --depth is haf_score_frames as ever.
 struct DepthView { std::string path; haf_frame frame; };
 // --map-out / --mask: the goal's votes in the pixels of the FIRST view (haf_grasp_map, haf_grasp_map_best)
-struct MapOptions { std::string out_prefix, mask_path; int min_vote = 1; };
+// --roi-mask: the request itself is restricted to the cells near the masked pixels' cells (haf_score_frames_roi)
+struct MapOptions { std::string out_prefix, mask_path, roi_path; int min_vote = 1; };
 
 static bool write_pgm16(const std::string &path, const int16_t *img, int w, int h)
 {
@@ -243,7 +248,20 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     haf_grasp_output out;
     const int32_t n_views = (int32_t)frames.size();
     int64_t n_points = 0;
-    if ((n_views == 1 ? haf_score_frames(eng, 1, frames.data(), &in, &out) : haf_score_views(eng, 1, &n_views, frames.data(), &in, &out, &n_points)) != HAF_OK) {
+    std::vector<uint8_t> roi_mask;
+    if (!mo.roi_path.empty()) {
+        int w = 0, h = 0;
+        if (!read_pgm8(mo.roi_path, roi_mask, w, h)) { fprintf(stderr, "%s: not a binary 8-bit PGM\n", mo.roi_path.c_str()); release(); return 1; }
+        if (w != frames[0].width || h != frames[0].height) {
+            fprintf(stderr, "%s: %d x %d, the depth image has %d x %d\n", mo.roi_path.c_str(), w, h, frames[0].width, frames[0].height);
+            release();
+            return 1;
+        }
+    }
+    const haf_roi roi = {roi_mask.data(), (size_t)frames[0].width, 0};
+    if ((!mo.roi_path.empty() ? haf_score_frames_roi(eng, 1, frames.data(), &roi, &in, &out)
+         : n_views == 1 ? haf_score_frames(eng, 1, frames.data(), &in, &out)
+                        : haf_score_views(eng, 1, &n_views, frames.data(), &in, &out, &n_points)) != HAF_OK) {
         fprintf(stderr, "%s: %s\n", path.c_str(), haf_last_error(eng));
         release();
         return 1;
@@ -324,6 +342,7 @@ int main(int argc, char **argv)
         else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
         else if (a == "--map-out") { need(1); map_opt.out_prefix = argv[++i]; }
         else if (a == "--mask") { need(1); map_opt.mask_path = argv[++i]; }
+        else if (a == "--roi-mask") { need(1); map_opt.roi_path = argv[++i]; }
         else if (a == "--mask-min-vote") { need(1); map_opt.min_vote = atoi(argv[++i]); }
         else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
@@ -340,6 +359,7 @@ int main(int argc, char **argv)
     }
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty())) ||
+        (!map_opt.roi_path.empty() && views.size() != 1) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);

@@ -84,6 +84,8 @@ void haf_destroy(haf_engine *e)
     if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_raw) (void)hipHostFree(e->h_raw);
     if (e->h_raw_xyz) (void)hipHostFree(e->h_raw_xyz);
+    e->d_roi_cells.release(); e->d_roi_mask.release();
+    if (e->h_roi_mask) (void)hipHostFree(e->h_roi_mask);
     if (e->h_out) (void)hipHostFree(e->h_out);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -506,6 +508,11 @@ int haf_score_batch(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, co
 int haf_score_frames(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out)
 {
     return guarded(e ? &e->error : nullptr, [&] { return score_frames_impl(e, n, frames, in, out); });
+}
+
+int haf_score_frames_roi(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in, haf_grasp_output *out)
+{
+    return guarded(e ? &e->error : nullptr, [&] { return score_frames_roi_impl(e, n, frames, rois, in, out); });
 }
 
 int haf_score_views(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,

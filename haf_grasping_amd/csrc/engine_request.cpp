@@ -264,6 +264,7 @@ struct Request {
     // haf_score_views: cloud b's points are the valid points of views[b] consecutive frames, compacted by k_view_points; the host then
     // sizes everything by the UPPER bound clouds[b].n_points = the pixels of those views, the live count is CloudDev::n on the device
     const int32_t *views = nullptr;
+    const RoiCall *roi = nullptr;        // haf_score_frames_roi: only the cells near the cells of the masked pixels are evaluated
     int n_frames = 0;                    // entries of frames / h_frames: B, or the sum of views
     FrameDev *h_frames = nullptr;
     const FrameDev *d_frames = nullptr;
@@ -484,7 +485,11 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
     // fewer than the grid could hold (the client's default 32 x 44 area on the 56 x 56 grid: a third).
     for (int b = 0; b < B; b++) {
         const long a2 = std::max(0, 2 * ((int)in[b].grasp_area_length_x / 2 - 7)) + 2, b2 = std::max(0, 2 * ((int)in[b].grasp_area_length_y / 2 - 7)) + 2;
-        q.evals_sel += (long)R * std::min<long>((long)(H - 14) * (W - 14), a2 * b2);
+        long sel = std::min<long>((long)(H - 14) * (W - 14), a2 * b2);
+        // an ROI request with a HOST mask: a masked pixel puts at most the 29 cells of the vote's footprint on a roll's list (the mask is
+        // an argument of the call: identical calls still take identical paths; a device-resident mask keeps the area bound)
+        if (q.roi && q.roi->masked[(size_t)b] >= 0) sel = std::min<long>(sel, 29 * q.roi->masked[(size_t)b]);
+        q.evals_sel += (long)R * sel;
     }
     const long work = q.evals_sel * (long)e->n_sv_pad;
     // A request whose whole SVM work is tiny goes straight to the fp64 MFMA tier (every evaluation enters its list): same
@@ -513,7 +518,8 @@ static int run_prestages(haf_engine *e, Request &q)
     if (e->d_attr.p) HIPCHK(e, hipMemsetAsync(e->d_attr.p, 0xFF, e->d_attr.n * sizeof(AttrRecord), s));   // debug: "not computed"
     mark(e, HAF_ST_BIN);
     // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
-    if (!e->prob_mode && !e->no_fused_pre)
+    // (an ROI request takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
+    if (!e->prob_mode && !e->no_fused_pre && !q.roi)
         q.fused_pre = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
                                        e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
                                        e->d_brslot.p, ++e->pre_epoch);
@@ -533,7 +539,13 @@ static int run_prestages(haf_engine *e, Request &q)
     mark(e, HAF_ST_INTEGRAL);
     launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
     mark(e, HAF_ST_MASK);
-    launch_mask_count(e->d_ii.p, q.d_geo, e->d_mask.p, e->d_rowcount.p, d, s);
+    if (q.roi) {
+        const int rc = roi_mark_cells(e, *q.roi, q.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s);
+        if (rc != HAF_OK) return rc;
+        launch_mask_count_roi(e->d_ii.p, q.d_geo, e->d_roi_cells.p, e->d_mask.p, e->d_rowcount.p, d, s);
+    } else {
+        launch_mask_count(e->d_ii.p, q.d_geo, e->d_mask.p, e->d_rowcount.p, d, s);
+    }
     launch_scan(e->d_rowcount.p, e->d_rowoff.p, e->d_brcount.p, e->d_counters.p, d, s);
     launch_compact(e->d_mask.p, e->d_rowcount.p, e->d_rowoff.p, e->d_evalcell.p, d, s);
     if (q.direct) launch_prob_list(e->d_counters.p, CNT_FLAGGED, e->d_flag_list.p, e->list_cap, s);
@@ -674,7 +686,11 @@ static int vote_and_wait(haf_engine *e, const Request &q)
 {
     const hipStream_t s = q.s;
     mark(e, HAF_ST_VOTE);
-    launch_vote(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, q.d, s);
+    if (q.roi)
+        launch_vote_roi(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p,
+                        e->d_rec.p, e->d_roi_cells.p, q.d, s);
+    else
+        launch_vote(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, q.d, s);
     mark(e, HAF_ST_DOWNLOAD);
     HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));   // counters + records
     mark(e, HAF_ST_COUNT);
@@ -861,6 +877,18 @@ static int adapt_screen_form(haf_engine *e, Request &q, int *mode, bool reprobe)
     return HAF_OK;
 }
 
+// An ROI request says nothing about how the model behaves on whole requests: it neither judges nor changes the screening form.  Only
+// when its screening pass left more undecided than the refinement list holds -- its labels are incomplete then -- the three-pass kernel
+// decides every evaluation of THIS call (same labels by construction); the engine's choice stays as it was
+static int roi_screen_overflow(haf_engine *e, Request &q, int *mode)
+{
+    if (e->h_counters[CNT_FLAGGED0] <= e->flag0_cap) return HAF_OK;
+    e->stat_flag0_overflows++;
+    *mode = MODE_SPLIT;
+    HIPCHK(e, hipMemsetAsync(e->d_counters.p + 1, 0, (CNT_COUNT - 1) * sizeof(int), q.s));
+    return decide(e, q, MODE_SPLIT, false);
+}
+
 static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact_grids, int roll_first, const haf_grasp_input *in,
                           haf_roll_record *records)
 {
@@ -906,18 +934,20 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
 }
 
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames, const int32_t *views)
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames, const int32_t *views, const RoiCall *roi)
 {
     if (!e) return HAF_E_ARG;
     Request q;
     q.frames = frames;
     q.views = views;
+    q.roi = roi;
     int rc = check_request(e, n_clouds, clouds, in, roll_first, roll_count, records, q);
     if (rc != HAF_OK) return rc;
     pack_headers(e, clouds, in, roll_first, q);
     q.s = e->stream;
     mark(e, 0);
     if ((rc = frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
+    if (roi && (rc = roi_upload_masks(e, *roi, frames, q.B, q.s)) != HAF_OK) return rc;
     classify_request(e, in, q);
     if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
     int mode = contraction_mode(e->cfg);
@@ -925,7 +955,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     if (mode == MODE_SCREEN && !e->screen_active) {
         // (the switch-off used to be for the engine's lifetime) every reprobe_every-th request that is large enough to judge by
         // runs the screening pass again; it costs that request one wasted pass at worst
-        if (!e->variant_forced && !e->prob_mode && !q.direct && q.evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
+        if (!roi && !e->variant_forced && !e->prob_mode && !q.direct && q.evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
             e->inactive_calls = 0;
             reprobe = true;
         } else {
@@ -939,15 +969,16 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         // height grids of this call may miss points.  Serve the request -- and this engine from now on -- with k_bin instead.
         e->no_bucket_sort = true;
         e->counters_clean = false;
-        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames, views);
+        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames, views, roi);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
-    if (mode == MODE_SCREEN && !e->prob_mode && !q.direct && (rc = adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
+    if (mode == MODE_SCREEN && !e->prob_mode && !q.direct &&
+        (rc = roi ? roi_screen_overflow(e, q, &mode) : adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
     return record_outcome(e, q, mode, inexact_grids, roll_first, in, records);
 }
 
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames, const int32_t *views)
+                     const haf_frame *frames, const int32_t *views, const RoiCall *roi)
 {
     if (!e) return HAF_E_ARG;
     if (!out) return fail(e, HAF_E_ARG, "haf_score_batch: null output");
@@ -960,7 +991,7 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     if (none_runs)
         e->last = LastCall{};
     else if (frames)
-        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames, views);
+        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames, views, roi);
     else
         rc = haf_score_rolls(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data());
     if (rc != HAF_OK) return rc;

@@ -6,6 +6,7 @@
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
 //   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
+//   engine_roi.cpp       haf_score_frames_roi: the checks, the ROI buffers, the masks' upload and the launch of k_roi_mark
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every translation unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
@@ -137,6 +138,13 @@ struct LastCall {
     // point count; staged = false for a device-resident xyz cloud, which lies in the caller's memory
     struct CloudSrc { size_t float_off = 0; size_t n = 0; bool staged = false; };
     std::vector<CloudSrc> clouds;
+};
+
+// haf_score_frames_roi: what the request path (engine_request.cpp) needs of the call, filled by engine_roi.cpp
+struct RoiCall {
+    const haf_roi *rois = nullptr;       // rois[b] goes with frame b
+    std::vector<long> masked;            // per request: the non-zero bytes of a host mask, -1 for a device-resident mask
+    std::vector<size_t> off;             // per request: where a host mask lies in d_roi_mask / h_roi_mask (packed rows, 16-byte aligned)
 };
 
 }  // namespace haf_host
@@ -337,6 +345,12 @@ struct haf_engine {
     DevBuf<char> d_map;
     char *h_map = nullptr;
     size_t h_map_cap = 0;
+    // haf_score_frames_roi (engine_roi.cpp), allocated on its first call: the ROI cell sets -- one bit per cell, max_clouds x max_rolls
+    // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes, every mask at a
+    // multiple of 16 bytes) with its pinned twin
+    DevBuf<unsigned long long> d_roi_cells;
+    DevBuf<unsigned char> d_roi_mask;
+    unsigned char *h_roi_mask = nullptr;
 };
 
 namespace haf_host {
@@ -469,14 +483,23 @@ int build_tables(haf_engine *e);
 int alloc_buffers(haf_engine *e);
 // engine_request.cpp
 // (frames != nullptr: cloud b's points are frame b's, deprojected on the device; clouds[b] then only carries its point count)
+// (roi != nullptr: haf_score_frames_roi -- frames given, no views; only the cells near the masked pixels' cells are evaluated)
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr, const int32_t *views = nullptr);
+                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr, const int32_t *views = nullptr,
+                     const RoiCall *roi = nullptr);
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames = nullptr, const int32_t *views = nullptr);
+                     const haf_frame *frames = nullptr, const int32_t *views = nullptr, const RoiCall *roi = nullptr);
 int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out);
 // (views != nullptr: cloud b's points are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count)
 int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
                      haf_grasp_output *out, int64_t *n_points);
+// engine_roi.cpp
+int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in, haf_grasp_output *out);
+// the staged host masks of the call to the device (no synchronisation)
+int roi_upload_masks(haf_engine *e, const RoiCall &roi, const haf_frame *frames, int B, hipStream_t s);
+// clears the B * R ROI cell sets and marks them: k_roi_mark per request, on the points k_frame_points left at h_clouds[b].xyz
+int roi_mark_cells(haf_engine *e, const RoiCall &roi, const haf_frame *frames, const CloudDev *h_clouds, const RollGeo *d_geo, const Dims &d,
+                   float r_row, float r_col, hipStream_t s);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

@@ -512,6 +512,18 @@ void launch_map_best(const short *vote, const short *roll, const unsigned char *
 // the record of cell (row, col) of (cloud, roll) br of the last batch: its vote, the 9x8 z window of k_top_grasps, the roll's n_evals
 void launch_cell_record(const short *ev16, const float *heights, const RollRecordDev *rec, int br, int row, int col, int H, int W,
                         RollRecordDev *out, hipStream_t s);
+// haf_score_frames_roi (roi.hip; ROI forms in prestages.hip and vote.hip).  The ROI cell set S of a (request, roll) is a bit set of H rows
+// of roi_row_words(W) 64-bit words: cell (row, col) is bit (col & 63) of word (col >> 6) of its row
+__host__ __device__ inline int roi_row_words(int W) { return (W + 63) >> 6; }
+// one request: the cells of its n = width * height pixels whose mask byte (mask[v * mask_stride + u]) is not zero and whose point (xyz,
+// packed, pixel order: what k_frame_points wrote) is finite, under the R rolls of geo, OR-ed into S (R grids, zeroed by the caller)
+void launch_roi_mark(const unsigned char *mask, size_t mask_stride, int width, int n, const float *xyz, const RollGeo *geo, int R,
+                     unsigned long long *S, int H, int W, float r_row, float r_col, hipStream_t s);
+// launch_mask_count with m = cell_in_box && any(S at c + T), T = the 29 taps of the vote; S: B * R grids
+void launch_mask_count_roi(const float *ii, const RollGeo *geo, const unsigned long long *S, uint8_t *mask, int *rowcount, Dims d, hipStream_t s);
+// launch_vote with v = 0 outside S, before the argmax key, the row maxima and the store
+void launch_vote_roi(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
+                     int *rowmax, RollRecordDev *rec, const unsigned long long *S, Dims d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

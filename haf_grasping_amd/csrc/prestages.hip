@@ -756,6 +756,50 @@ void launch_mask_count(const float *ii, const RollGeo *geo, uint8_t *mask, int *
     hipLaunchKernelGGL(k_mask_count, dim3((d.H + kRowsPerWg - 1) / kRowsPerWg, d.B * d.R), dim3(64 * kRowsPerWg), 0, s, ii, geo, mask, rowcount, d);
 }
 
+// The ROI form (haf_score_frames_roi; its own kernel, k_mask_count above is what it was): m = cell_in_box && any(S at c + T), S = the
+// roll's ROI cell set as k_roi_mark left it (roi.hip: a bit per cell, 64-bit words), T = the 29 taps of the vote (|dr| <= 2 and
+// |dc| <= 2, plus dr = 0 and |dc| = 3, 4; vote.hip).  A wave's 64 columns are ONE word of each of the five rows, so the dilation is
+// wave-uniform: per row the word and its two neighbours, shifted by 1..2 (1..4 in the cell's own row) both ways and OR-ed.  Mask bytes
+// and row counts go where k_mask_count puts them; k_scan, k_compact and everything behind them run on the shorter list.
+__global__ __launch_bounds__(64 * kRowsPerWg) void k_mask_count_roi(const float *__restrict__ ii, const RollGeo *__restrict__ geo,
+                                                                    const unsigned long long *__restrict__ S, uint8_t *__restrict__ mask,
+                                                                    int *__restrict__ rowcount, Dims d)
+{
+    // (the wave's row through readfirstlane: the words of S are then read by scalar loads)
+    const int i = blockIdx.x * kRowsPerWg + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), br = blockIdx.y, lane = threadIdx.x & 63;
+    const int H = d.H, W = d.W, W1 = W + 1, WP = roi_row_words(W);
+    if (i >= H) return;
+    const float *I = ii + (size_t)br * (H + 1) * W1;
+    const RollGeo &g = geo[br];
+    const unsigned long long *Sg = S + (size_t)br * H * WP;
+    uint8_t *mrow = mask + ((size_t)br * H + i) * W;
+    int cnt = 0;
+    for (int j0 = 0; j0 < W; j0 += 64) {
+        const int k = j0 >> 6;
+        unsigned long long near = 0;                                   // bit l: some cell of (i, j0 + l) + T is in S
+        for (int dr = -2; dr <= 2; dr++) {
+            const int rr = i + dr;
+            if (rr < 0 || rr >= H) continue;
+            const unsigned long long *row = Sg + (size_t)rr * WP;
+            const unsigned long long lo = k > 0 ? row[k - 1] : 0ull, mid = row[k], hi = k + 1 < WP ? row[k + 1] : 0ull;
+            const int reach = dr == 0 ? 4 : 2;
+            near |= mid;
+            for (int sh = 1; sh <= reach; sh++)
+                near |= (mid << sh) | (lo >> (64 - sh)) | (mid >> sh) | (hi << (64 - sh));
+        }
+        int j = j0 + lane;
+        bool m = (j < W) && ((near >> lane) & 1ull) && cell_in_box(I, W1, H, i, j, g);
+        if (j < W) mrow[j] = m ? 1 : 0;
+        cnt += __popcll(__ballot(m));
+    }
+    if (lane == 0) rowcount[br * H + i] = cnt;
+}
+
+void launch_mask_count_roi(const float *ii, const RollGeo *geo, const unsigned long long *S, uint8_t *mask, int *rowcount, Dims d, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mask_count_roi, dim3((d.H + kRowsPerWg - 1) / kRowsPerWg, d.B * d.R), dim3(64 * kRowsPerWg), 0, s, ii, geo, S, mask, rowcount, d);
+}
+
 // Evaluation order.  The evaluations of a grid row are its masked cells from left to right, cut into chunks of 64: the
 // whole chunks of all rows come first (region A, row by row), the left-over chunks (fewer than 64 cells) of all rows follow
 // (region B).  A wave of the feature kernel takes 64 consecutive evaluations, so in region A it nearly always holds 64

@@ -2,6 +2,9 @@
 // argmax, longest-run centring) and the z window of transform_gp_in_wcs_and_publish 1342-1351
 // (src/calc_grasppoints_action_server.cpp)
 //
+// k_vote_cells<ROI> / k_vote_small<ROI>: with ROI (haf_score_frames_roi) a cell outside the roll's ROI cell set S (roi.hip: a bit per cell)
+// scores 0 -- before the argmax key, the row maxima and the store.  The ungated instantiations never read S.
+//
 // Built with -ffp-contract=off: every fp32/fp64 expression that must match the CPU restatement bit for bit is
 // written with explicit *_rn intrinsics as well; fma() is used only where a fused operation is intended.
 #include "device_common.h"
@@ -57,8 +60,15 @@ __device__ __forceinline__ void vote_quad(const int8_t *__restrict__ g, int W, i
     }
 }
 
+__device__ __forceinline__ unsigned long long roi_word(const unsigned long long *__restrict__ S, int W, int row, int col)
+{
+    return S[(size_t)row * roi_row_words(W) + (col >> 6)] >> (col & 63);      // bit 0: cell (row, col); bit k: (row, col + k) while in the word
+}
+
+template <bool ROI>
 __global__ __launch_bounds__(256) void k_vote_cells(const int8_t *__restrict__ labels, short *__restrict__ ev16,
-                                                    unsigned long long *__restrict__ topkey, int *__restrict__ rowmax, Dims d)
+                                                    unsigned long long *__restrict__ topkey, int *__restrict__ rowmax, Dims d,
+                                                    const unsigned long long *__restrict__ S)
 {
     __shared__ unsigned long long red[256];
     __shared__ int rmax[kVoteCellsPerBlock / 8 + 2];                  // best vote of every grid row this block touches (W >= 15)
@@ -66,6 +76,7 @@ __global__ __launch_bounds__(256) void k_vote_cells(const int8_t *__restrict__ l
     const int H = d.H, W = d.W, HW = H * W;
     const int8_t *g = labels + (size_t)br * HW;
     short *ev = ev16 + (size_t)br * HW;
+    const unsigned long long *Sg = ROI ? S + (size_t)br * H * roi_row_words(W) : nullptr;
     unsigned long long best = 0;
     const int lo = blockIdx.x * kVoteCellsPerBlock, hi = min(HW, lo + kVoteCellsPerBlock);
     const int row_lo = lo / W, n_rows = (hi - 1) / W - row_lo + 1;
@@ -75,7 +86,15 @@ __global__ __launch_bounds__(256) void k_vote_cells(const int8_t *__restrict__ l
         for (int idx = lo + 4 * t; idx < hi; idx += 4 * 256) {       // (kVoteCellsPerBlock and W are multiples of 4: a quad never straddles)
             const int row = idx / W, col = idx - row * W;
             int v[4] = {0, 0, 0, 0};
-            if (row >= 2 && row < H - 2 && col >= 4 && col + 4 <= W - 4) vote_quad(g, W, row, col, v);   // 870-879 (the border scores 0)
+            if (row >= 2 && row < H - 2 && col >= 4 && col + 4 <= W - 4) {                                // 870-879 (the border scores 0)
+                vote_quad(g, W, row, col, v);
+                if constexpr (ROI) {
+                    const unsigned long long in = roi_word(Sg, W, row, col);     // (col is a multiple of 4: the quad lies in one word)
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (!((in >> k) & 1ull)) v[k] = 0;
+                }
+            }
             typedef short short4v __attribute__((ext_vector_type(4)));
             *reinterpret_cast<short4v *>(ev + idx) = short4v{(short)v[0], (short)v[1], (short)v[2], (short)v[3]};
             const int vm = max(max(v[0], v[1]), max(v[2], v[3]));
@@ -90,7 +109,8 @@ __global__ __launch_bounds__(256) void k_vote_cells(const int8_t *__restrict__ l
         for (int idx = lo + t; idx < hi; idx += 256) {
             int row = idx / W, col = idx - row * W;
             int v = 0;
-            if (g[idx] >= 0 && row >= 2 && row < H - 2 && col >= 4 && col < W - 4) v = vote_at(g, W, row, col);   // 870-879
+            if (g[idx] >= 0 && row >= 2 && row < H - 2 && col >= 4 && col < W - 4 && (!ROI || (roi_word(Sg, W, row, col) & 1ull)))
+                v = vote_at(g, W, row, col);                          // 870-879
             ev[idx] = (short)v;
             if (v > 0) atomicMax(&rmax[row - row_lo], v);
             unsigned long long key = ((unsigned long long)(unsigned)(v + 32768) << 32) | (unsigned)(0x7FFFFFFF - idx);
@@ -195,9 +215,10 @@ __global__ __launch_bounds__(64) void k_vote_record(const float *__restrict__ he
 // Small grids: labels, votes, argmax, run centring, z window and the record of one (cloud, roll) in ONE workgroup and one launch
 // (five launches and two memsets otherwise: more than the work at 56 x 56).
 constexpr int kVoteSmallCells = 16384;
+template <bool ROI>
 __global__ __launch_bounds__(256) void k_vote_small(const int8_t *__restrict__ labels, const float *__restrict__ heights,
                                                     const int *__restrict__ brcount, short *__restrict__ ev16,
-                                                    RollRecordDev *__restrict__ rec, Dims d)
+                                                    RollRecordDev *__restrict__ rec, Dims d, const unsigned long long *__restrict__ S)
 {
     extern __shared__ __attribute__((aligned(16))) short s_ev[];   // [H*W] votes, then [H*W] labels as bytes
     __shared__ unsigned long long red[256];
@@ -207,6 +228,7 @@ __global__ __launch_bounds__(256) void k_vote_small(const int8_t *__restrict__ l
     int8_t *s_g = reinterpret_cast<int8_t *>(s_ev + HW);
     const int8_t *g = labels + (size_t)br * HW;
     short *ev = ev16 + (size_t)br * HW;
+    const unsigned long long *Sg = ROI ? S + (size_t)br * H * roi_row_words(W) : nullptr;
     if ((HW & 15) == 0) {                                 // sixteen labels per load (byte by byte this loop was HW / 256 dependent round trips)
         for (int k = t; k < HW / 16; k += 256) reinterpret_cast<uint4 *>(s_g)[k] = reinterpret_cast<const uint4 *>(g)[k];
     } else {
@@ -217,7 +239,8 @@ __global__ __launch_bounds__(256) void k_vote_small(const int8_t *__restrict__ l
     for (int idx = t; idx < HW; idx += 256) {
         const int row = idx / W, col = idx - row * W;
         int v = 0;
-        if (s_g[idx] >= 0 && row >= 2 && row < H - 2 && col >= 4 && col < W - 4) v = vote_at(s_g, W, row, col);   // 870-879
+        if (s_g[idx] >= 0 && row >= 2 && row < H - 2 && col >= 4 && col < W - 4 && (!ROI || (roi_word(Sg, W, row, col) & 1ull)))
+            v = vote_at(s_g, W, row, col);                // 870-879
         s_ev[idx] = (short)v;
         ev[idx] = (short)v;
         const unsigned long long key = ((unsigned long long)(unsigned)(v + 32768) << 32) | (unsigned)(0x7FFFFFFF - idx);
@@ -280,21 +303,34 @@ __global__ __launch_bounds__(256) void k_vote_small(const int8_t *__restrict__ l
     }
 }
 
-void launch_vote(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
-                 int *rowmax, RollRecordDev *rec, Dims d, hipStream_t s)
+template <bool ROI>
+static void launch_vote_form(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
+                             int *rowmax, RollRecordDev *rec, const unsigned long long *S, Dims d, hipStream_t s)
 {
     if (d.H * d.W <= kVoteSmallCells) {                   // 3 bytes of LDS per cell: 48 KiB at most
-        hipLaunchKernelGGL(k_vote_small, dim3(d.B * d.R), dim3(256), (size_t)d.H * d.W * 3 + 16, s, labels, heights, brcount, ev16, rec, d);
+        hipLaunchKernelGGL(k_vote_small<ROI>, dim3(d.B * d.R), dim3(256), (size_t)d.H * d.W * 3 + 16, s, labels, heights, brcount, ev16, rec, d, S);
         return;
     }
     (void)hipMemsetAsync(rowmax, 0, (size_t)d.B * d.R * d.H * sizeof(int), s);
     // topkey: two arrays of B*R 64-bit words (top vote key, longest-run key)
     (void)hipMemsetAsync(topkey, 0, (size_t)2 * d.B * d.R * sizeof(unsigned long long), s);
     const int HW = d.H * d.W;
-    hipLaunchKernelGGL(k_vote_cells, dim3((HW + kVoteCellsPerBlock - 1) / kVoteCellsPerBlock, d.B * d.R), dim3(256), 0, s, labels, ev16,
-                       topkey, rowmax, d);
+    hipLaunchKernelGGL(k_vote_cells<ROI>, dim3((HW + kVoteCellsPerBlock - 1) / kVoteCellsPerBlock, d.B * d.R), dim3(256), 0, s, labels, ev16,
+                       topkey, rowmax, d, S);
     hipLaunchKernelGGL(k_vote_pick, dim3((d.H + 63) / 64, d.B * d.R), dim3(64), 0, s, ev16, topkey, rowmax, d);
     hipLaunchKernelGGL(k_vote_record, dim3(d.B * d.R), dim3(64), 0, s, heights, brcount, topkey, rec, d);
+}
+
+void launch_vote(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
+                 int *rowmax, RollRecordDev *rec, Dims d, hipStream_t s)
+{
+    launch_vote_form<false>(labels, heights, brcount, ev16, topkey, rowmax, rec, nullptr, d, s);
+}
+
+void launch_vote_roi(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
+                     int *rowmax, RollRecordDev *rec, const unsigned long long *S, Dims d, hipStream_t s)
+{
+    launch_vote_form<true>(labels, heights, brcount, ev16, topkey, rowmax, rec, S, d, s);
 }
 
 }  // namespace haf

@@ -77,14 +77,21 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
-    def execute_frame(self, goal: GraspInputMsg, frame) -> GraspOutputMsg:
+    def execute_frame(self, goal: GraspInputMsg, frame, roi_mask=None) -> GraspOutputMsg:
         """execute() for a goal whose cloud is still what the sensor delivered: `frame` is a capi.depth_frame (a 16UC1 / 32FC1 depth
         image with the camera's K and the sensor-to-base transform) or a capi.xyz_frame (an organised cloud in the sensor frame);
         goal.input_pc is not read.  The engine deprojects and transforms on the device (haf_score_frames): the step the reference does
-        with pcl_ros::transformPointCloud before the hot path (server.cpp:307-316).  top_grasps() works afterwards as after execute()."""
+        with pcl_ros::transformPointCloud before the hot path (server.cpp:307-316).  top_grasps() works afterwards as after execute().
+        roi_mask: uint8 [height, width] (e.g. a segmenter's instance mask synchronised with the depth topic), or (device_ptr,
+        row_stride_bytes): the whole frame still builds the scene, but only the cells near the cells of the masked pixels are scored
+        and the result is the best grasp there (haf_score_frames_roi); top_grasps(), grasp_map() and best_in_mask() then answer for
+        the restricted request."""
         if goal.goal_frame_id:
             self.base_frame_id = goal.goal_frame_id
-        out = self.engine.score_frames([frame], [goal.to_c()])[0]
+        if roi_mask is not None:
+            out = self.engine.score_frames_roi([frame], [roi_mask], [goal.to_c()])[0]
+        else:
+            out = self.engine.score_frames([frame], [goal.to_c()])[0]
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 

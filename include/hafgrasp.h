@@ -455,6 +455,48 @@ int  haf_cell_pose(haf_engine *e, int32_t request, int32_t roll, int32_t row, in
 int  haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, const uint8_t *mask, size_t mask_row_stride,
                         int32_t min_vote, haf_grasp_candidate *out, int32_t *u, int32_t *v, int32_t *found);
 
+/* ---- scoring only under a pixel mask: "grasp THIS object" without scoring the whole search area (csrc/roi.hip) ------------------
+ * haf_score_frames with, per request, an image-space mask over its frame (a segmenter's output).  The cloud of request b is exactly
+ * haf_score_frames' cloud of frames[b]: every pixel goes in, masked or not, because the height grids need the whole scene.  What the
+ * mask restricts is the set of cells that get a feature vector, a decision and a label.  Per roll r (global index):
+ *   ROI cells S_r     the cells haf_point_cells gives the haf_frame_points points of the pixels whose mask byte is not zero and whose
+ *                     point is finite in all three components (the rule of haf_view_points);
+ *   footprint T       the 29 taps of the vote (server.cpp:873-878): |dr| <= 2 and |dc| <= 2, plus dr = 0 and |dc| = 3, 4; T = -T;
+ *   evaluated E_r     the cells c the full request would evaluate (its mask: pnt_in_box, unchanged) with c + t in S_r for some t in T.
+ *                     Only these get a label; every other cell keeps label -1;
+ *   votes V'_r        the full request's vote V_r(c) for c in S_r, 0 elsewhere.  This holds by construction: a vote reads only c + T,
+ *                     all of which is in E_r or outside the full request's mask in both requests, and the labels on E_r are the full
+ *                     request's (decision VALUES are not part of the contract: another request composition may be decided by
+ *                     another tier);
+ *   record of roll r  the reference's rule (first-wins argmax, longest-run centring, 9x8 z window; server.cpp:882-932, 1342-1351)
+ *                     applied to V'_r, n_evals = |E_r|;
+ *   output            haf_finalize on those records.
+ * Consequence: the best vote over the rolls' records equals the maximum of the FULL request's haf_grasp_map vote over the masked
+ * pixels whenever that maximum is > 0.  An S_r that is empty in every roll gives the reference's "nothing found" (eval = -20,
+ * n_evals = 0) and HAF_OK.
+ *
+ * haf_roi_cells: the host definition of record, no device, no engine.  roi = S_r, eval = the T-dilation of S_r BEFORE the test of the
+ * full request's mask (E_r = eval AND that mask); grid_h * grid_w bytes each, 0 / 1, either may be NULL.  roll is the global index.
+ * HAF_E_ARG: a null cfg, in, frame or mask, grid_h / grid_w / n_rolls < 1, roll outside [0, n_rolls), mask_row_stride < width, a frame
+ * haf_frame_points would refuse (a device-resident one included); HAF_E_CAPACITY: a frame of more than INT32_MAX pixels. */
+typedef struct haf_roi {
+    const uint8_t *mask;      /* width x height of the frame it goes with; != 0 selects the pixel */
+    size_t  row_stride_bytes; /* >= width */
+    int32_t on_device;        /* 0 host, 1 device-resident (caller has synchronised its writer) */
+} haf_roi;
+int  haf_roi_cells(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const haf_frame *frame, const uint8_t *mask,
+                   size_t mask_row_stride, uint8_t *roi, uint8_t *eval);
+/* rois[b] goes with frames[b].  Afterwards the last-batch state is the ROI request's: haf_get_roll_grid returns V'_r and E_r, and
+ * haf_top_grasps, haf_grasp_map, haf_cell_pose, haf_grasp_map_best, haf_debug_fetch*, haf_last_* and haf_get_stage_ms work on it
+ * unchanged (the ROI kernels count as HAF_ST_MASK).  A request never changes which form of the screening pass serves the engine
+ * (haf_screen_form): the calls after it take the paths they would have taken without it.  Checked before any device work, a refused
+ * call leaves the engine as it was, the message names the request -- HAF_E_ARG: everything haf_score_frames refuses, a null rois or
+ * mask, on_device not 0 or 1, a row stride smaller than the width, an engine created with HAF_FLAG_PROBABILITY; HAF_E_CAPACITY as
+ * haf_score_frames.  The first call allocates the ROI cell sets (one bit per cell of max_clouds x max_rolls_per_call grids) and the
+ * area of uploaded host masks (max_points bytes).  Not through haf_score_views, haf_score_rolls or the sharded multi-GPU calls. */
+int  haf_score_frames_roi(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in,
+                          haf_grasp_output *out);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
