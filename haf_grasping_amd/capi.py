@@ -211,6 +211,8 @@ def _bind(path, testing):
         L.haf_test_snapshot_screen.argtypes = [E, C.c_int]
         L.haf_test_fetch_snapshot.argtypes = [E, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
         L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.haf_test_revote.argtypes = [E, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.haf_test_last_batch.argtypes = [E, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.haf_test_top_merge.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int] + [C.c_void_p] * 5 + \
             [C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return L
@@ -549,6 +551,40 @@ class Engine:
         if nbytes > 0:
             self._check(self._L.haf_test_fetch_snapshot(self._h, which, offset, buf.ctypes.data_as(C.c_void_p), nbytes, C.byref(avail)))
         return buf
+
+    def revote(self, labels=None, gridf=None, heights=None, roi_words=None):
+        """Testing build (haf_test_revote): replaces the last scored batch's B x R grids by `labels` (int8 [B, R, H, W]; a plain engine)
+        or `gridf` (float32; an engine with FLAG_PROBABILITY), optionally its height grids (float32 [B, R, H, W]) and ROI cell sets
+        (uint64 [B, R, H, (W + 63) // 64]; needs an earlier score_frames_roi), and runs the request path's vote launchers on them
+        -> the roll records [B, R].  roll_grid, top_grasps, grasp_map, best_in_mask and cell_pose then describe the re-voted grids."""
+        H, W = self.cfg.grid_h, self.cfg.grid_w
+        if (labels is None) == (gridf is None):
+            raise HafError(HAF_E_ARG, "revote: exactly one of labels and gridf")
+        # the hook reads B x R grids of the LAST BATCH from every pointer it is given: the arrays must have exactly that shape
+        b, r = C.c_int(), C.c_int()
+        self._check(self._L.haf_test_last_batch(self._h, C.byref(b), C.byref(r)))
+        B, R = b.value, r.value
+        if B < 1 or R < 1:                                   # no scored batch: the hook refuses before it reads anything
+            B, R = np.shape(labels if labels is not None else gridf)[:2]
+        for a in (labels, gridf, heights):
+            if a is not None and np.shape(a) != (B, R, H, W):
+                raise HafError(HAF_E_ARG, "revote: an array of shape %r, the last batch is %r" % (np.shape(a), (B, R, H, W)))
+        if roi_words is not None and np.shape(roi_words) != (B, R, H, (W + 63) // 64):
+            raise HafError(HAF_E_ARG, "revote: roi_words of shape %r, the last batch needs %r" % (np.shape(roi_words), (B, R, H, (W + 63) // 64)))
+        keep = []
+
+        def ptr(a, dt, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert a.shape == shape, (a.shape, shape)
+            keep.append(a)
+            return a.ctypes.data
+        rec = np.zeros((B, R), dtype=ROLL_RECORD_DTYPE)
+        self._check(self._L.haf_test_revote(self._h, ptr(labels, np.int8, (B, R, H, W)), ptr(gridf, np.float32, (B, R, H, W)),
+                                            ptr(heights, np.float32, (B, R, H, W)), ptr(roi_words, np.uint64, (B, R, H, (W + 63) // 64)),
+                                            rec.ctypes.data))
+        return rec
 
     def overflow_stats(self):
         """Testing build: how often this engine's requests met a list smaller than what it had to hold."""

@@ -142,7 +142,70 @@ int haf_test_poke_flag0_list(haf_engine *e, int at, int count, int v)
     return hipMemcpy(e->d_flag0_list.p + e->d_flag0_list.n + at, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess ? HAF_OK : HAF_E_DEVICE;
 }
 
-// ---- the hooks below exist in libhafgrasp_testing.so only (-DHAF_TESTING); the product library does not export them ----
+// the last scored batch as haf_test_revote sees it: *B clouds x *R rolls (0 x 0 before the first request)
+int haf_test_last_batch(haf_engine *e, int *B, int *R)
+{
+    if (!e || !B || !R) return HAF_E_ARG;
+    *B = e->last.B; *R = e->last.R;
+    return HAF_OK;
+}
+
+// Votes again on host-chosen grids: the last scored batch's B x R grids of grid_h x grid_w are replaced by `labels` (int8, a plain
+// engine) or `gridf` (fp32, an engine with HAF_FLAG_PROBABILITY) -- exactly one of the two, B*R*H*W values -- and, when given, the
+// height grids by `heights` (B*R*H*W floats) and the ROI cell sets by `roi_words` (B*R*H*roi_row_words(W) words, the layout of
+// haf_roi_cells; the engine must have served an ROI request before).  Then the request path's own launchers run on the engine's
+// stream: launch_vote, launch_vote_roi with roi_words, launch_probability_vote for gridf.  records_out: the B x R roll records.  The
+// device's records, vote grids and heights stay, so haf_get_roll_grid, haf_top_grasps, haf_grasp_map, haf_grasp_map_best and
+// haf_cell_pose describe the re-voted grids (they read the device's records; the pinned host copy is refreshed all the same).
+static int revote_impl(haf_engine *e, const int8_t *labels, const float *gridf, const float *heights, const unsigned long long *roi_words,
+                       haf_roll_record *records_out)
+{
+    if (!records_out || (labels != nullptr) == (gridf != nullptr)) return fail(e, HAF_E_ARG, "haf_test_revote: exactly one of labels and gridf, and records_out");
+    if ((gridf != nullptr) != e->prob_mode) return fail(e, HAF_E_ARG, "haf_test_revote: labels go with a plain engine, gridf with HAF_FLAG_PROBABILITY");
+    if (roi_words && !labels) return fail(e, HAF_E_ARG, "haf_test_revote: roi_words go with labels");
+    const LastCall &last = e->last;
+    if (last.B < 1 || last.R < 1 || last.B > e->cfg.max_clouds || last.R > e->max_rolls) return fail(e, HAF_E_ARG, "haf_test_revote: no scored batch");
+    const int H = e->cfg.grid_h, W = e->cfg.grid_w, BR = last.B * last.R;
+    const size_t cells = (size_t)BR * H * W, words = (size_t)BR * H * (size_t)roi_row_words(W);
+    if (cells > e->cells_cap || e->d_heights.n < cells || (labels ? e->d_labels.n < cells || e->d_ev16.n < cells : e->d_gridf.n < cells || e->d_evf.n < cells) ||
+        e->d_brcount.n < (size_t)BR || (labels && (H * W > 16384) && (e->d_topkey.n < (size_t)2 * BR || e->d_rowmax.n < (size_t)BR * H)))
+        return fail(e, HAF_E_ARG, "haf_test_revote: the batch does not fit the engine's buffers");
+    if (roi_words && (!e->d_roi_cells.p || e->d_roi_cells.n < words)) return fail(e, HAF_E_ARG, "haf_test_revote: no ROI cell sets (no ROI request yet)");
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const hipStream_t s = e->stream;
+    HIPCHK(e, hipStreamSynchronize(s));
+    if (labels) HIPCHK(e, hipMemcpyAsync(e->d_labels.p, labels, cells, hipMemcpyHostToDevice, s));
+    if (gridf) HIPCHK(e, hipMemcpyAsync(e->d_gridf.p, gridf, cells * sizeof(float), hipMemcpyHostToDevice, s));
+    if (heights) HIPCHK(e, hipMemcpyAsync(e->d_heights.p, heights, cells * sizeof(float), hipMemcpyHostToDevice, s));
+    if (roi_words) HIPCHK(e, hipMemcpyAsync(e->d_roi_cells.p, roi_words, words * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    Dims d{};
+    d.H = H; d.W = W; d.R = last.R; d.B = last.B; d.nf = e->nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->n_sv_tiles; d.sv_tile_neg = e->sv_tile_neg;
+    const float *hts = reinterpret_cast<const float *>(e->d_heights.p);
+    if (gridf)
+        launch_probability_vote(e->d_gridf.p, hts, e->d_brcount.p, e->d_evf.p, e->d_rec.p, d, s);
+    else if (roi_words)
+        launch_vote_roi(e->d_labels.p, hts, e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, e->d_roi_cells.p, d, s);
+    else
+        launch_vote(e->d_labels.p, hts, e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, d, s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_rec, e->d_rec.p, (size_t)BR * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    for (int i = 0; i < BR; i++) {
+        records_out[i].vote = e->h_rec[i].vote;
+        records_out[i].row = e->h_rec[i].row;
+        records_out[i].col = e->h_rec[i].col;
+        records_out[i].h_locmax = e->h_rec[i].h_locmax;
+        records_out[i].n_evals = e->h_rec[i].n_evals;
+    }
+    return HAF_OK;
+}
+int haf_test_revote(haf_engine *e, const int8_t *labels, const float *gridf, const float *heights, const unsigned long long *roi_words,
+                    haf_roll_record *records_out)
+{
+    if (!e) return HAF_E_ARG;
+    return guarded(&e->error, [&] { return revote_impl(e, labels, gridf, heights, roi_words, records_out); });
+}
+
 // host-only hooks: parsers, per-roll geometry and the cross-roll rule/pose, none of which touches a device
 int haf_test_feature_table(const char *path, int *n, int *reg /* cap*16 */, float *w /* cap*4 */, int cap)
 {

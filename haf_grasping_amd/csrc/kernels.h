@@ -392,6 +392,9 @@ void launch_prob_list(int *counters, int slot, int *list, int cap, hipStream_t s
 void launch_probability(const double *dec_exact, const int *evalcell, const int *counters, ProbParams P, int8_t *labels,
                         const uint8_t *mask, const int *rowcount, const int *brcount, const float *heights, float *own,
                         double *ptext, float *gridf, float *evf, RollRecordDev *rec, long evals_cap, Dims d, hipStream_t s);
+// its second half on its own: k_prob_vote_cells + k_prob_pick on the grids in gridf (launch_probability ends with this call)
+void launch_probability_vote(const float *gridf, const float *heights, const int *brcount, float *evf, RollRecordDev *rec, Dims d,
+                             hipStream_t s);
 
 void launch_fill_i32(int *p, int v, size_t n, hipStream_t s);
 // scratch of the bucket-sorted binning path (large grids): see prestages.hip

@@ -268,15 +268,22 @@ void launch_probability_eval(const double *dec_exact, const int *evalcell, const
                                    near_cap, counters_rw);
 }
 
+// the vote-and-pick half of the chain: the fp32 votes of the grids in gridf, then every (cloud, roll)'s record
+void launch_probability_vote(const float *gridf, const float *heights, const int *brcount, float *evf, RollRecordDev *rec, Dims d,
+                             hipStream_t s)
+{
+    const size_t cells = (size_t)d.B * d.R * d.H * d.W;
+    hipLaunchKernelGGL(k_prob_vote_cells, dim3((unsigned)std::min<size_t>(8192, (cells + 255) / 256)), dim3(256), 0, s, gridf, evf, d);
+    hipLaunchKernelGGL(k_prob_pick, dim3(d.B * d.R), dim3(1024), 0, s, evf, heights, brcount, rec, d);
+}
+
 void launch_probability(const double *dec_exact, const int *evalcell, const int *counters, ProbParams P, int8_t *labels,
                         const uint8_t *mask, const int *rowcount, const int *brcount, const float *heights, float *own,
                         double *ptext, float *gridf, float *evf, RollRecordDev *rec, long evals_cap, Dims d, hipStream_t s)
 {
     (void)dec_exact; (void)evalcell; (void)counters; (void)labels; (void)ptext; (void)evals_cap;   // (the estimates: launch_probability_eval)
     hipLaunchKernelGGL(k_prob_grid, dim3(d.B * d.R), dim3(256), 0, s, mask, rowcount, own, gridf, P.hdr, d);
-    const size_t cells = (size_t)d.B * d.R * d.H * d.W;
-    hipLaunchKernelGGL(k_prob_vote_cells, dim3((unsigned)std::min<size_t>(8192, (cells + 255) / 256)), dim3(256), 0, s, gridf, evf, d);
-    hipLaunchKernelGGL(k_prob_pick, dim3(d.B * d.R), dim3(1024), 0, s, evf, heights, brcount, rec, d);
+    launch_probability_vote(gridf, heights, brcount, evf, rec, d, s);
 }
 
 void launch_prob_list(int *counters, int slot, int *list, int cap, hipStream_t s)

@@ -18,6 +18,7 @@ import models
 import pcdio
 from haf_grasping_amd import capi
 from oracle import oracle as O
+from oracle_inputs import oracle_input
 
 pytestmark = pytest.mark.gpu
 
@@ -77,12 +78,6 @@ def make_engine(data_dir, model, mode=0, **cfg):
     cfg["flags"] |= mode
     cfg.setdefault("testing", any(k in os.environ for k in TEST_KNOBS))
     return capi.Engine(f, r, model, **cfg)
-
-
-def oracle_input(kw):
-    return O.make_input(center=kw.get("grasp_area_center", (0, 0, 0)), length_x=kw.get("grasp_area_length_x", 32),
-                        length_y=kw.get("grasp_area_length_y", 44), approach=kw.get("approach_vector", (0, 0, 1)),
-                        show_only_best=kw.get("show_only_best_grasp", 0), gripper_width=kw.get("gripper_opening_width", 1))
 
 
 def compare_full(eng, orc, xyz, cfg_kw, in_kw, check_dec=True):
