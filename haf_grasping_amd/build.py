@@ -22,10 +22,10 @@ LIB_TESTING = os.path.join(HERE, "libhafgrasp_testing.so")
 ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp", "engine_graspmap.cpp", "engine_roi.cpp"]
 TESTING_ONLY = ["engine_testing.cpp", "testkernels.hip"]         # libhafgrasp_testing.so only
 SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip", "frames.hip", "graspmap.hip", "roi.hip"] + \
-          ENGINE_SOURCES + ["parsers.cpp", "frames_host.cpp", "graspmap_host.cpp", "roi_host.cpp", "multi.cpp"]
+          ENGINE_SOURCES + ["parsers.cpp", "frames_host.cpp", "frame_stage.cpp", "graspmap_host.cpp", "roi_host.cpp", "multi.cpp"]
 # per-file extra flags (screen.hip: see its header)
 EXTRA = {"screen.hip": ["-fno-slp-vectorize"]}
-HEADERS = ["kernels.h", "device_common.h", "feature_device.h", "screen_band.h", "parsers.h", "decq.h", "engine_internal.h", "engine_state.h", "frame_points.h", "frames.h", "frame_group.h", "grasp_cells.h"] + TESTING_ONLY + [ os.path.join("..", "..", "include", "hafgrasp.h"),
+HEADERS = ["kernels.h", "device_common.h", "feature_device.h", "screen_band.h", "parsers.h", "decq.h", "engine_internal.h", "engine_state.h", "frame_points.h", "frames.h", "frame_stage.h", "frame_group.h", "grasp_cells.h"] + TESTING_ONLY + [ os.path.join("..", "..", "include", "hafgrasp.h"),
            os.path.join("..", "cli", "haf_grasp_cli.cpp"), os.path.join("..", "..", "ros_shim", "shim_core.h")]
 # -ffp-contract=off: the bit-exact stages spell out every rounding; nothing may be fused behind their back
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

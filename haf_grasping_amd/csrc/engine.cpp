@@ -64,7 +64,7 @@ void haf_destroy(haf_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &r : e->host_regs) (void)hipHostUnregister((void *)r.first);
     e->host_regs.clear();
-    e->d_in.release(); e->d_raw.release(); e->d_raw_xyz.release(); e->d_out.release(); e->d_sorted.release(); e->d_bkt.release(); e->d_heights.release(); e->d_rowsum.release(); e->d_inexact.release();
+    e->d_sorted.release(); e->d_bkt.release(); e->d_heights.release(); e->d_rowsum.release(); e->d_inexact.release();
     e->d_ii.release(); e->d_mask.release(); e->d_rowcount.release(); e->d_rowoff.release(); e->d_brcount.release();
     e->d_evalcell.release(); e->d_flag_list.release(); e->d_X.release(); e->d_ax.release();
     e->d_dec.release(); e->d_svt.release(); e->d_svt_h.release(); e->d_labels.release(); e->d_dec_exact.release(); e->d_strict_terms.release(); e->d_part64.release(); e->d_dec_exact2.release(); e->d_flag2_list.release(); e->d_x64.release(); e->d_sv64.release();
@@ -75,18 +75,9 @@ void haf_destroy(haf_engine *e)
     e->d_coef64.release(); e->d_ev16.release(); e->d_attr.release(); e->d_margin.release(); e->d_topkey.release(); e->d_rowmax.release(); e->d_fd.release();
     e->d_sd.release(); e->d_corr.release(); e->d_sd3.release(); e->d_fd_slot.release(); e->d_part1.release();
     e->d_svt_h_cr.release(); e->d_t1_tab.release(); e->d_t1_L.release(); e->d_flag0b_list.release(); e->d_screen_part.release();
-    e->d_svt0_cr.release(); e->d_fd_slot_cr.release(); e->d_sd_cr.release(); e->d_sd3_cr.release(); e->d_corr_cr.release();
-    e->d_top_scratch.release(); e->d_top_out.release();
-    if (e->h_top_out) (void)hipHostFree(e->h_top_out);
-    e->d_map.release();
-    if (e->h_map) (void)hipHostFree(e->h_map);
+    e->d_top_scratch.release(); e->d_roi_cells.release(); e->d_svt0_cr.release(); e->d_fd_slot_cr.release(); e->d_sd_cr.release(); e->d_sd3_cr.release(); e->d_corr_cr.release();
+    for (StageBuf *b : {&e->in_block, &e->raw, &e->raw_xyz, &e->out_block, &e->top_out, &e->map, &e->roi_mask}) b->release();
     e->d_brslot.release(); e->d_tier_words.release(); e->d_t1_flags.release(); e->d_lr_btiles.release(); e->d_svt_lr.release(); e->d_lr_btiles_in.release(); e->d_corr_lrp.release(); e->d_iiabs.release();
-    if (e->h_in) (void)hipHostFree(e->h_in);
-    if (e->h_raw) (void)hipHostFree(e->h_raw);
-    if (e->h_raw_xyz) (void)hipHostFree(e->h_raw_xyz);
-    e->d_roi_cells.release(); e->d_roi_mask.release();
-    if (e->h_roi_mask) (void)hipHostFree(e->h_roi_mask);
-    if (e->h_out) (void)hipHostFree(e->h_out);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
     delete e;

@@ -190,7 +190,7 @@ static int debug_fetch_points_impl(haf_engine *e, int32_t cloud, float *xyz, siz
     if (!c.staged) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: a device-resident xyz cloud lies in the caller's memory, the engine holds no copy");
     if (n_points < c.n) return fail(e, HAF_E_ARG, "haf_debug_fetch_points: xyz holds fewer points than the cloud has");
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    if (c.n) HIPCHK(e, hipMemcpy(xyz, reinterpret_cast<const float *>(e->d_in.p) + c.float_off, c.n * 12, hipMemcpyDeviceToHost));
+    if (c.n) HIPCHK(e, hipMemcpy(xyz, reinterpret_cast<const float *>(e->in_block.dev.p) + c.float_off, c.n * 12, hipMemcpyDeviceToHost));
     return HAF_OK;
 }
 

@@ -2,7 +2,7 @@
 // sensor frame (include/hafgrasp.h).  The device pass (graspmap.hip) reads the vote grids that batch left on the device and, for
 // haf_cell_pose, its height grids and records; nothing here writes to any of them, to the request's input block or to the raw areas
 // of haf_score_frames / haf_score_views: the frame's pixels, the roll transforms, the images and the mask live in one block of their
-// own (haf_engine::d_map).  The roll transforms are recomputed from the inputs the batch was scored with (LastCall::inputs) through
+// own (haf_engine::map).  The roll transforms are recomputed from the inputs the batch was scored with (LastCall::inputs) through
 // fill_roll_geo: the header of the request's input block may have been overwritten since.  Built with -ffp-contract=off.
 #include "engine_state.h"
 
@@ -14,8 +14,6 @@ namespace {
 
 constexpr size_t kMapHdr = 64;            // [0] the best key of k_map_best, [16] the record of k_cell_record
 constexpr size_t kMapRecOff = 16;
-
-size_t up16(size_t x) { return (x + 15) / 16 * 16; }
 
 struct MapLayout {
     size_t geo = 0, vote = 0, roll = 0, cell = 0, mask = 0, raw = 0, total = 0;
@@ -38,14 +36,7 @@ MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t ra
 int ensure_map(haf_engine *e, size_t bytes)
 {
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    if (e->d_map.n >= bytes && e->h_map_cap >= bytes) return HAF_OK;
-    e->d_map.release();
-    if (e->h_map) (void)hipHostFree(e->h_map);
-    e->h_map = nullptr;
-    e->h_map_cap = 0;
-    HIPCHK(e, e->d_map.alloc(bytes));
-    HIPCHK(e, hipHostMalloc((void **)&e->h_map, bytes, hipHostMallocDefault));
-    e->h_map_cap = bytes;
+    HIPCHK(e, e->map.ensure(bytes));
     return HAF_OK;
 }
 
@@ -65,72 +56,30 @@ int check_map_frame(haf_engine *e, const char *who, const haf_frame *f)
 {
     const std::string name(who);
     if (!f) return fail(e, HAF_E_ARG, name + ": null frame");
-    std::string msg;
-    const int rc = check_frame(*f, msg);
-    if (rc != HAF_OK) return fail(e, rc, name + ": " + msg);
-    if ((int64_t)f->width * (int64_t)f->height > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, name + ": more pixels than max_points");
+    const FrameBatch chk = check_frame_batch(f, 1, nullptr, e->cfg.max_points);
+    if (chk.code != HAF_OK) return fail(e, chk.code, name + ": " + (chk.text.empty() ? "more pixels than max_points" : chk.text));
     return HAF_OK;
 }
 
-#ifdef HAF_TESTING
-int check_guards(haf_engine *e)
-{
-    if (!test_env("HAF_CANARY_CHECK")) return HAF_OK;
-    std::string rep;
-    const int bad = canary_check(&rep);
-    if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
-    return HAF_OK;
-}
-#else
-int check_guards(haf_engine *) { return HAF_OK; }
-#endif
-
-// The device pass for one checked frame: stages a host frame's pixels as upload_frames does (in pieces of 256 KB, only the width
-// elements of a row, of an XYZ frame only the three floats of a point), uploads the roll transforms and launches k_grasp_map on the
-// engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
+// The device pass for one checked frame: stages a host frame's pixels (stage_frame, as the request path's upload_frames does), uploads the roll
+// transforms and launches k_grasp_map on the engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
 int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll, int *d_cell)
 {
-    constexpr size_t kPiece = 256 * 1024;
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
     const hipStream_t s = e->stream;
-    memset(e->h_map, 0, kMapHdr);
-    fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->h_map + l.geo));
-    HIPCHK(e, hipMemcpyAsync(e->d_map.p, e->h_map, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
-    FrameDev fd;
-    memset(&fd, 0, sizeof fd);
-    fd.width = f.width;
-    fd.n = f.width * f.height;
-    fd.kind = f.kind;
-    fd.m = frame_math(f);
-    const size_t px = frame_pixel_bytes(f.kind);
-    if (f.on_device == 1) {
-        fd.src = f.data;
-        fd.row_stride = f.row_stride_bytes;
-        fd.point_stride = (unsigned)frame_elem_bytes(f);
-    } else {
-        fd.src = e->d_map.p + l.raw;
-        fd.row_stride = (unsigned long long)f.width * px;
-        fd.point_stride = (unsigned)px;
-        const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
-        const size_t row_bytes = (size_t)f.width * px;
-        size_t staged = 0, sent = 0;
-        for (int v = 0; v < f.height; v++) {
-            const char *row = static_cast<const char *>(f.data) + (size_t)v * f.row_stride_bytes;
-            char *dst = e->h_map + l.raw + staged;
-            if (!xyz || f.point_stride_bytes == 12) memcpy(dst, row, row_bytes);
-            else for (int u = 0; u < f.width; u++) memcpy(dst + (size_t)u * 12, row + (size_t)u * f.point_stride_bytes, 12);
-            staged += row_bytes;
-            if (staged - sent >= kPiece || v + 1 == f.height) {
-                HIPCHK(e, hipMemcpyAsync(e->d_map.p + l.raw + sent, e->h_map + l.raw + sent, staged - sent, hipMemcpyHostToDevice, s));
-                sent = staged;
-            }
-        }
+    memset(e->map.host, 0, kMapHdr);
+    fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->map.host + l.geo));
+    HIPCHK(e, hipMemcpyAsync(e->map.dev.p, e->map.host, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
+    const FrameDev fd = describe_frame(f, e->map.dev.p + l.raw);
+    if (f.on_device != 1) {
+        const auto send = [&](size_t off, size_t bytes) { return hipMemcpyAsync(e->map.dev.p + l.raw + off, e->map.host + l.raw + off, bytes, hipMemcpyHostToDevice, s); };
+        HIPCHK(e, stage_frame(e->map.host + l.raw, f, send));
     }
     const int H = c.grid_h, W = c.grid_w;
     const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
     const short *ev = e->d_ev16.p + (size_t)request * last.R * (size_t)H * W;
-    launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(e->d_map.p + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll,
+    launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(e->map.dev.p + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll,
                      d_cell, s);
     HIPCHK(e, hipGetLastError());
     return HAF_OK;
@@ -146,22 +95,22 @@ int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *
     // (device outputs: the images are the caller's, the block only holds the header, the transforms and a host frame's pixels)
     const MapLayout use = map_layout(e, out_on_device ? 0 : n, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
     if ((rc = ensure_map(e, use.total)) != HAF_OK) return rc;
-    char *d = e->d_map.p;
+    char *d = e->map.dev.p;
     short *dv = !vote ? nullptr : out_on_device ? vote : reinterpret_cast<short *>(d + use.vote);
     short *dr = !roll ? nullptr : out_on_device ? roll : reinterpret_cast<short *>(d + use.roll);
     int *dc = !cell ? nullptr : out_on_device ? cell : reinterpret_cast<int *>(d + use.cell);
     if ((rc = launch_map(e, request, rolls, *f, use, dv, dr, dc)) != HAF_OK) return rc;
     if (!out_on_device) {
-        if (vote) HIPCHK(e, hipMemcpyAsync(e->h_map + use.vote, d + use.vote, n * 2, hipMemcpyDeviceToHost, e->stream));
-        if (roll) HIPCHK(e, hipMemcpyAsync(e->h_map + use.roll, d + use.roll, n * 2, hipMemcpyDeviceToHost, e->stream));
-        if (cell) HIPCHK(e, hipMemcpyAsync(e->h_map + use.cell, d + use.cell, n * 4, hipMemcpyDeviceToHost, e->stream));
+        if (vote) HIPCHK(e, hipMemcpyAsync(e->map.host + use.vote, d + use.vote, n * 2, hipMemcpyDeviceToHost, e->stream));
+        if (roll) HIPCHK(e, hipMemcpyAsync(e->map.host + use.roll, d + use.roll, n * 2, hipMemcpyDeviceToHost, e->stream));
+        if (cell) HIPCHK(e, hipMemcpyAsync(e->map.host + use.cell, d + use.cell, n * 4, hipMemcpyDeviceToHost, e->stream));
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
     if (!out_on_device) {
-        if (vote) memcpy(vote, e->h_map + use.vote, n * 2);
-        if (roll) memcpy(roll, e->h_map + use.roll, n * 2);
-        if (cell) memcpy(cell, e->h_map + use.cell, n * 4);
+        if (vote) memcpy(vote, e->map.host + use.vote, n * 2);
+        if (roll) memcpy(roll, e->map.host + use.roll, n * 2);
+        if (cell) memcpy(cell, e->map.host + use.cell, n * 4);
     }
     return HAF_OK;
 }
@@ -171,17 +120,17 @@ int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, ha
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
     int rc;
-    if (e->d_map.n < kMapHdr && (rc = ensure_map(e, map_layout(e, 0, 0, 0).total)) != HAF_OK) return rc;
+    if (e->map.dev.n < kMapHdr && (rc = ensure_map(e, map_layout(e, 0, 0, 0).total)) != HAF_OK) return rc;
     HIPCHK(e, hipSetDevice(c.device));
     const int br = request * last.R + (roll - last.roll_first);
-    RollRecordDev *d_rec = reinterpret_cast<RollRecordDev *>(e->d_map.p + kMapRecOff);
+    RollRecordDev *d_rec = reinterpret_cast<RollRecordDev *>(e->map.dev.p + kMapRecOff);
     launch_cell_record(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, br, row, col, c.grid_h, c.grid_w, d_rec, e->stream);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_map + kMapRecOff, d_rec, sizeof(RollRecordDev), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->map.host + kMapRecOff, d_rec, sizeof(RollRecordDev), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
     RollRecordDev q;
-    memcpy(&q, e->h_map + kMapRecOff, sizeof q);
+    memcpy(&q, e->map.host + kMapRecOff, sizeof q);
     haf_roll_record rec;
     rec.vote = q.vote; rec.row = q.row; rec.col = q.col; rec.h_locmax = q.h_locmax; rec.n_evals = q.n_evals;
     haf_grasp_candidate cand;
@@ -216,30 +165,30 @@ int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint
     const size_t n = (size_t)f->width * (size_t)f->height;
     const MapLayout l = map_layout(e, n, mask ? n : 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
     if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
-    char *d = e->d_map.p;
+    char *d = e->map.dev.p;
     short *dv = reinterpret_cast<short *>(d + l.vote), *dr = reinterpret_cast<short *>(d + l.roll);
     int *dc = reinterpret_cast<int *>(d + l.cell);
     if ((rc = launch_map(e, request, rolls, *f, l, dv, dr, dc)) != HAF_OK) return rc;
     if (mask) {
-        for (int r = 0; r < f->height; r++) memcpy(e->h_map + l.mask + (size_t)r * f->width, mask + (size_t)r * mask_row_stride, (size_t)f->width);
-        HIPCHK(e, hipMemcpyAsync(d + l.mask, e->h_map + l.mask, n, hipMemcpyHostToDevice, e->stream));
+        pack_rows(e->map.host + l.mask, reinterpret_cast<const char *>(mask), (size_t)f->height, (size_t)f->width, 1, 1, mask_row_stride);
+        HIPCHK(e, hipMemcpyAsync(d + l.mask, e->map.host + l.mask, n, hipMemcpyHostToDevice, e->stream));
     }
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d);      // (zeroed by launch_map's header copy)
     launch_map_best(dv, dr, mask ? reinterpret_cast<const unsigned char *>(d + l.mask) : nullptr, (unsigned)n, min_vote, d_key, e->stream);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_map, d_key, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->map.host, d_key, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
     unsigned long long key;
-    memcpy(&key, e->h_map, 8);
+    memcpy(&key, e->map.host, 8);
     if (key == 0ull) { *found = 0; return HAF_OK; }
     const size_t i = (size_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
     const int roll = 65535 - (int)((key >> 32) & 0xFFFFull);
     if (i >= n || roll < e->last.roll_first || roll >= e->last.roll_first + e->last.R) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed key");
     int32_t ci = -1;
-    HIPCHK(e, hipMemcpyAsync(e->h_map + 8, dc + i, 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->map.host + 8, dc + i, 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    memcpy(&ci, e->h_map + 8, 4);
+    memcpy(&ci, e->map.host + 8, 4);
     const int W = e->cfg.grid_w;
     if (ci < 0 || ci >= e->cfg.grid_h * W) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed cell");
     haf_grasp_candidate cand;

@@ -260,11 +260,7 @@ struct Request {
     long total_n = 0;
     bool bucket_ok = true;
     size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x n_frames])[points of the host clouds]
-    const haf_frame *frames = nullptr;   // haf_score_frames: cloud b's points are frame b's, written by k_frame_points
-    // haf_score_views: cloud b's points are the valid points of views[b] consecutive frames, compacted by k_view_points; the host then
-    // sizes everything by the UPPER bound clouds[b].n_points = the pixels of those views, the live count is CloudDev::n on the device
-    const int32_t *views = nullptr;
-    const RoiCall *roi = nullptr;        // haf_score_frames_roi: only the cells near the cells of the masked pixels are evaluated
+    FrameSource from;                    // (views: the host sizes everything by the UPPER bound clouds[b].n_points, the live count is CloudDev::n on the device)
     int n_frames = 0;                    // entries of frames / h_frames: B, or the sum of views
     FrameDev *h_frames = nullptr;
     const FrameDev *d_frames = nullptr;
@@ -313,24 +309,26 @@ static int check_request(haf_engine *e, int32_t n_clouds, const haf_cloud *cloud
     return HAF_OK;
 }
 
-// the request's input block (d_in / h_in): the two header arrays on the host, one copy carries them with the points
+// the request's input block (in_block): the two header arrays on the host, one copy carries them with the points
 static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp_input *in, int roll_first, Request &q)
 {
     const haf_config &c = e->cfg;
     const int B = q.B, R = q.R;
-    const size_t geo_off = ((size_t)B * sizeof(CloudDev) + 15) / 16 * 16;
-    const size_t frames_off = geo_off + ((size_t)B * R * sizeof(RollGeo) + 15) / 16 * 16;
+    const haf_frame *const frames = q.from.frames;
+    const int32_t *const views = q.from.views;
+    const size_t geo_off = up16((size_t)B * sizeof(CloudDev));
+    const size_t frames_off = geo_off + up16((size_t)B * R * sizeof(RollGeo));
     q.n_frames = 0;
-    for (int b = 0; q.frames && b < B; b++) q.n_frames += q.views ? q.views[b] : 1;
-    q.pts_off = frames_off + ((size_t)q.n_frames * sizeof(FrameDev) + 15) / 16 * 16;
-    q.h_frames = reinterpret_cast<FrameDev *>(e->h_in + frames_off);
-    q.d_frames = reinterpret_cast<const FrameDev *>(e->d_in.p + frames_off);
+    for (int b = 0; frames && b < B; b++) q.n_frames += views ? views[b] : 1;
+    q.pts_off = frames_off + up16((size_t)q.n_frames * sizeof(FrameDev));
+    q.h_frames = reinterpret_cast<FrameDev *>(e->in_block.host + frames_off);
+    q.d_frames = reinterpret_cast<const FrameDev *>(e->in_block.dev.p + frames_off);
     q.src.assign((size_t)B, LastCall::CloudSrc{});
-    q.h_clouds = reinterpret_cast<CloudDev *>(e->h_in);
-    RollGeo *h_geo = reinterpret_cast<RollGeo *>(e->h_in + geo_off);
-    q.d_clouds = reinterpret_cast<const CloudDev *>(e->d_in.p);
-    q.d_geo = reinterpret_cast<const RollGeo *>(e->d_in.p + geo_off);
-    const float *d_points = reinterpret_cast<const float *>(e->d_in.p + q.pts_off);
+    q.h_clouds = reinterpret_cast<CloudDev *>(e->in_block.host);
+    RollGeo *h_geo = reinterpret_cast<RollGeo *>(e->in_block.host + geo_off);
+    q.d_clouds = reinterpret_cast<const CloudDev *>(e->in_block.dev.p);
+    q.d_geo = reinterpret_cast<const RollGeo *>(e->in_block.dev.p + geo_off);
+    const float *d_points = reinterpret_cast<const float *>(e->in_block.dev.p + q.pts_off);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
         NormalisedInput n = normalise(in[b]);
@@ -340,12 +338,12 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
         cd.sorted_off = (int)q.total_n;
         cd.bucket_off = b * e->bkt_ints;
         q.total_n += (long)clouds[b].n_points;
-        cd.n = q.views ? 0 : (int)clouds[b].n_points;    // (views: the kernels count the valid points)
+        cd.n = views ? 0 : (int)clouds[b].n_points;      // (views: the kernels count the valid points)
         if (clouds[b].on_device == 1) {
             cd.xyz = clouds[b].xyz;
             cd.stride = (int)clouds[b].stride_floats;
         } else {
-            if (q.frames) off = (off + 3) / 4 * 4;       // a frame's points start 16-byte aligned: k_frame_points stores whole dwordx4
+            if (frames) off = (off + 3) / 4 * 4;         // a frame's points start 16-byte aligned: k_frame_points stores whole dwordx4
             cd.xyz = d_points + off * 3;
             cd.stride = 3;
             q.src[(size_t)b] = LastCall::CloudSrc{q.pts_off / sizeof(float) + off * 3, clouds[b].n_points, true};
@@ -355,71 +353,45 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     // the frames' descriptors: device-resident frames are read where they lie; a host XYZ frame is packed where its points go and
     // transformed in place; a host depth frame's pixels go through the raw area, every frame at a multiple of 16 bytes.
     // Views: compaction writes where other lanes have not read yet, so a host XYZ view is NOT staged in the points area but in a raw
-    // area of its own (d_raw_xyz); the views of a request share its region and its counter
+    // area of its own (raw_xyz); the views of a request share its region and its counter
     size_t raw = 0, raw_xyz = 0;
-    for (int b = 0, k = 0; q.frames && b < B; b++) {
-        for (int v = 0; v < (q.views ? q.views[b] : 1); v++, k++) {
-            const haf_frame &f = q.frames[k];
+    for (int b = 0, k = 0; frames && b < B; b++) {
+        for (int v = 0; v < (views ? views[b] : 1); v++, k++) {
+            const haf_frame &f = frames[k];
+            const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
             FrameDev &fd = q.h_frames[k];
+            fd = describe_frame(f, !xyz ? e->raw.dev.p + raw : views ? e->raw_xyz.dev.p + raw_xyz : reinterpret_cast<const char *>(q.h_clouds[b].xyz));
             fd.dst = const_cast<float *>(q.h_clouds[b].xyz);
-            fd.count = q.views ? const_cast<int *>(&q.d_clouds[b].n) : nullptr;
-            fd.width = f.width;
-            fd.n = f.width * f.height;
-            fd.kind = f.kind;
-            fd.m = frame_math(f);
-            const size_t px = frame_pixel_bytes(f.kind);
-            if (f.on_device == 1) {
-                fd.src = f.data;
-                fd.row_stride = f.row_stride_bytes;
-                fd.point_stride = (unsigned)frame_elem_bytes(f);
-            } else {
-                const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
-                fd.src = !xyz ? e->d_raw.p + raw : q.views ? e->d_raw_xyz.p + raw_xyz : reinterpret_cast<const char *>(fd.dst);
-                fd.row_stride = (unsigned long long)f.width * px;
-                fd.point_stride = (unsigned)px;
-                (xyz ? raw_xyz : raw) += ((size_t)fd.n * px + 15) / 16 * 16;
-            }
+            fd.count = views ? const_cast<int *>(&q.d_clouds[b].n) : nullptr;
+            (xyz ? raw_xyz : raw) += staged_bytes(f);
         }
     }
 }
 
-// Host frames go to the device as upload_clouds sends host clouds: in pieces of 256 KB, the DMA engine moving one while the host
-// copies the rows of the next -- only the width elements of a row, not its padding, and of an XYZ frame only the three floats of a
-// point.  Then ONE launch per kind writes the points of every frame of the batch (frames.hip).
+// Host frames go to the device as upload_clouds sends host clouds, in pieces, the DMA engine moving one while the host packs the rows
+// of the next (stage_frame, frame_stage.h).  Then ONE launch per kind writes the points of every frame of the batch (frames.hip).
 static int upload_frames(haf_engine *e, const Request &q)
 {
-    constexpr size_t kPiece = 256 * 1024;
     const hipStream_t s = q.s;
-    HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, q.pts_off, hipMemcpyHostToDevice, s));      // the three header arrays
+    const bool views = q.from.views != nullptr;
+    HIPCHK(e, hipMemcpyAsync(e->in_block.dev.p, e->in_block.host, q.pts_off, hipMemcpyHostToDevice, s));      // the three header arrays
     for (int b = 0; b < q.n_frames; b++) {
-        const haf_frame &f = q.frames[b];
+        const haf_frame &f = q.from.frames[b];
         if (f.on_device == 1) continue;
-        const FrameDev &fd = q.h_frames[b];
         const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
-        char *const dev = !xyz ? e->d_raw.p : q.views ? e->d_raw_xyz.p : e->d_in.p, *const host = !xyz ? e->h_raw : q.views ? e->h_raw_xyz : e->h_in;
-        const size_t at = (size_t)(static_cast<const char *>(fd.src) - dev);      // the frame's place in its block, device and pinned alike
-        const size_t row_bytes = (size_t)f.width * frame_pixel_bytes(f.kind);
-        size_t staged = 0, sent = 0;
-        for (int v = 0; v < f.height; v++) {
-            const char *row = static_cast<const char *>(f.data) + (size_t)v * f.row_stride_bytes;
-            char *dst = host + at + staged;
-            if (!xyz || f.point_stride_bytes == 12) memcpy(dst, row, row_bytes);
-            else for (int u = 0; u < f.width; u++) memcpy(dst + (size_t)u * 12, row + (size_t)u * f.point_stride_bytes, 12);
-            staged += row_bytes;
-            if (staged - sent >= kPiece || v + 1 == f.height) {
-                HIPCHK(e, hipMemcpyAsync(dev + at + sent, host + at + sent, staged - sent, hipMemcpyHostToDevice, s));
-                sent = staged;
-            }
-        }
+        char *const dev = !xyz ? e->raw.dev.p : views ? e->raw_xyz.dev.p : e->in_block.dev.p, *const host = !xyz ? e->raw.host : views ? e->raw_xyz.host : e->in_block.host;
+        const size_t at = (size_t)(static_cast<const char *>(q.h_frames[b].src) - dev);      // the frame's place in its block, device and pinned alike
+        const auto send = [&](size_t off, size_t bytes) { return hipMemcpyAsync(dev + at + off, host + at + off, bytes, hipMemcpyHostToDevice, s); };
+        HIPCHK(e, stage_frame(host + at, f, send));
     }
-    if (!q.views) {
+    if (!views) {
         launch_frame_points(q.d_frames, q.h_frames, q.B, s);
         return HAF_OK;
     }
     launch_view_points(q.d_frames, q.h_frames, q.n_frames, s);
     // the live counts, for n_points and the debug fetch: the CloudDev array back into the pinned header, where the host's copy of
     // CloudDev::n lies.  The call's own synchronisation (vote_and_wait) completes it: no wait here
-    HIPCHK(e, hipMemcpyAsync(e->h_in, e->d_in.p, (size_t)q.B * sizeof(CloudDev), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->in_block.host, e->in_block.dev.p, (size_t)q.B * sizeof(CloudDev), hipMemcpyDeviceToHost, s));
     return HAF_OK;
 }
 
@@ -427,31 +399,30 @@ static int upload_frames(haf_engine *e, const Request &q)
 // cloud -- C3 -- costs ~100 us of host memcpy; its transfer hides behind that).  The first copy carries the two header arrays.
 static int upload_clouds(haf_engine *e, const haf_cloud *clouds, const Request &q)
 {
-    constexpr size_t kPiece = 256 * 1024;                     // bytes of packed points per copy
     const hipStream_t s = q.s;
     const size_t pts_off = q.pts_off;
     size_t staged = 0, sent = 0;                              // bytes of the points area packed / handed to the DMA engine
     bool header_sent = false;
     auto flush = [&]() -> int {
         if (!header_sent) {
-            HIPCHK(e, hipMemcpyAsync(e->d_in.p, e->h_in, pts_off + staged, hipMemcpyHostToDevice, s));
+            HIPCHK(e, hipMemcpyAsync(e->in_block.dev.p, e->in_block.host, pts_off + staged, hipMemcpyHostToDevice, s));
             header_sent = true;
         } else if (staged > sent) {
-            HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + sent, e->h_in + pts_off + sent, staged - sent, hipMemcpyHostToDevice, s));
+            HIPCHK(e, hipMemcpyAsync(e->in_block.dev.p + pts_off + sent, e->in_block.host + pts_off + sent, staged - sent, hipMemcpyHostToDevice, s));
         }
         sent = staged;
         return HAF_OK;
     };
     for (int b = 0; b < q.B; b++) {
         if (clouds[b].on_device == 1 || clouds[b].n_points == 0) continue;
-        if (clouds[b].on_device == 2 && clouds[b].n_points * 12 >= kPiece) {
+        if (clouds[b].on_device == 2 && clouds[b].n_points * 12 >= kStagePiece) {
             // (a small cloud is cheaper packed into the one staged copy than as a DMA transfer of its own: ~10 us each)
             // page-locked caller memory: whatever has been packed so far goes out, then the DMA engine takes this cloud from
             // where it lies (the staging block keeps the same layout, its share of it stays unused)
             const int rc = flush();
             if (rc != HAF_OK) return rc;
             const size_t bytes = clouds[b].n_points * 12;
-            HIPCHK(e, hipMemcpyAsync(e->d_in.p + pts_off + staged, clouds[b].xyz, bytes, hipMemcpyHostToDevice, s));
+            HIPCHK(e, hipMemcpyAsync(e->in_block.dev.p + pts_off + staged, clouds[b].xyz, bytes, hipMemcpyHostToDevice, s));
             staged += bytes;
             sent = staged;
             continue;
@@ -459,14 +430,14 @@ static int upload_clouds(haf_engine *e, const haf_cloud *clouds, const Request &
         const float *src = clouds[b].xyz;
         const size_t st = clouds[b].stride_floats, n = clouds[b].n_points;
         for (size_t i0 = 0; i0 < n;) {
-            const size_t room = std::max<size_t>(1, (kPiece - (staged - sent)) / 12);
+            const size_t room = std::max<size_t>(1, (kStagePiece - (staged - sent)) / 12);
             const size_t cnt = std::min(n - i0, room);
-            float *dst = reinterpret_cast<float *>(e->h_in + pts_off + staged);
+            float *dst = reinterpret_cast<float *>(e->in_block.host + pts_off + staged);
             if (st == 3) memcpy(dst, src + i0 * 3, cnt * 12);
             else for (size_t i = 0; i < cnt; i++) { dst[i * 3] = src[(i0 + i) * st]; dst[i * 3 + 1] = src[(i0 + i) * st + 1]; dst[i * 3 + 2] = src[(i0 + i) * st + 2]; }
             staged += cnt * 12;
             i0 += cnt;
-            if (staged - sent >= kPiece) { const int rc = flush(); if (rc != HAF_OK) return rc; }
+            if (staged - sent >= kStagePiece) { const int rc = flush(); if (rc != HAF_OK) return rc; }
         }
     }
     return flush();
@@ -488,7 +459,7 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
         long sel = std::min<long>((long)(H - 14) * (W - 14), a2 * b2);
         // an ROI request with a HOST mask: a masked pixel puts at most the 29 cells of the vote's footprint on a roll's list (the mask is
         // an argument of the call: identical calls still take identical paths; a device-resident mask keeps the area bound)
-        if (q.roi && q.roi->masked[(size_t)b] >= 0) sel = std::min<long>(sel, 29 * q.roi->masked[(size_t)b]);
+        if (q.from.roi && q.from.roi->masked[(size_t)b] >= 0) sel = std::min<long>(sel, 29 * q.from.roi->masked[(size_t)b]);
         q.evals_sel += (long)R * sel;
     }
     const long work = q.evals_sel * (long)e->n_sv_pad;
@@ -519,7 +490,7 @@ static int run_prestages(haf_engine *e, Request &q)
     mark(e, HAF_ST_BIN);
     // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
     // (an ROI request takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
-    if (!e->prob_mode && !e->no_fused_pre && !q.roi)
+    if (!e->prob_mode && !e->no_fused_pre && !q.from.roi)
         q.fused_pre = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
                                        e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
                                        e->d_brslot.p, ++e->pre_epoch);
@@ -539,8 +510,8 @@ static int run_prestages(haf_engine *e, Request &q)
     mark(e, HAF_ST_INTEGRAL);
     launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
     mark(e, HAF_ST_MASK);
-    if (q.roi) {
-        const int rc = roi_mark_cells(e, *q.roi, q.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s);
+    if (q.from.roi) {
+        const int rc = roi_mark_cells(e, *q.from.roi, q.from.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s);
         if (rc != HAF_OK) return rc;
         launch_mask_count_roi(e->d_ii.p, q.d_geo, e->d_roi_cells.p, e->d_mask.p, e->d_rowcount.p, d, s);
     } else {
@@ -686,13 +657,13 @@ static int vote_and_wait(haf_engine *e, const Request &q)
 {
     const hipStream_t s = q.s;
     mark(e, HAF_ST_VOTE);
-    if (q.roi)
+    if (q.from.roi)
         launch_vote_roi(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p,
                         e->d_rec.p, e->d_roi_cells.p, q.d, s);
     else
         launch_vote(e->d_labels.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_brcount.p, e->d_ev16.p, e->d_topkey.p, e->d_rowmax.p, e->d_rec.p, q.d, s);
     mark(e, HAF_ST_DOWNLOAD);
-    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));   // counters + records
+    HIPCHK(e, hipMemcpyAsync(e->out_block.host, e->out_block.dev.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));   // counters + records
     mark(e, HAF_ST_COUNT);
     // a short request (tens to hundreds of microseconds on the device) is waited for by polling: the wake-up of a
     // blocked host thread costs more than the request's last kernels
@@ -729,7 +700,7 @@ static int finish_exact_tiers(haf_engine *e, Request &q, const TierPlan &p)
             // the fp64 tier's list has grown behind its first window: all of it again from the start (its results and the
             // strict tier's list are rebuilt; both are idempotent)
             HIPCHK(e, hipMemsetAsync(e->d_counters.p + list_counter(p.fp64_out), 0, sizeof(int), s));
-            HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
+            HIPCHK(e, hipMemcpyAsync(e->out_block.host, e->out_block.dev.p, kCntBytes, hipMemcpyDeviceToHost, s));
             HIPCHK(e, hipStreamSynchronize(s));
             done_fp64 = 0;
         }
@@ -796,7 +767,7 @@ static int decide_probability(haf_engine *e, Request &q)
     // the estimates; those a last-bit exp difference could move come back as a list and are finished on the host (round 4)
     launch_probability_eval(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_own.p, e->d_ptext.p,
                             e->d_flag_list.p, e->list_cap, e->d_counters.p, q.evals_cap, s);
-    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->out_block.host, e->out_block.dev.p, kCntBytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     const int rc = host_resolve_probability(e, d, s, &q.host_resolved);
     if (rc != HAF_OK) return rc;
@@ -805,7 +776,7 @@ static int decide_probability(haf_engine *e, Request &q)
                        e->d_brcount.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_own.p, e->d_ptext.p, e->d_gridf.p,
                        e->d_evf.p, e->d_rec.p, q.evals_cap, d, s);
     mark(e, HAF_ST_DOWNLOAD);
-    HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->out_block.host, e->out_block.dev.p, kCntBytes + (size_t)q.B * q.R * sizeof(RollRecordDev), hipMemcpyDeviceToHost, s));
     mark(e, HAF_ST_COUNT);
     HIPCHK(e, hipStreamSynchronize(s));
     HIPCHK(e, hipGetLastError());
@@ -910,19 +881,12 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
     l.i8 = q.i8_used;
     l.inputs.assign(in, in + q.B);
     l.clouds = q.src;
-    for (int b = 0; q.views && b < q.B; b++) l.clouds[(size_t)b].n = (size_t)q.h_clouds[b].n;      // (upload_frames: the live counts)
+    for (int b = 0; q.from.views && b < q.B; b++) l.clouds[(size_t)b].n = (size_t)q.h_clouds[b].n;      // (upload_frames: the live counts)
     // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
     if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), q.s) == hipSuccess) e->counters_clean = true;
     // (the tier lists hold every evaluation of a request: list_cap >= last.evals >= last.flagged >= last.flagged2)
     if (l.flagged > e->list_cap || l.flagged2 > e->list_cap || l.flaggedi > e->list_cap) return fail(e, HAF_E_INTERNAL, "recheck list counters exceed the number of evaluations");
-#ifdef HAF_TESTING
-    // testing build, HAF_CANARY_CHECK set (opt-in: engine_state.h): the guard zones around every device buffer after EVERY request
-    if (test_env("HAF_CANARY_CHECK")) {
-        std::string rep;
-        const int bad = canary_check(&rep);
-        if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
-    }
-#endif
+    if (const int rc = check_guards(e)) return rc;       // (testing build, opt-in: the guard zones around every device buffer after EVERY request)
     for (int i = 0; i < q.B * q.R; i++) {
         records[i].vote = e->h_rec[i].vote;
         records[i].row = e->h_rec[i].row;
@@ -934,20 +898,19 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
 }
 
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames, const int32_t *views, const RoiCall *roi)
+                     int32_t roll_count, haf_roll_record *records, const FrameSource *from)
 {
     if (!e) return HAF_E_ARG;
     Request q;
-    q.frames = frames;
-    q.views = views;
-    q.roi = roi;
+    if (from) q.from = *from;
+    const RoiCall *const roi = q.from.roi;
     int rc = check_request(e, n_clouds, clouds, in, roll_first, roll_count, records, q);
     if (rc != HAF_OK) return rc;
     pack_headers(e, clouds, in, roll_first, q);
     q.s = e->stream;
     mark(e, 0);
-    if ((rc = frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
-    if (roi && (rc = roi_upload_masks(e, *roi, frames, q.B, q.s)) != HAF_OK) return rc;
+    if ((rc = q.from.frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
+    if (roi && (rc = roi_upload_masks(e, *roi, q.from.frames, q.B, q.s)) != HAF_OK) return rc;
     classify_request(e, in, q);
     if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
     int mode = contraction_mode(e->cfg);
@@ -969,7 +932,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         // height grids of this call may miss points.  Serve the request -- and this engine from now on -- with k_bin instead.
         e->no_bucket_sort = true;
         e->counters_clean = false;
-        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, frames, views, roi);
+        return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, from);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
     if (mode == MODE_SCREEN && !e->prob_mode && !q.direct &&
@@ -978,7 +941,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
 }
 
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames, const int32_t *views, const RoiCall *roi)
+                     const FrameSource *from)
 {
     if (!e) return HAF_E_ARG;
     if (!out) return fail(e, HAF_E_ARG, "haf_score_batch: null output");
@@ -990,8 +953,8 @@ int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     int rc = HAF_OK;
     if (none_runs)
         e->last = LastCall{};
-    else if (frames)
-        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), frames, views, roi);
+    else if (from)
+        rc = score_rolls_impl(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data(), from);
     else
         rc = haf_score_rolls(e, n_clouds, clouds, in, 0, e->cfg.n_rolls, rec.data());
     if (rc != HAF_OK) return rc;
@@ -1010,19 +973,11 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
     if (!e) return HAF_E_ARG;
     if (!frames || !in || !out || n < 1) return fail(e, HAF_E_ARG, "haf_score_frames: null or empty argument");
     if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, "haf_score_frames: more frames than max_clouds");
-    int64_t total = 0;
-    std::vector<haf_cloud> clouds((size_t)n);
-    for (int b = 0; b < n; b++) {
-        std::string msg;
-        const int rc = check_frame(frames[b], msg);
-        if (rc != HAF_OK) return fail(e, rc, "haf_score_frames: frame " + std::to_string(b) + ": " + msg);
-        const size_t px = (size_t)frames[b].width * (size_t)frames[b].height;
-        total += (int64_t)px;
-        if (total > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, "haf_score_frames: more pixels than max_points");
-        // (xyz is never read on this path: the points area of the input block is the cloud; on_device = 0 reserves its place there)
-        clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[b].data), px, 3, 0};
-    }
-    return score_batch_impl(e, n, clouds.data(), in, out, frames);
+    const FrameBatch chk = check_frame_batch(frames, n, nullptr, e->cfg.max_points);
+    if (chk.code != HAF_OK && chk.text.empty()) return fail(e, chk.code, "haf_score_frames: more pixels than max_points");
+    if (chk.code != HAF_OK) return fail(e, chk.code, "haf_score_frames: frame " + std::to_string(chk.request) + ": " + chk.text);
+    const FrameSource from{frames, nullptr, nullptr};
+    return score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
 }
 
 // haf_score_views: every refusal before any device work, then the batch path with the views of request b as the source of cloud b's
@@ -1037,37 +992,19 @@ int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request,
     for (int b = 0; b < n; b++)
         if (views_per_request[b] < 1 || views_per_request[b] > HAF_MAX_VIEWS)
             return fail(e, HAF_E_ARG, "haf_score_views: request " + std::to_string(b) + ": view count outside [1, HAF_MAX_VIEWS]");
-    int64_t total = 0;
-    bool host_xyz = false;
-    std::vector<haf_cloud> clouds((size_t)n);
-    for (int b = 0, k = 0; b < n; b++) {
-        size_t upper = 0;
-        for (int v = 0; v < views_per_request[b]; v++, k++) {
-            std::string msg;
-            const int rc = check_frame(frames[k], msg);
-            if (rc != HAF_OK) return fail(e, rc, "haf_score_views: request " + std::to_string(b) + " view " + std::to_string(v) + ": " + msg);
-            const size_t px = (size_t)frames[k].width * (size_t)frames[k].height;
-            total += (int64_t)px;
-            if (total > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, "haf_score_views: more pixels than max_points");
-            upper += px;
-            host_xyz = host_xyz || (frames[k].kind == HAF_FRAME_XYZ_F32 && frames[k].on_device == 0);
-        }
-        // (xyz is never read on this path, as in score_frames_impl)
-        clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[k - 1].data), upper, 3, 0};
-    }
-    if (host_xyz && !e->d_raw_xyz.p) {
+    const FrameBatch chk = check_frame_batch(frames, n, views_per_request, e->cfg.max_points);
+    if (chk.code != HAF_OK && chk.text.empty()) return fail(e, chk.code, "haf_score_views: more pixels than max_points");
+    if (chk.code != HAF_OK) return fail(e, chk.code, "haf_score_views: request " + std::to_string(chk.request) + " view " + std::to_string(chk.view) + ": " + chk.text);
+    if (chk.host_xyz && !e->raw_xyz.host) {
         // the raw area of staged host XYZ views (12 bytes x max_points, every view at a multiple of 16 bytes) and its pinned twin: an
         // engine that never sees such a view never pays for them
         HIPCHK(e, hipSetDevice(e->cfg.device));
-        const size_t bytes = (size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16;
-        HIPCHK(e, e->d_raw_xyz.alloc(bytes));
-        if (hipHostMalloc((void **)&e->h_raw_xyz, bytes) != hipSuccess) {
-            e->d_raw_xyz.release();
-            e->h_raw_xyz = nullptr;
-            return fail(e, HAF_E_DEVICE, "haf_score_views: no pinned memory for the raw area of host XYZ views");
-        }
+        const hipError_t rc = e->raw_xyz.ensure((size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16);
+        if (e->raw_xyz.pinned_failed) return fail(e, HAF_E_DEVICE, "haf_score_views: no pinned memory for the raw area of host XYZ views");
+        if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, std::string("haf_score_views: no device memory for the raw area of host XYZ views: ") + hipGetErrorString(rc));
     }
-    const int rc = score_batch_impl(e, n, clouds.data(), in, out, frames, views_per_request);
+    const FrameSource from{frames, views_per_request, nullptr};
+    const int rc = score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
     if (rc != HAF_OK) return rc;
     // (a batch whose every budget is negative runs nothing, on the device either: no count exists)
     for (int b = 0; n_points && b < n; b++) n_points[b] = (size_t)b < e->last.clouds.size() ? (int64_t)e->last.clouds[(size_t)b].n : -1;

@@ -1,6 +1,6 @@
 // engine_roi.cpp -- haf_score_frames_roi (include/hafgrasp.h): haf_score_frames under an image-space mask per request.  The cloud, the
 // binning and the integral images are the whole frame's; what the mask restricts is the evaluation list.  This unit holds the call's
-// checks (all of them before any device work), the ROI buffers, the upload of host masks and the launch of k_roi_mark (roi.hip); the
+// checks (all of them before any device work), the ROI buffers, the packing and upload of host masks and the launch of k_roi_mark; the
 // request path itself is engine_request.cpp's, which takes three turns for a RoiCall:
 //   * run_prestages: no fused k_small_pre; behind the integral image the ROI cell sets are marked and k_mask_count_roi writes
 //     m = cell_in_box && any(S at c + T) -- k_scan, k_compact and every decision tier then run unchanged on the shorter list;
@@ -12,8 +12,6 @@ namespace haf_host {
 
 namespace {
 
-size_t up16(size_t x) { return (x + 15) / 16 * 16; }
-
 // the ROI cell sets and the masks' area, on the first call (the precedent: the raw area of host XYZ views, score_views_impl)
 int ensure_roi_buffers(haf_engine *e)
 {
@@ -22,19 +20,10 @@ int ensure_roi_buffers(haf_engine *e)
     HIPCHK(e, hipSetDevice(c.device));
     const size_t words = (size_t)c.max_clouds * (size_t)e->max_rolls * (size_t)c.grid_h * (size_t)roi_row_words(c.grid_w);
     const size_t mask_bytes = (size_t)c.max_points + (size_t)c.max_clouds * 16;
-    HIPCHK(e, e->d_roi_mask.alloc(mask_bytes));
-    if (hipHostMalloc((void **)&e->h_roi_mask, mask_bytes) != hipSuccess) {
-        e->d_roi_mask.release();
-        e->h_roi_mask = nullptr;
-        return fail(e, HAF_E_DEVICE, "haf_score_frames_roi: no pinned memory for the masks");
-    }
-    const hipError_t rc = e->d_roi_cells.alloc(words);
-    if (rc != hipSuccess) {
-        e->d_roi_mask.release();
-        (void)hipHostFree(e->h_roi_mask);
-        e->h_roi_mask = nullptr;
-        HIPCHK(e, rc);
-    }
+    hipError_t rc = e->roi_mask.ensure(mask_bytes);
+    if (e->roi_mask.pinned_failed) return fail(e, HAF_E_DEVICE, "haf_score_frames_roi: no pinned memory for the masks");
+    if (rc == hipSuccess && (rc = e->d_roi_cells.alloc(words)) != hipSuccess) e->roi_mask.release();      // all or nothing: the next call tries again
+    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, std::string("haf_score_frames_roi: no device memory for the ROI buffers: ") + hipGetErrorString(rc));
     return HAF_OK;
 }
 
@@ -45,7 +34,7 @@ int roi_upload_masks(haf_engine *e, const RoiCall &roi, const haf_frame *frames,
     for (int b = 0; b < B; b++) {
         if (roi.rois[b].on_device == 1) continue;
         const size_t n = (size_t)frames[b].width * (size_t)frames[b].height, at = roi.off[(size_t)b];
-        HIPCHK(e, hipMemcpyAsync(e->d_roi_mask.p + at, e->h_roi_mask + at, n, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->roi_mask.dev.p + at, e->roi_mask.host + at, n, hipMemcpyHostToDevice, s));
     }
     return HAF_OK;
 }
@@ -58,7 +47,8 @@ int roi_mark_cells(haf_engine *e, const RoiCall &roi, const haf_frame *frames, c
     for (int b = 0; b < d.B; b++) {
         const haf_roi &r = roi.rois[b];
         const bool dev = r.on_device == 1;
-        launch_roi_mark(dev ? r.mask : e->d_roi_mask.p + roi.off[(size_t)b], dev ? r.row_stride_bytes : (size_t)frames[b].width, frames[b].width,
+        const unsigned char *staged = reinterpret_cast<const unsigned char *>(e->roi_mask.dev.p) + roi.off[(size_t)b];
+        launch_roi_mark(dev ? r.mask : staged, dev ? r.row_stride_bytes : (size_t)frames[b].width, frames[b].width,
                         frames[b].width * frames[b].height, h_clouds[b].xyz, d_geo + (size_t)b * d.R, d.R,
                         e->d_roi_cells.p + (size_t)b * d.R * grid_words, d.H, d.W, r_row, r_col, s);
     }
@@ -76,22 +66,15 @@ int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, con
     if (e->prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
     if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, who + "more frames than max_clouds");
     if (e->cfg.n_rolls > e->max_rolls) return fail(e, HAF_E_CAPACITY, who + "more rolls in one call than max_rolls_per_call");
-    int64_t total = 0;
-    std::vector<haf_cloud> clouds((size_t)n);
-    for (int b = 0; b < n; b++) {
-        const std::string req = who + "request " + std::to_string(b) + ": ";
-        std::string msg;
-        const int rc = check_frame(frames[b], msg);
-        if (rc != HAF_OK) return fail(e, rc, req + msg);
-        const size_t px = (size_t)frames[b].width * (size_t)frames[b].height;
-        total += (int64_t)px;
-        if (total > e->cfg.max_points) return fail(e, HAF_E_CAPACITY, req + "more pixels than max_points");
-        if (!rois[b].mask) return fail(e, HAF_E_ARG, req + "null mask");
-        if (rois[b].on_device != 0 && rois[b].on_device != 1) return fail(e, HAF_E_ARG, req + "haf_roi: on_device must be 0 (host) or 1 (device-resident)");
-        if (rois[b].row_stride_bytes < (size_t)frames[b].width) return fail(e, HAF_E_ARG, req + "haf_roi: row_stride_bytes smaller than a row");
-        // (xyz is never read on this path, as in score_frames_impl)
-        clouds[(size_t)b] = haf_cloud{static_cast<const float *>(frames[b].data), px, 3, 0};
+    // request after request, its frame's refusals before its mask's: the masks of the requests in front of a refused frame come first
+    const FrameBatch chk = check_frame_batch(frames, n, nullptr, e->cfg.max_points);
+    const auto req = [&](int b) { return who + "request " + std::to_string(b) + ": "; };
+    for (int b = 0; b < (chk.code != HAF_OK ? chk.request : n); b++) {
+        if (!rois[b].mask) return fail(e, HAF_E_ARG, req(b) + "null mask");
+        if (rois[b].on_device != 0 && rois[b].on_device != 1) return fail(e, HAF_E_ARG, req(b) + "haf_roi: on_device must be 0 (host) or 1 (device-resident)");
+        if (rois[b].row_stride_bytes < (size_t)frames[b].width) return fail(e, HAF_E_ARG, req(b) + "haf_roi: row_stride_bytes smaller than a row");
     }
+    if (chk.code != HAF_OK) return fail(e, chk.code, req(chk.request) + (chk.text.empty() ? "more pixels than max_points" : chk.text));
     int rc = ensure_roi_buffers(e);
     if (rc != HAF_OK) return rc;
     // host masks: their rows without the padding into the pinned area, counted on the way (classify_request)
@@ -102,19 +85,17 @@ int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, con
     size_t at = 0;
     for (int b = 0; b < n; b++) {
         if (rois[b].on_device == 1) continue;
-        const size_t w = (size_t)frames[b].width;
+        const size_t w = (size_t)frames[b].width, px = w * (size_t)frames[b].height;
         call.off[(size_t)b] = at;
+        char *const dst = e->roi_mask.host + at;
+        pack_rows(dst, reinterpret_cast<const char *>(rois[b].mask), (size_t)frames[b].height, w, 1, 1, rois[b].row_stride_bytes);
         long cnt = 0;
-        for (int v = 0; v < frames[b].height; v++) {
-            const uint8_t *src = rois[b].mask + (size_t)v * rois[b].row_stride_bytes;
-            unsigned char *dst = e->h_roi_mask + at + (size_t)v * w;
-            memcpy(dst, src, w);
-            for (size_t u = 0; u < w; u++) cnt += src[u] != 0;
-        }
+        for (size_t i = 0; i < px; i++) cnt += dst[i] != 0;
         call.masked[(size_t)b] = cnt;
-        at += up16(w * (size_t)frames[b].height);
+        at += up16(px);
     }
-    return score_batch_impl(e, n, clouds.data(), in, out, frames, nullptr, &call);
+    const FrameSource from{frames, nullptr, &call};
+    return score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
 }
 
 }  // namespace haf_host

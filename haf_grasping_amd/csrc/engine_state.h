@@ -8,13 +8,14 @@
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
 //   engine_roi.cpp       haf_score_frames_roi: the checks, the ROI buffers, the masks' upload and the launch of k_roi_mark
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
-// Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every translation unit above is
+//   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
+// Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
 #pragma once
 #include "../../include/hafgrasp.h"
 #include "kernels.h"
 #include "parsers.h"
-#include "frames.h"
+#include "frame_stage.h"
 #include "decq.h"
 #include "engine_internal.h"
 
@@ -81,6 +82,9 @@ constexpr int kCanaryByte = 0xA5;
 void canary_register(void *user, size_t bytes, const char *file, int line);
 void canary_unregister(void *user);
 int canary_check(std::string *report);          // number of buffers with a damaged guard zone (engine_testing.cpp)
+int check_guards(haf_engine *e);                // with HAF_CANARY_CHECK set: HAF_E_INTERNAL and canary_check's report when it finds damage
+#else
+inline int check_guards(haf_engine *) { return HAF_OK; }
 #endif
 
 template <typename T> struct DevBuf {
@@ -118,6 +122,28 @@ template <typename T> struct DevBuf {
 #endif
 };
 
+// A device block and its pinned host twin of the same size.  ensure() gets both halves or neither: when either allocation fails the pair
+// it had stays in place and usable (the engine left as it was); growing replaces the pair, not its contents, once both exist
+struct StageBuf {
+    DevBuf<char> dev;                // dev.n: bytes of either half
+    char *host = nullptr;
+    bool pinned_failed = false;      // the last ensure() failed for want of the pinned half, not of the device half
+    hipError_t ensure(size_t bytes)
+    {
+        pinned_failed = false;
+        if (dev.n >= bytes) return hipSuccess;
+        DevBuf<char> d;
+        char *h = nullptr;
+        hipError_t rc = d.alloc(bytes);
+        pinned_failed = rc == hipSuccess && (rc = hipHostMalloc((void **)&h, bytes, hipHostMallocDefault)) != hipSuccess;
+        if (rc != hipSuccess) { d.release(); return rc; }
+        release();
+        dev = d; host = h;
+        return hipSuccess;
+    }
+    void release() { dev.release(); if (host) (void)hipHostFree(host); host = nullptr; }
+};
+
 // What the last scored call leaves for the getters (engine.cpp) and the debug reads (engine_debug.cpp, engine_testing.cpp).  A call
 // that scores nothing the caller asked for (the calibration requests, a batch whose every budget is negative) resets it: e->last = {}.
 struct LastCall {
@@ -134,7 +160,7 @@ struct LastCall {
     bool lr = false;             // the screening pass ran in the low-rank form
     bool i8 = false;             // tier 2a ran (then d_dec_exact holds ITS values and d_dec_exacti the fp64 tier's)
     std::vector<haf_grasp_input> inputs;
-    // where the kernels read every cloud of the batch (haf_debug_fetch_points): its first float inside the points area of d_in and its
+    // where the kernels read every cloud of the batch (haf_debug_fetch_points): its first float inside the points area of in_block and its
     // point count; staged = false for a device-resident xyz cloud, which lies in the caller's memory
     struct CloudSrc { size_t float_off = 0; size_t n = 0; bool staged = false; };
     std::vector<CloudSrc> clouds;
@@ -144,7 +170,14 @@ struct LastCall {
 struct RoiCall {
     const haf_roi *rois = nullptr;       // rois[b] goes with frame b
     std::vector<long> masked;            // per request: the non-zero bytes of a host mask, -1 for a device-resident mask
-    std::vector<size_t> off;             // per request: where a host mask lies in d_roi_mask / h_roi_mask (packed rows, 16-byte aligned)
+    std::vector<size_t> off;             // per request: where a host mask lies in roi_mask (packed rows, 16-byte aligned)
+};
+
+// Where a request's points come from when not from the caller's clouds (the request path takes a pointer, null for clouds)
+struct FrameSource {
+    const haf_frame *frames = nullptr;   // cloud b's points are frame b's, deprojected on the device; clouds[b] only carries its point count
+    const int32_t *views = nullptr;      // ... are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count
+    const RoiCall *roi = nullptr;        // haf_score_frames_roi (no views): only the cells near the masked pixels' cells are evaluated
 };
 
 }  // namespace haf_host
@@ -215,22 +248,18 @@ struct haf_engine {
 
     // ONE input block per request: [CloudDev x B][RollGeo x B*R][host clouds' points], packed at call time so that a single
     // host-to-device copy carries everything (a small request is bound by the number of stream operations); the
-    // pinned staging block h_in has the same layout
-    DevBuf<char> d_in;
-    char *h_in = nullptr;
+    // pinned half has the same layout
+    StageBuf in_block;
     size_t in_hdr_cap = 0;          // bytes reserved for the header arrays (CloudDev, RollGeo, FrameDev)
     // haf_score_frames: the raw pixels of host depth frames, 2 or 4 bytes each, go through their own pinned block and device area
-    // (4 bytes x max_points, every frame at a multiple of 16 bytes); k_frame_points writes their points into the points area of d_in.
+    // (raw: 4 bytes x max_points, every frame at a multiple of 16 bytes); k_frame_points writes their points into the points area of in_block.
     // Never converted inside the points area itself: a point's 12-byte slot overlaps raw pixels other lanes have not read yet
-    DevBuf<char> d_raw;
-    char *h_raw = nullptr;
+    StageBuf raw;
     // haf_score_views: the raw area of staged host XYZ views, 12 bytes x max_points, allocated by the first call that has one.  Such a
     // view cannot be converted in place as haf_score_frames does: compaction writes where other lanes have not read yet
-    DevBuf<char> d_raw_xyz;
-    char *h_raw_xyz = nullptr;
-    // ONE output block: [counters][roll records], fetched with a single device-to-host copy (d_counters / d_rec point into it)
-    DevBuf<char> d_out;
-    char *h_out = nullptr;
+    StageBuf raw_xyz;
+    // ONE output block: [counters][roll records], fetched with a single device-to-host copy (d_counters / d_rec, h_counters / h_rec point into it)
+    StageBuf out_block;
     bool counters_clean = false;    // the counters were zeroed behind the previous request's copy-out (off the next request's critical path)
     DevBuf<float> d_sorted;         // bucket-sorted copy of the clouds (binning of large grids, prestages.hip)
     DevBuf<int> d_bkt;              // 3 x max_clouds x kBktInts bucket counters / offsets / cursors
@@ -245,7 +274,7 @@ struct haf_engine {
     DevBuf<unsigned long long> d_tier_words;   // exact tiers: one "undecided" bit per entry of a window, for the ordered hand-over lists
     DevBuf<unsigned long long> d_brslot;   // k_small_pre: per (cloud, roll) {request epoch, evaluations} in one word (ordered evaluation list)
     unsigned pre_epoch = 0;
-    struct View { int *p = nullptr; } d_counters;      // inside d_out
+    struct View { int *p = nullptr; } d_counters;      // inside out_block
     DevBuf<float> d_X, d_ax, d_dec, d_svt;
     DevBuf<char> d_svt_h;            // split-fp16 SV tile images
     DevBuf<char> d_svt0;             // screening-pass SV tile images
@@ -286,7 +315,7 @@ struct haf_engine {
     DevBuf<short> d_ev16;
     DevBuf<float> d_margin;         // HAF_FLAG_KEEP_DEBUG, default mode: |dec^| / band of every evaluation the screening tier decided
     DevBuf<AttrRecord> d_attr;      // HAF_FLAG_KEEP_DEBUG: [max_evals][kKP] attribute records of the exact-form feature kernels
-    struct RecView { RollRecordDev *p = nullptr; } d_rec;   // inside d_out, behind the counters
+    struct RecView { RollRecordDev *p = nullptr; } d_rec;   // inside out_block, behind the counters
     DevBuf<unsigned long long> d_topkey;
     DevBuf<int> d_rowmax;           // best vote per grid row (k_vote_cells -> k_vote_pick)
     // probability-output mode (HAF_FLAG_PROBABILITY, prob.hip): per-cell value of the cell's own output line, the grid
@@ -305,7 +334,7 @@ struct haf_engine {
     long large_evals = 1L << 18;
     DevBuf<ScrDesc3> d_sd3;
 
-    // pinned host staging (views into h_in / h_out; the input views are set per request)
+    // views into the pinned half of out_block
     RollRecordDev *h_rec = nullptr;
     int *h_counters = nullptr;
     // requests whose whole SVM work (evaluations x support vectors) is at most this go straight to tier 2's arithmetic in one
@@ -337,20 +366,15 @@ struct haf_engine {
     // haf_top_grasps (engine_topgrasps.cpp), allocated on its first call: run-list scratch of its slots, the output block
     // [hdr: 4 ints per (cloud, roll)][TopCandDev x depth per (cloud, roll)] and its pinned host copy
     DevBuf<unsigned long long> d_top_scratch;
-    DevBuf<char> d_top_out;
-    char *h_top_out = nullptr;
-    size_t h_top_cap = 0;
+    StageBuf top_out;
     // haf_grasp_map (engine_graspmap.cpp), allocated on its first call and grown to the largest frame seen: the device block
     // [best key + cell record: 64 bytes][R x CellGeo][vote | roll | cell images][mask bytes] and its pinned host copy
-    DevBuf<char> d_map;
-    char *h_map = nullptr;
-    size_t h_map_cap = 0;
+    StageBuf map;
     // haf_score_frames_roi (engine_roi.cpp), allocated on its first call: the ROI cell sets -- one bit per cell, max_clouds x max_rolls
     // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes, every mask at a
     // multiple of 16 bytes) with its pinned twin
     DevBuf<unsigned long long> d_roi_cells;
-    DevBuf<unsigned char> d_roi_mask;
-    unsigned char *h_roi_mask = nullptr;
+    StageBuf roi_mask;
 };
 
 namespace haf_host {
@@ -378,7 +402,7 @@ constexpr int kShortListGate = 256;  // the short-list gate (engine_request.cpp)
 constexpr int kShortGateMinSv = 2048; // ... of a model with at least this many support vectors go straight to the fp64 MFMA tier
 constexpr int kStrictSlots = 64;     // evaluations per pass of the strict tier's spread form (a few per request reach it at most)
 
-constexpr size_t kCntBytes = (CNT_COUNT * sizeof(int) + 15) / 16 * 16;      // the counters' share of the output block (d_out)
+constexpr size_t kCntBytes = up16(CNT_COUNT * sizeof(int));                 // the counters' share of the output block (out_block)
 
 // contraction mode: default = screening pass + three-pass refinement; HAF_FLAG_SPLIT_F16 = three passes for everything;
 // HAF_FLAG_FP32_MFMA = one fp32 MFMA pass for everything
@@ -482,15 +506,12 @@ double sigma_upper_bound(const double *M, int n, int d);
 int build_tables(haf_engine *e);
 int alloc_buffers(haf_engine *e);
 // engine_request.cpp
-// (frames != nullptr: cloud b's points are frame b's, deprojected on the device; clouds[b] then only carries its point count)
-// (roi != nullptr: haf_score_frames_roi -- frames given, no views; only the cells near the masked pixels' cells are evaluated)
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,
-                     int32_t roll_count, haf_roll_record *records, const haf_frame *frames = nullptr, const int32_t *views = nullptr,
-                     const RoiCall *roi = nullptr);
+                     int32_t roll_count, haf_roll_record *records, const FrameSource *from = nullptr);
 int score_batch_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, haf_grasp_output *out,
-                     const haf_frame *frames = nullptr, const int32_t *views = nullptr, const RoiCall *roi = nullptr);
+                     const FrameSource *from = nullptr);
 int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_grasp_input *in, haf_grasp_output *out);
-// (views != nullptr: cloud b's points are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count)
+// (clouds[b].n_points is the UPPER bound there, the pixels of the request's views)
 int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
                      haf_grasp_output *out, int64_t *n_points);
 // engine_roi.cpp

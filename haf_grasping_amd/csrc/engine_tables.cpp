@@ -1114,14 +1114,14 @@ int alloc_buffers(haf_engine *e)
     // and their window-by-window consumers rely on exactly that (a counter never exceeds the list).
     if (const char *v = test_env("HAF_FLAG0_CAP")) e->flag0_cap = mode == MODE_SCREEN ? (int)std::min<long>(e->list_cap, std::max(256, atoi(v) / 256 * 256)) : 0;
     bool ok = true;
-    e->in_hdr_cap = (B * sizeof(CloudDev) + 15) / 16 * 16 + (B * R * sizeof(RollGeo) + 15) / 16 * 16 + (B * HAF_MAX_VIEWS * sizeof(FrameDev) + 15) / 16 * 16;     // (haf_score_views: up to HAF_MAX_VIEWS descriptors per request)
+    e->in_hdr_cap = up16(B * sizeof(CloudDev)) + up16(B * R * sizeof(RollGeo)) + up16(B * HAF_MAX_VIEWS * sizeof(FrameDev));     // (haf_score_views: up to HAF_MAX_VIEWS descriptors per request)
     // (+ 48 bytes per cloud: the points of a frame start at a multiple of four points, pack_headers)
-    ok &= hipSuccess == e->d_in.alloc(e->in_hdr_cap + (size_t)c.max_points * 3 * sizeof(float) + B * 48);
-    ok &= hipSuccess == e->d_raw.alloc((size_t)c.max_points * 4 + B * HAF_MAX_VIEWS * 16);
-    ok &= hipSuccess == e->d_out.alloc(kCntBytes + B * R * sizeof(RollRecordDev));
+    ok &= hipSuccess == e->in_block.ensure(e->in_hdr_cap + (size_t)c.max_points * 3 * sizeof(float) + B * 48);
+    ok &= hipSuccess == e->raw.ensure((size_t)c.max_points * 4 + B * HAF_MAX_VIEWS * 16);
+    ok &= hipSuccess == e->out_block.ensure(kCntBytes + B * R * sizeof(RollRecordDev));
     if (ok) {
-        e->d_counters.p = reinterpret_cast<int *>(e->d_out.p);
-        e->d_rec.p = reinterpret_cast<RollRecordDev *>(e->d_out.p + kCntBytes);
+        e->d_counters.p = reinterpret_cast<int *>(e->out_block.dev.p);
+        e->d_rec.p = reinterpret_cast<RollRecordDev *>(e->out_block.dev.p + kCntBytes);
     }
     {
         const int nb = bin_bucket_grid(c.grid_h, nullptr);
@@ -1196,11 +1196,8 @@ int alloc_buffers(haf_engine *e)
     ok &= hipSuccess == e->d_rowmax.alloc(B * R * H);
     ok &= hipSuccess == e->d_topkey.alloc(3 * B * R);          // top vote key, longest-run key, completion counter (k_vote_*)
     if (!ok) return fail(e, HAF_E_DEVICE, std::string("hipMalloc of working buffers failed: ") + hipGetErrorString(hipGetLastError()));
-    HIPCHK(e, hipHostMalloc((void **)&e->h_in, e->d_in.n));
-    HIPCHK(e, hipHostMalloc((void **)&e->h_raw, e->d_raw.n));
-    HIPCHK(e, hipHostMalloc((void **)&e->h_out, e->d_out.n));
-    e->h_counters = reinterpret_cast<int *>(e->h_out);
-    e->h_rec = reinterpret_cast<RollRecordDev *>(e->h_out + kCntBytes);
+    e->h_counters = reinterpret_cast<int *>(e->out_block.host);
+    e->h_rec = reinterpret_cast<RollRecordDev *>(e->out_block.host + kCntBytes);
     HIPCHK(e, hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), e->stream));
     e->counters_clean = true;
     return HAF_OK;

@@ -59,6 +59,15 @@ int canary_check(std::string *report)
     }
     return bad;
 }
+// what every entry point of the testing build ends with (engine_state.h): opt-in, the guard zones around every device buffer
+int check_guards(haf_engine *e)
+{
+    if (!test_env("HAF_CANARY_CHECK")) return HAF_OK;
+    std::string rep;
+    const int bad = canary_check(&rep);
+    if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
+    return HAF_OK;
+}
 }  // namespace haf_host
 
 extern "C" {

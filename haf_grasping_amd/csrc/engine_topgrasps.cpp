@@ -93,28 +93,18 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
     std::vector<int32_t> len;
     for (;;) {
         const size_t out_bytes = hdr_bytes + (size_t)BR * depth * sizeof(TopCandDev);
-        if (e->d_top_out.n < out_bytes) {
-            e->d_top_out.release();
-            HIPCHK(e, e->d_top_out.alloc(out_bytes));
-        }
-        if (e->h_top_cap < out_bytes) {
-            if (e->h_top_out) (void)hipHostFree(e->h_top_out);
-            e->h_top_out = nullptr;
-            e->h_top_cap = 0;
-            HIPCHK(e, hipHostMalloc((void **)&e->h_top_out, out_bytes, hipHostMallocDefault));
-            e->h_top_cap = out_bytes;
-        }
-        int *d_hdr = reinterpret_cast<int *>(e->d_top_out.p);
-        TopCandDev *d_cand = reinterpret_cast<TopCandDev *>(e->d_top_out.p + hdr_bytes);
+        HIPCHK(e, e->top_out.ensure(out_bytes));
+        int *d_hdr = reinterpret_cast<int *>(e->top_out.dev.p);
+        TopCandDev *d_cand = reinterpret_cast<TopCandDev *>(e->top_out.dev.p + hdr_bytes);
         Dims d{};
         d.H = H; d.W = W; d.R = R; d.B = B;
         launch_top_grasps(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, e->d_top_scratch.p, slot_words, n_slots,
                           d_hdr, d_cand, (int)depth, p->min_vote, p->cell_radius, d, e->stream);
         HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipMemcpyAsync(e->h_top_out, e->d_top_out.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->top_out.host, e->top_out.dev.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(e, hipStreamSynchronize(e->stream));
-        const int *hdr = reinterpret_cast<const int *>(e->h_top_out);
-        const TopCandDev *hc = reinterpret_cast<const TopCandDev *>(e->h_top_out + hdr_bytes);
+        const int *hdr = reinterpret_cast<const int *>(e->top_out.host);
+        const TopCandDev *hc = reinterpret_cast<const TopCandDev *>(e->top_out.host + hdr_bytes);
         bool again = false;
         for (int b = 0; b < B && !again; b++) {
             found[(size_t)b] = 0;
@@ -150,13 +140,7 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
         if (depth >= (long)HW) return fail(e, HAF_E_INTERNAL, "haf_top_grasps: a roll's sequence outgrew its grid");
         depth = std::min<long>(2 * depth, (long)HW);
     }
-#ifdef HAF_TESTING
-    if (test_env("HAF_CANARY_CHECK")) {
-        std::string rep;
-        const int bad = canary_check(&rep);
-        if (bad != 0) return fail(e, HAF_E_INTERNAL, "device buffer guard zones damaged (" + std::to_string(bad) + "): " + rep);
-    }
-#endif
+    if (const int rc = check_guards(e)) return rc;
     memcpy(out, res.data(), res.size() * sizeof(haf_grasp_candidate));
     memcpy(n_found, found.data(), found.size() * sizeof(int32_t));
     return HAF_OK;

@@ -1,5 +1,5 @@
-// frames.h -- what the host units share about sensor frames (haf_frame, include/hafgrasp.h): the argument checks every entry point
-// applies to a frame's own fields, and the per-frame constants of the arithmetic (frame_points.h).  frames_host.cpp defines them and
+// frames.h -- what the host units share about sensor frames (haf_frame, include/hafgrasp.h): the descriptor the kernels read, the argument
+// checks every entry point applies to a frame's own fields, and the per-frame constants of the arithmetic (frame_points.h).  frames_host.cpp defines them and
 // needs neither HIP nor an engine.
 #pragma once
 #include "../../include/hafgrasp.h"
@@ -8,6 +8,21 @@
 #include <string>
 
 namespace haf {
+
+// per sensor frame of a haf_score_frames batch (frames.hip): where its pixels lie and where its points go.  The array rides in the
+// request's header block behind the RollGeo array.  dst is 16-byte aligned (the points of a frame start at a multiple of four points).
+// haf_score_views: one entry per VIEW; dst is the start of the request's region (all its views share it) and count the request's live
+// point counter on the device, CloudDev::n, which k_view_points advances (null on the haf_score_frames path)
+struct FrameDev {
+    const void *src;                 // first pixel: the raw area (staged host depth frames), dst itself (staged host XYZ frames: in place), or the caller's device memory
+    float *dst;                      // packed xyz, width * height points: CloudDev::xyz of the same index
+    int *count;                      // views only: CloudDev::n of the request
+    unsigned long long row_stride;   // bytes between rows of src
+    unsigned point_stride;           // bytes between pixels of a row
+    int width, n;                    // n = width * height
+    int kind;                        // HAF_FRAME_*
+    haf_frame_math::FrameMath m;
+};
 
 // bytes between two pixels of a row: 2 / 4 for the depth kinds, point_stride_bytes for XYZ; 0 for an unknown kind
 size_t frame_elem_bytes(const haf_frame &f);

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "frame_points.h"
+#include "frames.h"           // FrameDev
 #include "grasp_cells.h"
 
 namespace haf {
@@ -249,21 +250,6 @@ struct CloudDev {
                      // where a point lands before the gripper roll -- only used to pre-sort the cloud into spatial buckets
     int sorted_off;  // first point of this cloud in the bucket-sorted copy (points), bucket_off: its first bucket counter
     int bucket_off;
-};
-
-// per sensor frame of a haf_score_frames batch (frames.hip): where its pixels lie and where its points go.  The array rides in the
-// request's header block behind the RollGeo array.  dst is 16-byte aligned (the points of a frame start at a multiple of four points).
-// haf_score_views: one entry per VIEW; dst is the start of the request's region (all its views share it) and count the request's live
-// point counter on the device, CloudDev::n, which k_view_points advances (null on the haf_score_frames path)
-struct FrameDev {
-    const void *src;                 // first pixel: the raw area (staged host depth frames), dst itself (staged host XYZ frames: in place), or the caller's device memory
-    float *dst;                      // packed xyz, width * height points: CloudDev::xyz of the same index
-    int *count;                      // views only: CloudDev::n of the request
-    unsigned long long row_stride;   // bytes between rows of src
-    unsigned point_stride;           // bytes between pixels of a row
-    int width, n;                    // n = width * height
-    int kind;                        // HAF_FRAME_*
-    haf_frame_math::FrameMath m;
 };
 
 // per (cloud, roll): rows 0..2 of the fp32 transform (server.cpp:483) and the rotated-rectangle scalars of

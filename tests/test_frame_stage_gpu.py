@@ -1,0 +1,139 @@
+"""The wiring of the sensor-frame staging code (csrc/frame_stage.h, StageBuf in csrc/engine_state.h) into the engine on the MI355X: host
+frames large enough to go to the device in several pieces, through every entry point that takes a haf_frame, against the same call on the
+same pixels handed over device-resident -- the route that stages nothing.  Every comparison is an equality.  The staging arithmetic itself
+is tested without a device (tests/test_frame_stage_cpu.py).  Testing build; the guard zones around every device buffer are checked after
+every request and after each test."""
+import os
+
+import numpy as np
+import pytest
+
+import frame_cases as fc
+import pcdio
+from haf_grasping_amd import capi
+from test_frames_gpu import C3_IN, K525, TABLE1, assert_same, device_copy, make_engine, render_depth, snapshot
+from test_roi_gpu import device_mask, strip
+from test_views_gpu import CAM_A, sorted_rows
+
+pytestmark = pytest.mark.gpu
+
+CFG = dict(n_rolls=6, roll_step_deg=30, max_points=700000)      # 56 x 56 grids
+K200 = dict(fx=164.0, fy=164.0, cx=99.5, cy=59.5)                # the 640 x 480 camera at 200 x 120
+
+
+@pytest.fixture(autouse=True)
+def _canaries(monkeypatch):
+    monkeypatch.setenv("HAF_CANARY_CHECK", "1")
+    yield
+    bad, report, n = capi.check_canaries()
+    assert bad == 0, report
+
+
+@pytest.fixture(scope="module")
+def scenes(data_dir):
+    """-> {name: (host frame, its array, device-resident copy, host mask with padded rows, (device mask, its keep-alive))}:
+    u16: 640 x 480 depth, rows padded by 3 elements: 614 400 packed bytes, three pieces;
+    xyz: 200 x 120 organised cloud, 20-byte points, rows padded by 2 points: 288 000 packed bytes, two pieces"""
+    table1 = pcdio.load_pcd(os.path.join(data_dir, TABLE1 + ".pcd"))
+    depth = fc.padded(render_depth(table1, CAM_A), 3)
+    u16 = capi.depth_frame(depth, sensor_to_base=CAM_A, **K525)
+    small = render_depth(table1, CAM_A, width=200, height=120, **K200)
+    wide = np.full((120, 202, 5), 7.0, np.float32)
+    wide[:, :200, :3] = capi.frame_points(capi.depth_frame(small, **K200)).reshape(120, 200, 3)      # identity pose: sensor-frame points
+    cloud = wide[:, :200]
+    xyz = capi.xyz_frame(cloud, sensor_to_base=CAM_A)
+    assert (u16.row_stride_bytes, xyz.row_stride_bytes, xyz.point_stride_bytes) == (643 * 2, 202 * 20, 20)
+    out = {}
+    for name, frame, image in (("u16", u16, depth), ("xyz", xyz, cloud)):
+        h, w = frame.height, frame.width
+        mask = np.full((h, w + 5), 9, np.uint8)
+        mask[:, :w] = 0
+        mask[h // 4:3 * h // 4, w // 4:3 * w // 4] = 1
+        mask = mask[:, :w]
+        assert np.isfinite(capi.frame_points(frame)).all(axis=1).mean() > 0.05      # (table1 fills an eighth of the image)
+        out[name] = (frame, image, device_copy(frame, image), mask, device_mask(mask))
+    return out
+
+
+@pytest.fixture(scope="module")
+def engine(data_dir, golden_dir):
+    eng = make_engine(data_dir, os.path.join(golden_dir, "surrogate.model"), **CFG)
+    yield eng
+    eng.close()
+
+
+def roi_state(eng, out):
+    """what an ROI request leaves, without the tier counts (a host mask is counted, a device-resident one is not: the same labels may
+    come from different tiers)"""
+    s = snapshot(eng, out)
+    del s["tiers"], s["exact"]
+    s["out"] = strip(out)
+    s["labels"] = [eng.debug(capi.DBG_LABELS, 0, r).tobytes() for r in range(eng.cfg.n_rolls)]
+    return s
+
+
+@pytest.mark.parametrize("name", ["u16", "xyz"])
+def test_staged_host_frame_equals_device_resident_frame_on_every_route(engine, scenes, name):
+    """haf_score_frames, haf_score_views (as the only view and as the second of two), haf_score_frames_roi with a host mask of padded rows
+    and haf_grasp_map: outputs, the points the kernels read (as a sorted multiset for views), the batch's grids, tier counts and ranked
+    candidates, and the three map images are those of the same call on the device-resident copy"""
+    eng, inp = engine, capi.default_input(**C3_IN)
+    host, _, dev, mask, (dmask, _) = scenes[name]
+    other = scenes["xyz" if name == "u16" else "u16"][2]          # device-resident in both calls
+    want_points = fc.words(capi.frame_points(host))
+
+    def frames_route(f):
+        out = eng.score_frames([f], [inp])[0]
+        return snapshot(eng, out), fc.words(eng.debug_points(0)), eng.grasp_map(0, f)
+
+    got, ref = frames_route(host), frames_route(dev)
+    assert_same(got[0], ref[0])
+    assert (got[1] == ref[1]).all() and (got[1] == want_points).all()
+    assert got[0]["out"]["n_evals"] > 1000 and got[0]["out"]["eval"] > 0          # (not a comparison of empty grids)
+    for k in ("vote", "roll", "cell"):
+        assert (got[2][k] == ref[2][k]).all(), k
+    assert (got[2]["cell"] >= 0).any()
+
+    def views_route(views):
+        outs, counts = eng.score_views([views], [inp])
+        return snapshot(eng, outs[0]), sorted_rows(eng.fetch_points(0)), counts
+
+    for views_host, views_dev in (([host], [dev]), ([other, host], [other, dev])):
+        got, ref = views_route(views_host), views_route(views_dev)
+        assert got[2] == ref[2] and got[2][0] > 1000
+        assert_same(got[0], ref[0])
+        assert got[1].shape == ref[1].shape and (got[1] == ref[1]).all()
+
+    def roi_route(f, m):
+        out = eng.score_frames_roi([f], [m], [inp])[0]
+        return roi_state(eng, out), fc.words(eng.debug_points(0))
+
+    got, ref = roi_route(host, mask), roi_route(dev, dmask)
+    assert_same(got[0], ref[0])
+    assert (got[1] == ref[1]).all() and (got[1] == want_points).all()
+    assert 0 < got[0]["out"]["n_evals"]
+
+
+def test_staging_blocks_grow_and_leave_results_as_they_were(data_dir, golden_dir, scenes):
+    """a fresh engine: a host XYZ view (the raw area of XYZ views is allocated), an ROI request (the mask area is) and a grasp map of the
+    200 x 120 frame (the map block is); then a grasp map of the 640 x 480 frame, for which the map block grows; then the first three
+    calls again: the same results"""
+    eng, inp = make_engine(data_dir, os.path.join(golden_dir, "surrogate.model"), **CFG), capi.default_input(**C3_IN)
+    xyz, _, _, mask, _ = scenes["xyz"]
+    u16 = scenes["u16"][0]
+
+    def three_calls():
+        outs, counts = eng.score_views([[xyz]], [inp])
+        views = (snapshot(eng, outs[0]), sorted_rows(eng.fetch_points(0)).tobytes(), counts)
+        roi = roi_state(eng, eng.score_frames_roi([xyz], [mask], [inp])[0])
+        return views, roi, {k: v.tobytes() for k, v in eng.grasp_map(0, xyz).items()}
+
+    before = three_calls()
+    large = eng.grasp_map(0, u16)
+    assert large["vote"].shape == (480, 640) and (large["cell"] >= 0).any()
+    after = three_calls()
+    assert before[0][1:] == after[0][1:] and before[2] == after[2]
+    assert_same(before[0][0], after[0][0])
+    assert_same(before[1], after[1])
+    assert (eng.grasp_map(0, u16)["vote"] == large["vote"]).all()
+    eng.close()
