@@ -17,6 +17,7 @@ DBG_HEIGHTS, DBG_INTEGRAL, DBG_MASK, DBG_LABELS, DBG_DECISION, DBG_TRANSFORM, DB
 SHARD_ROLLS, SHARD_CLOUDS = 0, 1
 FRAME_DEPTH_U16, FRAME_DEPTH_F32, FRAME_XYZ_F32 = 0, 1, 2
 MAP_NO_CELL = -32768                 # HAF_MAP_NO_CELL: a grasp-map pixel no roll has a cell for
+MAX_LABELS = 4096                    # HAF_MAX_LABELS: instance labels of one haf_grasp_map_labels call
 STAGES = ["upload", "bin", "integral", "mask", "features", "svm", "refine", "recheck", "vote", "download"]
 
 
@@ -74,6 +75,20 @@ class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
 
+
+class LabelImage(C.Structure):
+    """haf_label_image: an instance-label image that goes with a Frame of the same width x height (0 background, 1..n_labels instances)"""
+    _fields_ = [("data", C.c_void_p), ("elem_bytes", C.c_int32), ("on_device", C.c_int32), ("row_stride_bytes", C.c_size_t)]
+
+
+class LabelPick(C.Structure):
+    """haf_label_pick: the best pixel of one label and its grasp-map values"""
+    _fields_ = [("found", C.c_int32), ("u", C.c_int32), ("v", C.c_int32), ("vote", C.c_int32), ("roll", C.c_int32), ("cell", C.c_int32),
+                ("n_pixels", C.c_int32)]
+
+
+LABEL_PICK_DTYPE = np.dtype([(f, np.int32) for f in ("found", "u", "v", "vote", "roll", "cell", "n_pixels")])
+assert LABEL_PICK_DTYPE.itemsize == C.sizeof(LabelPick) == 28
 
 ATTR_RECORD_DTYPE = np.dtype([("feature", np.float32), ("pad", np.float32), ("q4", np.float64), ("scaled", np.float64)])
 assert ATTR_RECORD_DTYPE.itemsize == 24
@@ -155,6 +170,10 @@ def _bind(path, testing):
     L.haf_cell_pose.argtypes = [E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GraspCandidate)]
     L.haf_grasp_map_best.argtypes = [E, C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(GraspCandidate),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.haf_label_best_ref.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Frame),
+                                     C.POINTER(LabelImage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.haf_grasp_map_labels.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_int32)]
     L.haf_roi_cells.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_void_p,
                                 C.c_void_p]
     L.haf_score_frames_roi.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
@@ -449,6 +468,54 @@ def _host_mask(mask, frame):
     if keep.shape[0] > 1 and keep.strides[0] < keep.shape[1]:
         keep = np.ascontiguousarray(keep)
     return keep, keep.ctypes.data, (keep.strides[0] if keep.shape[0] > 1 else keep.shape[1])
+
+
+def label_image(labels, frame, n_labels=None):
+    """-> (LabelImage, n_labels) for `labels`: a numpy uint8 / uint16 [height, width] array (host; rows may be padded: a view into a
+    wider array; n_labels defaults to the image's maximum, at least 1), a device tensor of such a shape (anything with data_ptr(), element_size() and
+    stride(): a torch tensor, possibly a view), or (device_ptr, elem_bytes, row_stride_bytes); n_labels must be given for device images."""
+    if isinstance(labels, tuple):
+        ptr, eb, stride = (int(x) for x in labels)
+        img, keep = LabelImage(ptr, eb, 1, stride), None
+    elif hasattr(labels, "data_ptr"):
+        assert tuple(labels.shape) == (frame.height, frame.width) and (frame.width == 1 or labels.stride(1) == 1)
+        eb = labels.element_size()
+        img, keep = LabelImage(labels.data_ptr(), eb, 1, labels.stride(0) * eb if frame.height > 1 else frame.width * eb), labels
+    else:
+        keep = np.asarray(labels)
+        assert keep.dtype in (np.uint8, np.uint16) and keep.shape == (frame.height, frame.width)
+        if (keep.shape[1] > 1 and keep.strides[1] != keep.itemsize) or (keep.shape[0] > 1 and keep.strides[0] < keep.shape[1] * keep.itemsize):
+            keep = np.ascontiguousarray(keep)
+        if n_labels is None:
+            n_labels = max(1, int(keep.max()) if keep.size else 0)      # (an image without any object: one label, not found)
+        img = LabelImage(keep.ctypes.data, keep.itemsize, 0, keep.strides[0] if keep.shape[0] > 1 else keep.shape[1] * keep.itemsize)
+    if n_labels is None:
+        raise TypeError("n_labels must be given for a device-resident label image")
+    img._keep = keep
+    return img, int(n_labels)
+
+
+def _label_result(picks, order, n_found, poses=None):
+    out = dict(picks=picks, order=[int(x) for x in order[:n_found]])
+    if poses is not None:
+        out["poses"] = [candidate_to_dict(poses[k]) if picks["found"][k] else None for k in range(len(picks))]
+    return out
+
+
+def label_best_ref(cfg, grasp_input, roll_first, eval_grids, frame, labels, n_labels=None, min_vote=1):
+    """haf_label_best_ref: the host definition of record of the best pixel per instance label.  eval_grids and frame as grasp_map_ref
+    takes them; labels: a host uint8 / uint16 [height, width] array -> dict(picks: LABEL_PICK_DTYPE [n_labels] (label l is entry
+    l - 1), order: the found labels, best pick first)"""
+    g = np.ascontiguousarray(eval_grids, dtype=np.float32).reshape(-1, cfg.grid_h, cfg.grid_w)
+    img, n_labels = label_image(labels, frame, n_labels)
+    picks = np.zeros(max(1, n_labels), LABEL_PICK_DTYPE)
+    order = np.zeros(max(1, n_labels), np.int32)
+    nf = C.c_int32(0)
+    rc = lib().haf_label_best_ref(C.byref(cfg), C.byref(grasp_input), roll_first, g.shape[0], g.ctypes.data if g.size else None, C.byref(frame),
+                                  C.byref(img), n_labels, min_vote, picks.ctypes.data, order.ctypes.data, C.byref(nf))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_label_best_ref refused its arguments")
+    return _label_result(picks[:n_labels], order, nf.value)
 
 
 def roi_cells(cfg, grasp_input, roll, frame, mask, want=("roi", "eval")):
@@ -750,6 +817,20 @@ class Engine:
         self._check(self._L.haf_grasp_map_best(self._h, request, C.byref(frame), ptr, stride, min_vote, C.byref(c), C.byref(u), C.byref(v),
                                                C.byref(found)))
         return (candidate_to_dict(c), u.value, v.value) if found.value else None
+
+    def best_per_label(self, request, frame, labels, n_labels=None, min_vote=1):
+        """haf_grasp_map_labels: the best pixel of grasp_map(request, frame) for every instance of a label image (label_image(): a numpy
+        uint8 / uint16 array, a device tensor or a device pointer tuple) in one device pass -> dict(picks: LABEL_PICK_DTYPE [n_labels]
+        (label l is entry l - 1), poses: per label the candidate dict of cell_pose at its pick or None, order: the found labels, best
+        pick first)"""
+        img, n_labels = label_image(labels, frame, n_labels)
+        picks = np.zeros(max(1, n_labels), LABEL_PICK_DTYPE)
+        order = np.zeros(max(1, n_labels), np.int32)
+        poses = (GraspCandidate * max(1, n_labels))()
+        nf = C.c_int32(0)
+        self._check(self._L.haf_grasp_map_labels(self._h, request, C.byref(frame), C.byref(img), n_labels, min_vote, picks.ctypes.data, poses,
+                                                 order.ctypes.data, C.byref(nf)))
+        return _label_result(picks[:n_labels], order, nf.value, poses)
 
     def debug_attr(self, cloud, roll):
         """Attribute records of the masked cells of (cloud, roll): cells [n, 2], records [n, 324], computed [n]."""

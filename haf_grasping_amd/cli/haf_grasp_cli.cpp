@@ -25,6 +25,10 @@
 //   --mask FILE.pgm                   with --depth: an 8-bit binary PGM of the image's size; after the normal output one line
 //                                     "mask <u> <v> <hypothesis>" for the best pixel under its non-zero samples whose vote is at
 //                                     least --mask-min-vote (default 1), or "mask none" (haf_grasp_map_best)
+//   --labels FILE.pgm                 with --depth: an 8- or 16-bit binary PGM of the image's size, an instance-label image (0 background,
+//                                     1.. the objects); after the normal output one line "object <label> <u> <v> <hypothesis>" per object
+//                                     that has a pixel whose vote is at least --mask-min-vote, best first (haf_grasp_map_labels: one
+//                                     device pass for all objects); may be combined with --roi-mask
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
 //                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
 //                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
@@ -113,7 +117,7 @@ static void usage()
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
-            "  --map-out PREFIX  --mask FILE.pgm [--mask-min-vote N]      (with --depth)\n"
+            "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
@@ -144,7 +148,8 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 struct DepthView { std::string path; haf_frame frame; };
 // --map-out / --mask: the goal's votes in the pixels of the FIRST view (haf_grasp_map, haf_grasp_map_best)
 // --roi-mask: the request itself is restricted to the cells near the masked pixels' cells (haf_score_frames_roi)
-struct MapOptions { std::string out_prefix, mask_path, roi_path; int min_vote = 1; };
+// --labels: the best grasp per object of an instance-label image over the first view (haf_grasp_map_labels)
+struct MapOptions { std::string out_prefix, mask_path, roi_path, labels_path; int min_vote = 1; };
 
 static bool write_pgm16(const std::string &path, const int16_t *img, int w, int h)
 {
@@ -217,6 +222,37 @@ static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, c
         }
         if (found) printf("mask %d %d %s\n", u, v, hafshim::hypothesis_string(best.grasp, cfg.roll_step_deg).c_str());
         else printf("mask none\n");
+    }
+    if (!mo.labels_path.empty()) {
+        // 8-bit samples as they are, 16-bit ones through the library's reader; labels above HAF_MAX_LABELS are ignored like background
+        std::vector<uint8_t> lab8;
+        uint16_t *lab16 = nullptr;
+        int32_t w = 0, h = 0;
+        char err[256];
+        int w8 = 0, h8 = 0;
+        if (read_pgm8(mo.labels_path, lab8, w8, h8)) { w = w8; h = h8; }
+        else if (haf_pgm16_load(mo.labels_path.c_str(), &lab16, &w, &h, err, sizeof err) != HAF_OK) {
+            fprintf(stderr, "%s: not a binary 8- or 16-bit PGM (%s)\n", mo.labels_path.c_str(), err);
+            return 1;
+        }
+        int rc = 0;
+        if (w != f.width || h != f.height) {
+            fprintf(stderr, "%s: %d x %d, the depth image has %d x %d\n", mo.labels_path.c_str(), w, h, f.width, f.height);
+            rc = 1;
+        } else {
+            unsigned top = 0;
+            for (size_t i = 0; i < n; i++) top = std::max(top, lab16 ? (unsigned)lab16[i] : (unsigned)lab8[i]);
+            const haf_label_image img = {lab16 ? (const void *)lab16 : (const void *)lab8.data(), lab16 ? 2 : 1, 0, (size_t)w * (lab16 ? 2 : 1)};
+            std::vector<std::string> lines;
+            std::string serr;
+            if (top > 0 && hafshim::label_hypotheses(eng, cfg, f, img, (int32_t)std::min(top, (unsigned)HAF_MAX_LABELS), mo.min_vote, &lines, &serr) != HAF_OK) {
+                fprintf(stderr, "--labels: %s\n", serr.c_str());
+                rc = 1;
+            }
+            for (const std::string &l : lines) printf("object %s\n", l.c_str());
+        }
+        if (lab16) haf_free(lab16);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -343,6 +379,7 @@ int main(int argc, char **argv)
         else if (a == "--map-out") { need(1); map_opt.out_prefix = argv[++i]; }
         else if (a == "--mask") { need(1); map_opt.mask_path = argv[++i]; }
         else if (a == "--roi-mask") { need(1); map_opt.roi_path = argv[++i]; }
+        else if (a == "--labels") { need(1); map_opt.labels_path = argv[++i]; }
         else if (a == "--mask-min-vote") { need(1); map_opt.min_vote = atoi(argv[++i]); }
         else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
@@ -358,7 +395,7 @@ int main(int argc, char **argv)
         if (!views.empty()) views.back().frame = frame;       // (a sensor option applies to the view opened last)
     }
     const bool from_depth = !views.empty();
-    if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty())) ||
+    if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && views.size() != 1) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184

@@ -1,4 +1,4 @@
-// engine_graspmap.cpp -- haf_grasp_map, haf_cell_pose and haf_grasp_map_best: the votes of the last scored batch in the pixels of a
+// engine_graspmap.cpp -- haf_grasp_map, haf_cell_pose, haf_grasp_map_best and haf_grasp_map_labels: the votes of the last scored batch in the pixels of a
 // sensor frame (include/hafgrasp.h).  The device pass (graspmap.hip) reads the vote grids that batch left on the device and, for
 // haf_cell_pose, its height grids and records; nothing here writes to any of them, to the request's input block or to the raw areas
 // of haf_score_frames / haf_score_views: the frame's pixels, the roll transforms, the images and the mask live in one block of their
@@ -16,11 +16,12 @@ constexpr size_t kMapHdr = 64;            // [0] the best key of k_map_best, [16
 constexpr size_t kMapRecOff = 16;
 
 struct MapLayout {
-    size_t geo = 0, vote = 0, roll = 0, cell = 0, mask = 0, raw = 0, total = 0;
+    size_t geo = 0, vote = 0, roll = 0, cell = 0, mask = 0, raw = 0, labels = 0, ltab = 0, lout = 0, total = 0;
 };
 
-// the block for images of n_img pixels, a mask of n_mask bytes and raw_bytes of a staged host frame's pixels (each may be 0)
-MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t raw_bytes)
+// the block for images of n_img pixels, a mask of n_mask bytes and raw_bytes of a staged host frame's pixels (each may be 0); for
+// haf_grasp_map_labels also label_bytes of a staged host label image and, per label, the table's key and count and the output entry
+MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t raw_bytes, size_t label_bytes = 0, size_t n_labels = 0)
 {
     MapLayout l;
     l.geo = kMapHdr;
@@ -29,7 +30,10 @@ MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t ra
     l.cell = l.roll + up16(n_img * 2);
     l.mask = l.cell + up16(n_img * 4);
     l.raw = l.mask + up16(n_mask);
-    l.total = l.raw + up16(raw_bytes);
+    l.labels = l.raw + up16(raw_bytes);
+    l.ltab = l.labels + up16(label_bytes);
+    l.lout = l.ltab + up16(n_labels * 12);                  // [n_labels] 64-bit keys, then [n_labels] counts
+    l.total = l.lout + up16(n_labels * sizeof(LabelOutDev));
     return l;
 }
 
@@ -61,9 +65,9 @@ int check_map_frame(haf_engine *e, const char *who, const haf_frame *f)
     return HAF_OK;
 }
 
-// The device pass for one checked frame: stages a host frame's pixels (stage_frame, as the request path's upload_frames does), uploads the roll
-// transforms and launches k_grasp_map on the engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
-int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll, int *d_cell)
+// What every device pass over one checked frame starts with: the zeroed header and the roll transforms go up, a host frame's pixels are
+// staged (stage_frame, as the request path's upload_frames does); *fd = the frame as the kernels read it.  No synchronisation.
+int stage_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, FrameDev *fd_out)
 {
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
@@ -71,11 +75,23 @@ int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const 
     memset(e->map.host, 0, kMapHdr);
     fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->map.host + l.geo));
     HIPCHK(e, hipMemcpyAsync(e->map.dev.p, e->map.host, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
-    const FrameDev fd = describe_frame(f, e->map.dev.p + l.raw);
+    *fd_out = describe_frame(f, e->map.dev.p + l.raw);
     if (f.on_device != 1) {
         const auto send = [&](size_t off, size_t bytes) { return hipMemcpyAsync(e->map.dev.p + l.raw + off, e->map.host + l.raw + off, bytes, hipMemcpyHostToDevice, s); };
         HIPCHK(e, stage_frame(e->map.host + l.raw, f, send));
     }
+    return HAF_OK;
+}
+
+// stage_map, then k_grasp_map on the engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
+int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll, int *d_cell)
+{
+    const haf_config &c = e->cfg;
+    const LastCall &last = e->last;
+    const hipStream_t s = e->stream;
+    FrameDev fd;
+    int rc;
+    if ((rc = stage_map(e, request, rolls, f, l, &fd)) != HAF_OK) return rc;
     const int H = c.grid_h, W = c.grid_w;
     const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
     const short *ev = e->d_ev16.p + (size_t)request * last.R * (size_t)H * W;
@@ -115,6 +131,21 @@ int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *
     return HAF_OK;
 }
 
+// a cell's record as a candidate: haf_top_grasps' pose of it, run_length 0 (a cell is not a run).  haf_cell_pose and haf_grasp_map_labels
+int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out)
+{
+    haf_roll_record rec;
+    rec.vote = q.vote; rec.row = q.row; rec.col = q.col; rec.h_locmax = q.h_locmax; rec.n_evals = q.n_evals;
+    haf_grasp_candidate cand;
+    memset(&cand, 0, sizeof cand);
+    const int rc = candidate_pose_impl(e->cfg, &e->last.inputs[(size_t)request], rec, roll, &cand.grasp, e->error);
+    if (rc != HAF_OK) return rc;
+    cand.run_length = 0;
+    cand.h_locmax = rec.h_locmax;
+    *out = cand;
+    return HAF_OK;
+}
+
 int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, haf_grasp_candidate *out)
 {
     const haf_config &c = e->cfg;
@@ -131,16 +162,7 @@ int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, ha
     if ((rc = check_guards(e)) != HAF_OK) return rc;
     RollRecordDev q;
     memcpy(&q, e->map.host + kMapRecOff, sizeof q);
-    haf_roll_record rec;
-    rec.vote = q.vote; rec.row = q.row; rec.col = q.col; rec.h_locmax = q.h_locmax; rec.n_evals = q.n_evals;
-    haf_grasp_candidate cand;
-    memset(&cand, 0, sizeof cand);
-    rc = candidate_pose_impl(c, &last.inputs[(size_t)request], rec, roll, &cand.grasp, e->error);
-    if (rc != HAF_OK) return rc;
-    cand.run_length = 0;
-    cand.h_locmax = rec.h_locmax;
-    *out = cand;
-    return HAF_OK;
+    return record_candidate(e, request, roll, q, out);
 }
 
 int cell_pose_impl(haf_engine *e, int32_t request, int32_t roll, int32_t row, int32_t col, haf_grasp_candidate *out)
@@ -200,6 +222,73 @@ int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint
     return HAF_OK;
 }
 
+// haf_grasp_map_labels: k_map_labels over the frame, k_label_records over the labels, ONE copy back and ONE synchronisation
+int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const haf_label_image *labels, int32_t n_labels, int32_t min_vote,
+                    haf_label_pick *picks, haf_grasp_candidate *poses, int32_t *order, int32_t *n_found)
+{
+    int rolls = 0, rc;
+    if ((rc = check_last(e, "haf_grasp_map_labels", request, &rolls)) != HAF_OK) return rc;
+    if ((rc = check_map_frame(e, "haf_grasp_map_labels", f)) != HAF_OK) return rc;
+    std::string why;
+    if ((rc = check_label_image(labels, f->width, n_labels, picks, why)) != HAF_OK) return fail(e, rc, "haf_grasp_map_labels: " + why);
+    const haf_config &c = e->cfg;
+    const LastCall &last = e->last;
+    for (int32_t l = 0; l < n_labels; l++) label_pick_none(&picks[l]);
+    if (poses) memset(poses, 0, (size_t)n_labels * sizeof *poses);
+    if (n_found) *n_found = 0;
+    if (rolls == 0) return HAF_OK;                          // (a negative budget: no roll ran, no pixel has a roll)
+    const size_t n = (size_t)f->width * (size_t)f->height, eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
+    const bool host_labels = labels->on_device != 1;
+    const MapLayout l = map_layout(e, 0, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind), host_labels ? n * eb : 0, nl);
+    if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
+    char *d = e->map.dev.p;
+    const hipStream_t s = e->stream;
+    FrameDev fd;
+    if ((rc = stage_map(e, request, rolls, *f, l, &fd)) != HAF_OK) return rc;
+    const void *d_labels = labels->data;
+    size_t label_stride = labels->row_stride_bytes;
+    if (host_labels) {
+        pack_rows(e->map.host + l.labels, static_cast<const char *>(labels->data), (size_t)f->height, (size_t)f->width, eb, eb, labels->row_stride_bytes);
+        HIPCHK(e, hipMemcpyAsync(d + l.labels, e->map.host + l.labels, n * eb, hipMemcpyHostToDevice, s));
+        d_labels = d + l.labels;
+        label_stride = (size_t)f->width * eb;
+    }
+    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d + l.ltab);
+    unsigned *d_cnt = reinterpret_cast<unsigned *>(d + l.ltab + nl * 8);
+    LabelOutDev *d_out = reinterpret_cast<LabelOutDev *>(d + l.lout);
+    HIPCHK(e, hipMemsetAsync(d + l.ltab, 0, nl * 12, s));
+    const int H = c.grid_h, W = c.grid_w;
+    const size_t HW = (size_t)H * W, br0 = (size_t)request * last.R;
+    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    const CellGeo *d_geo = reinterpret_cast<const CellGeo *>(d + l.geo);
+    const short *ev = e->d_ev16.p + br0 * HW;
+    launch_map_labels(fd, d_geo, rolls, last.roll_first, ev, H, W, r_row, r_col, d_labels, label_stride, (int)eb, n_labels, min_vote, d_key, d_cnt, s);
+    HIPCHK(e, hipGetLastError());
+    launch_label_records(fd, d_geo, rolls, last.roll_first, ev, reinterpret_cast<const float *>(e->d_heights.p) + br0 * HW, e->d_rec.p + br0, H, W,
+                         r_row, r_col, n_labels, d_key, d_cnt, d_out, s);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->map.host + l.lout, d_out, nl * sizeof(LabelOutDev), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    const LabelOutDev *got = reinterpret_cast<const LabelOutDev *>(e->map.host + l.lout);
+    // every entry is checked before the first one is handed over
+    for (size_t k = 0; k < nl; k++) {
+        const LabelOutDev &o = got[k];
+        if (!o.found) continue;
+        if (o.cell < 0 || o.cell >= H * W || o.n_pixels < 1) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_labels: malformed key");
+        if (o.rec.vote != o.vote) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_labels: the record's vote is not the key's");
+    }
+    for (size_t k = 0; k < nl; k++) {
+        const LabelOutDev &o = got[k];
+        if (!o.found) continue;
+        haf_label_pick &p = picks[k];
+        p.found = 1; p.u = o.u; p.v = o.v; p.vote = o.vote; p.roll = o.roll; p.cell = o.cell; p.n_pixels = o.n_pixels;
+        if (poses && (rc = record_candidate(e, request, o.roll, o.rec, &poses[k])) != HAF_OK) return rc;
+    }
+    label_order(picks, n_labels, f->width, order, n_found);
+    return HAF_OK;
+}
+
 }  // namespace
 
 }  // namespace haf_host
@@ -223,6 +312,13 @@ int haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, c
 {
     if (!e) return HAF_E_ARG;
     return guarded(&e->error, [&] { return map_best_impl(e, request, frame, mask, mask_row_stride, min_vote, out, u, v, found); });
+}
+
+int haf_grasp_map_labels(haf_engine *e, int32_t request, const haf_frame *frame, const haf_label_image *labels, int32_t n_labels,
+                         int32_t min_vote, haf_label_pick *picks, haf_grasp_candidate *poses, int32_t *order, int32_t *n_found)
+{
+    if (!e) return HAF_E_ARG;
+    return guarded(&e->error, [&] { return map_labels_impl(e, request, frame, labels, n_labels, min_vote, picks, poses, order, n_found); });
 }
 
 }  // extern "C"

@@ -68,6 +68,12 @@ void fill_roll_geo(const haf_config &cfg, const haf_grasp_input &in, const Norma
 bool invert(const Mat4 &m, Mat4 &inv);
 // graspmap_host.cpp: rows 0..2 of the transforms of rolls roll_first .. roll_first + roll_count - 1 (fill_roll_geo's), 64 bytes each
 void fill_cell_geo(const haf_config &cfg, const haf_grasp_input &in, int roll_first, int roll_count, haf_cell_math::CellGeo *geo);
+// graspmap_host.cpp, shared by haf_label_best_ref and haf_grasp_map_labels: every refusal of a label image that goes with a frame `width`
+// pixels wide; the not-found pick; a pick's key (k_map_best's: its maximum is the best pick); the found labels, best pick first
+int check_label_image(const haf_label_image *l, int32_t width, int32_t n_labels, const void *picks, std::string &err);
+void label_pick_none(haf_label_pick *p);
+unsigned long long label_pick_key(const haf_label_pick &p, int32_t width);
+void label_order(const haf_label_pick *picks, int32_t n_labels, int32_t width, int32_t *order, int32_t *n_found);
 
 // Testing build: every device buffer lies between two guard zones filled with kCanaryByte -- kCanaryGuard bytes in front, and from
 // the buffer's last byte to the next multiple of kCanaryGuard plus kCanaryGuard behind -- and is registered with the source line that
@@ -368,7 +374,8 @@ struct haf_engine {
     DevBuf<unsigned long long> d_top_scratch;
     StageBuf top_out;
     // haf_grasp_map (engine_graspmap.cpp), allocated on its first call and grown to the largest frame seen: the device block
-    // [best key + cell record: 64 bytes][R x CellGeo][vote | roll | cell images][mask bytes] and its pinned host copy
+    // [best key + cell record: 64 bytes][R x CellGeo][vote | roll | cell images][mask bytes][a host frame's pixels][a host label image]
+    // [label table: keys, counts][label output entries] and its pinned host copy
     StageBuf map;
     // haf_score_frames_roi (engine_roi.cpp), allocated on its first call: the ROI cell sets -- one bit per cell, max_clouds x max_rolls
     // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes, every mask at a

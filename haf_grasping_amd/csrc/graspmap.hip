@@ -19,6 +19,8 @@
 // byte is not zero and whose vote is >= min_vote, then one 64-bit atomicMax per wave.  Key, most significant first: vote + 32768
 // (16 bits), 65535 - roll (16), 2^32 - 1 - pixel index (32): its maximum is vote descending, roll ascending, then v, then u ascending.
 // k_cell_record: the record of one arbitrary cell for haf_cell_pose, with the 9 x 8 z window of k_top_grasps.
+// k_map_labels / k_label_records: haf_grasp_map_labels -- the masked best of every label of an instance-label image in one pass over the
+// frame (a segmented arg-max of the same key in a per-workgroup LDS table), then one wave per label for its pick and its record.
 #include "frame_group.h"
 #include "grasp_cells.h"
 
@@ -27,6 +29,33 @@ namespace haf {
 using haf_cell_math::CellGeo;
 
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+// The roll loop of a group: for each of its G points that takes part (usable[k]) the best vote over the R rolls, that roll (global index)
+// and that cell; kNoCellVote, -1, -1 where no roll has a cell.  k_grasp_map and k_map_labels both call it: one arithmetic, one order
+template <unsigned G>
+__device__ __forceinline__ void group_best(const float (&p)[G * 3], const bool (&usable)[G], const CellGeo *__restrict__ geo, int R, int roll_first,
+                                           const short *__restrict__ ev16, int H, int W, float r_row, float r_col, int (&best)[G],
+                                           int (&best_roll)[G], int (&best_cell)[G])
+{
+#pragma unroll
+    for (unsigned k = 0; k < G; k++) { best[k] = haf_cell_math::kNoCellVote; best_roll[k] = -1; best_cell[k] = -1; }
+    const size_t HW = (size_t)H * (size_t)W;
+    for (int r = 0; r < R; r++) {
+        const CellGeo &g = geo[r];                        // (r is wave-uniform: sixteen scalar registers)
+        const global_ptr<const short> grid = as_global<const short>(ev16 + (size_t)r * HW);
+        int ci[G], val[G];
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) {
+            const int c = haf_cell_math::point_cell(g.m, p[3 * k], p[3 * k + 1], p[3 * k + 2], r_row, r_col, H, W);
+            ci[k] = usable[k] ? c : -1;
+        }
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) val[k] = ci[k] >= 0 ? (int)grid[ci[k]] : 0;      // (0 <= ci < H * W: inside roll r's grid)
+#pragma unroll
+        for (unsigned k = 0; k < G; k++)
+            if (ci[k] >= 0 && (best_roll[k] < 0 || val[k] > best[k])) { best[k] = val[k]; best_roll[k] = roll_first + r; best_cell[k] = ci[k]; }
+    }
+}
 
 template <int KIND>
 __global__ __launch_bounds__(kFrameThreads) void k_grasp_map(const FrameDev f, const CellGeo *__restrict__ geo, int R, int roll_first,
@@ -44,26 +73,8 @@ __global__ __launch_bounds__(kFrameThreads) void k_grasp_map(const FrameDev f, c
     bool usable[G];
     int best[G], best_roll[G], best_cell[G];
 #pragma unroll
-    for (unsigned k = 0; k < G; k++) {
-        usable[k] = i0 + k < n && haf_cell_math::point_usable(p + 3 * k);
-        best[k] = haf_cell_math::kNoCellVote; best_roll[k] = -1; best_cell[k] = -1;
-    }
-    const size_t HW = (size_t)H * (size_t)W;
-    for (int r = 0; r < R; r++) {
-        const CellGeo &g = geo[r];                        // (r is wave-uniform: sixteen scalar registers)
-        const global_ptr<const short> grid = as_global<const short>(ev16 + (size_t)r * HW);
-        int ci[G], val[G];
-#pragma unroll
-        for (unsigned k = 0; k < G; k++) {
-            const int c = haf_cell_math::point_cell(g.m, p[3 * k], p[3 * k + 1], p[3 * k + 2], r_row, r_col, H, W);
-            ci[k] = usable[k] ? c : -1;
-        }
-#pragma unroll
-        for (unsigned k = 0; k < G; k++) val[k] = ci[k] >= 0 ? (int)grid[ci[k]] : 0;      // (0 <= ci < H * W: inside roll r's grid)
-#pragma unroll
-        for (unsigned k = 0; k < G; k++)
-            if (ci[k] >= 0 && (best_roll[k] < 0 || val[k] > best[k])) { best[k] = val[k]; best_roll[k] = roll_first + r; best_cell[k] = ci[k]; }
-    }
+    for (unsigned k = 0; k < G; k++) usable[k] = i0 + k < n && haf_cell_math::point_usable(p + 3 * k);
+    group_best<G>(p, usable, geo, R, roll_first, ev16, H, W, r_row, r_col, best, best_roll, best_cell);
 
     // a 16-bit image's group is 2 G bytes, the cells' 4 G: vector stores where the caller's base makes the group's address a multiple of that
     unsigned pv[G / 2], pr[G / 2];
@@ -187,6 +198,183 @@ void launch_cell_record(const short *ev16, const float *heights, const RollRecor
                         RollRecordDev *out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_cell_record, dim3(1), dim3(64), 0, s, ev16, heights, rec, br, row, col, H, W, out);
+}
+
+// ---- the best pixel per instance label (haf_grasp_map_labels) ----
+// k_map_labels<KIND, LABEL_BYTES>: a lane owns the group of G pixels k_grasp_map gives it and reads the group's labels FIRST: a group
+// without a label in 1..n_labels is done before the deprojection and the R gathers (a background wave costs its label load).  A labelled
+// pixel's (vote, roll, cell) is group_best's, the map's own; a qualifying one (k_map_best's rule: a roll, vote >= min_vote) sends map_key(vote, roll, i) to
+// its label's slot of the workgroup's table in dynamic LDS -- n_labels 64-bit keys, then n_labels 32-bit counts: 12 bytes per label, at
+// most 48 KB -- with one LDS atomicMax and one atomicAdd.  At the end the workgroup walks its table and sends the non-zero slots on to
+// the global table (zeroed by the caller): one 64-bit atomicMax and one atomicAdd each.  A label outside 1..n_labels indexes nothing.
+template <int KIND, int LB>
+__global__ __launch_bounds__(kFrameThreads) void k_map_labels(const FrameDev f, const CellGeo *__restrict__ geo, int R, int roll_first,
+                                                              const short *__restrict__ ev16, int H, int W, float r_row, float r_col,
+                                                              const void *__restrict__ labels, unsigned long long label_stride, int n_labels,
+                                                              int min_vote, unsigned long long *__restrict__ g_key, unsigned *__restrict__ g_cnt)
+{
+    constexpr unsigned G = frame_group<KIND>();
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_key[];      // [n_labels] keys, then [n_labels] counts
+    unsigned *s_cnt = reinterpret_cast<unsigned *>(s_key + n_labels);
+    for (int l = threadIdx.x; l < n_labels; l += kFrameThreads) { s_key[l] = 0ull; s_cnt[l] = 0u; }
+    __syncthreads();
+
+    const unsigned n = (unsigned)f.n;
+    const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;
+    if (i0 < n) {                                         // (no early return: every lane meets the barrier below)
+        const unsigned Wf = (unsigned)f.width;
+        const unsigned v0 = i0 / Wf, u0 = i0 - v0 * Wf;
+        unsigned lab[G] = {};
+        const char *a = static_cast<const char *>(labels) + (size_t)v0 * label_stride + (size_t)u0 * LB;
+        if (i0 + G <= n && u0 + G <= Wf && (reinterpret_cast<uintptr_t>(a) & (G * LB - 1u)) == 0) {
+            unsigned w[G * LB / 4];                       // the group's labels in one load of G * LB bytes: inside one row
+            if constexpr (G * LB == 16) { const v4u q = *as_global<const v4u>(a); w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w; }
+            else if constexpr (G * LB == 8) { const v2u q = *as_global<const v2u>(a); w[0] = q.x; w[1] = q.y; }
+            else w[0] = *as_global<const unsigned>(a);
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) {
+                if constexpr (LB == 2) lab[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                else lab[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+            }
+        } else {
+            unsigned u = u0, v = v0;
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) {
+                if (i0 + k < n) {                         // (v < height: inside the label image)
+                    const char *s = static_cast<const char *>(labels) + (size_t)v * label_stride + (size_t)u * LB;
+                    if constexpr (LB == 2) lab[k] = *as_global<const uint16_t>(s);
+                    else lab[k] = *as_global<const unsigned char>(s);
+                }
+                if (++u == Wf) { u = 0; v++; }
+            }
+        }
+        bool any = false;
+#pragma unroll
+        for (unsigned k = 0; k < G; k++) {
+            if (lab[k] > (unsigned)n_labels) lab[k] = 0u;      // ignored like background, before it indexes anything
+            any |= lab[k] != 0u;
+        }
+        if (any) {
+            float p[G * 3];
+            group_points<KIND>(f, i0, n, p);
+            bool usable[G];
+            int best[G], best_roll[G], best_cell[G];
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) usable[k] = lab[k] != 0u && i0 + k < n && haf_cell_math::point_usable(p + 3 * k);
+            group_best<G>(p, usable, geo, R, roll_first, ev16, H, W, r_row, r_col, best, best_roll, best_cell);
+#pragma unroll
+            for (unsigned k = 0; k < G; k++)
+                if (lab[k] != 0u && best_roll[k] >= 0 && best[k] >= min_vote && best[k] > haf_cell_math::kNoCellVote) {      // (k_map_best's rule; 1 <= lab <= n_labels: inside the table)
+                    atomicMax(&s_key[lab[k] - 1u], map_key(best[k], best_roll[k], i0 + k));
+                    atomicAdd(&s_cnt[lab[k] - 1u], 1u);
+                }
+        }
+    }
+    __syncthreads();
+    for (int l = threadIdx.x; l < n_labels; l += kFrameThreads) {
+        const unsigned c = s_cnt[l];
+        if (c) { atomicMax(&g_key[l], s_key[l]); atomicAdd(&g_cnt[l], c); }
+    }
+}
+
+template <int KIND>
+static void launch_map_labels_kind(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row,
+                                   float r_col, const void *labels, size_t label_stride, int label_bytes, int n_labels, int min_vote,
+                                   unsigned long long *g_key, unsigned *g_cnt, hipStream_t s)
+{
+    constexpr unsigned G = frame_group<KIND>();
+    const unsigned groups = ((unsigned)f.n + G - 1) / G;
+    if (!groups) return;
+    const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
+    const size_t lds = (size_t)n_labels * 12;
+    if (label_bytes == 2)
+        hipLaunchKernelGGL((k_map_labels<KIND, 2>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
+                           (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
+    else
+        hipLaunchKernelGGL((k_map_labels<KIND, 1>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
+                           (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
+}
+
+void launch_map_labels(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row, float r_col,
+                       const void *labels, size_t label_stride, int label_bytes, int n_labels, int min_vote, unsigned long long *g_key,
+                       unsigned *g_cnt, hipStream_t s)
+{
+    if (f.kind == HAF_FRAME_DEPTH_U16)
+        launch_map_labels_kind<HAF_FRAME_DEPTH_U16>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
+    else if (f.kind == HAF_FRAME_DEPTH_F32)
+        launch_map_labels_kind<HAF_FRAME_DEPTH_F32>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
+    else
+        launch_map_labels_kind<HAF_FRAME_XYZ_F32>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
+}
+
+// k_label_records: one wave per label.  The label's key names its best pixel i and roll r; the pixel's point (frame_points.h) and its
+// cell under roll r (grasp_cells.h) are recomputed -- the arithmetic is deterministic: this is the cell k_map_labels saw -- and the rest
+// is k_cell_record's work at that cell.  out[l] = {the haf_label_pick image, the record}; cell = -2 marks a key that decodes to nothing
+// (the host answers HAF_E_INTERNAL).  ev16 / heights / rec: the request's first roll of the last batch
+__global__ __launch_bounds__(64) void k_label_records(const FrameDev f, const CellGeo *__restrict__ geo, int R, int roll_first,
+                                                      const short *__restrict__ ev16, const float *__restrict__ heights,
+                                                      const RollRecordDev *__restrict__ rec, int H, int W, float r_row, float r_col,
+                                                      const unsigned long long *__restrict__ g_key, const unsigned *__restrict__ g_cnt,
+                                                      LabelOutDev *__restrict__ out)
+{
+    const int l = blockIdx.x;
+    const unsigned long long key = g_key[l];
+    LabelOutDev o;
+    o.found = 0; o.u = o.v = o.roll = o.cell = -1; o.vote = haf_cell_math::kNoCellVote; o.n_pixels = 0;
+    o.rec.vote = 0; o.rec.row = o.rec.col = 0; o.rec.h_locmax = 0.0f; o.rec.n_evals = 0;
+    if (key == 0ull) {
+        if (threadIdx.x == 0) out[l] = o;
+        return;
+    }
+    const unsigned i = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull), r = roll - roll_first;
+    int ci = -2;
+    unsigned u = 0, v = 0;
+    if (i < (unsigned)f.n && r >= 0 && r < R) {
+        v = i / (unsigned)f.width; u = i - v * (unsigned)f.width;
+        const char *src = static_cast<const char *>(f.src) + (size_t)v * f.row_stride;
+        float p[3];
+        if (f.kind == HAF_FRAME_DEPTH_U16) point_u16(f.m, u, v, *as_global<const uint16_t>(src + (size_t)u * 2), p);
+        else if (f.kind == HAF_FRAME_DEPTH_F32) point_f32(f.m, u, v, *as_global<const float>(src + (size_t)u * 4), p);
+        else {
+            const global_ptr<const float> q = as_global<const float>(src + (size_t)u * f.point_stride);
+            point_xyz(f.m, q[0], q[1], q[2], p);
+        }
+        if (haf_cell_math::point_usable(p)) ci = haf_cell_math::point_cell(geo[r].m, p[0], p[1], p[2], r_row, r_col, H, W);
+        if (ci < 0) ci = -2;
+    }
+    o.found = 1; o.u = (int)u; o.v = (int)v; o.vote = (int)(key >> 48) - 32768; o.roll = roll; o.cell = ci; o.n_pixels = (int)g_cnt[l];
+    if (ci < 0) {
+        if (threadIdx.x == 0) out[l] = o;
+        return;
+    }
+    const int row = ci / W, col = ci - row * W;
+    const size_t HW = (size_t)H * W;
+    int zk = f2key(-10.0f);
+    for (int q = threadIdx.x; q < 72; q += 64) {
+        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
+        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
+            const float h = heights[(size_t)r * HW + (size_t)rr * W + cc];
+            if (-10.0f < h) zk = max(zk, f2key(h));
+        }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) zk = max(zk, __shfl_xor(zk, s, 64));
+    if (threadIdx.x == 0) {
+        o.rec.vote = ev16[(size_t)r * HW + (size_t)ci];
+        o.rec.row = (short)row; o.rec.col = (short)col;
+        o.rec.h_locmax = key2f(zk);
+        o.rec.n_evals = rec[r].n_evals;
+        out[l] = o;
+    }
+}
+
+void launch_label_records(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, const float *heights,
+                          const RollRecordDev *rec, int H, int W, float r_row, float r_col, int n_labels, const unsigned long long *g_key,
+                          const unsigned *g_cnt, LabelOutDev *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_label_records, dim3(n_labels), dim3(64), 0, s, f, geo, R, roll_first, ev16, heights, rec, H, W, r_row, r_col, g_key,
+                       g_cnt, out);
 }
 
 }  // namespace haf

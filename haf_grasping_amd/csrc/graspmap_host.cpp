@@ -1,5 +1,5 @@
-// graspmap_host.cpp -- the host definitions of record of the per-pixel grasp maps (include/hafgrasp.h): haf_point_cells and
-// haf_grasp_map_ref.  Neither touches a device or an engine: the roll transform is fill_roll_geo's (engine_geometry.cpp), the cell
+// graspmap_host.cpp -- the host definitions of record of the per-pixel grasp maps (include/hafgrasp.h): haf_point_cells,
+// haf_grasp_map_ref and haf_label_best_ref.  None touches a device or an engine: the roll transform is fill_roll_geo's (engine_geometry.cpp), the cell
 // arithmetic grasp_cells.h's and the pixel's point frame_points.h's, the sources the device kernel (graspmap.hip) is compiled from.
 // Built with -ffp-contract=off like every unit (build.py: FLAGS).
 #include "engine_state.h"
@@ -43,15 +43,11 @@ static int point_cells_impl(const haf_config *cfg, const haf_grasp_input *in, in
     return HAF_OK;
 }
 
-static int grasp_map_ref_impl(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
-                              const haf_frame *f, int16_t *vote, int16_t *roll, int32_t *cell)
+// haf_grasp_map_ref's per-pixel rule, written once: px(i, vote, roll, cell) for every pixel i = v * width + u of the host frame, in that order
+template <class Px>
+static int map_pixels(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                      const haf_frame *f, const Px &px)
 {
-    if (!check_grid(cfg) || !in || !f) return HAF_E_ARG;
-    if (roll_first < 0 || roll_count < 0 || (int64_t)roll_first + roll_count > cfg->n_rolls || (roll_count > 0 && !eval_grids)) return HAF_E_ARG;
-    std::string err;
-    const int rc = check_frame(*f, err);
-    if (rc != HAF_OK) return rc;
-    if (f->on_device != 0) return HAF_E_ARG;               // (host memory only: this function touches no device)
     std::vector<CellGeo> geo((size_t)std::max(1, roll_count));
     fill_cell_geo(*cfg, *in, roll_first, roll_count, geo.data());
     const int H = cfg->grid_h, W = cfg->grid_w;
@@ -85,12 +81,101 @@ static int grasp_map_ref_impl(const haf_config *cfg, const haf_grasp_input *in, 
                     if (best_roll < 0 || val > best) { best = val; best_roll = roll_first + r; best_cell = ci; }
                 }
             }
-            const size_t i = (size_t)v * (size_t)f->width + u;
-            if (vote) vote[i] = (int16_t)best;
-            if (roll) roll[i] = (int16_t)best_roll;
-            if (cell) cell[i] = best_cell;
+            px((size_t)v * (size_t)f->width + u, (int16_t)best, (int16_t)best_roll, (int32_t)best_cell);
         }
     }
+    return HAF_OK;
+}
+
+// what haf_grasp_map_ref and haf_label_best_ref refuse of their common arguments
+static int check_map_ref_args(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                              const haf_frame *f)
+{
+    if (!check_grid(cfg) || !in || !f) return HAF_E_ARG;
+    if (roll_first < 0 || roll_count < 0 || (int64_t)roll_first + roll_count > cfg->n_rolls || (roll_count > 0 && !eval_grids)) return HAF_E_ARG;
+    std::string err;
+    const int rc = check_frame(*f, err);
+    if (rc != HAF_OK) return rc;
+    if (f->on_device != 0) return HAF_E_ARG;               // (host memory only: this function touches no device)
+    return HAF_OK;
+}
+
+static int grasp_map_ref_impl(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                              const haf_frame *f, int16_t *vote, int16_t *roll, int32_t *cell)
+{
+    const int rc = check_map_ref_args(cfg, in, roll_first, roll_count, eval_grids, f);
+    if (rc != HAF_OK) return rc;
+    return map_pixels(cfg, in, roll_first, roll_count, eval_grids, f, [&](size_t i, int16_t bv, int16_t br, int32_t bc) {
+        if (vote) vote[i] = bv;
+        if (roll) roll[i] = br;
+        if (cell) cell[i] = bc;
+    });
+}
+
+int check_label_image(const haf_label_image *l, int32_t width, int32_t n_labels, const void *picks, std::string &err)
+{
+    if (!l || !l->data || !picks) { err = "null labels, label data or picks"; return HAF_E_ARG; }
+    if (l->elem_bytes != 1 && l->elem_bytes != 2) { err = "label elem_bytes must be 1 or 2"; return HAF_E_ARG; }
+    if (l->on_device != 0 && l->on_device != 1) { err = "label on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
+    const size_t eb = (size_t)l->elem_bytes;
+    if (l->row_stride_bytes < (size_t)std::max(0, width) * eb || l->row_stride_bytes % eb != 0) { err = "label row stride too small or misaligned"; return HAF_E_ARG; }
+    if (reinterpret_cast<uintptr_t>(l->data) % eb != 0) { err = "label data not aligned to its element"; return HAF_E_ARG; }
+    if (n_labels < 1 || n_labels > HAF_MAX_LABELS) { err = "n_labels outside 1..HAF_MAX_LABELS"; return HAF_E_ARG; }
+    return HAF_OK;
+}
+
+void label_pick_none(haf_label_pick *p)
+{
+    p->found = 0; p->u = p->v = p->roll = p->cell = -1; p->vote = HAF_MAP_NO_CELL; p->n_pixels = 0;
+}
+
+unsigned long long label_pick_key(const haf_label_pick &p, int32_t width)
+{
+    const unsigned i = (unsigned)((size_t)p.v * (size_t)width + (size_t)p.u);
+    return ((unsigned long long)(unsigned)(p.vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - p.roll) << 32) | (unsigned long long)(0xFFFFFFFFu - i);
+}
+
+void label_order(const haf_label_pick *picks, int32_t n_labels, int32_t width, int32_t *order, int32_t *n_found)
+{
+    std::vector<std::pair<unsigned long long, int32_t>> keys;
+    for (int32_t l = 0; l < n_labels; l++)
+        if (picks[l].found) keys.emplace_back(label_pick_key(picks[l], width), l + 1);
+    std::sort(keys.begin(), keys.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+    if (order)
+        for (size_t k = 0; k < keys.size(); k++) order[k] = keys[k].second;
+    if (n_found) *n_found = (int32_t)keys.size();
+}
+
+static int label_best_ref_impl(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                               const haf_frame *f, const haf_label_image *labels, int32_t n_labels, int32_t min_vote, haf_label_pick *picks,
+                               int32_t *order, int32_t *n_found)
+{
+    int rc = check_map_ref_args(cfg, in, roll_first, roll_count, eval_grids, f);
+    if (rc != HAF_OK) return rc;
+    std::string err;
+    if ((rc = check_label_image(labels, f->width, n_labels, picks, err)) != HAF_OK) return rc;
+    if (labels->on_device != 0) return HAF_E_ARG;           // (host memory only)
+    for (int32_t l = 0; l < n_labels; l++) label_pick_none(&picks[l]);
+    std::vector<unsigned long long> best((size_t)n_labels, 0ull);
+    const char *lbase = static_cast<const char *>(labels->data);
+    const size_t width = (size_t)f->width;
+    rc = map_pixels(cfg, in, roll_first, roll_count, eval_grids, f, [&](size_t i, int16_t bv, int16_t br, int32_t bc) {
+        const size_t v = i / width, u = i - v * width;
+        const char *at = lbase + v * labels->row_stride_bytes + u * (size_t)labels->elem_bytes;
+        unsigned lab;
+        if (labels->elem_bytes == 1) lab = *reinterpret_cast<const uint8_t *>(at);
+        else { uint16_t w; memcpy(&w, at, 2); lab = w; }
+        if (lab < 1u || lab > (unsigned)n_labels || br < 0 || (int)bv < min_vote || (int)bv <= HAF_MAP_NO_CELL) return;
+        haf_label_pick cand;
+        cand.found = 1; cand.u = (int32_t)u; cand.v = (int32_t)v; cand.vote = bv; cand.roll = br; cand.cell = bc;
+        haf_label_pick &p = picks[lab - 1];
+        cand.n_pixels = p.n_pixels + 1;
+        const unsigned long long key = label_pick_key(cand, f->width);
+        if (key > best[lab - 1]) { best[lab - 1] = key; p = cand; }
+        else p.n_pixels = cand.n_pixels;
+    });
+    if (rc != HAF_OK) return rc;
+    label_order(picks, n_labels, f->width, order, n_found);
     return HAF_OK;
 }
 
@@ -109,6 +194,15 @@ int haf_grasp_map_ref(const haf_config *cfg, const haf_grasp_input *in, int32_t 
                       const haf_frame *frame, int16_t *vote, int16_t *roll, int32_t *cell)
 {
     return guarded(nullptr, [&] { return grasp_map_ref_impl(cfg, in, roll_first, roll_count, eval_grids, frame, vote, roll, cell); });
+}
+
+int haf_label_best_ref(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                       const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, int32_t min_vote, haf_label_pick *picks,
+                       int32_t *order, int32_t *n_found)
+{
+    return guarded(nullptr, [&] {
+        return label_best_ref_impl(cfg, in, roll_first, roll_count, eval_grids, frame, labels, n_labels, min_vote, picks, order, n_found);
+    });
 }
 
 }  // extern "C"

@@ -501,6 +501,18 @@ void launch_map_best(const short *vote, const short *roll, const unsigned char *
 // the record of cell (row, col) of (cloud, roll) br of the last batch: its vote, the 9x8 z window of k_top_grasps, the roll's n_evals
 void launch_cell_record(const short *ev16, const float *heights, const RollRecordDev *rec, int br, int row, int col, int H, int W,
                         RollRecordDev *out, hipStream_t s);
+// haf_grasp_map_labels (graspmap.hip).  launch_map_labels: launch_grasp_map's arguments, the label image (label_bytes 1 or 2 per pixel, rows
+// label_stride bytes apart, device memory) and the global table -- n_labels 64-bit keys (launch_map_best's key) and n_labels counts, zeroed
+// by the caller: per label 1..n_labels the largest key and the number of its pixels that have a roll and a vote >= min_vote.  Dynamic LDS:
+// 12 bytes per label (n_labels <= HAF_MAX_LABELS).  launch_label_records: one wave per label -> out[l] = the haf_label_pick image of label
+// l + 1 and the record of its cell; ev16 / heights / rec: the request's first roll of the last batch
+struct LabelOutDev { int found, u, v, vote, roll, cell, n_pixels; RollRecordDev rec; };
+void launch_map_labels(const FrameDev &f, const haf_cell_math::CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row,
+                       float r_col, const void *labels, size_t label_stride, int label_bytes, int n_labels, int min_vote,
+                       unsigned long long *g_key, unsigned *g_cnt, hipStream_t s);
+void launch_label_records(const FrameDev &f, const haf_cell_math::CellGeo *geo, int R, int roll_first, const short *ev16, const float *heights,
+                          const RollRecordDev *rec, int H, int W, float r_row, float r_col, int n_labels, const unsigned long long *g_key,
+                          const unsigned *g_cnt, LabelOutDev *out, hipStream_t s);
 // haf_score_frames_roi (roi.hip; ROI forms in prestages.hip and vote.hip).  The ROI cell set S of a (request, roll) is a bit set of H rows
 // of roi_row_words(W) 64-bit words: cell (row, col) is bit (col & 63) of word (col >> 6) of its row
 __host__ __device__ inline int roi_row_words(int W) { return (W + 63) >> 6; }

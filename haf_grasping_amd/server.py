@@ -133,5 +133,26 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
                               c["approach_vector"], c["roll"]), u, v
 
+    def best_per_object(self, frame, labels, min_vote=1, n_labels=None):
+        """The best grasp of the last execute*() for every object of an instance-label image (uint8 / uint16 [height, width]: 0
+        background, 1.. the instances; e.g. a segmenter's output synchronised with the depth topic) in one device pass
+        (haf_grasp_map_labels) -> list of (label, GraspOutputMsg, u, v) for the objects that have a pixel with a vote >= min_vote,
+        best first: what best_in_mask(frame, labels == label) gives for each, ranked."""
+        res = self.engine.best_per_label(0, frame, labels, n_labels=n_labels, min_vote=min_vote)
+        out = []
+        for label in res["order"]:
+            c, p = res["poses"][label - 1], res["picks"][label - 1]
+            out.append((label, GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                                              c["approach_vector"], c["roll"]), int(p["u"]), int(p["v"])))
+        return out
+
+    def execute_frame_objects(self, goal: GraspInputMsg, frame, labels, min_vote=1):
+        """execute_frame() with roi_mask = (labels != 0), then best_per_object(): only the cells near the labelled pixels' cells are
+        scored, and every object gets its own best grasp -> (GraspOutputMsg of the request, best_per_object()'s list).  labels: a host
+        uint8 / uint16 [height, width] array."""
+        lab = np.asarray(labels)
+        res = self.execute_frame(goal, frame, roi_mask=(lab != 0).astype(np.uint8))
+        return res, self.best_per_object(frame, lab, min_vote=min_vote)
+
     def close(self):
         self.engine.close()

@@ -455,6 +455,48 @@ int  haf_cell_pose(haf_engine *e, int32_t request, int32_t roll, int32_t row, in
 int  haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, const uint8_t *mask, size_t mask_row_stride,
                         int32_t min_vote, haf_grasp_candidate *out, int32_t *u, int32_t *v, int32_t *found);
 
+/* ---- the best grasp per object from an instance-label image, in one device pass (csrc/graspmap.hip: k_map_labels) ---------------
+ * An instance segmenter's output is one label image: 0 for the background, 1..n_labels for the instances.  One call answers for all of
+ * them what haf_grasp_map_best answers for one mask.  A pixel QUALIFIES for label l when its label is l, haf_grasp_map gives it a roll
+ * (roll >= 0) and its vote is >= min_vote and above HAF_MAP_NO_CELL (haf_grasp_map_best's rule).  The pick of label l is the qualifying pixel that is best in haf_grasp_map_best's order --
+ * vote descending, then roll ascending, then v ascending, then u ascending: picks[l - 1] is what haf_grasp_map_best returns for the
+ * mask `labels == l`.  order[0 .. *n_found) lists the found labels, best pick first, in the same key order (pixel indices differ between
+ * labels: the order is total).
+ *
+ * haf_label_best_ref: the host definition of record, no device, no engine, on top of haf_grasp_map_ref's per-pixel rule.  The grids and
+ * the frame are those of haf_grasp_map_ref, the label image is a host image (on_device = 0).  order and n_found may be NULL.
+ * HAF_E_ARG: everything haf_grasp_map_ref refuses, a null labels, data or picks, elem_bytes not 1 or 2, on_device not 0, a stride too
+ * small or misaligned, misaligned uint16 data, n_labels outside 1..HAF_MAX_LABELS.  A refused call writes nothing.
+ *
+ * haf_grasp_map_labels: the same for request `request` of the LAST scored batch, on the device.  The frame may be host or device
+ * resident and of any kind; so may the label image, and a device-resident one is read where it lies, with its stride.  picks equals
+ * haf_label_best_ref on the request's haf_get_roll_grid grids in every field.  poses may be NULL; poses[l - 1] is haf_cell_pose(request,
+ * roll, cell / grid_w, cell % grid_w) of the pick, zeroed when the label is not found.  One device-to-host copy and one synchronisation
+ * whatever n_labels is.  Leaves all last-batch state as it was, like haf_grasp_map.  A request whose budget was negative finds nothing
+ * and returns HAF_OK.  Checked before any device work, the engine left as it was: everything haf_grasp_map refuses (an engine created
+ * with HAF_FLAG_PROBABILITY included), a null labels, data or picks, elem_bytes not 1 or 2, a stride too small or misaligned,
+ * misaligned uint16 data, on_device not 0 or 1, n_labels outside 1..HAF_MAX_LABELS.
+ *
+ * With haf_score_frames_roi: after a ROI request with the mask `labels != 0` every labelled pixel's cell lies in S_r, so V'_r = V_r
+ * there, and picks and order are those of the full request; the poses differ only in n_evals. */
+#define HAF_MAX_LABELS 4096
+typedef struct haf_label_image {   /* goes with a haf_frame of the same width x height */
+    const void *data;              /* 0 = background; 1..n_labels = instance; anything larger is ignored like background */
+    int32_t elem_bytes;            /* 1 (uint8) or 2 (uint16, host byte order) */
+    int32_t on_device;             /* 0 host, 1 device-resident (caller has synchronised its writer) */
+    size_t  row_stride_bytes;      /* >= width * elem_bytes, a multiple of elem_bytes; data aligned to elem_bytes */
+} haf_label_image;
+typedef struct haf_label_pick {    /* label l is entry l - 1 */
+    int32_t found;                 /* 0: no pixel of the label qualifies; then u = v = roll = cell = -1, vote = HAF_MAP_NO_CELL, n_pixels = 0 */
+    int32_t u, v, vote, roll, cell;/* the best pixel, and its haf_grasp_map values */
+    int32_t n_pixels;              /* pixels of the label that qualify */
+} haf_label_pick;
+int  haf_label_best_ref(const haf_config *cfg, const haf_grasp_input *in, int32_t roll_first, int32_t roll_count, const float *eval_grids,
+                        const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, int32_t min_vote, haf_label_pick *picks,
+                        int32_t *order, int32_t *n_found);
+int  haf_grasp_map_labels(haf_engine *e, int32_t request, const haf_frame *frame, const haf_label_image *labels, int32_t n_labels,
+                          int32_t min_vote, haf_label_pick *picks, haf_grasp_candidate *poses, int32_t *order, int32_t *n_found);
+
 /* ---- scoring only under a pixel mask: "grasp THIS object" without scoring the whole search area (csrc/roi.hip) ------------------
  * haf_score_frames with, per request, an image-space mask over its frame (a segmenter's output).  The cloud of request b is exactly
  * haf_score_frames' cloud of frames[b]: every pixel goes in, masked or not, because the height grids need the whole scene.  What the
@@ -487,7 +529,7 @@ typedef struct haf_roi {
 int  haf_roi_cells(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const haf_frame *frame, const uint8_t *mask,
                    size_t mask_row_stride, uint8_t *roi, uint8_t *eval);
 /* rois[b] goes with frames[b].  Afterwards the last-batch state is the ROI request's: haf_get_roll_grid returns V'_r and E_r, and
- * haf_top_grasps, haf_grasp_map, haf_cell_pose, haf_grasp_map_best, haf_debug_fetch*, haf_last_* and haf_get_stage_ms work on it
+ * haf_top_grasps, haf_grasp_map, haf_cell_pose, haf_grasp_map_best, haf_grasp_map_labels, haf_debug_fetch*, haf_last_* and haf_get_stage_ms work on it
  * unchanged (the ROI kernels count as HAF_ST_MASK).  A request never changes which form of the screening pass serves the engine
  * (haf_screen_form): the calls after it take the paths they would have taken without it.  Checked before any device work, a refused
  * call leaves the engine as it was, the message names the request -- HAF_E_ARG: everything haf_score_frames refuses, a null rois or

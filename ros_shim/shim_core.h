@@ -182,5 +182,30 @@ inline int top_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_t
     return HAF_OK;
 }
 
+// The best grasp per object of the engine's last scored goal from an instance-label image that goes with `frame` (haf_grasp_map_labels):
+// one line "<label> <u> <v> <hypothesis string>" per object that has a pixel with a vote >= min_vote, best first -- the next OBJECT for a
+// planner whose first choice fails, where top_hypotheses gives the next grasp.  An adapter with a label topic synchronised with the depth
+// topic would publish them after the goal's own result.  Returns the engine's status; on failure *err carries haf_last_error().
+inline int label_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_frame &frame, const haf_label_image &labels, int32_t n_labels,
+                            int32_t min_vote, std::vector<std::string> *lines, std::string *err)
+{
+    const size_t n = (size_t)(n_labels > 0 ? n_labels : 1);
+    std::vector<haf_label_pick> picks(n);
+    std::vector<haf_grasp_candidate> poses(n);
+    std::vector<int32_t> order(n, 0);
+    int32_t n_found = 0;
+    const int rc = haf_grasp_map_labels(engine, 0, &frame, &labels, n_labels, min_vote, picks.data(), poses.data(), order.data(), &n_found);
+    if (rc != HAF_OK) {
+        if (err) *err = haf_last_error(engine);
+        return rc;
+    }
+    for (int32_t k = 0; k < n_found; k++) {
+        const size_t l = (size_t)order[(size_t)k] - 1;
+        lines->push_back(std::to_string(order[(size_t)k]) + " " + std::to_string(picks[l].u) + " " + std::to_string(picks[l].v) + " " +
+                         hypothesis_string(poses[l].grasp, cfg.roll_step_deg));
+    }
+    return HAF_OK;
+}
+
 }  // namespace hafshim
 #endif  // HAF_SHIM_CORE_H_
