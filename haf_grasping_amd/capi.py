@@ -13,7 +13,7 @@ TESTLIB_PATH = os.environ.get("HAF_TESTLIB", os.path.join(HERE, "libhafgrasp_tes
 
 HAF_OK, HAF_E_ARG, HAF_E_IO, HAF_E_DEVICE, HAF_E_CAPACITY, HAF_E_BUDGET, HAF_E_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 FLAG_KEEP_DEBUG, FLAG_PROFILE, FLAG_FP32_MFMA, FLAG_SPLIT_F16, FLAG_PROBABILITY, FLAG_FULL_RANK = 1, 2, 4, 8, 16, 32
-DBG_HEIGHTS, DBG_INTEGRAL, DBG_MASK, DBG_LABELS, DBG_DECISION, DBG_TRANSFORM, DBG_SCREEN_MARGIN, DBG_PROBABILITY, DBG_GRASPSGRID = range(9)
+DBG_HEIGHTS, DBG_INTEGRAL, DBG_MASK, DBG_LABELS, DBG_DECISION, DBG_TRANSFORM, DBG_SCREEN_MARGIN, DBG_PROBABILITY, DBG_GRASPSGRID, DBG_ROI = range(10)
 SHARD_ROLLS, SHARD_CLOUDS = 0, 1
 FRAME_DEPTH_U16, FRAME_DEPTH_F32, FRAME_XYZ_F32 = 0, 1, 2
 MAP_NO_CELL = -32768                 # HAF_MAP_NO_CELL: a grasp-map pixel no roll has a cell for
@@ -72,7 +72,7 @@ class Frame(C.Structure):
 
 
 class Roi(C.Structure):
-    """haf_roi: the pixel mask of one request of haf_score_frames_roi"""
+    """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
 
 
@@ -177,6 +177,10 @@ def _bind(path, testing):
     L.haf_roi_cells.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_void_p,
                                 C.c_void_p]
     L.haf_score_frames_roi.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
+    L.haf_score_views_roi.argtypes = [E, C.c_int32, C.POINTER(C.c_int32), C.POINTER(Frame), C.POINTER(Roi), C.POINTER(GraspInput),
+                                      C.POINTER(GraspOutput), C.POINTER(C.c_int64)]
+    L.haf_roi_cells_views.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.c_int32,
+                                      C.c_void_p, C.c_void_p]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -531,6 +535,39 @@ def roi_cells(cfg, grasp_input, roll, frame, mask, want=("roi", "eval")):
     return out
 
 
+def _rois(frames, masks):
+    """per frame a host mask (uint8 [height, width]), a device mask ((device_ptr, row_stride_bytes)) or None -> (Roi array, keep-alive)"""
+    rois = (Roi * max(1, len(frames)))()
+    keep = []
+    for k, m in enumerate(masks):
+        if m is None:
+            rois[k] = Roi(None, 0, 0)
+        elif isinstance(m, tuple):
+            rois[k] = Roi(int(m[0]), int(m[1]), 1)
+        else:
+            kk, ptr, stride = _host_mask(m, frames[k])
+            keep.append(kk)
+            rois[k] = Roi(ptr, stride, 0)
+    return rois, keep
+
+
+def roi_cells_views(cfg, grasp_input, roll, frames, masks, want=("roi", "eval")):
+    """haf_roi_cells_views: the host definition of record of haf_score_views_roi's cell sets for roll `roll` (global index) -- roi: the
+    union over the views of the cells of their masked pixels' points, eval: its dilation by the vote's footprint -> dict of uint8
+    [grid_h, grid_w], only the grids named in `want`.  frames: host Frames; masks: per frame uint8 [height, width] or None."""
+    frames = list(frames)
+    if len(masks) != len(frames):
+        raise HafError(HAF_E_ARG, "roi_cells_views: one mask (or None) per frame")
+    arr = (Frame * max(1, len(frames)))(*frames)
+    rois, keep = _rois(frames, masks)
+    out = {k: np.empty((cfg.grid_h, cfg.grid_w), np.uint8) for k in want}
+    p = lambda k: out[k].ctypes.data if k in out else None
+    rc = lib().haf_roi_cells_views(C.byref(cfg), C.byref(grasp_input), roll, arr, rois, len(frames), p("roi"), p("eval"))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_roi_cells_views refused its arguments")
+    return out
+
+
 class Engine:
     """Owns one haf_engine handle (one GPU)."""
 
@@ -735,6 +772,26 @@ class Engine:
         self._last_points = [max(0, c) for c in counts]
         return [output_to_dict(o) for o in out[:n]], counts
 
+    def score_views_roi(self, view_sets, mask_sets, inputs):
+        """haf_score_views_roi: score_views with a pixel mask per view -- mask_sets[b][v] goes with view_sets[b][v]: uint8 [height, width]
+        (host; rows may be padded), (device_ptr, row_stride_bytes), or None for a view that contributes its points and selects nothing
+        -> (outputs, valid points per request)"""
+        n = len(view_sets)
+        flat = [f for vs in view_sets for f in vs]
+        masks = [m for ms in mask_sets for m in ms]
+        if [len(ms) for ms in mask_sets] != [len(vs) for vs in view_sets]:
+            raise HafError(HAF_E_ARG, "score_views_roi: one mask (or None) per view")
+        arr = (Frame * max(1, len(flat)))(*flat)
+        rois, keep = _rois(flat, masks)
+        per = (C.c_int32 * max(1, n))(*[len(vs) for vs in view_sets])
+        gi = (GraspInput * max(1, n))(*inputs)
+        out = (GraspOutput * max(1, n))()
+        cnt = (C.c_int64 * max(1, n))()
+        self._check(self._L.haf_score_views_roi(self._h, n, per, arr, rois, gi, out, cnt))
+        counts = [int(c) for c in cnt[:n]]
+        self._last_points = [max(0, c) for c in counts]
+        return [output_to_dict(o) for o in out[:n]], counts
+
     def fetch_points(self, cloud, n_points=None):
         """debug_points under the name of the C function: after score_views the request's fused cloud, its valid points in the order
         the device compacted them (unspecified; sort the rows to compare)"""
@@ -856,7 +913,7 @@ class Engine:
         shape, dt = {DBG_HEIGHTS: ((H, W), np.float32), DBG_INTEGRAL: ((H + 1, W + 1), np.float32),
                      DBG_MASK: ((H, W), np.uint8), DBG_LABELS: ((H, W), np.int8), DBG_DECISION: ((H, W), np.float64),
                      DBG_TRANSFORM: ((4, 4), np.float32), DBG_SCREEN_MARGIN: ((H, W), np.float32),
-                     DBG_PROBABILITY: ((H, W, 2), np.float64), DBG_GRASPSGRID: ((H, W), np.float32)}[what]
+                     DBG_PROBABILITY: ((H, W, 2), np.float64), DBG_GRASPSGRID: ((H, W), np.float32), DBG_ROI: ((H, W), np.uint8)}[what]
         a = np.zeros(shape, dt)
         self._check(self._L.haf_debug_fetch(self._h, what, cloud, roll, a.ctypes.data, a.nbytes))
         return a

@@ -32,6 +32,10 @@
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
 //                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
 //                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
+//   --view-roi-mask FILE.pgm          behind a --depth: the same kind of mask for the VIEW opened last, of as many views as there are; the
+//                                     fused request is scored only near the cells of the masked pixels of all masked views
+//                                     (haf_score_views_roi); a view without the option contributes its points and selects nothing.
+//                                     Not together with --roi-mask; --hypotheses, --top-k, --map-out and --labels work behind it
 //   --depth FILE.pgm --intrinsics fx fy cx cy   in place of the .pcd arguments: a 16-bit depth image (binary PGM) as the sensor
 //                                     delivers it, deprojected and transformed on the device (haf_score_frames); optional
 //                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
@@ -119,6 +123,7 @@ static void usage()
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
             "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
+            "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -145,9 +150,10 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 // device, and haf_top_grasps hands them back: with an in-roll radius of the whole grid and no cross-roll suppression its candidates
 // are exactly one per roll whose vote exceeds graspval_th, eval = vote - 20 (> 10, so the reference's clamp never acts).
 // Several --depth: the views of the one goal, fused on the device (haf_score_views); one --depth is haf_score_frames as ever.
-struct DepthView { std::string path; haf_frame frame; };
+struct DepthView { std::string path; haf_frame frame; std::string roi_path; };      // roi_path: --view-roi-mask of this view
 // --map-out / --mask: the goal's votes in the pixels of the FIRST view (haf_grasp_map, haf_grasp_map_best)
 // --roi-mask: the request itself is restricted to the cells near the masked pixels' cells (haf_score_frames_roi)
+// --view-roi-mask: the same for a fused request, a mask per view (haf_score_views_roi)
 // --labels: the best grasp per object of an instance-label image over the first view (haf_grasp_map_labels)
 struct MapOptions { std::string out_prefix, mask_path, roi_path, labels_path; int min_vote = 1; };
 
@@ -295,7 +301,24 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         }
     }
     const haf_roi roi = {roi_mask.data(), (size_t)frames[0].width, 0};
+    // --view-roi-mask: a mask per view, null for a view without one
+    std::vector<std::vector<uint8_t>> view_masks(views.size());
+    std::vector<haf_roi> view_rois(views.size(), haf_roi{nullptr, 0, 0});
+    bool view_roi = false;
+    for (size_t v = 0; v < views.size(); v++) {
+        if (views[v].roi_path.empty()) continue;
+        int w = 0, h = 0;
+        if (!read_pgm8(views[v].roi_path, view_masks[v], w, h)) { fprintf(stderr, "%s: not a binary 8-bit PGM\n", views[v].roi_path.c_str()); release(); return 1; }
+        if (w != frames[v].width || h != frames[v].height) {
+            fprintf(stderr, "%s: %d x %d, the depth image %s has %d x %d\n", views[v].roi_path.c_str(), w, h, views[v].path.c_str(), frames[v].width, frames[v].height);
+            release();
+            return 1;
+        }
+        view_rois[v] = haf_roi{view_masks[v].data(), (size_t)w, 0};
+        view_roi = true;
+    }
     if ((!mo.roi_path.empty() ? haf_score_frames_roi(eng, 1, frames.data(), &roi, &in, &out)
+         : view_roi ? haf_score_views_roi(eng, 1, &n_views, frames.data(), view_rois.data(), &in, &out, &n_points)
          : n_views == 1 ? haf_score_frames(eng, 1, frames.data(), &in, &out)
                         : haf_score_views(eng, 1, &n_views, frames.data(), &in, &out, &n_points)) != HAF_OK) {
         fprintf(stderr, "%s: %s\n", path.c_str(), haf_last_error(eng));
@@ -328,7 +351,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     else snprintf(size, sizeof size, "%lld pixels in %d views", pixels, n_views);
     fprintf(stderr, "%s: %s, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", path.c_str(), size,
             (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
-    if (n_views > 1) fprintf(stderr, "%d views fused: %lld valid points\n", n_views, (long long)n_points);
+    if (n_views > 1 || view_roi) fprintf(stderr, "%d views fused: %lld valid points\n", n_views, (long long)n_points);
     release();
     return rc;
 }
@@ -379,6 +402,7 @@ int main(int argc, char **argv)
         else if (a == "--map-out") { need(1); map_opt.out_prefix = argv[++i]; }
         else if (a == "--mask") { need(1); map_opt.mask_path = argv[++i]; }
         else if (a == "--roi-mask") { need(1); map_opt.roi_path = argv[++i]; }
+        else if (a == "--view-roi-mask") { need(1); if (views.empty()) { usage(); return 2; } views.back().roi_path = argv[++i]; }
         else if (a == "--labels") { need(1); map_opt.labels_path = argv[++i]; }
         else if (a == "--mask-min-vote") { need(1); map_opt.min_vote = atoi(argv[++i]); }
         else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
@@ -396,7 +420,7 @@ int main(int argc, char **argv)
     }
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
-        (!map_opt.roi_path.empty() && views.size() != 1) ||
+        (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);

@@ -506,6 +506,12 @@ int haf_score_frames_roi(haf_engine *e, int32_t n, const haf_frame *frames, cons
     return guarded(e ? &e->error : nullptr, [&] { return score_frames_roi_impl(e, n, frames, rois, in, out); });
 }
 
+int haf_score_views_roi(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_roi *rois,
+                        const haf_grasp_input *in, haf_grasp_output *out, int64_t *n_points)
+{
+    return guarded(e ? &e->error : nullptr, [&] { return score_views_roi_impl(e, n, views_per_request, frames, rois, in, out, n_points); });
+}
+
 int haf_score_views(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
                     haf_grasp_output *out, int64_t *n_points)
 {

@@ -48,6 +48,18 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             if (!need(HW)) break;
             HIPCHK(e, hipMemcpy(dst, e->d_labels.p + br * HW, HW, hipMemcpyDeviceToHost));
             return HAF_OK;
+        case HAF_DBG_ROI: {
+            // the ROI cell set of the (request, roll): the bit set the kernels read (roi.hip), one byte per cell
+            if (!e->last.roi) return fail(e, HAF_E_ARG, "haf_debug_fetch: HAF_DBG_ROI needs an ROI request as the last batch");
+            if (!need(HW)) break;
+            const size_t WP = (size_t)roi_row_words((int)W);
+            std::vector<unsigned long long> words(H * WP);
+            HIPCHK(e, hipMemcpy(words.data(), e->d_roi_cells.p + br * H * WP, words.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            uint8_t *g = (uint8_t *)dst;
+            for (size_t i = 0; i < H; i++)
+                for (size_t j = 0; j < W; j++) g[i * W + j] = (uint8_t)((words[i * WP + (j >> 6)] >> (j & 63)) & 1ull);
+            return HAF_OK;
+        }
         case HAF_DBG_TRANSFORM: {
             if (!need(16 * 4)) break;
             NormalisedInput n = normalise(e->last.inputs[(size_t)cloud]);

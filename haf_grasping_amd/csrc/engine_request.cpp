@@ -259,11 +259,13 @@ struct Request {
     int B = 0, R = 0, max_n = 0;
     long total_n = 0;
     bool bucket_ok = true;
-    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x n_frames])[points of the host clouds]
+    size_t pts_off = 0;                  // the points area of the input block: [CloudDev x B][RollGeo x B*R]([FrameDev x n_frames]([RoiViewDev x n_frames]))[points of the host clouds]
     FrameSource from;                    // (views: the host sizes everything by the UPPER bound clouds[b].n_points, the live count is CloudDev::n on the device)
     int n_frames = 0;                    // entries of frames / h_frames: B, or the sum of views
     FrameDev *h_frames = nullptr;
     const FrameDev *d_frames = nullptr;
+    RoiViewDev *h_roi_views = nullptr;   // views under masks (haf_score_views_roi): one per view, behind the FrameDev array
+    const RoiViewDev *d_roi_views = nullptr;
     std::vector<LastCall::CloudSrc> src; // where every cloud's points lie (LastCall::clouds)
     CloudDev *h_clouds = nullptr;
     const CloudDev *d_clouds = nullptr;
@@ -320,7 +322,13 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     const size_t frames_off = geo_off + up16((size_t)B * R * sizeof(RollGeo));
     q.n_frames = 0;
     for (int b = 0; frames && b < B; b++) q.n_frames += views ? views[b] : 1;
-    q.pts_off = frames_off + up16((size_t)q.n_frames * sizeof(FrameDev));
+    const size_t roi_off = frames_off + up16((size_t)q.n_frames * sizeof(FrameDev));
+    const bool roi_views = views && q.from.roi;
+    q.pts_off = roi_off + (roi_views ? up16((size_t)q.n_frames * sizeof(RoiViewDev)) : 0);
+    if (roi_views) {
+        q.h_roi_views = reinterpret_cast<RoiViewDev *>(e->in_block.host + roi_off);
+        q.d_roi_views = reinterpret_cast<const RoiViewDev *>(e->in_block.dev.p + roi_off);
+    }
     q.h_frames = reinterpret_cast<FrameDev *>(e->in_block.host + frames_off);
     q.d_frames = reinterpret_cast<const FrameDev *>(e->in_block.dev.p + frames_off);
     q.src.assign((size_t)B, LastCall::CloudSrc{});
@@ -366,6 +374,7 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
             (xyz ? raw_xyz : raw) += staged_bytes(f);
         }
     }
+    if (roi_views) roi_describe_views(e, *q.from.roi, frames, views, B, R, c.grid_h, c.grid_w, q.d_geo, q.h_roi_views);
 }
 
 // Host frames go to the device as upload_clouds sends host clouds, in pieces, the DMA engine moving one while the host packs the rows
@@ -489,7 +498,7 @@ static int run_prestages(haf_engine *e, Request &q)
     if (e->d_attr.p) HIPCHK(e, hipMemsetAsync(e->d_attr.p, 0xFF, e->d_attr.n * sizeof(AttrRecord), s));   // debug: "not computed"
     mark(e, HAF_ST_BIN);
     // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
-    // (an ROI request takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
+    // (an ROI request, of frames or of views, takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
     if (!e->prob_mode && !e->no_fused_pre && !q.from.roi)
         q.fused_pre = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
                                        e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
@@ -511,7 +520,8 @@ static int run_prestages(haf_engine *e, Request &q)
     launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
     mark(e, HAF_ST_MASK);
     if (q.from.roi) {
-        const int rc = roi_mark_cells(e, *q.from.roi, q.from.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s);
+        const RoiViews rv{q.d_frames, q.h_frames, q.d_roi_views, q.h_roi_views, q.n_frames};
+        const int rc = roi_mark_cells(e, *q.from.roi, q.from.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s, q.from.views ? &rv : nullptr);
         if (rc != HAF_OK) return rc;
         launch_mask_count_roi(e->d_ii.p, q.d_geo, e->d_roi_cells.p, e->d_mask.p, e->d_rowcount.p, d, s);
     } else {
@@ -881,6 +891,7 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
     l.i8 = q.i8_used;
     l.inputs.assign(in, in + q.B);
     l.clouds = q.src;
+    l.roi = q.from.roi != nullptr;
     for (int b = 0; q.from.views && b < q.B; b++) l.clouds[(size_t)b].n = (size_t)q.h_clouds[b].n;      // (upload_frames: the live counts)
     // zero the counters for the next request now, behind this one's copy-out: off that request's critical path
     if (hipMemsetAsync(e->d_counters.p, 0, CNT_COUNT * sizeof(int), q.s) == hipSuccess) e->counters_clean = true;
@@ -910,7 +921,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     q.s = e->stream;
     mark(e, 0);
     if ((rc = q.from.frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
-    if (roi && (rc = roi_upload_masks(e, *roi, q.from.frames, q.B, q.s)) != HAF_OK) return rc;
+    if (roi && (rc = roi_upload_masks(e, *roi, q.from.frames, q.n_frames, q.s)) != HAF_OK) return rc;
     classify_request(e, in, q);
     if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
     int mode = contraction_mode(e->cfg);
@@ -980,6 +991,18 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
     return score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
 }
 
+// the raw area of staged host XYZ views (12 bytes x max_points, every view at a multiple of 16 bytes) and its pinned twin: an engine
+// that never sees such a view never pays for them
+int ensure_raw_xyz(haf_engine *e, const std::string &who)
+{
+    if (e->raw_xyz.host) return HAF_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const hipError_t rc = e->raw_xyz.ensure((size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16);
+    if (e->raw_xyz.pinned_failed) return fail(e, HAF_E_DEVICE, who + ": no pinned memory for the raw area of host XYZ views");
+    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, who + ": no device memory for the raw area of host XYZ views: " + hipGetErrorString(rc));
+    return HAF_OK;
+}
+
 // haf_score_views: every refusal before any device work, then the batch path with the views of request b as the source of cloud b's
 // points.  clouds[b].n_points is the UPPER bound, the pixels of the request's views: it sizes the request's region, sorted_off, max_n,
 // total_n and every launch grid; the kernels stop at the live count on the device
@@ -995,14 +1018,8 @@ int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request,
     const FrameBatch chk = check_frame_batch(frames, n, views_per_request, e->cfg.max_points);
     if (chk.code != HAF_OK && chk.text.empty()) return fail(e, chk.code, "haf_score_views: more pixels than max_points");
     if (chk.code != HAF_OK) return fail(e, chk.code, "haf_score_views: request " + std::to_string(chk.request) + " view " + std::to_string(chk.view) + ": " + chk.text);
-    if (chk.host_xyz && !e->raw_xyz.host) {
-        // the raw area of staged host XYZ views (12 bytes x max_points, every view at a multiple of 16 bytes) and its pinned twin: an
-        // engine that never sees such a view never pays for them
-        HIPCHK(e, hipSetDevice(e->cfg.device));
-        const hipError_t rc = e->raw_xyz.ensure((size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16);
-        if (e->raw_xyz.pinned_failed) return fail(e, HAF_E_DEVICE, "haf_score_views: no pinned memory for the raw area of host XYZ views");
-        if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, std::string("haf_score_views: no device memory for the raw area of host XYZ views: ") + hipGetErrorString(rc));
-    }
+    int rc0 = HAF_OK;
+    if (chk.host_xyz && (rc0 = ensure_raw_xyz(e, "haf_score_views")) != HAF_OK) return rc0;
     const FrameSource from{frames, views_per_request, nullptr};
     const int rc = score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
     if (rc != HAF_OK) return rc;

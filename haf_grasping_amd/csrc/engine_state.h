@@ -6,7 +6,7 @@
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
 //   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
-//   engine_roi.cpp       haf_score_frames_roi: the checks, the ROI buffers, the masks' upload and the launch of k_roi_mark
+//   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
@@ -170,20 +170,24 @@ struct LastCall {
     // point count; staged = false for a device-resident xyz cloud, which lies in the caller's memory
     struct CloudSrc { size_t float_off = 0; size_t n = 0; bool staged = false; };
     std::vector<CloudSrc> clouds;
+    bool roi = false;            // the batch was an ROI request: d_roi_cells holds its B x R cell sets (HAF_DBG_ROI)
 };
 
-// haf_score_frames_roi: what the request path (engine_request.cpp) needs of the call, filled by engine_roi.cpp
+// haf_score_frames_roi / haf_score_views_roi: what the request path (engine_request.cpp) needs of the call, filled by engine_roi.cpp.
+// Per VIEW, by the flat view index (haf_score_frames_roi: one view per request); a view of haf_score_views_roi may have no mask
 struct RoiCall {
-    const haf_roi *rois = nullptr;       // rois[b] goes with frame b
-    std::vector<long> masked;            // per request: the non-zero bytes of a host mask, -1 for a device-resident mask
-    std::vector<size_t> off;             // per request: where a host mask lies in roi_mask (packed rows, 16-byte aligned)
+    const haf_roi *rois = nullptr;       // rois[k] goes with frame k
+    std::vector<long> masked;            // per REQUEST: the non-zero bytes of its host masks, -1 when any of its masks is device-resident
+    std::vector<size_t> off;             // per view: where a host mask lies in roi_mask (packed rows, 16-byte aligned)
+    // a view's mask goes through the staging area (roi_mask): it has one and it lies in host memory
+    static bool staged(const haf_roi &r) { return r.mask != nullptr && r.on_device != 1; }
 };
 
 // Where a request's points come from when not from the caller's clouds (the request path takes a pointer, null for clouds)
 struct FrameSource {
     const haf_frame *frames = nullptr;   // cloud b's points are frame b's, deprojected on the device; clouds[b] only carries its point count
     const int32_t *views = nullptr;      // ... are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count
-    const RoiCall *roi = nullptr;        // haf_score_frames_roi (no views): only the cells near the masked pixels' cells are evaluated
+    const RoiCall *roi = nullptr;        // haf_score_frames_roi, haf_score_views_roi (with views): only the cells near the masked pixels' cells are evaluated
 };
 
 }  // namespace haf_host
@@ -256,7 +260,7 @@ struct haf_engine {
     // host-to-device copy carries everything (a small request is bound by the number of stream operations); the
     // pinned half has the same layout
     StageBuf in_block;
-    size_t in_hdr_cap = 0;          // bytes reserved for the header arrays (CloudDev, RollGeo, FrameDev)
+    size_t in_hdr_cap = 0;          // bytes reserved for the header arrays (CloudDev, RollGeo, FrameDev, RoiViewDev)
     // haf_score_frames: the raw pixels of host depth frames, 2 or 4 bytes each, go through their own pinned block and device area
     // (raw: 4 bytes x max_points, every frame at a multiple of 16 bytes); k_frame_points writes their points into the points area of in_block.
     // Never converted inside the points area itself: a point's 12-byte slot overlaps raw pixels other lanes have not read yet
@@ -378,8 +382,8 @@ struct haf_engine {
     // [label table: keys, counts][label output entries] and its pinned host copy
     StageBuf map;
     // haf_score_frames_roi (engine_roi.cpp), allocated on its first call: the ROI cell sets -- one bit per cell, max_clouds x max_rolls
-    // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes, every mask at a
-    // multiple of 16 bytes) with its pinned twin
+    // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes and 16 bytes of slack
+    // per view, every mask at a multiple of 16 bytes) with its pinned twin.  haf_score_views_roi shares both
     DevBuf<unsigned long long> d_roi_cells;
     StageBuf roi_mask;
 };
@@ -521,13 +525,27 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
 // (clouds[b].n_points is the UPPER bound there, the pixels of the request's views)
 int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
                      haf_grasp_output *out, int64_t *n_points);
+// the raw area of staged host XYZ views, on the first call that has one (`who`: the calling function, for the message)
+int ensure_raw_xyz(haf_engine *e, const std::string &who);
 // engine_roi.cpp
 int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in, haf_grasp_output *out);
-// the staged host masks of the call to the device (no synchronisation)
-int roi_upload_masks(haf_engine *e, const RoiCall &roi, const haf_frame *frames, int B, hipStream_t s);
-// clears the B * R ROI cell sets and marks them: k_roi_mark per request, on the points k_frame_points left at h_clouds[b].xyz
+int score_views_roi_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_roi *rois,
+                         const haf_grasp_input *in, haf_grasp_output *out, int64_t *n_points);
+// the staged host masks of the call's n_views views to the device (no synchronisation)
+int roi_upload_masks(haf_engine *e, const RoiCall &roi, const haf_frame *frames, int n_views, hipStream_t s);
+// haf_score_views_roi: the descriptors of the call's views (views[b] per request) for k_roi_mark_view, into the request's header block
+void roi_describe_views(const haf_engine *e, const RoiCall &roi, const haf_frame *frames, const int32_t *views, int B, int R, int H, int W,
+                        const RollGeo *d_geo, RoiViewDev *out);
+// What roi_mark_cells needs of a request with views: its FrameDev and RoiViewDev arrays, device and pinned (null: haf_score_frames_roi)
+struct RoiViews {
+    const FrameDev *d_frames = nullptr, *h_frames = nullptr;
+    const RoiViewDev *d_roi = nullptr, *h_roi = nullptr;
+    int n_views = 0;
+};
+// clears the B * R ROI cell sets and marks them: k_roi_mark per request, on the points k_frame_points left at h_clouds[b].xyz; with
+// views, k_roi_mark_view over every view of the batch, on the raw pixels k_view_points read
 int roi_mark_cells(haf_engine *e, const RoiCall &roi, const haf_frame *frames, const CloudDev *h_clouds, const RollGeo *d_geo, const Dims &d,
-                   float r_row, float r_col, hipStream_t s);
+                   float r_row, float r_col, hipStream_t s, const RoiViews *views = nullptr);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

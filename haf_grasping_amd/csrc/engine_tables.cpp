@@ -1114,7 +1114,7 @@ int alloc_buffers(haf_engine *e)
     // and their window-by-window consumers rely on exactly that (a counter never exceeds the list).
     if (const char *v = test_env("HAF_FLAG0_CAP")) e->flag0_cap = mode == MODE_SCREEN ? (int)std::min<long>(e->list_cap, std::max(256, atoi(v) / 256 * 256)) : 0;
     bool ok = true;
-    e->in_hdr_cap = up16(B * sizeof(CloudDev)) + up16(B * R * sizeof(RollGeo)) + up16(B * HAF_MAX_VIEWS * sizeof(FrameDev));     // (haf_score_views: up to HAF_MAX_VIEWS descriptors per request)
+    e->in_hdr_cap = up16(B * sizeof(CloudDev)) + up16(B * R * sizeof(RollGeo)) + up16(B * HAF_MAX_VIEWS * sizeof(FrameDev)) + up16(B * HAF_MAX_VIEWS * sizeof(RoiViewDev));     // (haf_score_views: up to HAF_MAX_VIEWS descriptors per request)
     // (+ 48 bytes per cloud: the points of a frame start at a multiple of four points, pack_headers)
     ok &= hipSuccess == e->in_block.ensure(e->in_hdr_cap + (size_t)c.max_points * 3 * sizeof(float) + B * 48);
     ok &= hipSuccess == e->raw.ensure((size_t)c.max_points * 4 + B * HAF_MAX_VIEWS * 16);

@@ -520,6 +520,17 @@ __host__ __device__ inline int roi_row_words(int W) { return (W + 63) >> 6; }
 // packed, pixel order: what k_frame_points wrote) is finite, under the R rolls of geo, OR-ed into S (R grids, zeroed by the caller)
 void launch_roi_mark(const unsigned char *mask, size_t mask_stride, int width, int n, const float *xyz, const RollGeo *geo, int R,
                      unsigned long long *S, int H, int W, float r_row, float r_col, hipStream_t s);
+// haf_score_views_roi: per VIEW of the batch, next to its FrameDev: its mask (device memory; null: the view selects nothing), the bytes
+// between the mask's rows, and its request's first ROI grid and first RollGeo.  One launch per frame kind present marks every view of the
+// batch: the masked pixels are deprojected again from the views' raw pixels (the compacted points have no pixel index)
+struct RoiViewDev {
+    const unsigned char *mask;
+    unsigned long long stride;
+    unsigned long long *S;
+    const RollGeo *geo;
+};
+void launch_roi_mark_views(const FrameDev *views_dev, const FrameDev *views_host, const RoiViewDev *roi_dev, const RoiViewDev *roi_host,
+                           int n_views, int R, int H, int W, float r_row, float r_col, hipStream_t s);
 // launch_mask_count with m = cell_in_box && any(S at c + T), T = the 29 taps of the vote; S: B * R grids
 void launch_mask_count_roi(const float *ii, const RollGeo *geo, const unsigned long long *S, uint8_t *mask, int *rowcount, Dims d, hipStream_t s);
 // launch_vote with v = 0 outside S, before the argmax key, the row maxima and the store

@@ -95,14 +95,20 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
-    def execute_views(self, goal: GraspInputMsg, frames) -> GraspOutputMsg:
+    def execute_views(self, goal: GraspInputMsg, frames, roi_masks=None) -> GraspOutputMsg:
         """execute_frame() for a goal seen by several sensors, or by one sensor from several poses: `frames` is a list of up to
         capi.MAX_VIEWS capi.depth_frame / capi.xyz_frame, each with its own intrinsics and sensor-to-base transform.  The engine fuses
         the valid points of all of them into one cloud on the device (haf_score_views); the result is execute()'s on
-        capi.view_points(frames)."""
+        capi.view_points(frames).
+        roi_masks: one entry per frame -- a mask as execute_frame() takes it, or None for a camera without a segmenter: every view
+        still builds the scene, but only the cells near the cells of the masked pixels of the masked views are scored
+        (haf_score_views_roi), and what follows answers for the restricted request."""
         if goal.goal_frame_id:
             self.base_frame_id = goal.goal_frame_id
-        out = self.engine.score_views([list(frames)], [goal.to_c()])[0][0]
+        if roi_masks is not None:
+            out = self.engine.score_views_roi([list(frames)], [list(roi_masks)], [goal.to_c()])[0][0]
+        else:
+            out = self.engine.score_views([list(frames)], [goal.to_c()])[0][0]
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 

@@ -257,7 +257,9 @@ enum { HAF_DBG_HEIGHTS = 0, HAF_DBG_INTEGRAL = 1, HAF_DBG_MASK = 2, HAF_DBG_LABE
                                         (> 1 by construction), 0 for the cells it handed on, NaN elsewhere */
        HAF_DBG_PROBABILITY = 7,      /* HAF_FLAG_PROBABILITY: H*W*2 f64, the two probabilities of the cell's own output line as
                                         atof reads them ("%g" text), NaN unmasked */
-       HAF_DBG_GRASPSGRID = 8 };     /* HAF_FLAG_PROBABILITY: H*W f32, the grid show_predicted_gps builds (831-841) */
+       HAF_DBG_GRASPSGRID = 8,       /* HAF_FLAG_PROBABILITY: H*W f32, the grid show_predicted_gps builds (831-841) */
+       HAF_DBG_ROI = 9 };            /* H*W u8, 0 / 1: the ROI cells S_r of the last batch as the device marked them; HAF_E_ARG when that
+                                        batch was not haf_score_frames_roi's or haf_score_views_roi's */
 int haf_debug_fetch(haf_engine *e, int32_t what, int32_t cloud, int32_t roll, void *dst, size_t dst_bytes);
 
 /* The attribute pipeline of the masked cells of one (cloud, roll) of the last scored batch, as the exact-form feature
@@ -535,9 +537,37 @@ int  haf_roi_cells(const haf_config *cfg, const haf_grasp_input *in, int32_t rol
  * call leaves the engine as it was, the message names the request -- HAF_E_ARG: everything haf_score_frames refuses, a null rois or
  * mask, on_device not 0 or 1, a row stride smaller than the width, an engine created with HAF_FLAG_PROBABILITY; HAF_E_CAPACITY as
  * haf_score_frames.  The first call allocates the ROI cell sets (one bit per cell of max_clouds x max_rolls_per_call grids) and the
- * area of uploaded host masks (max_points bytes).  Not through haf_score_views, haf_score_rolls or the sharded multi-GPU calls. */
+ * area of uploaded host masks (max_points bytes).  Fused views take masks through haf_score_views_roi, below.  Not through
+ * haf_score_rolls or the sharded multi-GPU calls. */
 int  haf_score_frames_roi(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in,
                           haf_grasp_output *out);
+/* ---- fused views under per-view masks (csrc/roi.hip: k_roi_mark_view) -------------------------------------------------------
+ * haf_score_views with a mask per VIEW: the fused scene of two cameras, evaluated only near one object.  rois[i] goes with frames[i],
+ * the flat view index of haf_score_views.  A view whose rois[i].mask is NULL contributes its points and selects nothing (a camera
+ * without a segmenter); its on_device and row_stride_bytes are ignored.
+ *   cloud             of request b: exactly haf_score_views' cloud, every valid point of every view, masked or not;
+ *   ROI cells S_r     the UNION over the request's views of the cells haf_point_cells gives the haf_frame_points points of that view's
+ *                     masked pixels whose point is finite in all three components;
+ *   E_r, V'_r, the record of roll r, n_evals and the output follow from S_r word for word as above, V being the vote of the full
+ *                     haf_score_views request on the same views.
+ * This is NOT haf_score_frames_roi on one of the cameras: the height grids are the fused scene's, so labels and votes differ wherever
+ * the second camera fills what the first one does not see.  n_points as in haf_score_views.  A request whose S_r is empty in every roll
+ * (every mask NULL, zero, or over invalid pixels only) returns "nothing found" (eval = -20, n_evals = 0) and HAF_OK.  Afterwards the
+ * last-batch state is the restricted request's for every call that reads it, as after haf_score_frames_roi, and the call never
+ * re-chooses the form of the screening pass.  One kernel launch per frame kind present in the batch marks the cells of all its views.
+ * Checked before any device work, a refused call leaves the engine as it was, the message names the request and the view; view after
+ * view, a view's frame before its mask: everything haf_score_views refuses; HAF_E_ARG: a null rois, an engine created with
+ * HAF_FLAG_PROBABILITY, for a non-null mask an on_device that is not 0 or 1 or a row stride smaller than the width.  Shares the ROI
+ * buffers of haf_score_frames_roi (the masks' area: max_points bytes and 16 per view).
+ *
+ * haf_roi_cells_views: the host definition of record, no device, no engine.  roi = the OR of haf_roi_cells over the views that have a
+ * mask, eval = its T-dilation; either may be NULL; all zero when no view has a mask.  Host frames and host masks only.  Refusals per
+ * view as haf_roi_cells (a NULL mask is no refusal here), plus a null frames or rois and n_views outside 1..HAF_MAX_VIEWS; every view is
+ * checked before anything is written. */
+int  haf_score_views_roi(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_roi *rois,
+                         const haf_grasp_input *in, haf_grasp_output *out, int64_t *n_points);
+int  haf_roi_cells_views(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const haf_frame *frames, const haf_roi *rois,
+                         int32_t n_views, uint8_t *roi, uint8_t *eval);
 
 int haf_abi_version(void);
 
