@@ -71,6 +71,11 @@ class Frame(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("sensor_to_base", C.c_float * 12)]
 
 
+class DepthFilter(C.Structure):
+    """haf_depth_filter: the parameters of haf_filter_depth"""
+    _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("tol_abs", C.c_float), ("tol_rel", C.c_float), ("min_valid", C.c_int32)]
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -181,6 +186,11 @@ def _bind(path, testing):
                                       C.POINTER(GraspOutput), C.POINTER(C.c_int64)]
     L.haf_roi_cells_views.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.c_int32,
                                       C.c_void_p, C.c_void_p]
+    L.haf_depth_filter_default.argtypes = [C.POINTER(DepthFilter)]
+    L.haf_depth_filter_default.restype = None
+    L.haf_filter_depth_ref.argtypes = [C.POINTER(Frame), C.c_int32, C.POINTER(DepthFilter), C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
+    L.haf_filter_depth.argtypes = [E, C.POINTER(Frame), C.c_int32, C.POINTER(DepthFilter), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Frame),
+                                   C.POINTER(C.c_int64)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -421,6 +431,43 @@ def frame_points(frame):
 
 
 MAX_VIEWS = 16
+MAX_STACK = 8                        # HAF_MAX_STACK: exposures of one haf_filter_depth call
+
+
+def depth_filter(**kw):
+    """haf_depth_filter with the library's defaults (radius 2, min_support 6, tol_abs 0.004, tol_rel 0.01, min_valid 1) and `kw` over them"""
+    p = DepthFilter()
+    lib().haf_depth_filter_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_depth_filter field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _filter_image(frame, out):
+    """the host output image of a filter call for exposures like `frame`: `out` (uint16 / float32 [height, width], rows may be padded) or a
+    new packed one -> (array, pointer, row stride)"""
+    dt = np.uint16 if frame.kind == FRAME_DEPTH_U16 else np.float32
+    if out is None or out is True:
+        out = np.empty((max(0, frame.height), max(0, frame.width)), dt)
+    assert out.ndim == 2 and out.dtype == dt and out.shape == (frame.height, frame.width) and out.strides[1] == out.itemsize
+    return out, out.ctypes.data, out.strides[0] if frame.height > 1 else frame.width * out.itemsize
+
+
+def filter_depth_ref(frames, params=None, out=None):
+    """haf_filter_depth_ref: the host definition of record of the depth filter on `frames` (1..8 host Frames, exposures of one depth
+    camera) -> (image: uint16 / float32 [height, width], stats: [pixels, valid after the temporal stage, kept]).  out: the array to
+    write into (rows may be padded: a view into a wider array)."""
+    L, n = lib(), len(frames)
+    arr = (Frame * max(1, n))(*frames)
+    p = params if params is not None else depth_filter()
+    img, ptr, stride = _filter_image(arr[0], out)
+    stats = (C.c_int64 * 3)()
+    rc = L.haf_filter_depth_ref(arr, n, C.byref(p), ptr, stride, stats)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_filter_depth_ref refused its arguments")
+    return img, [int(x) for x in stats]
 
 
 def view_points(frames):
@@ -857,6 +904,32 @@ class Engine:
         ptr = lambda k: out[k].ctypes.data if k in out else None
         self._check(self._L.haf_grasp_map(self._h, request, C.byref(frame), ptr("vote"), ptr("roll"), ptr("cell"), 0))
         return out
+
+    def filter_depth(self, frames, params=None, device_out=None, host_out=None):
+        """haf_filter_depth: 1..8 exposures of one depth camera (Frames, host or device-resident) -> (frame, stats): one conditioned depth
+        image as a Frame of the exposures' kind and parameters, ready for score_frames, score_views, their _roi forms and the grasp maps,
+        and [pixels, valid after the temporal stage, kept].  Without an output argument the frame is the engine's own device image, valid
+        until the next filter_depth or close().  device_out: a device pointer, or (pointer, row_stride_bytes), of the caller's image (as
+        grasp_map's: written there; the caller keeps it alive).  host_out: True for a new numpy image, or the array to write into (rows
+        may be padded); the frame then keeps it alive and frame.image is the array."""
+        n = len(frames)
+        arr = (Frame * max(1, n))(*frames)
+        p = params if params is not None else depth_filter()
+        got, stats = Frame(), (C.c_int64 * 3)()
+        keep = None
+        if host_out is not None and host_out is not False:
+            keep, ptr, stride = _filter_image(arr[0], host_out)
+            rc = self._L.haf_filter_depth(self._h, arr, n, C.byref(p), ptr, stride, 0, C.byref(got), stats)
+        elif device_out is not None:
+            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
+            stride = stride or arr[0].width * (2 if arr[0].kind == FRAME_DEPTH_U16 else 4)
+            rc = self._L.haf_filter_depth(self._h, arr, n, C.byref(p), int(ptr), stride, 1, C.byref(got), stats)
+        else:
+            rc = self._L.haf_filter_depth(self._h, arr, n, C.byref(p), None, 0, 1, C.byref(got), stats)
+        self._check(rc)
+        got._keep = keep
+        got.image = keep
+        return got, [int(x) for x in stats]
 
     def cell_pose(self, request, roll, row, col):
         """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""

@@ -36,6 +36,12 @@
 //                                     fused request is scored only near the cells of the masked pixels of all masked views
 //                                     (haf_score_views_roi); a view without the option contributes its points and selects nothing.
 //                                     Not together with --roi-mask; --hypotheses, --top-k, --map-out and --labels work behind it
+//   --stack FILE.pgm                  behind a --depth: a further exposure of that view (same camera, same pose, same size), up to
+//                                     HAF_MAX_STACK per view; read only with --depth-filter
+//   --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID]   ("default": 2,6,0.004,0.01,1) every view's exposures go through
+//                                     haf_filter_depth -- per pixel the lower median of the valid samples, then the spatial support
+//                                     test -- and the filtered image is scored in the view's place; --filtered-out FILE.pgm writes
+//                                     the first view's filtered image as a 16-bit PGM.  Without --depth-filter nothing changes
 //   --depth FILE.pgm --intrinsics fx fy cx cy   in place of the .pcd arguments: a 16-bit depth image (binary PGM) as the sensor
 //                                     delivers it, deprojected and transformed on the device (haf_score_frames); optional
 //                                     --depth-scale S (metres per unit, default 0.001), --depth-range MIN MAX (metres, 0 = no limit),
@@ -123,6 +129,8 @@ static void usage()
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
             "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
+            "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
+            "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
@@ -150,12 +158,53 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
 // device, and haf_top_grasps hands them back: with an in-roll radius of the whole grid and no cross-roll suppression its candidates
 // are exactly one per roll whose vote exceeds graspval_th, eval = vote - 20 (> 10, so the reference's clamp never acts).
 // Several --depth: the views of the one goal, fused on the device (haf_score_views); one --depth is haf_score_frames as ever.
-struct DepthView { std::string path; haf_frame frame; std::string roi_path; };      // roi_path: --view-roi-mask of this view
+struct DepthView { std::string path; haf_frame frame; std::string roi_path; std::vector<std::string> stack; };      // roi_path: --view-roi-mask of this view; stack: its --stack exposures
 // --map-out / --mask: the goal's votes in the pixels of the FIRST view (haf_grasp_map, haf_grasp_map_best)
 // --roi-mask: the request itself is restricted to the cells near the masked pixels' cells (haf_score_frames_roi)
 // --view-roi-mask: the same for a fused request, a mask per view (haf_score_views_roi)
 // --labels: the best grasp per object of an instance-label image over the first view (haf_grasp_map_labels)
-struct MapOptions { std::string out_prefix, mask_path, roi_path, labels_path; int min_vote = 1; };
+// --depth-filter: every view's exposures (its --depth and its --stack files) through haf_filter_depth before the view is scored;
+// --filtered-out: the filtered image of the first view
+struct MapOptions {
+    std::string out_prefix, mask_path, roi_path, labels_path;
+    int min_vote = 1;
+    bool filter = false;
+    haf_depth_filter filter_params;
+    std::string filtered_out;
+};
+
+// --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] or "default"
+static bool parse_depth_filter(const char *arg, haf_depth_filter *p)
+{
+    haf_depth_filter_default(p);
+    if (strcmp(arg, "default") == 0) return true;
+    int radius = 0, support = 0, min_valid = 1;
+    float tol_abs = 0, tol_rel = 0;
+    char tail = 0;
+    const int n = sscanf(arg, "%d,%d,%f,%f,%d%c", &radius, &support, &tol_abs, &tol_rel, &min_valid, &tail);
+    if (n != 4 && n != 5) return false;
+    p->radius = radius; p->min_support = support; p->tol_abs = tol_abs; p->tol_rel = tol_rel; p->min_valid = n == 5 ? min_valid : 1;
+    return true;
+}
+
+// a depth image as a 16-bit binary PGM, samples as they are
+static bool write_depth_pgm16(const std::string &path, const uint16_t *img, int w, int h)
+{
+    FILE *fp = fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    fprintf(fp, "P5\n%d %d\n65535\n", w, h);
+    std::vector<unsigned char> row((size_t)w * 2);
+    bool ok = true;
+    for (int v = 0; v < h && ok; v++) {
+        for (int u = 0; u < w; u++) {
+            const unsigned x = img[(size_t)v * w + u];
+            row[2 * (size_t)u] = (unsigned char)(x >> 8);
+            row[2 * (size_t)u + 1] = (unsigned char)(x & 255u);
+        }
+        ok = fwrite(row.data(), 1, row.size(), fp) == row.size();
+    }
+    return fclose(fp) == 0 && ok;
+}
 
 static bool write_pgm16(const std::string &path, const int16_t *img, int w, int h)
 {
@@ -279,6 +328,42 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         f.data = depth;
         f.row_stride_bytes = (size_t)f.width * 2;
         frames.push_back(f);
+    }
+    // --depth-filter: the exposures of every view -> one image that takes the view's place (haf_filter_depth, into host memory: every
+    // view keeps its own image until the request is scored)
+    for (size_t v = 0; mo.filter && v < views.size(); v++) {
+        std::vector<uint16_t *> extra;
+        std::vector<haf_frame> stack(1, frames[v]);
+        int bad = 0;
+        for (const std::string &sp : views[v].stack) {
+            haf_frame f = frames[v];
+            uint16_t *depth = nullptr;
+            if (haf_pgm16_load(sp.c_str(), &depth, &f.width, &f.height, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", sp.c_str(), err); bad = 1; break; }
+            extra.push_back(depth);
+            f.data = depth;
+            f.row_stride_bytes = (size_t)f.width * 2;
+            stack.push_back(f);
+        }
+        uint16_t *filtered = bad ? nullptr : (uint16_t *)malloc(std::max<size_t>(1, (size_t)frames[v].width * (size_t)frames[v].height) * 2);
+        int64_t stats[3] = {0, 0, 0};
+        if (!bad && (!filtered || stack.size() > (size_t)HAF_MAX_STACK ||
+                     haf_filter_depth(eng, stack.data(), (int32_t)stack.size(), &mo.filter_params, filtered, (size_t)frames[v].width * 2, 0, nullptr, stats) != HAF_OK)) {
+            fprintf(stderr, "%s: --depth-filter: %s\n", views[v].path.c_str(),
+                    !filtered ? "out of host memory" : stack.size() > (size_t)HAF_MAX_STACK ? "more than HAF_MAX_STACK exposures" : haf_last_error(eng));
+            bad = 1;
+        }
+        for (uint16_t *p : extra) haf_free(p);
+        if (bad) { free(filtered); release(); return 1; }
+        haf_free(images[v]);
+        images[v] = filtered;                              // (haf_free is free)
+        frames[v].data = filtered;
+        fprintf(stderr, "%s: %d exposure(s) filtered: %lld of %lld pixels valid, %lld kept\n", views[v].path.c_str(), (int)stack.size(),
+                (long long)stats[1], (long long)stats[0], (long long)stats[2]);
+    }
+    if (mo.filter && !mo.filtered_out.empty() && !write_depth_pgm16(mo.filtered_out, images[0], frames[0].width, frames[0].height)) {
+        fprintf(stderr, "--filtered-out: cannot write %s\n", mo.filtered_out.c_str());
+        release();
+        return 1;
     }
     // what the messages below are about: the file of a single view; every file of a fused request ("a.pgm + b.pgm"), in view order, so
     // that the library's "request 0 view V" finds its file
@@ -405,7 +490,10 @@ int main(int argc, char **argv)
         else if (a == "--view-roi-mask") { need(1); if (views.empty()) { usage(); return 2; } views.back().roi_path = argv[++i]; }
         else if (a == "--labels") { need(1); map_opt.labels_path = argv[++i]; }
         else if (a == "--mask-min-vote") { need(1); map_opt.min_vote = atoi(argv[++i]); }
-        else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame}); }
+        else if (a == "--depth") { need(1); views.push_back(DepthView{argv[++i], frame, std::string(), {}}); }
+        else if (a == "--stack") { need(1); if (views.empty()) { usage(); return 2; } views.back().stack.push_back(argv[++i]); }
+        else if (a == "--depth-filter") { need(1); if (!parse_depth_filter(argv[++i], &map_opt.filter_params)) { usage(); return 2; } map_opt.filter = true; }
+        else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
         else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
         else if (a == "--depth-range") { need(2); frame.min_depth = (float)atof(argv[++i]); frame.max_depth = (float)atof(argv[++i]); }

@@ -7,6 +7,7 @@
 //   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
 //   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
+//   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
@@ -386,6 +387,10 @@ struct haf_engine {
     // per view, every mask at a multiple of 16 bytes) with its pinned twin.  haf_score_views_roi shares both
     DevBuf<unsigned long long> d_roi_cells;
     StageBuf roi_mask;
+    // haf_filter_depth (engine_depthfilter.cpp) with out == NULL: the engine's own output image, 4 bytes x max_points, allocated by the
+    // first call that asks for it.  Everything else of that call -- staged host exposures, the counters, a host output image -- passes
+    // through the raw area above
+    DevBuf<char> d_filter_image;
 };
 
 namespace haf_host {

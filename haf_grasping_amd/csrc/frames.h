@@ -34,5 +34,10 @@ int check_frame(const haf_frame &f, std::string &err);
 haf_frame_math::FrameMath frame_math(const haf_frame &f);
 // haf_view_points (include/hafgrasp.h) with its refusal's text: the valid points of host frames, in order
 int view_points_impl(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid, std::string &err);
+// depthfilter_host.cpp, shared by haf_filter_depth_ref and haf_filter_depth: every refusal of an exposure stack and of the filter's
+// parameters that needs no engine (the text names the frame), and every refusal of the output image that goes with a checked stack
+// (out may be null only with out_on_device = 1)
+int check_depth_stack(const haf_frame *frames, int32_t n_frames, const haf_depth_filter *p, std::string &err);
+int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, size_t out_row_stride_bytes, int32_t out_on_device, std::string &err);
 
 }  // namespace haf

@@ -536,6 +536,21 @@ void launch_mask_count_roi(const float *ii, const RollGeo *geo, const unsigned l
 // launch_vote with v = 0 outside S, before the argmax key, the row maxima and the store
 void launch_vote_roi(const int8_t *labels, const float *heights, const int *brcount, short *ev16, unsigned long long *topkey,
                      int *rowmax, RollRecordDev *rec, const unsigned long long *S, Dims d, hipStream_t s);
+// haf_filter_depth (depthfilter.hip): the exposures of one depth camera as the kernel reads them -- a kernel argument, so every field is a
+// scalar load.  src[j] / row_stride[j], j < n_frames: device memory, samples of `kind` (2 or 4 bytes); out: rows out_stride bytes apart;
+// counters[2], zeroed by the caller: pixels valid after stage T, pixels kept.  m: frame_math of the first exposure (scale and limits)
+struct DepthStackDev {
+    const void *src[HAF_MAX_STACK];
+    unsigned long long row_stride[HAF_MAX_STACK];
+    void *out;
+    unsigned long long out_stride;
+    unsigned *counters;
+    int width, height, n_frames;
+    int min_valid, min_support;
+    float tol_abs, tol_rel;
+    haf_frame_math::FrameMath m;
+};
+void launch_depth_filter(const DepthStackDev &d, int kind, int radius, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

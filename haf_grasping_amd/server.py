@@ -95,6 +95,15 @@ class CalcGraspPointsServer:
         return GraspOutputMsg(self.base_frame_id, out["eval"], out["grasp_point1"], out["grasp_point2"],
                               out["averaged_grasp_point"], out["approach_vector"], out["roll"])
 
+    def execute_frame_filtered(self, goal: GraspInputMsg, frames, params=None, roi_mask=None) -> GraspOutputMsg:
+        """execute_frame() on the conditioned image of `frames`: 1..capi.MAX_STACK capi.depth_frame exposures of one depth camera in
+        one pose (N synchronised depth messages of a static scene).  The engine takes, per pixel, the lower median of the valid samples
+        and drops every pixel that too few of its neighbours support (haf_filter_depth; params: a capi.depth_filter(), default the
+        library's); the filtered image stays on the device and is scored from there.  self.last_filter_stats = [pixels, valid after
+        the temporal stage, kept]."""
+        frame, self.last_filter_stats = self.engine.filter_depth(frames, params)
+        return self.execute_frame(goal, frame, roi_mask=roi_mask)
+
     def execute_views(self, goal: GraspInputMsg, frames, roi_masks=None) -> GraspOutputMsg:
         """execute_frame() for a goal seen by several sensors, or by one sensor from several poses: `frames` is a list of up to
         capi.MAX_VIEWS capi.depth_frame / capi.xyz_frame, each with its own intrinsics and sensor-to-base transform.  The engine fuses

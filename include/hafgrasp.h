@@ -569,6 +569,56 @@ int  haf_score_views_roi(haf_engine *e, int32_t n, const int32_t *views_per_requ
 int  haf_roi_cells_views(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const haf_frame *frames, const haf_roi *rois,
                          int32_t n_views, uint8_t *roi, uint8_t *eval);
 
+/* ---- conditioning depth frames on the device: 1..8 exposures of one camera -> one depth image (csrc/depthfilter.hip) -------------
+ * frames[0..n_frames) are exposures of ONE depth camera in one pose: the same kind (U16 or F32), width, height, depth_scale, min_depth
+ * and max_depth (floats compared by value); strides and residence may differ.  The result is one depth image of that kind, just
+ * another haf_frame for every call above.  Two stages, one pass:
+ *
+ * Stage T, temporal selection.  Per pixel the VALID samples of the exposures -- valid exactly as haf_frame defines it above: U16
+ * d != 0, F32 d finite and > 0, both z = (float)d * depth_scale finite and inside min_depth / max_depth.  c = their number.  c <
+ * min_valid: the pixel is invalid.  Otherwise M = the LOWER MEDIAN, the sample of 0-based rank (c - 1) / 2 in ascending order (U16
+ * compare as integers, F32 as floats).  M is one of the input samples bit for bit; no arithmetic is performed.
+ *
+ * Stage S, spatial support.  For a pixel p with a valid M_p: z_p = (float)M_p * depth_scale, t_p = tol_abs + tol_rel * z_p;
+ * support(p) = the number of pixels q != p with |u_q - u_p| <= radius, |v_q - v_p| <= radius, inside the image, M_q valid and
+ * fabs(z_q - z_p) <= t_p.  Every step one correctly rounded fp32 operation, never a fused multiply-add; fabs clears the sign bit.
+ * Pixels outside the image do not count (a corner with radius 1 has 3 candidates).  p is kept when support(p) >= min_support;
+ * min_support = 0 switches the stage off.  Support is counted on stage T's image, not on the filtered one.
+ *
+ * Output: M_p for a kept pixel; for every other pixel the invalid sample -- 0 (U16), the word 0x7FC00000 (F32).  Every output sample
+ * is therefore invalid or valid under the same frame parameters.
+ *
+ * stats (may be NULL): [0] pixels, [1] pixels valid after stage T, [2] pixels kept.
+ * out: samples of the input kind, rows out_row_stride_bytes apart (>= width * element size, a multiple of the element size, data
+ * aligned to the element); bytes between a row's end and the next row are not written; must not overlap an input.
+ *
+ * haf_filter_depth_ref: the host definition of record -- no device, no engine, host frames and host output only.
+ * haf_filter_depth: equal to it in every word and in stats.  out_on_device = 1: out is the caller's device memory, written on the
+ * engine's stream and complete when the call returns; out == NULL with out_on_device = 1: the engine writes a packed image of its own
+ * (4 bytes x max_points, allocated by the first call that asks for it, valid until the next haf_filter_depth or haf_destroy).
+ * out_frame (may be NULL): a copy of frames[0] whose data, on_device and row_stride_bytes describe the output.  The call neither reads
+ * nor changes last-batch state or stage timings, and works with HAF_FLAG_PROBABILITY and before any request.
+ * Refusals, all before any device work, nothing written, the message naming the frame -- HAF_E_ARG: everything haf_score_frames
+ * refuses for a frame, a null frames or p, n_frames outside 1..HAF_MAX_STACK, an XYZ frame, a frame that differs from frames[0] in a
+ * field named above, a parameter outside its range or not finite, out_on_device not 0 or 1, out == NULL with out_on_device = 0, a
+ * stride or alignment fault of out, out overlapping an input of the same residence, for the _ref form a device-resident frame;
+ * HAF_E_CAPACITY: width * height > max_points, or the pixels of the host-resident frames plus one image for a host out > max_points
+ * (what the raw staging area of haf_score_frames holds). */
+#define HAF_MAX_STACK 8
+typedef struct haf_depth_filter {
+    int32_t radius;       /* 1..3: window (2 radius + 1)^2                                   */
+    int32_t min_support;  /* 0..(2 radius + 1)^2 - 1; 0 = stage S off                        */
+    float   tol_abs;      /* metres (units of z), finite, >= 0                               */
+    float   tol_rel;      /* per metre of z_p, finite, >= 0                                  */
+    int32_t min_valid;    /* 1..n_frames                                                     */
+} haf_depth_filter;
+void haf_depth_filter_default(haf_depth_filter *p);   /* 2, 6, 0.004f, 0.01f, 1 */
+int  haf_filter_depth_ref(const haf_frame *frames, int32_t n_frames, const haf_depth_filter *p,
+                          void *out, size_t out_row_stride_bytes, int64_t *stats /* [3], may be NULL */);
+int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, const haf_depth_filter *p,
+                      void *out, size_t out_row_stride_bytes, int32_t out_on_device,
+                      haf_frame *out_frame /* may be NULL */, int64_t *stats /* [3], may be NULL */);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
