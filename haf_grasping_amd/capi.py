@@ -76,6 +76,21 @@ class DepthFilter(C.Structure):
     _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("tol_abs", C.c_float), ("tol_rel", C.c_float), ("min_valid", C.c_int32)]
 
 
+class SegmentParams(C.Structure):
+    """haf_segment_params: the parameters of haf_segment_frame"""
+    _fields_ = [("plane", C.c_float * 4), ("min_height", C.c_float), ("max_height", C.c_float), ("max_gap", C.c_float),
+                ("min_pixels", C.c_int32), ("max_labels", C.c_int32)]
+
+
+class SegmentInfo(C.Structure):
+    """haf_segment_info: pixel count, anchor and inclusive bounding box of one label"""
+    _fields_ = [(f, C.c_int32) for f in ("n_pixels", "anchor_u", "anchor_v", "u_min", "v_min", "u_max", "v_max")]
+
+
+SEGMENT_INFO_DTYPE = np.dtype([(f, np.int32) for f in ("n_pixels", "anchor_u", "anchor_v", "u_min", "v_min", "u_max", "v_max")])
+assert SEGMENT_INFO_DTYPE.itemsize == C.sizeof(SegmentInfo) == 28
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -191,6 +206,12 @@ def _bind(path, testing):
     L.haf_filter_depth_ref.argtypes = [C.POINTER(Frame), C.c_int32, C.POINTER(DepthFilter), C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
     L.haf_filter_depth.argtypes = [E, C.POINTER(Frame), C.c_int32, C.POINTER(DepthFilter), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Frame),
                                    C.POINTER(C.c_int64)]
+    L.haf_segment_default.argtypes = [C.POINTER(SegmentParams)]
+    L.haf_segment_default.restype = None
+    L.haf_segment_ref.argtypes = [C.POINTER(Frame), C.POINTER(SegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.haf_segment_frame.argtypes = [E, C.POINTER(Frame), C.POINTER(SegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_int32,
+                                    C.POINTER(LabelImage), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -470,6 +491,45 @@ def filter_depth_ref(frames, params=None, out=None):
     return img, [int(x) for x in stats]
 
 
+def segment_params(**kw):
+    """haf_segment_params with the library's defaults (plane (0, 0, 1, 0), min_height 0.01, max_height 0 = none, max_gap 0.02, min_pixels
+    50, max_labels 255) and `kw` over them; plane: four floats"""
+    p = SegmentParams()
+    lib().haf_segment_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_segment_params field %r" % k)
+        if k == "plane":
+            v = (C.c_float * 4)(*np.asarray(v, dtype=np.float32).reshape(-1)[:4])
+        setattr(p, k, v)
+    return p
+
+
+def _label_out(frame, dtype, out):
+    """the host label image of a segment call for `frame`: `out` (uint8 / uint16 [height, width], rows may be padded) or a new packed one
+    -> (array, pointer, element size, row stride)"""
+    dt = np.dtype(dtype)
+    assert dt in (np.uint8, np.uint16)
+    if out is None:
+        out = np.empty((max(0, frame.height), max(0, frame.width)), dt)
+    assert out.ndim == 2 and out.dtype == dt and out.shape == (frame.height, frame.width) and out.strides[1] == out.itemsize
+    return out, out.ctypes.data, dt.itemsize, out.strides[0] if frame.height > 1 else frame.width * dt.itemsize
+
+
+def segment_ref(frame, params=None, dtype=np.uint8, out=None):
+    """haf_segment_ref: the host definition of record of the tabletop segmentation of a host Frame -> (labels: uint8 / uint16 [height,
+    width], infos: SEGMENT_INFO_DTYPE [n_labels], stats: [pixels, foreground, components, components that pass the size rule]).
+    out: the array to write into (rows may be padded: a view into a wider array)."""
+    p = params if params is not None else segment_params()
+    img, ptr, elem, stride = _label_out(frame, dtype, out)
+    info = np.zeros(max(1, p.max_labels), SEGMENT_INFO_DTYPE)
+    n, stats = C.c_int32(-1), (C.c_int64 * 4)()
+    rc = lib().haf_segment_ref(C.byref(frame), C.byref(p), ptr, elem, stride, info.ctypes.data, C.byref(n), stats)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_segment_ref refused its arguments")
+    return img, info[:n.value].copy(), [int(x) for x in stats]
+
+
 def view_points(frames):
     """haf_view_points: the host definition of record of a request's fused cloud -- the valid points of `frames` (host Frames), frame
     after frame in pixel order -> float32 [n_valid, 3]"""
@@ -524,8 +584,11 @@ def _host_mask(mask, frame):
 def label_image(labels, frame, n_labels=None):
     """-> (LabelImage, n_labels) for `labels`: a numpy uint8 / uint16 [height, width] array (host; rows may be padded: a view into a
     wider array; n_labels defaults to the image's maximum, at least 1), a device tensor of such a shape (anything with data_ptr(), element_size() and
-    stride(): a torch tensor, possibly a view), or (device_ptr, elem_bytes, row_stride_bytes); n_labels must be given for device images."""
-    if isinstance(labels, tuple):
+    stride(): a torch tensor, possibly a view), (device_ptr, elem_bytes, row_stride_bytes), or a LabelImage as it is (what
+    Engine.segment(..., device_out=True) returns); n_labels must be given for device images."""
+    if isinstance(labels, LabelImage):
+        img, keep = labels, getattr(labels, "_keep", None)
+    elif isinstance(labels, tuple):
         ptr, eb, stride = (int(x) for x in labels)
         img, keep = LabelImage(ptr, eb, 1, stride), None
     elif hasattr(labels, "data_ptr"):
@@ -930,6 +993,30 @@ class Engine:
         got._keep = keep
         got.image = keep
         return got, [int(x) for x in stats]
+
+    def segment(self, frame, params=None, dtype=np.uint8, device_out=False, host_out=None):
+        """haf_segment_frame: a Frame (any kind, host or device-resident) -> (labels, infos, stats) as segment_ref gives them, computed on
+        the device.  labels is a new uint8 / uint16 [height, width] array (host_out: the array to write into, rows may be padded).
+        device_out=True: the engine's own packed device image, returned as a LabelImage (valid until the next segment or close(), across
+        scoring and map calls; as uint8 its data is also a device mask for score_frames_roi); device_out=(pointer, row_stride_bytes) or a
+        pointer: the caller's device image, likewise described by the LabelImage returned."""
+        p = params if params is not None else segment_params()
+        info = np.zeros(max(1, p.max_labels), SEGMENT_INFO_DTYPE)
+        n, stats, got = C.c_int32(-1), (C.c_int64 * 4)(), LabelImage()
+        elem = np.dtype(dtype).itemsize
+        if device_out is True:
+            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), None, elem, 0, 1, C.byref(got), info.ctypes.data, C.byref(n), stats)
+            img = got
+        elif device_out is not False and device_out is not None:
+            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
+            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), int(ptr), elem, stride or frame.width * elem, 1, C.byref(got),
+                                           info.ctypes.data, C.byref(n), stats)
+            img = got
+        else:
+            img, ptr, elem, stride = _label_out(frame, dtype, host_out)
+            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), info.ctypes.data, C.byref(n), stats)
+        self._check(rc)
+        return img, info[:n.value].copy(), [int(x) for x in stats]
 
     def cell_pose(self, request, roll, row, col):
         """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""

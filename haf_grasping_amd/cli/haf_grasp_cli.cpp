@@ -29,6 +29,14 @@
 //                                     1.. the objects); after the normal output one line "object <label> <u> <v> <hypothesis>" per object
 //                                     that has a pixel whose vote is at least --mask-min-vote, best first (haf_grasp_map_labels: one
 //                                     device pass for all objects); may be combined with --roi-mask
+//   --segment MIN_H,MAX_H,GAP,MIN_PX | default
+//                                     with --depth: no segmenter at hand -- the first view is clustered into objects on the device
+//                                     (haf_segment_frame: pixels MIN_H..MAX_H metres above the support plane, MAX_H <= 0: no upper limit;
+//                                     4-neighbours closer than GAP metres are one object; objects of fewer than MIN_PX pixels are dropped;
+//                                     at most 255 objects).  --plane A B C D: the plane, height = A x + B y + C z + D in the base frame
+//                                     (default: through --center, normal = the approach vector: the caller owns the table height).
+//                                     Without --labels the label image feeds the "object" lines; --labels-out FILE.pgm writes it as an
+//                                     8-bit PGM; --segment-roi also scores only under it (with ONE --depth, not with --roi-mask)
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
 //                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
 //                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
@@ -132,6 +140,7 @@ static void usage()
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
             "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
+            "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -171,7 +180,39 @@ struct MapOptions {
     bool filter = false;
     haf_depth_filter filter_params;
     std::string filtered_out;
+    // --segment: the first view is clustered into objects (haf_segment_frame, a uint8 image: at most 255 objects) after the filter and
+    // before the request; without --labels its image feeds the "object" lines; --segment-roi scores under labels != 0; --plane: the
+    // support plane (default: through --center with the approach vector as its normal); --labels-out: the image as an 8-bit PGM
+    bool segment = false, segment_roi = false, have_plane = false;
+    haf_segment_params segment_params;
+    float plane[4] = {0, 0, 1, 0};
+    std::string labels_out;
+    std::vector<uint8_t> seg_labels;     // filled by run_depth
+    int32_t seg_n = 0;
 };
+
+// --segment MIN_H,MAX_H,GAP,MIN_PX or "default"
+static bool parse_segment(const char *arg, haf_segment_params *p)
+{
+    haf_segment_default(p);
+    if (strcmp(arg, "default") == 0) return true;
+    float min_h = 0, max_h = 0, gap = 0;
+    int min_px = 0;
+    char tail = 0;
+    if (sscanf(arg, "%f,%f,%f,%d%c", &min_h, &max_h, &gap, &min_px, &tail) != 4) return false;
+    p->min_height = min_h; p->max_height = max_h; p->max_gap = gap; p->min_pixels = min_px;
+    return true;
+}
+
+static bool write_pgm8(const std::string &path, const uint8_t *img, int w, int h)
+{
+    FILE *fp = fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    fprintf(fp, "P5\n%d %d\n255\n", w, h);
+    const size_t n = (size_t)w * (size_t)h;
+    const bool ok = fwrite(img, 1, n, fp) == n;
+    return fclose(fp) == 0 && ok;
+}
 
 // --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] or "default"
 static bool parse_depth_filter(const char *arg, haf_depth_filter *p)
@@ -256,6 +297,16 @@ static bool read_pgm8(const std::string &path, std::vector<uint8_t> &img, int &w
 static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, const MapOptions &mo)
 {
     const size_t n = (size_t)f.width * (size_t)f.height;
+    if (mo.labels_path.empty() && mo.segment && mo.seg_n > 0) {      // --segment without --labels: the objects are the segmentation's
+        const haf_label_image img = {mo.seg_labels.data(), 1, 0, (size_t)f.width};
+        std::vector<std::string> lines;
+        std::string serr;
+        if (hafshim::label_hypotheses(eng, cfg, f, img, mo.seg_n, mo.min_vote, &lines, &serr) != HAF_OK) {
+            fprintf(stderr, "--segment: %s\n", serr.c_str());
+            return 1;
+        }
+        for (const std::string &l : lines) printf("object %s\n", l.c_str());
+    }
     if (!mo.out_prefix.empty()) {
         std::vector<int16_t> vote(n), roll(n);
         if (haf_grasp_map(eng, 0, &f, vote.data(), roll.data(), nullptr, 0) != HAF_OK) { fprintf(stderr, "--map-out: %s\n", haf_last_error(eng)); return 1; }
@@ -313,7 +364,7 @@ static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, c
 }
 
 static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::vector<DepthView> &views,
-                     bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist, const MapOptions &mo)
+                     bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist, MapOptions &mo)
 {
     std::vector<uint16_t *> images;
     std::vector<haf_frame> frames;
@@ -365,6 +416,32 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         release();
         return 1;
     }
+    // --segment: the first view (filtered or not) into a label image, before the request: the call needs no scored batch
+    if (mo.segment) {
+        haf_segment_params sp = mo.segment_params;
+        if (mo.have_plane) memcpy(sp.plane, mo.plane, sizeof sp.plane);
+        else {
+            hafshim::GoalFields g;
+            haf_segment_params from_goal;
+            for (int k = 0; k < 3; k++) { g.center[k] = in.grasp_area_center[k]; g.approach_vector[k] = in.approach_vector[k]; }
+            hafshim::segment_params_from_goal(g, &from_goal);
+            memcpy(sp.plane, from_goal.plane, sizeof sp.plane);
+        }
+        mo.seg_labels.assign((size_t)frames[0].width * (size_t)frames[0].height, 0);
+        int64_t stats[4] = {0, 0, 0, 0};
+        if (haf_segment_frame(eng, &frames[0], &sp, mo.seg_labels.data(), 1, (size_t)frames[0].width, 0, nullptr, nullptr, &mo.seg_n, stats) != HAF_OK) {
+            fprintf(stderr, "%s: --segment: %s\n", views[0].path.c_str(), haf_last_error(eng));
+            release();
+            return 1;
+        }
+        fprintf(stderr, "%s: segmented: %d object(s); %lld of %lld pixels foreground, %lld component(s), %lld pass the size rule\n", views[0].path.c_str(),
+                (int)mo.seg_n, (long long)stats[1], (long long)stats[0], (long long)stats[2], (long long)stats[3]);
+        if (!mo.labels_out.empty() && !write_pgm8(mo.labels_out, mo.seg_labels.data(), frames[0].width, frames[0].height)) {
+            fprintf(stderr, "--labels-out: cannot write %s\n", mo.labels_out.c_str());
+            release();
+            return 1;
+        }
+    }
     // what the messages below are about: the file of a single view; every file of a fused request ("a.pgm + b.pgm"), in view order, so
     // that the library's "request 0 view V" finds its file
     std::string path = views[0].path;
@@ -385,7 +462,8 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
             return 1;
         }
     }
-    const haf_roi roi = {roi_mask.data(), (size_t)frames[0].width, 0};
+    const bool seg_roi = mo.segment && mo.segment_roi;      // (labels != 0 selects: the uint8 label image IS the mask)
+    const haf_roi roi = {seg_roi ? mo.seg_labels.data() : roi_mask.data(), (size_t)frames[0].width, 0};
     // --view-roi-mask: a mask per view, null for a view without one
     std::vector<std::vector<uint8_t>> view_masks(views.size());
     std::vector<haf_roi> view_rois(views.size(), haf_roi{nullptr, 0, 0});
@@ -402,7 +480,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         view_rois[v] = haf_roi{view_masks[v].data(), (size_t)w, 0};
         view_roi = true;
     }
-    if ((!mo.roi_path.empty() ? haf_score_frames_roi(eng, 1, frames.data(), &roi, &in, &out)
+    if ((!mo.roi_path.empty() || seg_roi ? haf_score_frames_roi(eng, 1, frames.data(), &roi, &in, &out)
          : view_roi ? haf_score_views_roi(eng, 1, &n_views, frames.data(), view_rois.data(), &in, &out, &n_points)
          : n_views == 1 ? haf_score_frames(eng, 1, frames.data(), &in, &out)
                         : haf_score_views(eng, 1, &n_views, frames.data(), &in, &out, &n_points)) != HAF_OK) {
@@ -494,6 +572,10 @@ int main(int argc, char **argv)
         else if (a == "--stack") { need(1); if (views.empty()) { usage(); return 2; } views.back().stack.push_back(argv[++i]); }
         else if (a == "--depth-filter") { need(1); if (!parse_depth_filter(argv[++i], &map_opt.filter_params)) { usage(); return 2; } map_opt.filter = true; }
         else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
+        else if (a == "--segment") { need(1); if (!parse_segment(argv[++i], &map_opt.segment_params)) { usage(); return 2; } map_opt.segment = true; }
+        else if (a == "--segment-roi") map_opt.segment_roi = true;
+        else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) map_opt.plane[k] = (float)atof(argv[++i]); map_opt.have_plane = true; }
+        else if (a == "--labels-out") { need(1); map_opt.labels_out = argv[++i]; }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
         else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
         else if (a == "--depth-range") { need(2); frame.min_depth = (float)atof(argv[++i]); frame.max_depth = (float)atof(argv[++i]); }
@@ -509,6 +591,8 @@ int main(int argc, char **argv)
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
+        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || map_opt.have_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.segment_roi && (views.size() != 1 || !views[0].roi_path.empty() || !map_opt.roi_path.empty())) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184
     in.grasp_area_length_y = (float)(sy + 14);

@@ -8,6 +8,7 @@
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
 //   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
 //   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
+//   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
@@ -391,6 +392,12 @@ struct haf_engine {
     // first call that asks for it.  Everything else of that call -- staged host exposures, the counters, a host output image -- passes
     // through the raw area above
     DevBuf<char> d_filter_image;
+    // haf_segment_frame (engine_segment.cpp), allocated by its first call: the parent and size words (4 bytes x max_points each) with the
+    // scan's block totals behind them; the block [counters][per-label table, HAF_MAX_LABELS entries][a host output image, 2 bytes x
+    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which no other call touches
+    DevBuf<int> d_seg_words;
+    StageBuf seg_out;
+    DevBuf<char> d_seg_image;
 };
 
 namespace haf_host {

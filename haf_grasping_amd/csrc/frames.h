@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/hafgrasp.h"
 #include "frame_points.h"
+#include "segment_rules.h"
 
 #include <string>
 
@@ -39,5 +40,10 @@ int view_points_impl(const haf_frame *frames, int32_t n_views, float *xyz, size_
 // (out may be null only with out_on_device = 1)
 int check_depth_stack(const haf_frame *frames, int32_t n_frames, const haf_depth_filter *p, std::string &err);
 int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, size_t out_row_stride_bytes, int32_t out_on_device, std::string &err);
+// segment_host.cpp, shared by haf_segment_ref and haf_segment_frame: every refusal of a frame, of the parameters and of the label image
+// that needs no engine (labels may be null only with out_on_device = 1); the predicates' constants, gap2 formed here
+int check_segment(const haf_frame *frame, const haf_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
+                  int32_t out_on_device, const int32_t *n_labels, std::string &err);
+haf_segment_math::SegmentRules segment_rules(const haf_segment_params &p);
 
 }  // namespace haf

@@ -551,6 +551,26 @@ struct DepthStackDev {
     haf_frame_math::FrameMath m;
 };
 void launch_depth_filter(const DepthStackDev &d, int kind, int radius, hipStream_t s);
+// haf_segment_frame (segment.hip): one frame as the kernels read it -- a kernel argument, so every field is a scalar load.  f: the frame
+// (dst and count are not read); parent / size: f.n words each; totals: segment_scan_blocks(f.n) words; counters[4], zeroed by the caller:
+// foreground pixels, components, components that pass the size rule; table: max_labels entries of 7 ints (haf_segment_info), written for
+// the labels that exist; out: the label image, elem_bytes 1 or 2 per pixel, rows out_stride bytes apart.  All of it device memory
+struct SegmentDev {
+    FrameDev f;
+    int height;
+    haf_segment_math::SegmentRules r;
+    int min_pixels, max_labels;
+    int *parent, *size, *totals;
+    unsigned *counters;
+    int *table;
+    void *out;
+    unsigned long long out_stride;
+    int elem_bytes;
+};
+constexpr int kSegScanPixels = 1024;               // pixels per workgroup of the numbering scan
+inline size_t segment_scan_blocks(size_t n) { return (n + kSegScanPixels - 1) / kSegScanPixels; }
+// the seven launches of one call, in stream order: tile, seam, flatten, block totals, scan of the totals, numbering, write
+void launch_segment(const SegmentDev &d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

@@ -169,5 +169,31 @@ class CalcGraspPointsServer:
         res = self.execute_frame(goal, frame, roi_mask=(lab != 0).astype(np.uint8))
         return res, self.best_per_object(frame, lab, min_vote=min_vote)
 
+    @staticmethod
+    def segment_params_from_goal(goal: GraspInputMsg, **kw):
+        """capi.segment_params() whose support plane is the plane through the goal's grasp area centre c with the goal's unit approach
+        vector n as its normal: plane = (n, -n.c), so a point's height is its distance from that plane along the approach direction.
+        THE CALLER OWNS THE TABLE HEIGHT: the centre of the grasp area must lie on the support surface (or min_height must make up for
+        it).  kw: the other fields (min_height, max_height, max_gap, min_pixels, max_labels) over the library's defaults."""
+        n = np.asarray(goal.approach_vector, np.float64)
+        n = n / np.linalg.norm(n) if np.linalg.norm(n) > 0 else np.array([0.0, 0.0, 1.0])
+        c = np.asarray(goal.grasp_area_center, np.float64)
+        return capi.segment_params(plane=[n[0], n[1], n[2], -float(n @ c)], **kw)
+
+    def execute_frame_segmented(self, goal: GraspInputMsg, frame, params=None, min_vote=1):
+        """execute_frame_objects() without a segmenter: the frame is clustered into objects on the device (haf_segment_frame: geometric
+        tabletop clustering -- a height band over the support plane, 4-neighbours closer than max_gap are one object; touching objects
+        are one object), the request is scored under that image as the device mask (haf_score_frames_roi) and every object gets its own
+        best grasp from the same device image (haf_grasp_map_labels); the label image never leaves the device
+        -> (GraspOutputMsg of the request, best_per_object()'s list).  params: a capi.segment_params(); None:
+        segment_params_from_goal(goal), whose plane passes through the goal's grasp area centre -- the caller owns the table height.
+        self.last_segment_infos / self.last_segment_stats: the objects' pixel counts, anchors and boxes, and [pixels, foreground,
+        components, components that pass the size rule]."""
+        p = params if params is not None else self.segment_params_from_goal(goal)
+        img, self.last_segment_infos, self.last_segment_stats = self.engine.segment(frame, p, np.uint8, device_out=True)
+        res = self.execute_frame(goal, frame, roi_mask=(img.data, img.row_stride_bytes))
+        n = len(self.last_segment_infos)
+        return res, (self.best_per_object(frame, img, min_vote=min_vote, n_labels=n) if n else [])
+
     def close(self):
         self.engine.close()

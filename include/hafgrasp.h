@@ -619,6 +619,60 @@ int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
                       void *out, size_t out_row_stride_bytes, int32_t out_on_device,
                       haf_frame *out_frame /* may be NULL */, int64_t *stats /* [3], may be NULL */);
 
+/* ---- a depth frame into object labels on the device: geometric tabletop clustering (csrc/segment.hip) ---------------------------
+ * The classic organised-cloud clustering, for the caller with one camera over a table and no segmenter: the label image every
+ * haf_label_image and (as uint8) every haf_roi mask above asks for, from the frame itself.  It is geometry only -- a height band
+ * over a plane the CALLER supplies and a distance between neighbouring pixels' points; touching objects are one object.
+ *
+ *   point       pixel i = v * width + u has haf_frame_points' three words; any kind of frame.
+ *   foreground  all three words finite (the rule of haf_view_points) and, with
+ *               h = ((plane[0] x + plane[1] y) + plane[2] z) + plane[3], every step ONE correctly rounded fp32 operation in this order,
+ *               never a fused multiply-add: h is no NaN, h >= min_height, and max_height <= 0 or h <= max_height.
+ *   link        foreground pixels p, q that are horizontal or vertical neighbours inside the image: dx = x_q - x_p, dy, dz likewise,
+ *               d2 = ((dx dx + dy dy) + dz dz), rounded as above; linked when d2 is finite and d2 <= gap2, gap2 = max_gap * max_gap
+ *               formed once on the host in fp32.  Symmetric by construction: a - b = -(b - a) exactly.
+ *   component   a connected component of the link graph; its ANCHOR is its lowest pixel index.
+ *   labels      components of fewer than min_pixels pixels are background; the others are numbered 1, 2, ... in ascending order of
+ *               anchor; those numbered above max_labels are background too.  *n_labels = min(kept, max_labels).  Every pixel of a
+ *               numbered component carries its number, every other pixel 0.
+ *   info[l - 1] the component's pixel count, its anchor and its inclusive bounding box (first *n_labels entries written).
+ *   stats       [0] pixels, [1] foreground pixels, [2] components before the size rule, [3] components that pass it, before the cap.
+ *   labels      elem_bytes 1 (uint8) or 2 (uint16, host byte order) per pixel, rows row_stride_bytes apart: strides and alignment as
+ *               haf_label_image; bytes between rows are not written; must not overlap the frame.  A uint8 image is at the same time
+ *               a valid haf_roi mask (a non-zero byte selects the pixel).
+ * Nothing above depends on an order of evaluation: the result is one image, whoever computes it.
+ *
+ * haf_segment_ref: the host definition of record -- no device, no engine, a host frame and a host output only.
+ * haf_segment_frame: equal to it in every label word, every info field, n_labels and stats.  out_on_device = 1: labels is the caller's
+ * device memory, written on the engine's stream and complete when the call returns; labels == NULL with out_on_device = 1: a packed
+ * image the engine owns (2 bytes x max_points, allocated by the first call that asks for it), valid until the next haf_segment_frame
+ * or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
+ * haf_grasp_map_labels; its data as a uint8 image is a haf_roi mask.  The first call allocates the scratch: 8 bytes x max_points of
+ * parent and size words, the per-label table and the copy-back block.  Like haf_filter_depth the call neither reads nor changes
+ * last-batch state or stage timings, and works before any request and with HAF_FLAG_PROBABILITY.
+ * Refusals, all before any device work, nothing written -- HAF_E_ARG: everything haf_score_frames refuses for a frame, a null frame, p
+ * or n_labels, a plane entry or height that is not finite, max_gap not finite or not > 0, min_pixels < 1, max_labels outside
+ * 1..HAF_MAX_LABELS (1..255 with elem_bytes 1), elem_bytes not 1 or 2, a stride or alignment fault of labels, out_on_device not 0 or
+ * 1, labels == NULL with out_on_device = 0, labels overlapping a frame of the same residence, for the _ref form a device-resident
+ * frame; HAF_E_CAPACITY: width * height > max_points. */
+typedef struct haf_segment_params {
+    float   plane[4];     /* height above the support, base frame: h = ((plane[0] x + plane[1] y) + plane[2] z) + plane[3] */
+    float   min_height;   /* metres; foreground needs h >= min_height                                  */
+    float   max_height;   /* metres; > 0: foreground needs h <= max_height; <= 0: no upper limit       */
+    float   max_gap;      /* metres, finite, > 0: 4-neighbours closer than this are one object         */
+    int32_t min_pixels;   /* >= 1: smaller components become background                                */
+    int32_t max_labels;   /* 1..HAF_MAX_LABELS (1..255 when the output is uint8)                       */
+} haf_segment_params;
+typedef struct haf_segment_info {   /* label l is entry l - 1 */
+    int32_t n_pixels, anchor_u, anchor_v, u_min, v_min, u_max, v_max;
+} haf_segment_info;
+void haf_segment_default(haf_segment_params *p);   /* (0,0,1,0), 0.01f, 0, 0.02f, 50, 255 */
+int  haf_segment_ref(const haf_frame *frame, const haf_segment_params *p, void *labels, int32_t elem_bytes, size_t row_stride_bytes,
+                     haf_segment_info *info /* [max_labels], may be NULL */, int32_t *n_labels, int64_t *stats /* [4], may be NULL */);
+int  haf_segment_frame(haf_engine *e, const haf_frame *frame, const haf_segment_params *p, void *labels, int32_t elem_bytes,
+                       size_t row_stride_bytes, int32_t out_on_device, haf_label_image *out_image /* may be NULL */,
+                       haf_segment_info *info /* [max_labels], may be NULL */, int32_t *n_labels, int64_t *stats /* [4], may be NULL */);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus

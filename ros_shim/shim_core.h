@@ -12,6 +12,7 @@
 
 #include <hafgrasp.h>
 
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <sstream>
@@ -205,6 +206,23 @@ inline int label_hypotheses(haf_engine *engine, const haf_config &cfg, const haf
                          hypothesis_string(poses[l].grasp, cfg.roll_step_deg));
     }
     return HAF_OK;
+}
+
+// No segmenter on the robot: the parameters of haf_segment_frame for a goal.  The support plane passes through the goal's grasp area
+// centre c with the goal's unit approach vector n as its normal, plane = (n, -n.c), so a point's height is its distance from that plane
+// along the approach direction; the other fields are the library's defaults.  THE CALLER OWNS THE TABLE HEIGHT: the centre must lie on
+// the support surface, or min_height must make up for it.  The adapter segments the depth frame into the engine's uint8 image, scores
+// with haf_score_frames_roi under that image as the device mask, and hands the same image to label_hypotheses.
+inline void segment_params_from_goal(const GoalFields &g, haf_segment_params *p)
+{
+    haf_segment_default(p);
+    double n[3] = {g.approach_vector[0], g.approach_vector[1], g.approach_vector[2]};
+    double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(len > 0.0)) { n[0] = 0.0; n[1] = 0.0; n[2] = 1.0; len = 1.0; }                     // (a zero or NaN vector: the default approach, +z)
+    double d = 0.0;
+    for (int k = 0; k < 3; k++) { n[k] /= len; d -= n[k] * g.center[k]; }
+    for (int k = 0; k < 3; k++) p->plane[k] = (float)n[k];
+    p->plane[3] = (float)d;
 }
 
 }  // namespace hafshim
