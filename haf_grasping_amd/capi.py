@@ -91,6 +91,21 @@ SEGMENT_INFO_DTYPE = np.dtype([(f, np.int32) for f in ("n_pixels", "anchor_u", "
 assert SEGMENT_INFO_DTYPE.itemsize == C.sizeof(SegmentInfo) == 28
 
 
+class PlaneParams(C.Structure):
+    """haf_plane_params: the parameters of haf_fit_plane"""
+    _fields_ = [("tol", C.c_float), ("min_area2", C.c_float), ("up", C.c_float * 3), ("max_tilt", C.c_float), ("n_hyp", C.c_int32),
+                ("min_inliers", C.c_int32), ("seed", C.c_uint32)]
+
+
+class PlaneResult(C.Structure):
+    """haf_plane_result: the fitted plane, what it was fitted on and the integers behind it"""
+    _fields_ = [("plane", C.c_float * 4), ("found", C.c_int32), ("winner", C.c_int32), ("n_inliers", C.c_int32), ("reserved", C.c_int32),
+                ("rms", C.c_double), ("stats", C.c_int64 * 4), ("moments", C.c_int64 * 10)]
+
+
+MAX_PLANE_HYP = 1024
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -212,6 +227,10 @@ def _bind(path, testing):
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.haf_segment_frame.argtypes = [E, C.POINTER(Frame), C.POINTER(SegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_int32,
                                     C.POINTER(LabelImage), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.haf_plane_default.argtypes = [C.POINTER(PlaneParams)]
+    L.haf_plane_default.restype = None
+    L.haf_fit_plane_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
+    L.haf_fit_plane.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -528,6 +547,53 @@ def segment_ref(frame, params=None, dtype=np.uint8, out=None):
     if rc != HAF_OK:
         raise HafError(rc, "haf_segment_ref refused its arguments")
     return img, info[:n.value].copy(), [int(x) for x in stats]
+
+
+def plane_params(**kw):
+    """haf_plane_params with the library's defaults (tol 0.005, min_area2 1e-6, up (0, 0, 0) = no tilt test, max_tilt 0, n_hyp 256,
+    min_inliers 100, seed 1) and `kw` over them; up: three floats"""
+    p = PlaneParams()
+    lib().haf_plane_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_plane_params field %r" % k)
+        if k == "up":
+            v = (C.c_float * 3)(*np.asarray(v, dtype=np.float32).reshape(-1)[:3])
+        setattr(p, k, v)
+    return p
+
+
+def _plane_mask(frame, mask):
+    """None, a host mask (uint8 [height, width], rows may be padded) or a device mask ((device_ptr, row_stride_bytes)) -> (Roi or None, keep-alive)"""
+    if mask is None:
+        return None, None
+    if isinstance(mask, tuple):
+        return Roi(int(mask[0]), int(mask[1]), 1), None
+    keep, ptr, stride = _host_mask(mask, frame)
+    return Roi(ptr, stride, 0), keep
+
+
+def _plane_result(res, n_hyp, counts, hyps, debug):
+    out = dict(plane=np.array(list(res.plane), np.float32), found=bool(res.found), winner=int(res.winner), n_inliers=int(res.n_inliers),
+               rms=float(res.rms), stats=[int(x) for x in res.stats])
+    if debug:
+        out.update(moments=[int(x) for x in res.moments], counts=counts[:n_hyp].copy(), hyps=hyps[:n_hyp].copy())
+    return out
+
+
+def fit_plane_ref(frame, params=None, mask=None, debug=False):
+    """haf_fit_plane_ref: the host definition of record of the dominant plane of a host Frame -> dict(plane: float32 [4], assignable to
+    segment_params(plane=...); found, winner, n_inliers, rms, stats: [pixels, usable, hypotheses that are not void, best count]).
+    mask: uint8 [height, width], a non-zero byte admits the pixel.  debug=True adds moments (ten ints), counts (int32 [n_hyp]) and hyps
+    (float32 [n_hyp, 4]: the un-normalised n and d of every hypothesis)."""
+    p = params if params is not None else plane_params()
+    roi, keep = _plane_mask(frame, mask)
+    res, counts, hyps = PlaneResult(), np.zeros(MAX_PLANE_HYP, np.int32), np.zeros((MAX_PLANE_HYP, 4), np.float32)
+    rc = lib().haf_fit_plane_ref(C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(p), C.byref(res),
+                                 counts.ctypes.data if debug else None, hyps.ctypes.data if debug else None)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_fit_plane_ref refused its arguments")
+    return _plane_result(res, p.n_hyp, counts, hyps, debug)
 
 
 def view_points(frames):
@@ -1017,6 +1083,16 @@ class Engine:
             rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), info.ctypes.data, C.byref(n), stats)
         self._check(rc)
         return img, info[:n.value].copy(), [int(x) for x in stats]
+
+    def fit_plane(self, frame, params=None, mask=None, debug=False):
+        """haf_fit_plane: a Frame (any kind, host or device-resident) -> the dict fit_plane_ref gives, computed on the device.  mask: a host
+        uint8 [height, width] array or (device_ptr, row_stride_bytes)."""
+        p = params if params is not None else plane_params()
+        roi, keep = _plane_mask(frame, mask)
+        res, counts, hyps = PlaneResult(), np.zeros(MAX_PLANE_HYP, np.int32), np.zeros((MAX_PLANE_HYP, 4), np.float32)
+        self._check(self._L.haf_fit_plane(self._h, C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(p), C.byref(res),
+                                          counts.ctypes.data if debug else None, hyps.ctypes.data if debug else None))
+        return _plane_result(res, p.n_hyp, counts, hyps, debug)
 
     def cell_pose(self, request, roll, row, col):
         """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""

@@ -35,6 +35,11 @@
 //                                     4-neighbours closer than GAP metres are one object; objects of fewer than MIN_PX pixels are dropped;
 //                                     at most 255 objects).  --plane A B C D: the plane, height = A x + B y + C z + D in the base frame
 //                                     (default: through --center, normal = the approach vector: the caller owns the table height).
+//                                     --plane fit[,TOL,N_HYP]: the plane is the view's dominant plane, fitted on the device
+//                                     (haf_fit_plane: points within TOL metres, N_HYP hypotheses; defaults 0.005, 256); --plane-mask
+//                                     FILE.pgm: only the pixels under its non-zero samples take part in the fit.  One line
+//                                     "plane <a> <b> <c> <d> inliers <n> rms <r>" goes to stdout before everything else; where no plane
+//                                     is found ("plane none") the default plane stands in.
 //                                     Without --labels the label image feeds the "object" lines; --labels-out FILE.pgm writes it as an
 //                                     8-bit PGM; --segment-roi also scores only under it (with ONE --depth, not with --roi-mask)
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
@@ -140,7 +145,7 @@ static void usage()
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
             "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
-            "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
+            "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D | --plane fit[,TOL,N_HYP] [--plane-mask FILE.pgm]] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -186,6 +191,10 @@ struct MapOptions {
     bool segment = false, segment_roi = false, have_plane = false;
     haf_segment_params segment_params;
     float plane[4] = {0, 0, 1, 0};
+    // --plane fit[,TOL,N_HYP]: the plane is haf_fit_plane's of the first view; --plane-mask: the haf_roi of that fit
+    bool fit_plane = false;
+    haf_plane_params plane_params;
+    std::string plane_mask;
     std::string labels_out;
     std::vector<uint8_t> seg_labels;     // filled by run_depth
     int32_t seg_n = 0;
@@ -201,6 +210,22 @@ static bool parse_segment(const char *arg, haf_segment_params *p)
     char tail = 0;
     if (sscanf(arg, "%f,%f,%f,%d%c", &min_h, &max_h, &gap, &min_px, &tail) != 4) return false;
     p->min_height = min_h; p->max_height = max_h; p->max_gap = gap; p->min_pixels = min_px;
+    return true;
+}
+
+// --plane fit[,TOL[,N_HYP]]
+static bool parse_plane_fit(const char *arg, haf_plane_params *p)
+{
+    haf_plane_default(p);
+    if (strcmp(arg, "fit") == 0) return true;
+    float tol = 0;
+    int n_hyp = 0;
+    char tail = 0;
+    const int got = sscanf(arg, "fit,%f,%d%c", &tol, &n_hyp, &tail);
+    if (got != 1 && got != 2) return false;
+    if (got == 1 && strchr(arg + 4, ',')) return false;   // ("fit,0.005," or "fit,0.005,x")
+    p->tol = tol;
+    if (got == 2) p->n_hyp = n_hyp;
     return true;
 }
 
@@ -420,12 +445,32 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     if (mo.segment) {
         haf_segment_params sp = mo.segment_params;
         if (mo.have_plane) memcpy(sp.plane, mo.plane, sizeof sp.plane);
-        else {
+        else {                                             // (also the fall-back of --plane fit)
             hafshim::GoalFields g;
             haf_segment_params from_goal;
             for (int k = 0; k < 3; k++) { g.center[k] = in.grasp_area_center[k]; g.approach_vector[k] = in.approach_vector[k]; }
             hafshim::segment_params_from_goal(g, &from_goal);
             memcpy(sp.plane, from_goal.plane, sizeof sp.plane);
+        }
+        if (mo.fit_plane) {
+            std::vector<uint8_t> pm;
+            haf_roi roi = {nullptr, 0, 0};
+            if (!mo.plane_mask.empty()) {
+                int w = 0, h = 0;
+                if (!read_pgm8(mo.plane_mask, pm, w, h)) { fprintf(stderr, "%s: not a binary 8-bit PGM\n", mo.plane_mask.c_str()); release(); return 1; }
+                if (w != frames[0].width || h != frames[0].height) { fprintf(stderr, "%s: %d x %d, the depth image is %d x %d\n", mo.plane_mask.c_str(), w, h, frames[0].width, frames[0].height); release(); return 1; }
+                roi.mask = pm.data(); roi.row_stride_bytes = (size_t)w;
+            }
+            haf_plane_result fit;
+            if (haf_fit_plane(eng, &frames[0], roi.mask ? &roi : nullptr, &mo.plane_params, &fit, nullptr, nullptr) != HAF_OK) {
+                fprintf(stderr, "%s: --plane fit: %s\n", views[0].path.c_str(), haf_last_error(eng));
+                release();
+                return 1;
+            }
+            if (fit.found) {
+                memcpy(sp.plane, fit.plane, sizeof sp.plane);
+                printf("plane %.9g %.9g %.9g %.9g inliers %d rms %.6g\n", fit.plane[0], fit.plane[1], fit.plane[2], fit.plane[3], (int)fit.n_inliers, fit.rms);
+            } else printf("plane none\n");
         }
         mo.seg_labels.assign((size_t)frames[0].width * (size_t)frames[0].height, 0);
         int64_t stats[4] = {0, 0, 0, 0};
@@ -574,6 +619,8 @@ int main(int argc, char **argv)
         else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
         else if (a == "--segment") { need(1); if (!parse_segment(argv[++i], &map_opt.segment_params)) { usage(); return 2; } map_opt.segment = true; }
         else if (a == "--segment-roi") map_opt.segment_roi = true;
+        else if (a == "--plane" && i + 1 < argc && strncmp(argv[i + 1], "fit", 3) == 0) { if (!parse_plane_fit(argv[++i], &map_opt.plane_params)) { usage(); return 2; } map_opt.fit_plane = true; }
+        else if (a == "--plane-mask") { need(1); map_opt.plane_mask = argv[++i]; }
         else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) map_opt.plane[k] = (float)atof(argv[++i]); map_opt.have_plane = true; }
         else if (a == "--labels-out") { need(1); map_opt.labels_out = argv[++i]; }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
@@ -591,7 +638,8 @@ int main(int argc, char **argv)
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
-        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || map_opt.have_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || map_opt.have_plane || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.fit_plane && map_opt.have_plane) || (!map_opt.fit_plane && !map_opt.plane_mask.empty()) ||
         (map_opt.segment_roi && (views.size() != 1 || !views[0].roi_path.empty() || !map_opt.roi_path.empty())) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
     in.grasp_area_length_x = (float)(sx + 14);     // client.cpp:183-184

@@ -9,6 +9,7 @@
 //   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
 //   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
 //   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
+//   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
@@ -398,6 +399,11 @@ struct haf_engine {
     DevBuf<int> d_seg_words;
     StageBuf seg_out;
     DevBuf<char> d_seg_image;
+    // haf_fit_plane (engine_plane.cpp), allocated by its first call: the points as three arrays of max_points words, one usable bit per
+    // pixel and one count per block of 1024 pixels behind them; the block [counters][moments][counts][hypothesis words][thresholds]
+    // [a host mask, max_points bytes] with its pinned twin
+    DevBuf<char> d_plane_scratch;
+    StageBuf plane_io;
 };
 
 namespace haf_host {

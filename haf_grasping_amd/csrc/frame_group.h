@@ -83,4 +83,16 @@ __device__ __forceinline__ void group_points(const FrameDev &f, unsigned i0, uns
     }
 }
 
+// the point of ONE pixel (u, v) inside the frame: for the kernels that own their pixels singly (segment.hip, plane.hip)
+template <int KIND> __device__ __forceinline__ void pixel_point(const FrameDev &f, int u, int v, float *p)
+{
+    const char *row = static_cast<const char *>(f.src) + (size_t)v * f.row_stride;
+    if constexpr (KIND == HAF_FRAME_DEPTH_U16) point_u16(f.m, (uint32_t)u, (uint32_t)v, *as_global<const uint16_t>(row + (size_t)u * 2), p);
+    else if constexpr (KIND == HAF_FRAME_DEPTH_F32) point_f32(f.m, (uint32_t)u, (uint32_t)v, __uint_as_float(*as_global<const unsigned>(row + (size_t)u * 4)), p);
+    else {
+        const global_ptr<const unsigned> s = as_global<const unsigned>(row + (size_t)u * f.point_stride);
+        point_xyz(f.m, __uint_as_float(s[0]), __uint_as_float(s[1]), __uint_as_float(s[2]), p);
+    }
+}
+
 }  // namespace haf

@@ -5,6 +5,7 @@
 #include "../../include/hafgrasp.h"
 #include "frame_points.h"
 #include "segment_rules.h"
+#include "plane_rules.h"
 
 #include <string>
 
@@ -45,5 +46,16 @@ int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, 
 int check_segment(const haf_frame *frame, const haf_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
                   int32_t out_on_device, const int32_t *n_labels, std::string &err);
 haf_segment_math::SegmentRules segment_rules(const haf_segment_params &p);
+// plane_host.cpp, shared by haf_fit_plane_ref and haf_fit_plane: every refusal of a frame, of the mask and of the parameters that needs
+// no engine; the rules' constants, tol2, cos2 and uu formed here; the winner of a count array (largest count, ties to the lowest k)
+int check_plane(const haf_frame *frame, const haf_roi *mask, const haf_plane_params *p, const haf_plane_result *out, std::string &err);
+haf_plane_math::PlaneRules plane_rules(const haf_plane_params &p);
+int plane_winner(const int32_t *counts, int32_t n_hyp);
+// THE plane of a fit, from integers only: the ten moments of the winner's inliers, the winner's four hypothesis words (the fall-back),
+// up (all zero: none) and the sensor's origin in the base frame -> plane[4] in metres, rounded to float, and the inliers' rms distance.
+// Both entry points call this one function on the same integers, so its double arithmetic need not be pinned across machines
+void plane_from_moments(const int64_t *moments, const float *hyp, const float *up, const float *origin, float *plane, double *rms);
+// everything of a result that follows the counts, the hypothesis words and the moments -- out->moments and stats[0..2] are filled by the caller
+void plane_finish(const haf_frame &f, const haf_plane_params &p, const int32_t *counts, const float *hyps, haf_plane_result *out);
 
 }  // namespace haf

@@ -571,6 +571,29 @@ constexpr int kSegScanPixels = 1024;               // pixels per workgroup of th
 inline size_t segment_scan_blocks(size_t n) { return (n + kSegScanPixels - 1) / kSegScanPixels; }
 // the seven launches of one call, in stream order: tile, seam, flatten, block totals, scan of the totals, numbering, write
 void launch_segment(const SegmentDev &d, hipStream_t s);
+// haf_fit_plane (plane.hip): one frame as the kernels read it -- a kernel argument, so every field is a scalar load.  f: the frame (dst
+// and count are not read); mask: null, or one byte per pixel, rows mask_stride bytes apart; x / y / z: f.n words each, the points with
+// every unusable one as three NaNs; bits: one 64-bit word per 64 pixels of plane_blocks(f.n) blocks, the usable pixels; prefix: a word
+// per block, its usable count, then the count of all blocks before it.  counters[4] (usable pixels, hypotheses that are not void),
+// moments[10] and counts[r.n_hyp] are zeroed by the caller; hyps: r.n_hyp x 4 words; thr: r.n_hyp words.  All of it device memory
+struct PlaneDev {
+    FrameDev f;
+    int height;
+    const unsigned char *mask;
+    unsigned long long mask_stride;
+    haf_plane_math::PlaneRules r;
+    float *x, *y, *z;
+    unsigned long long *bits;
+    int *prefix;
+    unsigned *counters;
+    unsigned long long *moments;
+    int *counts;
+    float *hyps, *thr;
+};
+constexpr int kPlaneBlockPixels = 1024;            // pixels per workgroup of the point and moment kernels, and per prefix word
+inline size_t plane_blocks(size_t n) { return (n + kPlaneBlockPixels - 1) / kPlaneBlockPixels; }
+// the five launches of one call, in stream order: points and usable bits, scan of the block counts, hypotheses, score, moments
+void launch_plane(const PlaneDev &d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

@@ -67,17 +67,6 @@ template <bool LDS> __device__ __forceinline__ void uf_unite(int *parent, int a,
     }
 }
 
-template <int KIND> __device__ __forceinline__ void pixel_point(const FrameDev &f, int u, int v, float *p)
-{
-    const char *row = static_cast<const char *>(f.src) + (size_t)v * f.row_stride;
-    if constexpr (KIND == HAF_FRAME_DEPTH_U16) point_u16(f.m, (uint32_t)u, (uint32_t)v, *as_global<const uint16_t>(row + (size_t)u * 2), p);
-    else if constexpr (KIND == HAF_FRAME_DEPTH_F32) point_f32(f.m, (uint32_t)u, (uint32_t)v, __uint_as_float(*as_global<const unsigned>(row + (size_t)u * 4)), p);
-    else {
-        const global_ptr<const unsigned> s = as_global<const unsigned>(row + (size_t)u * f.point_stride);
-        point_xyz(f.m, __uint_as_float(s[0]), __uint_as_float(s[1]), __uint_as_float(s[2]), p);
-    }
-}
-
 __device__ __forceinline__ int seg_tiles_x(int width) { return (width + kSegTileW - 1) / kSegTileW; }
 
 template <int KIND>

@@ -5,6 +5,7 @@ msg/GraspInput.msg:3-15, msg/GraspOutput.msg:1-7, and the server object CCalc_Gr
 (src/calc_grasppoints_action_server.cpp:107-229).  Field names and meanings are the reference's; the point
 cloud is a float32 [N, 3] array already in the base frame (the server transforms it at :316 before the hot path).
 """
+import ctypes as C
 import dataclasses
 from typing import Sequence
 
@@ -180,16 +181,28 @@ class CalcGraspPointsServer:
         c = np.asarray(goal.grasp_area_center, np.float64)
         return capi.segment_params(plane=[n[0], n[1], n[2], -float(n @ c)], **kw)
 
-    def execute_frame_segmented(self, goal: GraspInputMsg, frame, params=None, min_vote=1):
+    def execute_frame_segmented(self, goal: GraspInputMsg, frame, params=None, min_vote=1, plane=None):
         """execute_frame_objects() without a segmenter: the frame is clustered into objects on the device (haf_segment_frame: geometric
         tabletop clustering -- a height band over the support plane, 4-neighbours closer than max_gap are one object; touching objects
         are one object), the request is scored under that image as the device mask (haf_score_frames_roi) and every object gets its own
         best grasp from the same device image (haf_grasp_map_labels); the label image never leaves the device
         -> (GraspOutputMsg of the request, best_per_object()'s list).  params: a capi.segment_params(); None:
-        segment_params_from_goal(goal), whose plane passes through the goal's grasp area centre -- the caller owns the table height.
+        segment_params_from_goal(goal), whose plane passes through the goal's grasp area centre -- the caller owns the table height,
+        unless plane="fit" takes it from the frame.
         self.last_segment_infos / self.last_segment_stats: the objects' pixel counts, anchors and boxes, and [pixels, foreground,
-        components, components that pass the size rule]."""
+        components, components that pass the size rule].
+        plane: None -- the plane of `params` as it stands; "fit" or a capi.plane_params() -- the frame's dominant plane, fitted on the
+        device (haf_fit_plane) with the library's defaults or with those parameters, replaces it when one is found (else the plane of
+        `params` stays: the fall-back).  self.last_plane_fit: that fit's dict, None without one."""
         p = params if params is not None else self.segment_params_from_goal(goal)
+        self.last_plane_fit = None
+        if plane is not None:
+            if isinstance(plane, str) and plane != "fit":
+                raise ValueError("plane: None, \"fit\" or a capi.plane_params()")
+            self.last_plane_fit = self.engine.fit_plane(frame, None if isinstance(plane, str) else plane)
+            if self.last_plane_fit["found"]:
+                p = capi.SegmentParams.from_buffer_copy(p)
+                p.plane = (C.c_float * 4)(*self.last_plane_fit["plane"])
         img, self.last_segment_infos, self.last_segment_stats = self.engine.segment(frame, p, np.uint8, device_out=True)
         res = self.execute_frame(goal, frame, roi_mask=(img.data, img.row_stride_bytes))
         n = len(self.last_segment_infos)

@@ -622,7 +622,8 @@ int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
 /* ---- a depth frame into object labels on the device: geometric tabletop clustering (csrc/segment.hip) ---------------------------
  * The classic organised-cloud clustering, for the caller with one camera over a table and no segmenter: the label image every
  * haf_label_image and (as uint8) every haf_roi mask above asks for, from the frame itself.  It is geometry only -- a height band
- * over a plane the CALLER supplies and a distance between neighbouring pixels' points; touching objects are one object.
+ * over a plane the CALLER supplies (haf_fit_plane, below, estimates one from the same frame) and a distance between neighbouring
+ * pixels' points; touching objects are one object.
  *
  *   point       pixel i = v * width + u has haf_frame_points' three words; any kind of frame.
  *   foreground  all three words finite (the rule of haf_view_points) and, with
@@ -672,6 +673,67 @@ int  haf_segment_ref(const haf_frame *frame, const haf_segment_params *p, void *
 int  haf_segment_frame(haf_engine *e, const haf_frame *frame, const haf_segment_params *p, void *labels, int32_t elem_bytes,
                        size_t row_stride_bytes, int32_t out_on_device, haf_label_image *out_image /* may be NULL */,
                        haf_segment_info *info /* [max_labels], may be NULL */, int32_t *n_labels, int64_t *stats /* [4], may be NULL */);
+
+/* ---- the support plane of a depth frame, estimated on the device (csrc/plane.hip) -------------------------------------------------
+ * haf_segment_params.plane from the frame itself: the DOMINANT plane of the frame's points by a fixed set of three-point hypotheses
+ * and an exact integer refit of the winner's inliers.  One plane per call; no multi-plane bins, no smoothing over time.
+ *
+ *   usable point  pixel i = v * width + u has haf_frame_points' three words.  It is usable when all three are finite, |x|, |y|, |z|
+ *                 <= 16 m, and the mask -- a haf_roi over the frame, NULL or a NULL mask pointer meaning every pixel -- has a non-zero
+ *                 byte there.  n_usable counts them; the RANK of a usable pixel is its position among them in raster order.
+ *   sample        hypothesis k in [0, n_hyp), corner j in {0, 1, 2}: the usable pixel of rank
+ *                 (uint64(mix32(seed + 3 k + j)) * n_usable) >> 32, seed + 3 k + j wrapping in 32 bits,
+ *                 mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  (uint32 throughout).
+ *   hypothesis    a = p1 - p0, b = p2 - p0 componentwise; n = a x b, n0 = a1 b2 - a2 b1, n1 = a2 b0 - a0 b2, n2 = a0 b1 - a1 b0;
+ *                 d = -((n0 x0 + n1 y0) + n2 z0); nn = (n0 n0 + n1 n1) + n2 n2.  Every step ONE correctly rounded fp32 operation in
+ *                 the order written, never a fused multiply-add; the negation flips the sign bit.  VOID when two of its ranks coincide,
+ *                 nn is not finite, nn <= min_area2, or -- up not all zero -- with c = (n0 up0 + n1 up1) + n2 up2 NOT
+ *                 c c >= cos2 (nn uu); cos2 = (float)(cos(max_tilt)^2) and uu = (up0 up0 + up1 up1) + up2 up2 formed once on the host.
+ *   score         usable point p: r = ((n0 x + n1 y) + n2 z) + d; an inlier of k when r r <= tol2 nn, tol2 = tol * tol formed once on
+ *                 the host in fp32.  count[k] = the inliers of k, 0 for a void k.
+ *   winner        the largest count[k], ties to the lowest k.  found = count[winner] >= min_inliers and n_usable >= 3.
+ *   refit         over the winner's inliers, q = round-to-nearest-even(coordinate * 4096) as int32 (the product is exact, |q| <= 2^16):
+ *                 the ten int64 moments N, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of (qx, qy, qz).  All zero for a void winner.
+ *   plane         found only; else plane = 0, rms = 0.  From the moments' covariance numerators N Sab - Sa Sb (exact, 128 bits) the
+ *                 eigenvector of the smallest eigenvalue in double, d through the centroid, metres; oriented so that n . up > 0 when up
+ *                 is given and not perpendicular, else so that the sensor's origin (sensor_to_base[3], [7], [11]) has h > 0; rounded to
+ *                 float.  Where N < 3 or the two smallest eigenvalues coincide: the winning hypothesis, normalised and oriented.  rms =
+ *                 sqrt of the inliers' mean squared distance to the plane, metres.  plane is a haf_segment_params.plane as it stands.
+ *   stats         [0] pixels, [1] n_usable, [2] hypotheses that are not void, [3] count[winner].
+ *   counts, hyps  (either may be NULL) count[k], and per k the four words n0, n1, n2, d (any NaN as 0x7FC00000; four such words when
+ *                 n_usable = 0): what the two entry points are compared in.
+ * Counts and moments are integers: no result depends on an order of evaluation.
+ *
+ * haf_fit_plane_ref: the host definition of record -- no device, no engine, a host frame and a host mask only.
+ * haf_fit_plane: equal to it in every word of the result, of counts and of hyps; a host or device-resident frame, a host or
+ * device-resident mask.  Like haf_segment_frame the call neither reads nor changes last-batch state or stage timings, works before any
+ * request and with HAF_FLAG_PROBABILITY, and allocates its scratch (13 bytes x max_points, the copy-back block) on first use.
+ * Refusals, all before any device work, nothing written -- HAF_E_ARG: everything haf_score_frames refuses for a frame, a null frame, p
+ * or out, a parameter that is not finite, tol <= 0, min_area2 < 0, n_hyp outside 1..HAF_MAX_PLANE_HYP, min_inliers < 3, max_tilt
+ * outside [0, pi/2], a mask stride smaller than the width, a mask's on_device not 0 or 1, for the _ref form a device-resident frame or
+ * mask; HAF_E_CAPACITY: a frame of more than 2^28 pixels, width * height > max_points. */
+#define HAF_MAX_PLANE_HYP 1024
+typedef struct haf_plane_params {
+    float    tol;         /* metres, finite, > 0: a point within tol of a hypothesis is its inlier                */
+    float    min_area2;   /* m^4, finite, >= 0: hypotheses with |a x b|^2 <= this are void (collinear triples)   */
+    float    up[3];       /* base frame; all zero: no tilt test, the normal points at the sensor                 */
+    float    max_tilt;    /* radians in [0, pi/2]: largest angle between the plane's normal and +-up              */
+    int32_t  n_hyp;       /* 1..HAF_MAX_PLANE_HYP                                                                */
+    int32_t  min_inliers; /* >= 3                                                                                */
+    uint32_t seed;
+} haf_plane_params;
+typedef struct haf_plane_result {
+    float   plane[4];
+    int32_t found, winner, n_inliers, reserved;
+    double  rms;
+    int64_t stats[4];
+    int64_t moments[10];
+} haf_plane_result;
+void haf_plane_default(haf_plane_params *p);   /* 0.005f, 1e-6f, (0,0,0), 0, 256, 100, 1 */
+int  haf_fit_plane_ref(const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_plane_params *p, haf_plane_result *out,
+                       int32_t *counts /* [n_hyp], may be NULL */, float *hyps /* [n_hyp][4], may be NULL */);
+int  haf_fit_plane(haf_engine *e, const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_plane_params *p,
+                   haf_plane_result *out, int32_t *counts /* [n_hyp], may be NULL */, float *hyps /* [n_hyp][4], may be NULL */);
 
 int haf_abi_version(void);
 

@@ -14,6 +14,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <sstream>
 #include <string>
@@ -223,6 +224,25 @@ inline void segment_params_from_goal(const GoalFields &g, haf_segment_params *p)
     for (int k = 0; k < 3; k++) { n[k] /= len; d -= n[k] * g.center[k]; }
     for (int k = 0; k < 3; k++) p->plane[k] = (float)n[k];
     p->plane[3] = (float)d;
+}
+
+// The same without owning the table height: the support plane is the frame's dominant plane, fitted on the device (haf_fit_plane) with
+// `fit` (null: the library's defaults).  p comes in filled -- by segment_params_from_goal, say -- and only its plane changes, and only
+// when a plane was found: with *found == 0 the goal's plane stays, the fall-back.  result (may be null): the whole fit.  Returns
+// haf_fit_plane's status; on an error p is untouched and *found is 0.
+inline int segment_params_from_fit(haf_engine *e, const haf_frame *frame, haf_segment_params *p, int *found,
+                                   const haf_plane_params *fit = nullptr, haf_plane_result *result = nullptr)
+{
+    haf_plane_params defaults;
+    haf_plane_default(&defaults);
+    haf_plane_result r;
+    *found = 0;
+    const int rc = haf_fit_plane(e, frame, nullptr, fit ? fit : &defaults, &r, nullptr, nullptr);
+    if (rc != HAF_OK) return rc;
+    *found = r.found;
+    if (r.found) memcpy(p->plane, r.plane, sizeof p->plane);
+    if (result) *result = r;
+    return HAF_OK;
 }
 
 }  // namespace hafshim
