@@ -282,6 +282,7 @@ def _bind(path, testing):
         L.haf_test_overflow_stats.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_list.argtypes = [E, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.haf_test_snapshot_screen.argtypes = [E, C.c_int]
+        L.haf_test_prestage_forms.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_snapshot.argtypes = [E, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
         L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.haf_test_revote.argtypes = [E, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -815,6 +816,17 @@ class Engine:
         n = C.c_int()
         self._check(self._L.haf_test_fetch_list(self._h, which, buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return buf[:min(n.value, cap)].copy()
+
+    BIN_FORMS = ("k_bin", "k_bin_lds", "k_bin_tiles", "k_small_pre<true>", "k_bin_lds+k_small_pre<false>")
+    INTEGRAL_FORMS = ("k_integral_small", "k_integral_band", "k_small_pre")
+
+    def prestage_forms(self):
+        """Testing build (haf_test_prestage_forms): which pre-stage kernels served the last request -- bin (index into BIN_FORMS),
+        integral (index into INTEGRAL_FORMS), bucket_refused (the bucket-sorted binning path was refused because the grid's bucket count
+        exceeds its LDS histogram) and n_inexact_grids."""
+        out = (C.c_int * 4)()
+        self._check(self._L.haf_test_prestage_forms(self._h, out))
+        return dict(bin=out[0], integral=out[1], bucket_refused=bool(out[2]), n_inexact_grids=out[3])
 
     def snapshot_screen(self, on=True):
         """Testing build: from now on every request keeps a copy of what its screening feature pass wrote (fetch_snapshot)."""

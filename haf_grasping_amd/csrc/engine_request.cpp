@@ -499,11 +499,14 @@ static int run_prestages(haf_engine *e, Request &q)
     mark(e, HAF_ST_BIN);
     // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
     // (an ROI request, of frames or of views, takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
+    int fused_bin = -1;
     if (!e->prob_mode && !e->no_fused_pre && !q.from.roi)
-        q.fused_pre = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
-                                       e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
-                                       e->d_brslot.p, ++e->pre_epoch);
+        fused_bin = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
+                                     e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
+                                     e->d_brslot.p, ++e->pre_epoch);
+    q.fused_pre = fused_bin >= 0;
     if (q.fused_pre) {
+        e->pre_forms = PrestageForms{fused_bin, INTEGRAL_FUSED, false};
         mark(e, HAF_ST_INTEGRAL);
         mark(e, HAF_ST_MASK);
         return HAF_OK;
@@ -514,10 +517,11 @@ static int run_prestages(haf_engine *e, Request &q)
     bs.bkt_count = e->d_bkt.p; bs.bkt_off = e->d_bkt.p ? e->d_bkt.p + (size_t)c.max_clouds * e->bkt_ints : nullptr;
     bs.bkt_cursor = e->d_bkt.p ? e->d_bkt.p + (size_t)2 * c.max_clouds * e->bkt_ints : nullptr;
     bs.bkt_cap = e->d_bkt.p ? c.max_clouds * e->bkt_ints : 0;
-    launch_bin(q.d_clouds, q.h_clouds, q.max_n, q.total_n, q.d_geo, e->d_heights.p, d, q.r_row, q.r_col, q.bucket_ok && !e->no_bucket_sort, bs,
-               e->d_counters.p, s);
+    const BinChoice bin = launch_bin(q.d_clouds, q.h_clouds, q.max_n, q.total_n, q.d_geo, e->d_heights.p, d, q.r_row, q.r_col,
+                                     q.bucket_ok && !e->no_bucket_sort, bs, e->d_counters.p, s);
     mark(e, HAF_ST_INTEGRAL);
-    launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
+    const int integral = launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
+    e->pre_forms = PrestageForms{bin.form, integral, bin.bucket_refused};
     mark(e, HAF_ST_MASK);
     if (q.from.roi) {
         const RoiViews rv{q.d_frames, q.h_frames, q.d_roi_views, q.h_roi_views, q.n_frames};

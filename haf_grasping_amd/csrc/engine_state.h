@@ -176,6 +176,10 @@ struct LastCall {
     bool roi = false;            // the batch was an ROI request: d_roi_cells holds its B x R cell sets (HAF_DBG_ROI)
 };
 
+// which forms of the pre-stages the launchers chose for the last request that reached them (kernels.h: BinForm, IntegralForm); read by
+// the testing build's haf_test_prestage_forms only
+struct PrestageForms { int bin = -1, integral = -1; bool bucket_refused = false; };
+
 // haf_score_frames_roi / haf_score_views_roi: what the request path (engine_request.cpp) needs of the call, filled by engine_roi.cpp.
 // Per VIEW, by the flat view index (haf_score_frames_roi: one view per request); a view of haf_score_views_roi may have no mask
 struct RoiCall {
@@ -287,6 +291,7 @@ struct haf_engine {
     DevBuf<unsigned long long> d_tier_words;   // exact tiers: one "undecided" bit per entry of a window, for the ordered hand-over lists
     DevBuf<unsigned long long> d_brslot;   // k_small_pre: per (cloud, roll) {request epoch, evaluations} in one word (ordered evaluation list)
     unsigned pre_epoch = 0;
+    PrestageForms pre_forms;        // run_prestages (engine_request.cpp)
     struct View { int *p = nullptr; } d_counters;      // inside out_block
     DevBuf<float> d_X, d_ax, d_dec, d_svt;
     DevBuf<char> d_svt_h;            // split-fp16 SV tile images

@@ -113,6 +113,16 @@ int haf_test_overflow_stats(haf_engine *e, long long *out2)
     out2[0] = e->stat_flag0_overflows; out2[1] = e->stat_extra_windows;
     return HAF_OK;
 }
+// which pre-stage kernels served the last request, as run_prestages got it from the launchers (kernels.h: BinForm, IntegralForm):
+// out[0] the binning form -- 0 k_bin, 1 k_bin_lds, 2 bucket-sorted k_bin_tiles, 3 inside k_small_pre<true>, 4 k_bin_lds followed by
+// k_small_pre<false>; out[1] the integral form -- 0 k_integral_small, 1 band form, 2 inside k_small_pre; out[2] 1 when launch_bin refused the
+// bucket-sorted path because the bucket grid exceeds kBktMaxBuckets; out[3] n_inexact_grids.  -1, -1, 0, 0 before the first request.
+int haf_test_prestage_forms(haf_engine *e, int *out4)
+{
+    if (!e || !out4) return HAF_E_ARG;
+    out4[0] = e->pre_forms.bin; out4[1] = e->pre_forms.integral; out4[2] = e->pre_forms.bucket_refused ? 1 : 0; out4[3] = e->last.inexact;
+    return HAF_OK;
+}
 // Snapshot of the screening feature pass: with on != 0 every later request whose screening tier runs its feature kernel copies what that
 // kernel wrote -- the fp16 operand images (20 KiB per tile of 32 evaluations), the 8 band floats per evaluation (the RAW sums in the
 // low-rank form) and a_x -- aside before the sweep, the projection and the later tiers reuse the buffers.  Sized for the engine's

@@ -393,16 +393,32 @@ struct BinScratch {
     int bkt_cap;         // bucket counters per array
 };
 int bin_bucket_grid(int H, int *bucket_cells);     // buckets per side for a grid of H cells; bucket edge in cells
-// returns true when the bucket-sorted path ran (it also fills the empty cells: no separate fill launch needed)
-bool launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, long total_n, const RollGeo *geo, int *hkeys, Dims d,
-                float r_row, float r_col, bool bucket_ok, BinScratch bs, int *counters, hipStream_t s);   // counters[CNT_ERROR]: a tile's bucket list overflowed
-// small grids: a1 (tail) + a2 + a3 + a4 in one launch, one workgroup per (cloud, roll); false when the grid does not fit LDS
-bool launch_small_pre(const CloudDev *clouds, const RollGeo *geo, int max_n, int *hkeys, float *ii, uint8_t *mask, int *rowcount,
-                      int *brcount, int8_t *labels, int *evalcell, int *counters, int *flag_list, bool direct, Dims d, float r_row,
-                      float r_col, hipStream_t s, unsigned long long *brslot = nullptr, unsigned epoch = 0);
+// Which form of the binning and of the integral image served a request: the launchers choose by shape thresholds and say what they
+// chose (the testing build hands it on: haf_test_prestage_forms)
+enum BinForm { BIN_GLOBAL = 0,        // k_bin: one global atomicMax per (point, roll); also a request without points (the fill alone)
+               BIN_LDS = 1,           // k_bin_lds
+               BIN_TILES = 2,         // the bucket-sorted path: k_bkt_* + k_bin_tiles
+               BIN_FUSED = 3,         // inside k_small_pre<true>
+               BIN_LDS_FUSED = 4 };   // k_bin_lds, then k_small_pre<false>
+enum IntegralForm { INTEGRAL_SMALL = 0,   // k_integral_small
+                    INTEGRAL_BAND = 1,    // k_integral_totals + k_integral_band (+ k_integral_seq for a grid whose sums were inexact)
+                    INTEGRAL_FUSED = 2 }; // inside k_small_pre
+struct BinChoice {
+    int form;                // BinForm
+    bool bucket_refused;     // everything asked for the bucket-sorted path but the bucket grid exceeds its LDS histogram: k_bin instead
+};
+// the bucket-sorted path also fills the empty cells: no separate fill launch needed
+BinChoice launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, long total_n, const RollGeo *geo, int *hkeys, Dims d,
+                     float r_row, float r_col, bool bucket_ok, BinScratch bs, int *counters, hipStream_t s);   // counters[CNT_ERROR]: a tile's bucket list overflowed
+// small grids: a1 (tail) + a2 + a3 + a4 in one launch, one workgroup per (cloud, roll); -1 when the grid does not fit LDS, else the
+// BinForm that ran (BIN_FUSED or BIN_LDS_FUSED)
+int launch_small_pre(const CloudDev *clouds, const RollGeo *geo, int max_n, int *hkeys, float *ii, uint8_t *mask, int *rowcount,
+                     int *brcount, int8_t *labels, int *evalcell, int *counters, int *flag_list, bool direct, Dims d, float r_row,
+                     float r_col, hipStream_t s, unsigned long long *brslot = nullptr, unsigned epoch = 0);
 size_t small_pre_lds(int H, int W);
-void launch_integral(int *hkeys_heights, double *rowsum, float *ii, int *inexact_flags, int *counters, Dims d, hipStream_t s,
-                     unsigned long long *abs_total = nullptr);   // per (cloud, roll): sum of |height| in units of 2^-20 m, rounded up (parallel form only; low-rank screening form)
+// -> the IntegralForm that ran
+int launch_integral(int *hkeys_heights, double *rowsum, float *ii, int *inexact_flags, int *counters, Dims d, hipStream_t s,
+                    unsigned long long *abs_total = nullptr);   // per (cloud, roll): sum of |height| in units of 2^-20 m, rounded up (parallel form only; low-rank screening form)
 void launch_mask_count(const float *ii, const RollGeo *geo, uint8_t *mask, int *rowcount, Dims d, hipStream_t s);
 void launch_scan(const int *rowcount, int *rowoff, int *brcount, int *counters, Dims d, hipStream_t s);
 void launch_compact(const uint8_t *mask, const int *rowcount, const int *rowoff, int *evalcell, Dims d, hipStream_t s);

@@ -140,13 +140,18 @@ __global__ __launch_bounds__(256) void k_bin_lds(const CloudDev *__restrict__ cl
 // max is order independent and the cell of a point is computed by the same fp32 expression: the grid is k_bin's bit for bit.
 constexpr int kBinTile = 64;
 constexpr int kBktChunk = 2048;                  // points per workgroup in the counting-sort passes
-constexpr int kBktMaxBuckets = 9216;             // LDS histogram (36 KiB); bin_bucket_grid keeps nb*nb below it
+// LDS histogram (36 KiB).  bin_bucket_grid does NOT keep nb*nb + 1 below it for every grid: nb = floor(2 Rb / bs) + 1 with the bucket edge
+// bc = max(H / 64, 8) cells, so nb grows with H until H / 64 steps up -- 93 at 512 and at 576, but 96 at 527 and 97 at 601.  From
+// nb = 96 on (9 217 counters) launch_bin refuses the bucket-sorted path and such a request is binned by k_bin, one global atomicMax per
+// point and roll: correct, slower.  That is the upper part of every 64-step above 512 -- H in 527..575, 592..639, 658..703, 724..767,
+// 790..831, ... 2302..2303: 718 grid sizes, none above 2303 (bc has grown enough by then) and none up to 526.
+constexpr int kBktMaxBuckets = 9216;
 constexpr int kBktListCap = 1024;                // candidate buckets of one tile (a 64-cell tile reaches ~120 buckets of 8 cells)
 constexpr float kBktSlack = 0.002f;              // metres
 
 int bin_bucket_grid(int H, int *bucket_cells)
 {
-    int bc = H / 64 > 8 ? H / 64 : 8;              // bucket edge in cells: nb stays ~ 1.414 * 64 + 3 for any grid size
+    int bc = H / 64 > 8 ? H / 64 : 8;              // bucket edge in cells: nb is ~ 1.414 * H / bc + 3, up to 102 (kBktMaxBuckets)
     const double r = 0.005 * H, bs = 0.01 * bc, Rb = r * 1.41422 + bs;
     int nb = (int)(2.0 * Rb / bs) + 1;
     if (bucket_cells) *bucket_cells = bc;
@@ -351,8 +356,8 @@ __global__ __launch_bounds__(kBinTileThreads) void k_bin_tiles(const CloudDev *_
     }
 }
 
-bool launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, long total_n, const RollGeo *geo, int *hkeys, Dims d,
-                float r_row, float r_col, bool bucket_ok, BinScratch bs, int *counters, hipStream_t s)
+BinChoice launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, long total_n, const RollGeo *geo, int *hkeys, Dims d,
+                     float r_row, float r_col, bool bucket_ok, BinScratch bs, int *counters, hipStream_t s)
 {
     const int HW = d.H * d.W;
     float minus_one = -1.0f;
@@ -363,8 +368,9 @@ bool launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, 
     const int nb = bin_bucket_grid(d.H, &bc);
     const long nbk1 = (long)nb * nb + 1;
     // the bucket-sorted path: grids too large for k_bin_lds, enough points for the three sorting passes to pay, square grid
-    if (bucket_ok && HW > kBinLdsCells && total_n >= 32768 && d.H == d.W && nbk1 <= kBktMaxBuckets && total_n <= bs.sorted_cap &&
-        nbk1 * d.B <= bs.bkt_cap) {
+    const bool bucket_wanted = bucket_ok && HW > kBinLdsCells && total_n >= 32768 && d.H == d.W && total_n <= bs.sorted_cap && nbk1 * d.B <= bs.bkt_cap;
+    const bool bucket_fits = nbk1 <= kBktMaxBuckets;                 // (the LDS histograms of k_bkt_count / k_bkt_scatter)
+    if (bucket_wanted && bucket_fits) {
         (void)hipMemsetAsync(bs.bkt_count, 0, (size_t)nbk1 * d.B * sizeof(int), s);
         dim3 grid((max_n + kBktChunk - 1) / kBktChunk, d.B);
         hipLaunchKernelGGL(k_bkt_count, grid, dim3(256), 0, s, clouds, bs.bkt_count, d);
@@ -373,19 +379,20 @@ bool launch_bin(const CloudDev *clouds, const CloudDev *clouds_host, int max_n, 
         const int tiles = ((d.H + kBinTile - 1) / kBinTile) * ((d.W + kBinTile - 1) / kBinTile);
         hipLaunchKernelGGL(k_bin_tiles, dim3(tiles, d.B * d.R), dim3(kBinTileThreads), 0, s, clouds, geo, bs.sorted, bs.bkt_off, hkeys, d, r_row, r_col,
                            key_empty, counters);
-        return true;
+        return BinChoice{BIN_TILES, false};
     }
+    const bool refused = bucket_wanted && !bucket_fits;
     (void)clouds_host;
     launch_fill_i32(hkeys, key_empty, (size_t)d.B * d.R * HW, s);
-    if (max_n <= 0) return false;
+    if (max_n <= 0) return BinChoice{BIN_GLOBAL, refused};
     if (HW <= kBinLdsCells && max_n >= 4 * kBinChunk) {
         dim3 grid((max_n + kBinChunk - 1) / kBinChunk, d.B * d.R);
         hipLaunchKernelGGL(k_bin_lds, grid, dim3(256), (size_t)HW * sizeof(int), s, clouds, geo, hkeys, d, r_row, r_col, key_empty);
-        return false;
+        return BinChoice{BIN_LDS, refused};
     }
     dim3 grid((max_n + 255) / 256, d.B * d.R);
     hipLaunchKernelGGL(k_bin, grid, dim3(256), 0, s, clouds, geo, hkeys, d, r_row, r_col);
-    return false;
+    return BinChoice{BIN_GLOBAL, refused};
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -647,7 +654,7 @@ __global__ __launch_bounds__(kIThreads) void k_integral_band(int *hk, const doub
     if (__syncthreads_or(inexact) && tid == 0) atomicOr(&inexact_flags[br], 1);
 }
 
-// Small grids (the reference's 56 x 56, up to ~70 x 70): the whole grid of a roll fits LDS, and three launches cost more than the
+// Small grids (the reference's 56 x 56, up to 70 x 70: launch_integral): the whole grid of a roll fits LDS, and three launches cost more than the
 // work.  One workgroup per (cloud, roll) does the SEQUENTIAL summation itself -- a thread per row, then a thread per column,
 // fp64, in LDS -- which is the reference's order by construction (no exactness check needed), in one launch.
 constexpr int kISmallCells = 8192;               // H * W up to this is worth checking; the LDS need decides (launch_integral)
@@ -689,14 +696,14 @@ __global__ __launch_bounds__(256) void k_integral_small(int *hk, float *__restri
     }
 }
 
-void launch_integral(int *hk, double *rowsum, float *ii, int *inexact_flags, int *counters, Dims d, hipStream_t s, unsigned long long *abs_total)
+int launch_integral(int *hk, double *rowsum, float *ii, int *inexact_flags, int *counters, Dims d, hipStream_t s, unsigned long long *abs_total)
 {
     if (d.H * d.W <= kISmallCells) {
         const int pitch = ((d.W + 15) / 16) * 16 + 1;
         const size_t lds = (size_t)d.H * pitch * sizeof(double) + (size_t)d.H * d.W * sizeof(float);
-        if (lds <= 64 * 1024) {                               // (the default dynamic-LDS limit: grids up to ~70 x 70)
+        if (lds <= 64 * 1024) {                               // (the default dynamic-LDS limit: square grids up to 70 x 70)
             hipLaunchKernelGGL(k_integral_small, dim3(d.B * d.R), dim3(256), lds, s, hk, ii, d);
-            return;
+            return INTEGRAL_SMALL;
         }
     }
     // rowsum doubles as the band-total scratch of the parallel form ([B*R][bands][W] doubles, far smaller) and as the row-sum
@@ -708,6 +715,7 @@ void launch_integral(int *hk, double *rowsum, float *ii, int *inexact_flags, int
     hipLaunchKernelGGL(k_integral_band, dim3(n_bands, d.B * d.R), dim3(kIThreads), 0, s, hk, rowsum, ii, inexact_flags, d);
     // sequential order for the grids whose parallel sums were not exact (practically never; the kernels exit at once otherwise)
     hipLaunchKernelGGL(k_integral_seq, dim3(d.B * d.R), dim3(256), 0, s, hk, rowsum, ii, inexact_flags, counters, d);
+    return INTEGRAL_BAND;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1074,13 +1082,14 @@ __global__ __launch_bounds__(kSmallPreThreads) void k_small_pre(const CloudDev *
     }
 }
 
-// true when the fused form ran (then nothing else of a1 tail / a2 / a3 / a4 has to be launched, and the labels are initialised)
-bool launch_small_pre(const CloudDev *clouds, const RollGeo *geo, int max_n, int *hkeys, float *ii, uint8_t *mask, int *rowcount,
-                      int *brcount, int8_t *labels, int *evalcell, int *counters, int *flag_list, bool direct, Dims d, float r_row,
-                      float r_col, hipStream_t s, unsigned long long *brslot, unsigned epoch)
+// the binning form when the fused form ran (then nothing else of a1 tail / a2 / a3 / a4 has to be launched, and the labels are
+// initialised), -1 when it did not
+int launch_small_pre(const CloudDev *clouds, const RollGeo *geo, int max_n, int *hkeys, float *ii, uint8_t *mask, int *rowcount,
+                     int *brcount, int8_t *labels, int *evalcell, int *counters, int *flag_list, bool direct, Dims d, float r_row,
+                     float r_col, hipStream_t s, unsigned long long *brslot, unsigned epoch)
 {
     const size_t lds = small_pre_lds(d.H, d.W);
-    if (lds > 64 * 1024) return false;                    // (the default dynamic-LDS limit: grids up to ~58 x 58)
+    if (lds > 64 * 1024) return -1;                       // (the default dynamic-LDS limit: square grids up to 63 x 63 -- 65 272 bytes; 64 x 64 needs 66 820)
     float minus_one = -1.0f;
     int key_empty;
     memcpy(&key_empty, &minus_one, 4);
@@ -1088,15 +1097,15 @@ bool launch_small_pre(const CloudDev *clouds, const RollGeo *geo, int max_n, int
     if (max_n <= kSmallPreMaxPoints) {
         hipLaunchKernelGGL(k_small_pre<true>, dim3(d.B * d.R), dim3(kSmallPreThreads), lds, s, clouds, geo, hkeys, ii, mask, rowcount, brcount,
                            labels, evalcell, counters, flag_list, direct ? 1 : 0, d, r_row, r_col, key_empty, brslot, epoch);
-    } else {
-        // a large cloud: many workgroups bin it (k_bin_lds: LDS-private grids, one global atomicMax per touched cell), then the rest
-        launch_fill_i32(hkeys, key_empty, (size_t)d.B * d.R * d.H * d.W, s);
-        dim3 grid((max_n + kBinChunk - 1) / kBinChunk, d.B * d.R);
-        hipLaunchKernelGGL(k_bin_lds, grid, dim3(256), (size_t)d.H * d.W * sizeof(int), s, clouds, geo, hkeys, d, r_row, r_col, key_empty);
-        hipLaunchKernelGGL(k_small_pre<false>, dim3(d.B * d.R), dim3(kSmallPreThreads), lds, s, clouds, geo, hkeys, ii, mask, rowcount, brcount,
-                           labels, evalcell, counters, flag_list, direct ? 1 : 0, d, r_row, r_col, key_empty, brslot, epoch);
+        return BIN_FUSED;
     }
-    return true;
+    // a large cloud: many workgroups bin it (k_bin_lds: LDS-private grids, one global atomicMax per touched cell), then the rest
+    launch_fill_i32(hkeys, key_empty, (size_t)d.B * d.R * d.H * d.W, s);
+    dim3 grid((max_n + kBinChunk - 1) / kBinChunk, d.B * d.R);
+    hipLaunchKernelGGL(k_bin_lds, grid, dim3(256), (size_t)d.H * d.W * sizeof(int), s, clouds, geo, hkeys, d, r_row, r_col, key_empty);
+    hipLaunchKernelGGL(k_small_pre<false>, dim3(d.B * d.R), dim3(kSmallPreThreads), lds, s, clouds, geo, hkeys, ii, mask, rowcount, brcount,
+                       labels, evalcell, counters, flag_list, direct ? 1 : 0, d, r_row, r_col, key_empty, brslot, epoch);
+    return BIN_LDS_FUSED;
 }
 
 }  // namespace haf
