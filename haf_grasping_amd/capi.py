@@ -125,6 +125,28 @@ class LabelPick(C.Structure):
 LABEL_PICK_DTYPE = np.dtype([(f, np.int32) for f in ("found", "u", "v", "vote", "roll", "cell", "n_pixels")])
 assert LABEL_PICK_DTYPE.itemsize == C.sizeof(LabelPick) == 28
 
+SHAPE_DIRS = 12                      # HAF_SHAPE_DIRS: directions of haf_measure_labels' fan, 15 degrees apart
+SHAPE_COS = (8192, 7913, 7094, 5793, 4096, 2120, 0, -2120, -4096, -5793, -7094, -7913)      # HAF_SHAPE_COS
+SHAPE_SIN = (0, 2120, 4096, 5793, 7094, 7913, 8192, 7913, 7094, 5793, 4096, 2120)           # HAF_SHAPE_SIN
+SHAPE_NN = tuple(c * c + s_ * s_ for c, s_ in zip(SHAPE_COS, SHAPE_SIN))                    # HAF_SHAPE_NN
+
+
+class LabelShape(C.Structure):
+    """haf_label_shape: the integers of one label's points in the base frame and the box derived from them"""
+    _fields_ = [("sum", C.c_int64 * 3), ("found", C.c_int32), ("n_pixels", C.c_int32), ("n_points", C.c_int32), ("narrow_dir", C.c_int32),
+                ("q_min", C.c_int32 * 3), ("q_max", C.c_int32 * 3), ("t_min", C.c_int32 * SHAPE_DIRS), ("t_max", C.c_int32 * SHAPE_DIRS),
+                ("h_max", C.c_float), ("centroid", C.c_float * 3), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("width", C.c_float * SHAPE_DIRS), ("narrow_width", C.c_float), ("long_width", C.c_float), ("yaw", C.c_float),
+                ("diameter", C.c_float), ("height", C.c_float), ("reserved", C.c_int32)]
+
+
+LABEL_SHAPE_DTYPE = np.dtype([("sum", np.int64, 3), ("found", np.int32), ("n_pixels", np.int32), ("n_points", np.int32), ("narrow_dir", np.int32),
+                              ("q_min", np.int32, 3), ("q_max", np.int32, 3), ("t_min", np.int32, SHAPE_DIRS), ("t_max", np.int32, SHAPE_DIRS),
+                              ("h_max", np.float32), ("centroid", np.float32, 3), ("box_min", np.float32, 3), ("box_max", np.float32, 3),
+                              ("width", np.float32, SHAPE_DIRS), ("narrow_width", np.float32), ("long_width", np.float32), ("yaw", np.float32),
+                              ("diameter", np.float32), ("height", np.float32), ("reserved", np.int32)])
+assert LABEL_SHAPE_DTYPE.itemsize == C.sizeof(LabelShape) == 272
+
 ATTR_RECORD_DTYPE = np.dtype([("feature", np.float32), ("pad", np.float32), ("q4", np.float64), ("scaled", np.float64)])
 assert ATTR_RECORD_DTYPE.itemsize == 24
 
@@ -231,6 +253,9 @@ def _bind(path, testing):
     L.haf_plane_default.restype = None
     L.haf_fit_plane_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
     L.haf_fit_plane.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
+    L.haf_measure_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
+    L.haf_measure_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
+    L.haf_object_input.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_void_p, C.c_int32, C.POINTER(GraspInput), C.POINTER(C.c_int32)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -595,6 +620,46 @@ def fit_plane_ref(frame, params=None, mask=None, debug=False):
     if rc != HAF_OK:
         raise HafError(rc, "haf_fit_plane_ref refused its arguments")
     return _plane_result(res, p.n_hyp, counts, hyps, debug)
+
+
+def _shape_plane(plane):
+    """None or four floats -> (pointer or None, keep-alive)"""
+    if plane is None:
+        return None, None
+    keep = np.ascontiguousarray(np.asarray(plane, dtype=np.float32).reshape(-1)[:4])
+    assert keep.size == 4
+    return keep.ctypes.data, keep
+
+
+def measure_labels_ref(frame, labels, n_labels=None, plane=None):
+    """haf_measure_labels_ref: the host definition of record of every label's box in the base frame.  frame: a host Frame; labels: a host
+    uint8 / uint16 [height, width] array (label_image()); plane: None or the four floats of a segment_params plane, for the heights
+    -> LABEL_SHAPE_DTYPE [n_labels] (label l is entry l - 1)."""
+    img, n_labels = label_image(labels, frame, n_labels)
+    ptr, keep = _shape_plane(plane)
+    shapes = np.zeros(max(1, n_labels), LABEL_SHAPE_DTYPE)
+    rc = lib().haf_measure_labels_ref(C.byref(frame), C.byref(img), n_labels, ptr, shapes.ctypes.data)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_measure_labels_ref refused its arguments")
+    return shapes[:n_labels]
+
+
+def shape_to_dict(shape):
+    """one entry of a LABEL_SHAPE_DTYPE array -> dict of plain Python values (lists for the arrays)"""
+    return {k: (shape[k].tolist() if np.ndim(shape[k]) else shape[k].item()) for k in LABEL_SHAPE_DTYPE.names if k != "reserved"}
+
+
+def object_input(cfg, base, shape, margin_cells=4):
+    """haf_object_input: the GraspInput `base` re-centred on the box of `shape` (one entry of a LABEL_SHAPE_DTYPE array) with a square
+    grasp area that covers the object and margin_cells more cells under every roll -> (GraspInput, fits); fits is False when the area
+    had to be cut to the engine's grid (Config `cfg`)."""
+    one = np.zeros(1, LABEL_SHAPE_DTYPE)
+    one[0] = shape
+    out, fits = GraspInput(), C.c_int32(-1)
+    rc = lib().haf_object_input(C.byref(cfg), C.byref(base), one.ctypes.data, margin_cells, C.byref(out), C.byref(fits))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_object_input refused its arguments")
+    return out, bool(fits.value)
 
 
 def view_points(frames):
@@ -1105,6 +1170,16 @@ class Engine:
         self._check(self._L.haf_fit_plane(self._h, C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(p), C.byref(res),
                                           counts.ctypes.data if debug else None, hyps.ctypes.data if debug else None))
         return _plane_result(res, p.n_hyp, counts, hyps, debug)
+
+    def measure_labels(self, frame, labels, n_labels=None, plane=None):
+        """haf_measure_labels: a Frame (any kind, host or device-resident) and its label image (label_image(): a numpy uint8 / uint16
+        array, a device tensor, a device pointer tuple, or the LabelImage segment(..., device_out=True) returned) -> the array
+        measure_labels_ref gives, computed on the device in one pass.  plane: None or four floats, for the heights."""
+        img, n_labels = label_image(labels, frame, n_labels)
+        ptr, keep = _shape_plane(plane)
+        shapes = np.zeros(max(1, n_labels), LABEL_SHAPE_DTYPE)
+        self._check(self._L.haf_measure_labels(self._h, C.byref(frame), C.byref(img), n_labels, ptr, shapes.ctypes.data))
+        return shapes[:n_labels]
 
     def cell_pose(self, request, roll, row, col):
         """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""

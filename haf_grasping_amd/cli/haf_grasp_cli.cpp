@@ -29,6 +29,13 @@
 //                                     1.. the objects); after the normal output one line "object <label> <u> <v> <hypothesis>" per object
 //                                     that has a pixel whose vote is at least --mask-min-vote, best first (haf_grasp_map_labels: one
 //                                     device pass for all objects); may be combined with --roi-mask
+//   --labels FILE.pgm --measure       no request is scored: one line "shape <label> found <0|1> pixels <n> points <n> centroid <x y z> box
+//                                     <xmin ymin zmin xmax ymax zmax> width <narrow_width> long <long_width> yaw <deg> diameter <d>
+//                                     height <h>" per label 1..max (haf_measure_labels; --plane A B C D gives the heights, else nan)
+//   --segment ... --per-object [MARGIN]   instead of the one request around --center: one request per segmented object, centred on its
+//                                     box with a grasp area that covers it and MARGIN (default 4) more cells (haf_measure_labels,
+//                                     haf_object_input, batched haf_score_frames_roi under the label image); one line "object <label>
+//                                     <u> <v> <hypothesis> width <narrow_width> yaw <deg> height <h>" per object, best first
 //   --segment MIN_H,MAX_H,GAP,MIN_PX | default
 //                                     with --depth: no segmenter at hand -- the first view is clustered into objects on the device
 //                                     (haf_segment_frame: pixels MIN_H..MAX_H metres above the support plane, MAX_H <= 0: no upper limit;
@@ -145,6 +152,7 @@ static void usage()
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
             "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
+            "  --labels FILE.pgm --measure [--plane A B C D]     --segment ... --per-object [MARGIN]      (with ONE --depth)\n"
             "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D | --plane fit[,TOL,N_HYP] [--plane-mask FILE.pgm]] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
@@ -198,6 +206,10 @@ struct MapOptions {
     std::string labels_out;
     std::vector<uint8_t> seg_labels;     // filled by run_depth
     int32_t seg_n = 0;
+    float seg_plane[4] = {0, 0, 1, 0};   // the plane the segmentation ran over (filled by run_depth)
+    // --per-object [MARGIN]: a request per segmented object; --measure: the shapes of --labels, no request
+    bool per_object = false, measure = false;
+    int margin_cells = 4;
 };
 
 // --segment MIN_H,MAX_H,GAP,MIN_PX or "default"
@@ -388,6 +400,102 @@ static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, c
     return 0;
 }
 
+// an 8- or 16-bit binary PGM of w x h label samples -> the image as the library reads it; *lab16 is the caller's to haf_free
+static bool load_labels(const std::string &path, int w, int h, std::vector<uint8_t> &lab8, uint16_t **lab16, haf_label_image *img, unsigned *top)
+{
+    int w8 = 0, h8 = 0;
+    int32_t w16 = 0, h16 = 0;
+    char err[256];
+    *lab16 = nullptr;
+    if (read_pgm8(path, lab8, w8, h8)) { w16 = w8; h16 = h8; }
+    else if (haf_pgm16_load(path.c_str(), lab16, &w16, &h16, err, sizeof err) != HAF_OK) {
+        fprintf(stderr, "%s: not a binary 8- or 16-bit PGM (%s)\n", path.c_str(), err);
+        return false;
+    }
+    if (w16 != w || h16 != h) { fprintf(stderr, "%s: %d x %d, the depth image has %d x %d\n", path.c_str(), (int)w16, (int)h16, w, h); return false; }
+    *top = 0;
+    for (size_t i = 0; i < (size_t)w * (size_t)h; i++) *top = std::max(*top, *lab16 ? (unsigned)(*lab16)[i] : (unsigned)lab8[i]);
+    *img = haf_label_image{*lab16 ? (const void *)*lab16 : (const void *)lab8.data(), *lab16 ? 2 : 1, 0, (size_t)w * (*lab16 ? 2 : 1)};
+    return true;
+}
+
+// --labels FILE.pgm --measure: the shapes of the label image over the frame, no request
+static int run_measure(haf_engine *eng, const haf_frame &f, const MapOptions &mo)
+{
+    std::vector<uint8_t> lab8;
+    uint16_t *lab16 = nullptr;
+    haf_label_image img;
+    unsigned top = 0;
+    if (!load_labels(mo.labels_path, f.width, f.height, lab8, &lab16, &img, &top)) { if (lab16) haf_free(lab16); return 1; }
+    const int32_t n = (int32_t)std::min(std::max(top, 1u), (unsigned)HAF_MAX_LABELS);
+    std::vector<haf_label_shape> shapes((size_t)n);
+    const int rc = haf_measure_labels(eng, &f, &img, n, mo.have_plane ? mo.plane : nullptr, shapes.data());
+    if (lab16) haf_free(lab16);
+    if (rc != HAF_OK) { fprintf(stderr, "--measure: %s\n", haf_last_error(eng)); return 1; }
+    for (int32_t l = 0; l < n; l++) {
+        const haf_label_shape &s = shapes[(size_t)l];
+        printf("shape %d found %d pixels %d points %d centroid %.9g %.9g %.9g box %.9g %.9g %.9g %.9g %.9g %.9g width %.9g long %.9g yaw %d diameter %.9g height %.9g\n",
+               (int)l + 1, (int)s.found, (int)s.n_pixels, (int)s.n_points, s.centroid[0], s.centroid[1], s.centroid[2], s.box_min[0], s.box_min[1],
+               s.box_min[2], s.box_max[0], s.box_max[1], s.box_max[2], s.narrow_width, s.long_width, (int)s.narrow_dir * 15, s.diameter, s.height);
+    }
+    return 0;
+}
+
+// --segment ... --per-object: one request per object of the segmentation (mo.seg_labels, mo.seg_n, mo.seg_plane), each centred on its
+// object, in chunks of cfg.max_clouds requests that share the frame and the label image as their mask
+static int run_per_object(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const haf_frame &f, const MapOptions &mo)
+{
+    if (mo.seg_n < 1) return 0;
+    const size_t n = (size_t)mo.seg_n;
+    const haf_label_image img = {mo.seg_labels.data(), 1, 0, (size_t)f.width};
+    std::vector<haf_label_shape> shapes(n);
+    if (haf_measure_labels(eng, &f, &img, mo.seg_n, mo.seg_plane, shapes.data()) != HAF_OK) { fprintf(stderr, "--per-object: %s\n", haf_last_error(eng)); return 1; }
+    struct Todo { int32_t label; haf_grasp_input in; int32_t fits; };
+    std::vector<Todo> todo;
+    for (size_t l = 0; l < n; l++) {
+        Todo t;
+        t.label = (int32_t)l + 1;
+        if (shapes[l].found && haf_object_input(&cfg, &in, &shapes[l], mo.margin_cells, &t.in, &t.fits) == HAF_OK) todo.push_back(t);
+    }
+    const size_t px = (size_t)f.width * (size_t)f.height;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)cfg.max_clouds, (size_t)cfg.max_points / std::max<size_t>(1, px)));
+    struct Hit { unsigned long long key; std::string line; };
+    std::vector<Hit> hits;
+    std::vector<haf_label_pick> picks(n);
+    std::vector<haf_grasp_candidate> poses(n);
+    for (size_t c0 = 0; c0 < todo.size(); c0 += chunk) {
+        const size_t k = std::min(chunk, todo.size() - c0);
+        std::vector<haf_frame> frames(k, f);
+        std::vector<haf_roi> rois(k, haf_roi{mo.seg_labels.data(), (size_t)f.width, 0});
+        std::vector<haf_grasp_input> ins(k);
+        std::vector<haf_grasp_output> outs(k);
+        for (size_t b = 0; b < k; b++) ins[b] = todo[c0 + b].in;
+        if (haf_score_frames_roi(eng, (int32_t)k, frames.data(), rois.data(), ins.data(), outs.data()) != HAF_OK) {
+            fprintf(stderr, "--per-object: %s\n", haf_last_error(eng));
+            return 1;
+        }
+        for (size_t b = 0; b < k; b++) {
+            if (haf_grasp_map_labels(eng, (int32_t)b, &f, &img, mo.seg_n, mo.min_vote, picks.data(), poses.data(), nullptr, nullptr) != HAF_OK) {
+                fprintf(stderr, "--per-object: %s\n", haf_last_error(eng));
+                return 1;
+            }
+            const size_t l = (size_t)todo[c0 + b].label - 1;
+            const haf_label_pick &p = picks[l];
+            if (!p.found) continue;
+            const unsigned i = (unsigned)((size_t)p.v * (size_t)f.width + (size_t)p.u);      // haf_grasp_map_labels' key: vote, then roll, then pixel
+            const unsigned long long key = ((unsigned long long)(unsigned)(p.vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - p.roll) << 32) |
+                                           (unsigned long long)(0xFFFFFFFFu - i);
+            char tail[128];
+            snprintf(tail, sizeof tail, " width %.9g yaw %d height %.9g", shapes[l].narrow_width, (int)shapes[l].narrow_dir * 15, shapes[l].height);
+            hits.push_back(Hit{key, "object " + std::to_string(todo[c0 + b].label) + " " + std::to_string(p.u) + " " + std::to_string(p.v) + " " +
+                                        hafshim::hypothesis_string(poses[l].grasp, cfg.roll_step_deg) + tail});
+        }
+    }
+    std::sort(hits.begin(), hits.end(), [](const Hit &a, const Hit &b) { return a.key > b.key; });
+    for (const Hit &h : hits) printf("%s\n", h.line.c_str());
+    return 0;
+}
+
 static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_input &in, const std::vector<DepthView> &views,
                      bool hypotheses, int top_k, int top_radius, int top_rolls, double top_dist, MapOptions &mo)
 {
@@ -441,6 +549,11 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         release();
         return 1;
     }
+    if (mo.measure) {
+        const int mrc = run_measure(eng, frames[0], mo);
+        release();
+        return mrc;
+    }
     // --segment: the first view (filtered or not) into a label image, before the request: the call needs no scored batch
     if (mo.segment) {
         haf_segment_params sp = mo.segment_params;
@@ -472,6 +585,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
                 printf("plane %.9g %.9g %.9g %.9g inliers %d rms %.6g\n", fit.plane[0], fit.plane[1], fit.plane[2], fit.plane[3], (int)fit.n_inliers, fit.rms);
             } else printf("plane none\n");
         }
+        memcpy(mo.seg_plane, sp.plane, sizeof mo.seg_plane);
         mo.seg_labels.assign((size_t)frames[0].width * (size_t)frames[0].height, 0);
         int64_t stats[4] = {0, 0, 0, 0};
         if (haf_segment_frame(eng, &frames[0], &sp, mo.seg_labels.data(), 1, (size_t)frames[0].width, 0, nullptr, nullptr, &mo.seg_n, stats) != HAF_OK) {
@@ -486,6 +600,11 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
             release();
             return 1;
         }
+    }
+    if (mo.per_object) {
+        const int prc = run_per_object(eng, cfg, in, frames[0], mo);
+        release();
+        return prc;
     }
     // what the messages below are about: the file of a single view; every file of a fused request ("a.pgm + b.pgm"), in view order, so
     // that the library's "request 0 view V" finds its file
@@ -619,6 +738,8 @@ int main(int argc, char **argv)
         else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
         else if (a == "--segment") { need(1); if (!parse_segment(argv[++i], &map_opt.segment_params)) { usage(); return 2; } map_opt.segment = true; }
         else if (a == "--segment-roi") map_opt.segment_roi = true;
+        else if (a == "--per-object") { map_opt.per_object = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') map_opt.margin_cells = atoi(argv[++i]); }
+        else if (a == "--measure") map_opt.measure = true;
         else if (a == "--plane" && i + 1 < argc && strncmp(argv[i + 1], "fit", 3) == 0) { if (!parse_plane_fit(argv[++i], &map_opt.plane_params)) { usage(); return 2; } map_opt.fit_plane = true; }
         else if (a == "--plane-mask") { need(1); map_opt.plane_mask = argv[++i]; }
         else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) map_opt.plane[k] = (float)atof(argv[++i]); map_opt.have_plane = true; }
@@ -638,7 +759,9 @@ int main(int argc, char **argv)
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
-        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || map_opt.have_plane || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || (map_opt.have_plane && !map_opt.measure) || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.per_object && (!map_opt.segment || views.size() != 1 || map_opt.segment_roi || map_opt.measure || !map_opt.roi_path.empty() || !map_opt.labels_path.empty())) ||
+        (map_opt.measure && (map_opt.labels_path.empty() || views.size() != 1 || map_opt.segment || map_opt.fit_plane)) ||
         (map_opt.fit_plane && map_opt.have_plane) || (!map_opt.fit_plane && !map_opt.plane_mask.empty()) ||
         (map_opt.segment_roi && (views.size() != 1 || !views[0].roi_path.empty() || !map_opt.roi_path.empty())) ||
         (from_depth ? (first_cloud < argc || !have_intrinsics || gpus > 0 || views.size() > (size_t)HAF_MAX_VIEWS) : first_cloud >= argc)) { usage(); return 2; }
@@ -648,6 +771,7 @@ int main(int argc, char **argv)
     cfg.range_file = range.c_str();
     cfg.model_file = model.c_str();
     cfg.max_points = 1 << 22;
+    if (map_opt.per_object) cfg.max_clouds = std::max(cfg.max_clouds, 8);      // requests of one chunk
 
     if (gpus > 0) return run_multi(cfg, in, gpus, shards_per_gpu, shard, argc, argv, first_cloud);
 

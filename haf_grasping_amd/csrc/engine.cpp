@@ -76,7 +76,7 @@ void haf_destroy(haf_engine *e)
     e->d_sd.release(); e->d_corr.release(); e->d_sd3.release(); e->d_fd_slot.release(); e->d_part1.release();
     e->d_svt_h_cr.release(); e->d_t1_tab.release(); e->d_t1_L.release(); e->d_flag0b_list.release(); e->d_screen_part.release();
     e->d_top_scratch.release(); e->d_roi_cells.release(); e->d_filter_image.release(); e->d_seg_words.release(); e->d_seg_image.release(); e->d_plane_scratch.release(); e->d_svt0_cr.release(); e->d_fd_slot_cr.release(); e->d_sd_cr.release(); e->d_sd3_cr.release(); e->d_corr_cr.release();
-    for (StageBuf *b : {&e->in_block, &e->raw, &e->raw_xyz, &e->out_block, &e->top_out, &e->map, &e->roi_mask, &e->seg_out, &e->plane_io}) b->release();
+    for (StageBuf *b : {&e->in_block, &e->raw, &e->raw_xyz, &e->out_block, &e->top_out, &e->map, &e->roi_mask, &e->seg_out, &e->plane_io, &e->shape_io}) b->release();
     e->d_brslot.release(); e->d_tier_words.release(); e->d_t1_flags.release(); e->d_lr_btiles.release(); e->d_svt_lr.release(); e->d_lr_btiles_in.release(); e->d_corr_lrp.release(); e->d_iiabs.release();
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);

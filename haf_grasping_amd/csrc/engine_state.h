@@ -10,6 +10,7 @@
 //   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
 //   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
+//   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
@@ -409,6 +410,9 @@ struct haf_engine {
     // [a host mask, max_points bytes] with its pinned twin
     DevBuf<char> d_plane_scratch;
     StageBuf plane_io;
+    // haf_measure_labels (engine_labelshape.cpp), allocated by its first call: the block [per-label table, HAF_MAX_LABELS rows of 160 bytes]
+    // [a host label image, 2 bytes x max_points] with its pinned twin
+    StageBuf shape_io;
 };
 
 namespace haf_host {

@@ -6,6 +6,7 @@
 #include "frame_points.h"
 #include "segment_rules.h"
 #include "plane_rules.h"
+#include "label_shape.h"
 
 #include <string>
 
@@ -57,5 +58,14 @@ int plane_winner(const int32_t *counts, int32_t n_hyp);
 void plane_from_moments(const int64_t *moments, const float *hyp, const float *up, const float *origin, float *plane, double *rms);
 // everything of a result that follows the counts, the hypothesis words and the moments -- out->moments and stats[0..2] are filled by the caller
 void plane_finish(const haf_frame &f, const haf_plane_params &p, const int32_t *counts, const float *hyps, haf_plane_result *out);
+// labelshape_host.cpp, shared by haf_measure_labels_ref and haf_measure_labels: every refusal of a frame, of the label image, of the plane
+// and of the output that needs no engine
+int check_measure(const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, const float *plane, const haf_label_shape *shapes,
+                  std::string &err);
+// THE derived fields of a shape, from its integers and h_max only (found .. height; reserved = 0).  Both entry points call this one
+// function on the same integers, so its double arithmetic need not be pinned across machines
+void shape_finish(haf_label_shape *s);
+// a label's row of the device table (label_shape.h: kShapeRowWords words, as copied back) -> its integers and h_max, then shape_finish
+void shape_from_row(const uint32_t *row, haf_label_shape *s);
 
 }  // namespace haf

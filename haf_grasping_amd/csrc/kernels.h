@@ -610,6 +610,20 @@ constexpr int kPlaneBlockPixels = 1024;            // pixels per workgroup of th
 inline size_t plane_blocks(size_t n) { return (n + kPlaneBlockPixels - 1) / kPlaneBlockPixels; }
 // the five launches of one call, in stream order: points and usable bits, scan of the block counts, hypotheses, score, moments
 void launch_plane(const PlaneDev &d, hipStream_t s);
+// haf_measure_labels (labelshape.hip): one frame and its label image as the kernel reads them -- a kernel argument, so every field is a
+// scalar load.  f: the frame (dst and count are not read); labels: label_bytes 1 or 2 per pixel, rows label_stride bytes apart; plane:
+// read when use_plane is set; table: n_labels rows of haf_shape_math::kShapeRowWords words (label_shape.h), zeroed by the caller.  All
+// of it device memory
+struct ShapeDev {
+    FrameDev f;
+    const void *labels;
+    unsigned long long label_stride;
+    int label_bytes, n_labels;
+    float plane[4];
+    int use_plane;
+    unsigned *table;
+};
+void launch_label_shape(const ShapeDev &d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

@@ -208,5 +208,56 @@ class CalcGraspPointsServer:
         n = len(self.last_segment_infos)
         return res, (self.best_per_object(frame, img, min_vote=min_vote, n_labels=n) if n else [])
 
+    def execute_frame_per_object(self, goal: GraspInputMsg, frame, params=None, plane=None, min_vote=1, margin_cells=4):
+        """execute_frame_segmented() for objects ANYWHERE in the frame: one request per object, each centred on its object, instead of
+        the one grid around the goal's grasp_area_center (objects outside that grid have no grasp there: no height grid contains
+        them).  The frame is segmented into the engine's device image (params, plane: as execute_frame_segmented takes them), every
+        label's box in the base frame is measured from that image (haf_measure_labels, heights over the segmentation's plane), every
+        found object gets the goal re-centred on its box with a square grasp area that covers it and margin_cells more
+        (haf_object_input; the goal keeps its z, approach vector and every other field), and the requests are scored in chunks that
+        respect max_clouds and max_points -- each chunk ONE haf_score_frames_roi call whose requests share the frame and the device
+        mask -- followed by one haf_grasp_map_labels call per request, of which only the entry of that request's object is read.
+        -> list of (label, GraspOutputMsg, u, v, shape dict, fits), best first in haf_grasp_map_labels' order (vote descending, then
+        roll, then pixel index ascending); objects without a pixel of vote >= min_vote are left out.  fits is False when the grasp
+        area had to be cut to the engine's grid.  self.last_shapes: the capi.LABEL_SHAPE_DTYPE array of all labels; the other last_*
+        attributes as execute_frame_segmented leaves them.
+        THE COST: a host frame is staged once per request of a chunk (a device-resident frame is read where it lies), and there is
+        one label call per object; a fused form does not exist."""
+        if goal.goal_frame_id:
+            self.base_frame_id = goal.goal_frame_id
+        p = params if params is not None else self.segment_params_from_goal(goal)
+        self.last_plane_fit = None
+        if plane is not None:
+            if isinstance(plane, str) and plane != "fit":
+                raise ValueError("plane: None, \"fit\" or a capi.plane_params()")
+            self.last_plane_fit = self.engine.fit_plane(frame, None if isinstance(plane, str) else plane)
+            if self.last_plane_fit["found"]:
+                p = capi.SegmentParams.from_buffer_copy(p)
+                p.plane = (C.c_float * 4)(*self.last_plane_fit["plane"])
+        img, self.last_segment_infos, self.last_segment_stats = self.engine.segment(frame, p, np.uint8, device_out=True)
+        n = len(self.last_segment_infos)
+        self.last_shapes = np.zeros(0, capi.LABEL_SHAPE_DTYPE)
+        if not n:
+            return []
+        self.last_shapes = self.engine.measure_labels(frame, img, n_labels=n, plane=list(p.plane))
+        cfg, base = self.engine.cfg, goal.to_c()
+        todo = [(l + 1,) + capi.object_input(cfg, base, self.last_shapes[l], margin_cells) for l in range(n) if self.last_shapes["found"][l]]
+        chunk = max(1, min(int(cfg.max_clouds), int(cfg.max_points) // max(1, frame.width * frame.height)))
+        mask = (img.data, img.row_stride_bytes)
+        hits = []
+        for c0 in range(0, len(todo), chunk):
+            part = todo[c0:c0 + chunk]
+            self.engine.score_frames_roi([frame] * len(part), [mask] * len(part), [inp for _, inp, _ in part])
+            for b, (label, _, fits) in enumerate(part):
+                res = self.engine.best_per_label(b, frame, img, n_labels=n, min_vote=min_vote)
+                pick, c = res["picks"][label - 1], res["poses"][label - 1]
+                if not pick["found"]:
+                    continue
+                msg = GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                                     c["approach_vector"], c["roll"])
+                key = (-int(pick["vote"]), int(pick["roll"]), int(pick["v"]) * frame.width + int(pick["u"]))
+                hits.append((key, (label, msg, int(pick["u"]), int(pick["v"]), capi.shape_to_dict(self.last_shapes[label - 1]), fits)))
+        return [h for _, h in sorted(hits, key=lambda kh: kh[0])]
+
     def close(self):
         self.engine.close()

@@ -735,6 +735,72 @@ int  haf_fit_plane_ref(const haf_frame *frame, const haf_roi *mask /* may be NUL
 int  haf_fit_plane(haf_engine *e, const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_plane_params *p,
                    haf_plane_result *out, int32_t *counts /* [n_hyp], may be NULL */, float *hyps /* [n_hyp][4], may be NULL */);
 
+/* ---- every object's box in the base frame, and a request per object (csrc/labelshape.hip) ----------------------------------------
+ * What a label image lacks to become one request per object: WHERE each object is (the centre of its request), how LARGE it is (the
+ * request's window) and how WIDE it is at its narrowest, in which direction (does the gripper span it, which roll is plausible).
+ * haf_segment_info only has pixel counts and pixel boxes; this is the geometry per label in the base frame.
+ *
+ *   point       pixel i = v * width + u has haf_frame_points' three words; any kind of frame.
+ *   label       l = the label image's value at i, read as haf_grasp_map_labels reads it; 0 and values above n_labels are ignored.
+ *   usable      all three words finite and of magnitude <= 16 m (haf_fit_plane's rule).
+ *   words       q = round-to-nearest-even(coordinate * 4096) as int32, haf_fit_plane's refit word: exact product, |q| <= 2^16.
+ *   per label   in integers only -- n_pixels: all pixels carrying l; over the USABLE ones: n_points, sum[3] (int64 sums of qx, qy,
+ *               qz), q_min[3], q_max[3], and for k in [0, HAF_SHAPE_DIRS): t_k = C[k] qx + S[k] qy in int32, t_min[k], t_max[k].
+ *   directions  (C, S)[k] = round(8192 (cos, sin)(15 deg k)): HAF_SHAPE_COS, HAF_SHAPE_SIN below, their squared norms HAF_SHAPE_NN.
+ *               (C, S)[k + 6] = (-S, C)[k] exactly: k and (k + 6) mod 12 are perpendicular and of equal norm.  |t| <= 2^16 x 11586
+ *               < 2^30: no overflow.
+ *   height      with a plane[4] (may be NULL): h = ((plane[0] x + plane[1] y) + plane[2] z) + plane[3], haf_segment_frame's height to
+ *               the bit; h_max = the largest non-NaN h of the usable pixels, -0 below +0.
+ *   empty       a label without a usable point: sums 0, mins INT32_MAX, maxes INT32_MIN, h_max the word 0x7FC00000 -- as h_max of
+ *               every label is without a plane.
+ * No value depends on an order of evaluation, the float maximum included.
+ *
+ * The derived fields come from those integers through ONE host function both entry points call, in double, rounded once to float:
+ * found = n_points > 0; centroid = sum / (4096 n_points); box_min / box_max = q / 4096; width[k] = (t_max - t_min) / (4096
+ * sqrt(nn[k])); narrow_dir = the k that minimises (t_max - t_min)^2 / nn[k], compared exactly by 128-bit cross products, ties to the
+ * lowest k; narrow_width = width[narrow_dir], long_width = width[(narrow_dir + 6) % 12], yaw = narrow_dir x 15 deg in radians,
+ * diameter = the largest width[k], height = h_max.  All of them zero when not found.
+ * This is the minimum-width box over a FIXED FAN of twelve directions, not the exact minimum-area rectangle, and the extents are those
+ * of the QUANTISED points in the base frame's xy plane: meant for approach vectors near the base z.  It says nothing about how well a
+ * sensor saw the object.
+ *
+ * haf_measure_labels_ref: the host definition of record -- no device, no engine, a host frame and a host image only.
+ * haf_measure_labels: equal to it in every word of every entry.  The frame and the label image may each be host or device resident; a
+ * device-resident one is read where it lies, with its strides -- the image haf_segment_frame left in the engine included.  One
+ * device-to-host copy and one synchronisation whatever n_labels is.  Like haf_fit_plane the call neither reads nor changes last-batch
+ * state or stage timings, works before any request and with HAF_FLAG_PROBABILITY, and allocates its table and copy-back block (160
+ * bytes x HAF_MAX_LABELS and 2 bytes x max_points for a host image) on first use.
+ * Refusals, all before any device work, nothing written -- HAF_E_ARG: everything haf_grasp_map_labels refuses for a frame and a label
+ * image, a null shapes, a plane entry that is not finite, for the _ref form a device-resident frame or image; HAF_E_CAPACITY: width *
+ * height > max_points.
+ *
+ * haf_object_input: pure host.  *out = *base with grasp_area_center[0], [1] = the midpoint of the box, (q_min + q_max) / 8192 in double
+ * (z is base's), and grasp_area_length_x = grasp_area_length_y = 2 (ceil(50 diameter) + margin_cells + 7) clamped to [16, the even part
+ * of min(grid_h, grid_w)]: the search interior 2 (length / 2 - 7) of the request then covers the object and the margin under every
+ * roll.  *fits = 0 when the upper clamp acted, else 1.  HAF_E_ARG: a shape that is not found, margin_cells outside 0..64, a null
+ * argument. */
+#define HAF_SHAPE_DIRS 12
+#define HAF_SHAPE_COS { 8192, 7913, 7094, 5793, 4096, 2120, 0, -2120, -4096, -5793, -7094, -7913 }
+#define HAF_SHAPE_SIN { 0, 2120, 4096, 5793, 7094, 7913, 8192, 7913, 7094, 5793, 4096, 2120 }
+#define HAF_SHAPE_NN  { 67108864, 67109969, 67102052, 67117698, 67102052, 67109969, 67108864, 67109969, 67102052, 67117698, 67102052, 67109969 }
+typedef struct haf_label_shape {    /* label l is entry l - 1 */
+    int64_t sum[3];                 /* of qx, qy, qz over the usable pixels */
+    int32_t found, n_pixels, n_points, narrow_dir;
+    int32_t q_min[3], q_max[3];
+    int32_t t_min[HAF_SHAPE_DIRS], t_max[HAF_SHAPE_DIRS];
+    float   h_max;                  /* 0x7FC00000: no plane, or no usable point */
+    float   centroid[3], box_min[3], box_max[3];   /* metres, base frame */
+    float   width[HAF_SHAPE_DIRS];  /* metres: the extent along direction k */
+    float   narrow_width, long_width, yaw, diameter, height;
+    int32_t reserved;               /* 0 */
+} haf_label_shape;
+int  haf_measure_labels_ref(const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, const float *plane /* [4], may be NULL */,
+                            haf_label_shape *shapes /* [n_labels] */);
+int  haf_measure_labels(haf_engine *e, const haf_frame *frame, const haf_label_image *labels, int32_t n_labels,
+                        const float *plane /* [4], may be NULL */, haf_label_shape *shapes /* [n_labels] */);
+int  haf_object_input(const haf_config *cfg, const haf_grasp_input *base, const haf_label_shape *shape, int32_t margin_cells,
+                      haf_grasp_input *out, int32_t *fits);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
