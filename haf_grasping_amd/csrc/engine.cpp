@@ -64,23 +64,9 @@ void haf_destroy(haf_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &r : e->host_regs) (void)hipHostUnregister((void *)r.first);
     e->host_regs.clear();
-    e->d_sorted.release(); e->d_bkt.release(); e->d_heights.release(); e->d_rowsum.release(); e->d_inexact.release();
-    e->d_ii.release(); e->d_mask.release(); e->d_rowcount.release(); e->d_rowoff.release(); e->d_brcount.release();
-    e->d_evalcell.release(); e->d_flag_list.release(); e->d_X.release(); e->d_ax.release();
-    e->d_dec.release(); e->d_svt.release(); e->d_svt_h.release(); e->d_labels.release(); e->d_dec_exact.release(); e->d_strict_terms.release(); e->d_part64.release(); e->d_dec_exact2.release(); e->d_flag2_list.release(); e->d_x64.release(); e->d_sv64.release();
-    e->snap_X.release(); e->snap_gband.release(); e->snap_ax.release();
-    e->d_svt0.release(); e->d_X1.release(); e->d_ax1.release(); e->d_gband.release(); e->d_flag0_list.release(); e->d_flag0_words.release(); e->d_flag0_wgcount.release();
-    e->d_own.release(); e->d_gridf.release(); e->d_evf.release(); e->d_ptext.release();
-    e->d_sv_i8.release(); e->d_flagi_list.release(); e->d_dec_exacti.release();
-    e->d_coef64.release(); e->d_ev16.release(); e->d_attr.release(); e->d_margin.release(); e->d_topkey.release(); e->d_rowmax.release(); e->d_fd.release();
-    e->d_sd.release(); e->d_corr.release(); e->d_sd3.release(); e->d_fd_slot.release(); e->d_part1.release();
-    e->d_svt_h_cr.release(); e->d_t1_tab.release(); e->d_t1_L.release(); e->d_flag0b_list.release(); e->d_screen_part.release();
-    e->d_top_scratch.release(); e->d_roi_cells.release(); e->d_filter_image.release(); e->d_seg_words.release(); e->d_seg_image.release(); e->d_plane_scratch.release(); e->d_svt0_cr.release(); e->d_fd_slot_cr.release(); e->d_sd_cr.release(); e->d_sd3_cr.release(); e->d_corr_cr.release();
-    for (StageBuf *b : {&e->in_block, &e->raw, &e->raw_xyz, &e->out_block, &e->top_out, &e->map, &e->roi_mask, &e->seg_out, &e->plane_io, &e->shape_io}) b->release();
-    e->d_brslot.release(); e->d_tier_words.release(); e->d_t1_flags.release(); e->d_lr_btiles.release(); e->d_svt_lr.release(); e->d_lr_btiles_in.release(); e->d_corr_lrp.release(); e->d_iiabs.release();
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;      // frees every DevBuf and StageBuf member: the stream was synchronised above, so nothing still runs on them
 }
 // Default mode: which screening variant serves this MODEL is found out here, at creation, not on the first goals of a fresh
 // action server: up to three requests on a synthetic table scene (a plane with a few dozen boxes and domes of 2-12 cm, a point

@@ -1,7 +1,7 @@
 // engine_depthfilter.cpp -- haf_filter_depth (include/hafgrasp.h): 1..8 exposures of one depth camera -> one conditioned depth image, on
 // the device.  Every refusal comes before any device work (check_depth_stack / check_depth_out of depthfilter_host.cpp, then the
-// capacities); then the host exposures are staged through stage_frame into the raw area of haf_score_frames, each at a multiple of 16
-// bytes, ONE launch of k_depth_filter (depthfilter.hip) runs on the engine's stream, ONE copy brings back the counters -- and, for a host
+// capacities); then the host exposures go up (upload_frame of engine_stage.cpp) into the raw area of haf_score_frames, each at a multiple
+// of 16 bytes, ONE launch of k_depth_filter (depthfilter.hip) runs on the engine's stream, ONE copy brings back the counters -- and, for a host
 // `out`, the packed image behind them -- and ONE synchronisation ends the call.  Nothing of the last scored batch is read or written: the
 // raw area is only read inside the request that filled it, the stage timings are not touched.
 #include "engine_state.h"
@@ -38,13 +38,7 @@ int filter_depth_impl(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
     const size_t cnt_at = at, img_at = at + kFiltCounterBytes;
     if (img_at + (host_out ? px * elem : 0) > e->raw.dev.n) return fail(e, HAF_E_CAPACITY, who + "the raw staging area is too small");
     HIPCHK(e, hipSetDevice(c.device));
-    if (!out && !e->d_filter_image.p) {
-        const hipError_t hrc = e->d_filter_image.alloc((size_t)c.max_points * 4);
-        if (hrc != hipSuccess) {
-            e->d_filter_image.release();
-            return fail(e, HAF_E_DEVICE, who + "no device memory for the engine's output image: " + hipGetErrorString(hrc));
-        }
-    }
+    if (!out && (rc = ensure_dev(e, e->d_filter_image, (size_t)c.max_points * 4, who, "the engine's output image")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->raw.dev.p, *const host = e->raw.host;
 
@@ -55,12 +49,10 @@ int filter_depth_impl(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
         const FrameDev fd = describe_frame(f, dev + off[k]);
         d.src[k] = fd.src;
         d.row_stride[k] = fd.row_stride;
-        if (f.on_device == 1) continue;
-        const auto send = [&](size_t o, size_t bytes) { return hipMemcpyAsync(dev + off[k] + o, host + off[k] + o, bytes, hipMemcpyHostToDevice, s); };
-        HIPCHK(e, stage_frame(host + off[k], f, send));
+        if (f.on_device != 1 && (rc = upload_frame(e, f, host + off[k], dev + off[k], s)) != HAF_OK) return rc;
     }
-    d.out = host_out ? dev + img_at : out ? out : e->d_filter_image.p;
-    d.out_stride = (host_out || !out) ? (unsigned long long)f0.width * elem : (unsigned long long)out_row_stride_bytes;
+    const OutputDev o = describe_output(out, out_on_device, out_row_stride_bytes, (size_t)f0.width, elem, dev + img_at, e->d_filter_image.p);
+    d.out = o.dst; d.out_stride = o.dst_stride;
     d.counters = reinterpret_cast<unsigned *>(dev + cnt_at);
     d.width = f0.width; d.height = f0.height; d.n_frames = n_frames;
     d.min_valid = p->min_valid; d.min_support = p->min_support;
@@ -72,10 +64,7 @@ int filter_depth_impl(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
     HIPCHK(e, hipMemcpyAsync(host + cnt_at, dev + cnt_at, kFiltCounterBytes + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    if (host_out) {                                      // the packed rows into the caller's: the bytes between them are not written
-        const size_t row = (size_t)f0.width * elem;
-        for (size_t v = 0; v < (size_t)f0.height; v++) memcpy(static_cast<char *>(out) + v * out_row_stride_bytes, host + img_at + v * row, row);
-    }
+    if (host_out) unpack_rows(static_cast<char *>(out), out_row_stride_bytes, host + img_at, (size_t)f0.height, (size_t)f0.width * elem);
     if (stats) {
         unsigned cnt[2];
         memcpy(cnt, host + cnt_at, sizeof cnt);
@@ -83,9 +72,7 @@ int filter_depth_impl(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
     }
     if (out_frame) {
         *out_frame = f0;
-        out_frame->data = host_out ? out : d.out;
-        out_frame->on_device = host_out ? 0 : 1;
-        out_frame->row_stride_bytes = host_out ? out_row_stride_bytes : (size_t)d.out_stride;
+        out_frame->data = o.data; out_frame->on_device = o.on_device; out_frame->row_stride_bytes = o.row_stride_bytes;
     }
     return HAF_OK;
 }

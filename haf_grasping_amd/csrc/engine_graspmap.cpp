@@ -66,7 +66,7 @@ int check_map_frame(haf_engine *e, const char *who, const haf_frame *f)
 }
 
 // What every device pass over one checked frame starts with: the zeroed header and the roll transforms go up, a host frame's pixels are
-// staged (stage_frame, as the request path's upload_frames does); *fd = the frame as the kernels read it.  No synchronisation.
+// staged (upload_frame, engine_stage.cpp); *fd = the frame as the kernels read it.  No synchronisation.
 int stage_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, FrameDev *fd_out)
 {
     const haf_config &c = e->cfg;
@@ -76,11 +76,7 @@ int stage_map(haf_engine *e, int request, int rolls, const haf_frame &f, const M
     fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->map.host + l.geo));
     HIPCHK(e, hipMemcpyAsync(e->map.dev.p, e->map.host, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
     *fd_out = describe_frame(f, e->map.dev.p + l.raw);
-    if (f.on_device != 1) {
-        const auto send = [&](size_t off, size_t bytes) { return hipMemcpyAsync(e->map.dev.p + l.raw + off, e->map.host + l.raw + off, bytes, hipMemcpyHostToDevice, s); };
-        HIPCHK(e, stage_frame(e->map.host + l.raw, f, send));
-    }
-    return HAF_OK;
+    return f.on_device == 1 ? HAF_OK : upload_frame(e, f, e->map.host + l.raw, e->map.dev.p + l.raw, s);
 }
 
 // stage_map, then k_grasp_map on the engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
@@ -191,12 +187,10 @@ int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint
     short *dv = reinterpret_cast<short *>(d + l.vote), *dr = reinterpret_cast<short *>(d + l.roll);
     int *dc = reinterpret_cast<int *>(d + l.cell);
     if ((rc = launch_map(e, request, rolls, *f, l, dv, dr, dc)) != HAF_OK) return rc;
-    if (mask) {
-        pack_rows(e->map.host + l.mask, reinterpret_cast<const char *>(mask), (size_t)f->height, (size_t)f->width, 1, 1, mask_row_stride);
-        HIPCHK(e, hipMemcpyAsync(d + l.mask, e->map.host + l.mask, n, hipMemcpyHostToDevice, e->stream));
-    }
+    ImageDev md;                                            // (a host mask; k_map_best reads it packed)
+    if ((rc = upload_image(e, *f, mask, 0, mask_row_stride, 1, e->map, l.mask, e->stream, &md)) != HAF_OK) return rc;
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d);      // (zeroed by launch_map's header copy)
-    launch_map_best(dv, dr, mask ? reinterpret_cast<const unsigned char *>(d + l.mask) : nullptr, (unsigned)n, min_vote, d_key, e->stream);
+    launch_map_best(dv, dr, static_cast<const unsigned char *>(md.src), (unsigned)n, min_vote, d_key, e->stream);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(e->map.host, d_key, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -238,21 +232,14 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     if (n_found) *n_found = 0;
     if (rolls == 0) return HAF_OK;                          // (a negative budget: no roll ran, no pixel has a roll)
     const size_t n = (size_t)f->width * (size_t)f->height, eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
-    const bool host_labels = labels->on_device != 1;
-    const MapLayout l = map_layout(e, 0, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind), host_labels ? n * eb : 0, nl);
+    const MapLayout l = map_layout(e, 0, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind), labels->on_device != 1 ? n * eb : 0, nl);
     if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
     char *d = e->map.dev.p;
     const hipStream_t s = e->stream;
     FrameDev fd;
     if ((rc = stage_map(e, request, rolls, *f, l, &fd)) != HAF_OK) return rc;
-    const void *d_labels = labels->data;
-    size_t label_stride = labels->row_stride_bytes;
-    if (host_labels) {
-        pack_rows(e->map.host + l.labels, static_cast<const char *>(labels->data), (size_t)f->height, (size_t)f->width, eb, eb, labels->row_stride_bytes);
-        HIPCHK(e, hipMemcpyAsync(d + l.labels, e->map.host + l.labels, n * eb, hipMemcpyHostToDevice, s));
-        d_labels = d + l.labels;
-        label_stride = (size_t)f->width * eb;
-    }
+    ImageDev ld;
+    if ((rc = upload_image(e, *f, labels->data, labels->on_device, labels->row_stride_bytes, eb, e->map, l.labels, s, &ld)) != HAF_OK) return rc;
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d + l.ltab);
     unsigned *d_cnt = reinterpret_cast<unsigned *>(d + l.ltab + nl * 8);
     LabelOutDev *d_out = reinterpret_cast<LabelOutDev *>(d + l.lout);
@@ -262,7 +249,7 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
     const CellGeo *d_geo = reinterpret_cast<const CellGeo *>(d + l.geo);
     const short *ev = e->d_ev16.p + br0 * HW;
-    launch_map_labels(fd, d_geo, rolls, last.roll_first, ev, H, W, r_row, r_col, d_labels, label_stride, (int)eb, n_labels, min_vote, d_key, d_cnt, s);
+    launch_map_labels(fd, d_geo, rolls, last.roll_first, ev, H, W, r_row, r_col, ld.src, (size_t)ld.row_stride, (int)eb, n_labels, min_vote, d_key, d_cnt, s);
     HIPCHK(e, hipGetLastError());
     launch_label_records(fd, d_geo, rolls, last.roll_first, ev, reinterpret_cast<const float *>(e->d_heights.p) + br0 * HW, e->d_rec.p + br0, H, W,
                          r_row, r_col, n_labels, d_key, d_cnt, d_out, s);

@@ -1,10 +1,9 @@
 // engine_labelshape.cpp -- haf_measure_labels (include/hafgrasp.h): every label's box in the base frame, on the device.  Every refusal
-// comes before any device work (check_measure of labelshape_host.cpp, then the capacity); then a host frame is staged through
-// stage_frame as haf_fit_plane's is, a host label image is packed into the pinned half of the call's block and sent behind it, the
-// table is zeroed, the one launch of labelshape.hip runs on the engine's stream, ONE copy brings back the n_labels rows and ONE
-// synchronisation ends the call.  The shapes are shape_from_row's (labelshape_host.cpp) -- the code haf_measure_labels_ref ends with, on
-// the same integers.  Nothing of the last scored batch is read or written: the raw areas are only read inside the request that filled
-// them, the stage timings are not touched, and the block is this call's own.
+// comes before any device work (check_measure of labelshape_host.cpp, then the capacity); then the frame goes through the single-frame
+// input of engine_stage.cpp and a host label image through its upload_image, the table is zeroed, the one launch of labelshape.hip runs
+// on the engine's stream, ONE copy brings back the n_labels rows and ONE synchronisation ends the call.  The shapes are shape_from_row's
+// (labelshape_host.cpp) -- the code haf_measure_labels_ref ends with, on the same integers.  Nothing of the last scored batch is read or
+// written: the stage timings are not touched, and the block is this call's own.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -24,34 +23,20 @@ int measure_labels_impl(haf_engine *e, const haf_frame *frame, const haf_label_i
     std::string why;
     int rc;
     if ((rc = check_measure(frame, labels, n_labels, plane, shapes, why)) != HAF_OK) return fail(e, rc, who + why);
-    const haf_config &c = e->cfg;
     const haf_frame &f = *frame;
-    const size_t px = (size_t)f.width * (size_t)f.height, eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
-    if ((int64_t)px > (int64_t)c.max_points) return fail(e, HAF_E_CAPACITY, who + "more pixels than max_points");
-    const bool host_in = f.on_device == 0, xyz = f.kind == HAF_FRAME_XYZ_F32, host_labels = labels->on_device == 0;
-    HIPCHK(e, hipSetDevice(c.device));
-    if (host_in && xyz && (rc = ensure_raw_xyz(e, "haf_measure_labels")) != HAF_OK) return rc;
-    StageBuf &in = xyz ? e->raw_xyz : e->raw;
-    if (host_in && staged_bytes(f) > in.dev.n) return fail(e, HAF_E_CAPACITY, who + "the raw staging area is too small");
-    const hipError_t arc = e->shape_io.ensure(kShapeLabelsAt + (size_t)c.max_points * 2);
-    if (e->shape_io.pinned_failed) return fail(e, HAF_E_DEVICE, who + "no pinned memory for the copy-back block");
-    if (arc != hipSuccess) return fail(e, HAF_E_DEVICE, who + "no device memory for the copy-back block: " + hipGetErrorString(arc));
+    const size_t eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
+    StageBuf *in = nullptr;
+    if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
+    if ((rc = ensure_stage(e, e->shape_io, kShapeLabelsAt + (size_t)e->cfg.max_points * 2, who, "the copy-back block")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->shape_io.dev.p, *const host = e->shape_io.host;
 
-    if (host_in) {
-        const auto send = [&](size_t o, size_t bytes) { return hipMemcpyAsync(in.dev.p + o, in.host + o, bytes, hipMemcpyHostToDevice, s); };
-        HIPCHK(e, stage_frame(in.host, f, send));
-    }
-    if (host_labels) {                                    // packed rows: the bytes between the caller's rows are not read
-        pack_rows(host + kShapeLabelsAt, static_cast<const char *>(labels->data), (size_t)f.height, (size_t)f.width, eb, eb, labels->row_stride_bytes);
-        HIPCHK(e, hipMemcpyAsync(dev + kShapeLabelsAt, host + kShapeLabelsAt, px * eb, hipMemcpyHostToDevice, s));
-    }
     ShapeDev d;
     memset(&d, 0, sizeof d);
-    d.f = describe_frame(f, in.dev.p);
-    d.labels = host_labels ? dev + kShapeLabelsAt : labels->data;
-    d.label_stride = host_labels ? (unsigned long long)f.width * eb : (unsigned long long)labels->row_stride_bytes;
+    if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
+    ImageDev ld;
+    if ((rc = upload_image(e, f, labels->data, labels->on_device, labels->row_stride_bytes, eb, e->shape_io, kShapeLabelsAt, s, &ld)) != HAF_OK) return rc;
+    d.labels = ld.src; d.label_stride = ld.row_stride;
     d.label_bytes = labels->elem_bytes;
     d.n_labels = n_labels;
     if (plane) memcpy(d.plane, plane, sizeof d.plane);

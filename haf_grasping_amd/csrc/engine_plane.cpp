@@ -1,10 +1,9 @@
 // engine_plane.cpp -- haf_fit_plane (include/hafgrasp.h): the dominant plane of one sensor frame, on the device.  Every refusal comes
-// before any device work (check_plane of plane_host.cpp, then the capacity); then a host frame is staged through stage_frame as
-// haf_segment_frame's is, a host mask is packed into the pinned half of the call's block and sent behind it, the five launches of
-// plane.hip run on the engine's stream, ONE copy brings back the counters, the moments, the counts and the hypothesis words, and ONE
-// synchronisation ends the call.  The plane itself is plane_finish's (plane_host.cpp) -- the code haf_fit_plane_ref runs on the same
-// integers.  Nothing of the last scored batch is read or written: the raw areas are only read inside the request that filled them, the
-// stage timings are not touched, and the scratch is this call's own.
+// before any device work (check_plane of plane_host.cpp, then the capacity); then the frame goes through the single-frame input of
+// engine_stage.cpp and a host mask through its upload_image, the five launches of plane.hip run on the engine's stream, ONE copy brings
+// back the counters, the moments, the counts and the hypothesis words, and ONE synchronisation ends the call.  The plane itself is
+// plane_finish's (plane_host.cpp) -- the code haf_fit_plane_ref runs on the same integers.  Nothing of the last scored batch is read or
+// written: the stage timings are not touched, and the scratch is this call's own.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -21,22 +20,6 @@ constexpr size_t plane_hyps_at(size_t n_hyp) { return up16(kPlaneCountsAt + n_hy
 constexpr size_t plane_thr_at(size_t n_hyp) { return plane_hyps_at(n_hyp) + n_hyp * 16; }
 constexpr size_t kPlaneMaskAt = up16(plane_thr_at(HAF_MAX_PLANE_HYP) + (size_t)HAF_MAX_PLANE_HYP * 4);
 
-int plane_buffers(haf_engine *e, const std::string &who)
-{
-    const size_t mp = (size_t)e->cfg.max_points, blocks = plane_blocks(mp);
-    if (!e->d_plane_scratch.p) {
-        const hipError_t rc = e->d_plane_scratch.alloc(up16(mp * 12) + blocks * (kPlaneBlockPixels / 64) * 8 + blocks * 4);
-        if (rc != hipSuccess) {
-            e->d_plane_scratch.release();
-            return fail(e, HAF_E_DEVICE, who + "no device memory for the points, the usable bits and the block counts: " + hipGetErrorString(rc));
-        }
-    }
-    const hipError_t rc = e->plane_io.ensure(kPlaneMaskAt + mp);
-    if (e->plane_io.pinned_failed) return fail(e, HAF_E_DEVICE, who + "no pinned memory for the copy-back block");
-    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, who + "no device memory for the copy-back block: " + hipGetErrorString(rc));
-    return HAF_OK;
-}
-
 int fit_plane_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask, const haf_plane_params *p, haf_plane_result *out,
                    int32_t *counts, float *hyps)
 {
@@ -44,40 +27,31 @@ int fit_plane_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask, c
     std::string why;
     int rc;
     if ((rc = check_plane(frame, mask, p, out, why)) != HAF_OK) return fail(e, rc, who + why);
-    const haf_config &c = e->cfg;
     const haf_frame &f = *frame;
     const size_t px = (size_t)f.width * (size_t)f.height, K = (size_t)p->n_hyp;
-    if ((int64_t)px > (int64_t)c.max_points) return fail(e, HAF_E_CAPACITY, who + "more pixels than max_points");
-    const bool host_in = f.on_device == 0, xyz = f.kind == HAF_FRAME_XYZ_F32, masked = mask && mask->mask, host_mask = masked && mask->on_device == 0;
-    HIPCHK(e, hipSetDevice(c.device));
-    if (host_in && xyz && (rc = ensure_raw_xyz(e, "haf_fit_plane")) != HAF_OK) return rc;
-    StageBuf &in = xyz ? e->raw_xyz : e->raw;
-    if (host_in && staged_bytes(f) > in.dev.n) return fail(e, HAF_E_CAPACITY, who + "the raw staging area is too small");
-    if ((rc = plane_buffers(e, who)) != HAF_OK) return rc;
+    const haf_roi m = mask ? *mask : haf_roi{};            // (no haf_roi, or one without a mask: the whole frame)
+    StageBuf *in = nullptr;
+    if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
+    const size_t hyps_at = plane_hyps_at(K), thr_at = plane_thr_at(K), mp = (size_t)e->cfg.max_points, blocks = plane_blocks(mp);
+    if ((rc = ensure_dev(e, e->d_plane_scratch, up16(mp * 12) + blocks * (kPlaneBlockPixels / 64) * 8 + blocks * 4, who,
+                         "the points, the usable bits and the block counts")) != HAF_OK) return rc;
+    if ((rc = ensure_stage(e, e->plane_io, kPlaneMaskAt + mp, who, "the copy-back block")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->plane_io.dev.p, *const host = e->plane_io.host, *const scratch = e->d_plane_scratch.p;
-    const size_t hyps_at = plane_hyps_at(K), thr_at = plane_thr_at(K), mp = (size_t)c.max_points;
 
-    if (host_in) {
-        const auto send = [&](size_t o, size_t bytes) { return hipMemcpyAsync(in.dev.p + o, in.host + o, bytes, hipMemcpyHostToDevice, s); };
-        HIPCHK(e, stage_frame(in.host, f, send));
-    }
-    if (host_mask) {                                      // packed rows: the bytes between the caller's rows are not read
-        for (size_t v = 0; v < (size_t)f.height; v++) memcpy(host + kPlaneMaskAt + v * (size_t)f.width, mask->mask + v * mask->row_stride_bytes, (size_t)f.width);
-        HIPCHK(e, hipMemcpyAsync(dev + kPlaneMaskAt, host + kPlaneMaskAt, px, hipMemcpyHostToDevice, s));
-    }
     PlaneDev d;
     memset(&d, 0, sizeof d);
-    d.f = describe_frame(f, in.dev.p);
+    if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
+    ImageDev md;
+    if ((rc = upload_image(e, f, m.mask, m.on_device, m.row_stride_bytes, 1, e->plane_io, kPlaneMaskAt, s, &md)) != HAF_OK) return rc;
     d.height = f.height;
-    d.mask = !masked ? nullptr : host_mask ? reinterpret_cast<const unsigned char *>(dev + kPlaneMaskAt) : mask->mask;
-    d.mask_stride = host_mask ? (unsigned long long)f.width : masked ? (unsigned long long)mask->row_stride_bytes : 0ull;
+    d.mask = static_cast<const unsigned char *>(md.src); d.mask_stride = md.row_stride;
     d.r = plane_rules(*p);
     d.x = reinterpret_cast<float *>(scratch);
     d.y = d.x + mp;
     d.z = d.y + mp;
     d.bits = reinterpret_cast<unsigned long long *>(scratch + up16(mp * 12));
-    d.prefix = reinterpret_cast<int *>(d.bits + plane_blocks(mp) * (kPlaneBlockPixels / 64));
+    d.prefix = reinterpret_cast<int *>(d.bits + blocks * (kPlaneBlockPixels / 64));
     d.counters = reinterpret_cast<unsigned *>(dev);
     d.moments = reinterpret_cast<unsigned long long *>(dev + kPlaneCounterBytes);
     d.counts = reinterpret_cast<int *>(dev + kPlaneCountsAt);

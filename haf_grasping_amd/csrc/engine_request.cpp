@@ -378,7 +378,7 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
 }
 
 // Host frames go to the device as upload_clouds sends host clouds, in pieces, the DMA engine moving one while the host packs the rows
-// of the next (stage_frame, frame_stage.h).  Then ONE launch per kind writes the points of every frame of the batch (frames.hip).
+// of the next (upload_frame, engine_stage.cpp).  Then ONE launch per kind writes the points of every frame of the batch (frames.hip).
 static int upload_frames(haf_engine *e, const Request &q)
 {
     const hipStream_t s = q.s;
@@ -390,8 +390,7 @@ static int upload_frames(haf_engine *e, const Request &q)
         const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
         char *const dev = !xyz ? e->raw.dev.p : views ? e->raw_xyz.dev.p : e->in_block.dev.p, *const host = !xyz ? e->raw.host : views ? e->raw_xyz.host : e->in_block.host;
         const size_t at = (size_t)(static_cast<const char *>(q.h_frames[b].src) - dev);      // the frame's place in its block, device and pinned alike
-        const auto send = [&](size_t off, size_t bytes) { return hipMemcpyAsync(dev + at + off, host + at + off, bytes, hipMemcpyHostToDevice, s); };
-        HIPCHK(e, stage_frame(host + at, f, send));
+        if (const int rc = upload_frame(e, f, host + at, dev + at, s)) return rc;
     }
     if (!views) {
         launch_frame_points(q.d_frames, q.h_frames, q.B, s);
@@ -995,18 +994,6 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
     return score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
 }
 
-// the raw area of staged host XYZ views (12 bytes x max_points, every view at a multiple of 16 bytes) and its pinned twin: an engine
-// that never sees such a view never pays for them
-int ensure_raw_xyz(haf_engine *e, const std::string &who)
-{
-    if (e->raw_xyz.host) return HAF_OK;
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    const hipError_t rc = e->raw_xyz.ensure((size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16);
-    if (e->raw_xyz.pinned_failed) return fail(e, HAF_E_DEVICE, who + ": no pinned memory for the raw area of host XYZ views");
-    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, who + ": no device memory for the raw area of host XYZ views: " + hipGetErrorString(rc));
-    return HAF_OK;
-}
-
 // haf_score_views: every refusal before any device work, then the batch path with the views of request b as the source of cloud b's
 // points.  clouds[b].n_points is the UPPER bound, the pixels of the request's views: it sizes the request's region, sorted_off, max_n,
 // total_n and every launch grid; the kernels stop at the live count on the device
@@ -1023,7 +1010,7 @@ int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request,
     if (chk.code != HAF_OK && chk.text.empty()) return fail(e, chk.code, "haf_score_views: more pixels than max_points");
     if (chk.code != HAF_OK) return fail(e, chk.code, "haf_score_views: request " + std::to_string(chk.request) + " view " + std::to_string(chk.view) + ": " + chk.text);
     int rc0 = HAF_OK;
-    if (chk.host_xyz && (rc0 = ensure_raw_xyz(e, "haf_score_views")) != HAF_OK) return rc0;
+    if (chk.host_xyz && (rc0 = ensure_raw_xyz(e, "haf_score_views: ")) != HAF_OK) return rc0;
     const FrameSource from{frames, views_per_request, nullptr};
     const int rc = score_batch_impl(e, n, chk.clouds.data(), in, out, &from);
     if (rc != HAF_OK) return rc;

@@ -22,11 +22,9 @@ int ensure_roi_buffers(haf_engine *e, const std::string &who)
     HIPCHK(e, hipSetDevice(c.device));
     const size_t words = (size_t)c.max_clouds * (size_t)e->max_rolls * (size_t)c.grid_h * (size_t)roi_row_words(c.grid_w);
     const size_t mask_bytes = (size_t)c.max_points + (size_t)c.max_clouds * HAF_MAX_VIEWS * 16;      // (every view's mask at a multiple of 16 bytes)
-    hipError_t rc = e->roi_mask.ensure(mask_bytes);
-    if (e->roi_mask.pinned_failed) return fail(e, HAF_E_DEVICE, who + "no pinned memory for the masks");
-    if (rc == hipSuccess && (rc = e->d_roi_cells.alloc(words)) != hipSuccess) e->roi_mask.release();      // all or nothing: the next call tries again
-    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, who + "no device memory for the ROI buffers: " + hipGetErrorString(rc));
-    return HAF_OK;
+    int rc = ensure_stage(e, e->roi_mask, mask_bytes, who, "the masks");
+    if (rc == HAF_OK && (rc = ensure_dev(e, e->d_roi_cells, words, who, "the ROI buffers")) != HAF_OK) e->roi_mask.release();      // all or nothing: the next call tries again
+    return rc;
 }
 
 }  // namespace
@@ -73,9 +71,8 @@ void roi_describe_views(const haf_engine *e, const RoiCall &roi, const haf_frame
     for (int b = 0, k = 0; b < B; b++)
         for (int v = 0; v < views[b]; v++, k++) {
             const haf_roi &r = roi.rois[k];
-            const bool staged = RoiCall::staged(r);
-            out[k].mask = staged ? reinterpret_cast<const unsigned char *>(e->roi_mask.dev.p) + roi.off[(size_t)k] : r.mask;
-            out[k].stride = !r.mask ? 0 : staged ? (unsigned long long)frames[k].width : (unsigned long long)r.row_stride_bytes;
+            const ImageDev m = describe_image(r.mask, r.on_device, r.row_stride_bytes, (size_t)frames[k].width, 1, e->roi_mask.dev.p + roi.off[(size_t)k]);
+            out[k].mask = static_cast<const unsigned char *>(m.src); out[k].stride = m.row_stride;
             out[k].S = e->d_roi_cells.p + (size_t)b * R * grid_words;
             out[k].geo = d_geo + (size_t)b * R;
         }
@@ -93,9 +90,8 @@ int roi_mark_cells(haf_engine *e, const RoiCall &roi, const haf_frame *frames, c
     }
     for (int b = 0; b < d.B; b++) {
         const haf_roi &r = roi.rois[b];
-        const bool dev = r.on_device == 1;
-        const unsigned char *staged = reinterpret_cast<const unsigned char *>(e->roi_mask.dev.p) + roi.off[(size_t)b];
-        launch_roi_mark(dev ? r.mask : staged, dev ? r.row_stride_bytes : (size_t)frames[b].width, frames[b].width,
+        const ImageDev m = describe_image(r.mask, r.on_device, r.row_stride_bytes, (size_t)frames[b].width, 1, e->roi_mask.dev.p + roi.off[(size_t)b]);
+        launch_roi_mark(static_cast<const unsigned char *>(m.src), (size_t)m.row_stride, frames[b].width,
                         frames[b].width * frames[b].height, h_clouds[b].xyz, d_geo + (size_t)b * d.R, d.R,
                         e->d_roi_cells.p + (size_t)b * d.R * grid_words, d.H, d.W, r_row, r_col, s);
     }
@@ -160,7 +156,7 @@ int score_views_roi_impl(haf_engine *e, int32_t n, const int32_t *views_per_requ
         }
     if (chk.code != HAF_OK) return fail(e, chk.code, at(chk.request, chk.view) + (chk.text.empty() ? "more pixels than max_points" : chk.text));
     int rc = HAF_OK;
-    if (chk.host_xyz && (rc = ensure_raw_xyz(e, "haf_score_views_roi")) != HAF_OK) return rc;
+    if (chk.host_xyz && (rc = ensure_raw_xyz(e, who)) != HAF_OK) return rc;
     if ((rc = ensure_roi_buffers(e, who)) != HAF_OK) return rc;
     const RoiCall call = stage_masks(e, frames, rois, n, first);
     const FrameSource from{frames, views_per_request, &call};

@@ -12,6 +12,7 @@
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
+//   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
@@ -32,6 +33,8 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 using namespace haf;
@@ -97,13 +100,21 @@ int check_guards(haf_engine *e);                // with HAF_CANARY_CHECK set: HA
 inline int check_guards(haf_engine *) { return HAF_OK; }
 #endif
 
+// A device array that frees itself: the engine's are released by `delete e` (haf_destroy), in no list of names.  A failed alloc() leaves
+// it empty (p == nullptr, n == 0), so n tells whether it can be used.  Move-only.  (file, line: the allocating source line, which the
+// testing build's guard report names; ensure_dev passes its caller's on)
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }      // (o frees what this held)
+    ~DevBuf() { release(); }
 #ifdef HAF_TESTING
     hipError_t alloc(size_t count, const char *file = __builtin_FILE(), int line = __builtin_LINE())
     {
-        n = count;
         if (!count) return hipSuccess;
         const size_t bytes = count * sizeof(T), padded = (bytes + kCanaryGuard - 1) / kCanaryGuard * kCanaryGuard;
         char *raw = nullptr;
@@ -113,6 +124,7 @@ template <typename T> struct DevBuf {
         if (rc == hipSuccess) rc = hipMemset(raw + kCanaryGuard + bytes, kCanaryByte, padded - bytes + kCanaryGuard);
         if (rc != hipSuccess) { (void)hipFree(raw); return rc; }
         p = reinterpret_cast<T *>(raw + kCanaryGuard);
+        n = count;
         canary_register(p, bytes, file, line);
         return hipSuccess;
     }
@@ -122,22 +134,29 @@ template <typename T> struct DevBuf {
         p = nullptr; n = 0;
     }
 #else
-    hipError_t alloc(size_t count)
+    hipError_t alloc(size_t count, const char * = nullptr, int = 0)
     {
-        n = count;
         if (!count) return hipSuccess;
-        return hipMalloc((void **)&p, count * sizeof(T));
+        const hipError_t rc = hipMalloc((void **)&p, count * sizeof(T));
+        if (rc == hipSuccess) n = count; else p = nullptr;
+        return rc;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 #endif
 };
+static_assert(!std::is_copy_constructible_v<DevBuf<char>> && !std::is_copy_assignable_v<DevBuf<char>>, "a DevBuf has one owner");
 
-// A device block and its pinned host twin of the same size.  ensure() gets both halves or neither: when either allocation fails the pair
-// it had stays in place and usable (the engine left as it was); growing replaces the pair, not its contents, once both exist
+// A device block and its pinned host twin of the same size, freed with the object.  ensure() gets both halves or neither: when either
+// allocation fails the pair it had stays in place and usable (the engine left as it was); growing replaces the pair, not its
+// contents, once both exist
 struct StageBuf {
     DevBuf<char> dev;                // dev.n: bytes of either half
     char *host = nullptr;
     bool pinned_failed = false;      // the last ensure() failed for want of the pinned half, not of the device half
+    StageBuf() = default;
+    StageBuf(const StageBuf &) = delete;
+    StageBuf &operator=(const StageBuf &) = delete;
+    ~StageBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         pinned_failed = false;
@@ -146,13 +165,14 @@ struct StageBuf {
         char *h = nullptr;
         hipError_t rc = d.alloc(bytes);
         pinned_failed = rc == hipSuccess && (rc = hipHostMalloc((void **)&h, bytes, hipHostMallocDefault)) != hipSuccess;
-        if (rc != hipSuccess) { d.release(); return rc; }
+        if (rc != hipSuccess) return rc;                 // (d frees the device half it may have got)
         release();
-        dev = d; host = h;
+        dev = std::move(d); host = h;
         return hipSuccess;
     }
     void release() { dev.release(); if (host) (void)hipHostFree(host); host = nullptr; }
 };
+static_assert(!std::is_copy_constructible_v<StageBuf> && !std::is_copy_assignable_v<StageBuf>, "a StageBuf has one owner");
 
 // What the last scored call leaves for the getters (engine.cpp) and the debug reads (engine_debug.cpp, engine_testing.cpp).  A call
 // that scores nothing the caller asked for (the calibration requests, a batch whose every budget is negative) resets it: e->last = {}.
@@ -552,8 +572,27 @@ int score_frames_impl(haf_engine *e, int32_t n, const haf_frame *frames, const h
 // (clouds[b].n_points is the UPPER bound there, the pixels of the request's views)
 int score_views_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_grasp_input *in,
                      haf_grasp_output *out, int64_t *n_points);
-// the raw area of staged host XYZ views, on the first call that has one (`who`: the calling function, for the message)
-int ensure_raw_xyz(haf_engine *e, const std::string &who);
+// engine_stage.cpp: the first-use buffers and the staging of the calls that take a haf_frame; the policies are described there.
+// `who`: the message's prefix, "haf_<call>: "; `what`: the site's words for the buffer ("no device memory for <what>: ...")
+// at least `count` elements in b (a larger need replaces it: the contents are nobody's)
+template <class T> int ensure_dev(haf_engine *e, DevBuf<T> &b, size_t count, const std::string &who, const char *what, const char *file = __builtin_FILE(), int line = __builtin_LINE())
+{
+    if (b.n >= count) return HAF_OK;
+    b.release();
+    const hipError_t rc = b.alloc(count, file, line);
+    return rc == hipSuccess ? HAF_OK : fail(e, HAF_E_DEVICE, who + "no device memory for " + what + ": " + hipGetErrorString(rc));
+}
+// at least `bytes` in both halves of b (StageBuf::ensure: the old pair stays usable when growing fails)
+int ensure_stage(haf_engine *e, StageBuf &b, size_t bytes, const std::string &who, const char *what);
+int ensure_raw_xyz(haf_engine *e, const std::string &who);      // the raw area of staged host XYZ views, on the first call that has one
+// a host frame's packed rows to host_at (pinned) and from there to dev_at, in pieces; no synchronisation
+int upload_frame(haf_engine *e, const haf_frame &f, char *host_at, char *dev_at, hipStream_t s);
+// ONE checked frame as a call's input.  prepare: its refusals and the raw area it goes through (*area), no stream operation.
+// upload: a host frame goes up; *fd = the frame as the kernels read it
+int frame_input_prepare(haf_engine *e, const haf_frame &f, const std::string &who, StageBuf **area);
+int frame_input_upload(haf_engine *e, const haf_frame &f, StageBuf &area, hipStream_t s, FrameDev *fd);
+// a side image of frame f (f.height x f.width elements): a host one through `block` at `at`, one copy; *id = where the kernels read it
+int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, StageBuf &block, size_t at, hipStream_t s, ImageDev *id);
 // engine_roi.cpp
 int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in, haf_grasp_output *out);
 int score_views_roi_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_roi *rois,

@@ -82,10 +82,7 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
     // a C5 request at once: 288 x 4 MiB), the workgroups loop over the rest
     const size_t slot_words = HW;
     const int n_slots = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BR, 1024, ((size_t)2 << 30) / (2 * slot_words * 8)}));
-    if (e->d_top_scratch.n < (size_t)n_slots * 2 * slot_words) {
-        e->d_top_scratch.release();
-        HIPCHK(e, e->d_top_scratch.alloc((size_t)n_slots * 2 * slot_words));
-    }
+    if (const int rc = ensure_dev(e, e->d_top_scratch, (size_t)n_slots * 2 * slot_words, "haf_top_grasps: ", "the run-list scratch")) return rc;
     const size_t hdr_bytes = (size_t)BR * 4 * sizeof(int);      // 16-byte aligned: TopCandDev follows
     std::vector<haf_grasp_candidate> res((size_t)B * p->k);
     std::vector<int32_t> found((size_t)B, 0);
@@ -93,7 +90,7 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
     std::vector<int32_t> len;
     for (;;) {
         const size_t out_bytes = hdr_bytes + (size_t)BR * depth * sizeof(TopCandDev);
-        HIPCHK(e, e->top_out.ensure(out_bytes));
+        if (const int rc = ensure_stage(e, e->top_out, out_bytes, "haf_top_grasps: ", "the output block")) return rc;
         int *d_hdr = reinterpret_cast<int *>(e->top_out.dev.p);
         TopCandDev *d_cand = reinterpret_cast<TopCandDev *>(e->top_out.dev.p + hdr_bytes);
         Dims d{};

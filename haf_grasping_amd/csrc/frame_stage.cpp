@@ -32,6 +32,26 @@ void pack_rows(char *dst, const char *src, size_t height, size_t width, size_t e
     }
 }
 
+void unpack_rows(char *dst, size_t dst_row_stride, const char *src_packed, size_t height, size_t row_bytes)
+{
+    for (size_t v = 0; v < height; v++) memcpy(dst + v * dst_row_stride, src_packed + v * row_bytes, row_bytes);
+}
+
+ImageDev describe_image(const void *data, int on_device, size_t row_stride_bytes, size_t width, size_t elem_bytes, const void *staged_at)
+{
+    if (!data) return {nullptr, 0};
+    if (on_device == 1) return {data, (unsigned long long)row_stride_bytes};
+    return {staged_at, (unsigned long long)width * elem_bytes};
+}
+
+OutputDev describe_output(void *out, int out_on_device, size_t out_row_stride_bytes, size_t width, size_t elem_bytes, void *packed_at, void *own)
+{
+    const unsigned long long packed = (unsigned long long)width * elem_bytes;
+    if (out_on_device == 0) return {packed_at, packed, out, 0, out_row_stride_bytes};
+    if (out) return {out, (unsigned long long)out_row_stride_bytes, out, 1, out_row_stride_bytes};
+    return {own, packed, own, 1, (size_t)packed};
+}
+
 FrameBatch check_frame_batch(const haf_frame *frames, int32_t n, const int32_t *views_per_request, int64_t max_points)
 {
     FrameBatch r;

@@ -1,6 +1,8 @@
 // frame_stage.h -- a sensor frame (haf_frame) on its way to the device, without a device: its descriptor (FrameDev, frames.h), the packing
-// of a host frame's or mask's rows into a pinned block and their upload in pieces, the checks of a batch before any device work.  Every
-// entry point that takes a haf_frame goes through here.  Needs neither HIP nor an engine: tests/sanitize/stage_paths.cpp drives it.
+// of a host frame's or mask's rows into a pinned block and their upload in pieces, the checks of a batch before any device work; and the
+// images that travel with it: where the kernels read a mask or a label image, where they write an output image and how its packed rows
+// reach the caller's.  Every entry point that takes a haf_frame goes through here; engine_stage.cpp is the half that needs an engine.
+// Needs neither HIP nor an engine: tests/sanitize/stage_paths.cpp drives it.
 #pragma once
 #include "frames.h"
 
@@ -21,6 +23,22 @@ size_t staged_bytes(const haf_frame &f);
 // height rows of width elements (elem_stride bytes apart, rows row_stride bytes apart) to dst, packed: of every element its first
 // elem_bytes bytes.  Reads (width - 1) * elem_stride + elem_bytes bytes of a source row and no more: the caller's last row may end there
 void pack_rows(char *dst, const char *src, size_t height, size_t width, size_t elem_bytes, size_t elem_stride, size_t row_stride);
+
+// the inverse, for an output image: writes exactly row_bytes per row and nothing between the rows: the caller's last row may end there
+void unpack_rows(char *dst, size_t dst_row_stride, const char *src_packed, size_t height, size_t row_bytes);
+
+// a side image of a frame `width` pixels wide (a haf_roi's mask, a haf_label_image) as the kernels read it: a device-resident one where it
+// lies, with the caller's stride; a host one at staged_at, where its rows lie packed; no image (data == nullptr): null and 0
+struct ImageDev { const void *src; unsigned long long row_stride; };
+ImageDev describe_image(const void *data, int on_device, size_t row_stride_bytes, size_t width, size_t elem_bytes, const void *staged_at);
+
+// an output image `width` elements wide: a host one (out_on_device == 0) is written packed at packed_at, inside the block the call copies
+// back, and unpack_rows takes it to `out`; the caller's device image where it lies; without one (out == nullptr) the engine's own, packed
+struct OutputDev {
+    void *dst; unsigned long long dst_stride;                   // the kernel's
+    void *data; int32_t on_device; size_t row_stride_bytes;     // the descriptor handed back
+};
+OutputDev describe_output(void *out, int out_on_device, size_t out_row_stride_bytes, size_t width, size_t elem_bytes, void *packed_at, void *own);
 
 // pack_rows row after row, with send(offset into dst, bytes) whenever at least kStagePiece packed bytes are unsent and after the last
 // row: every piece ends at a row's end.  Stops at the first send that does not return 0 and returns what it returned (an int, a hipError_t)

@@ -1,7 +1,8 @@
 // stage_paths.cpp -- sanitizer driver of the sensor-frame staging code that needs no device (csrc/frame_stage.h; tests/test_frame_stage_cpu.py
 // builds it with -fsanitize=address,undefined, host only): pack_rows and stage_rows over frames and masks of every kind, shape and stride
-// against a byte-by-byte loop, the pieces stage_rows sends against the upload loop it replaced, describe_frame / staged_bytes field by
-// field, check_frame_batch over the refusals of tests/frame_cases.py.  Every source and destination is a heap block of EXACTLY the bytes
+// against a byte-by-byte loop, unpack_rows into padded targets whose bytes between the rows must stay, the pieces stage_rows sends against
+// the upload loop it replaced, describe_frame / staged_bytes / describe_image / describe_output field by field, check_frame_batch over the
+// refusals of tests/frame_cases.py.  Every source and destination is a heap block of EXACTLY the bytes
 // the frame describes -- the last source row ends at its last kept element -- so one byte read or written past either is a report.
 // argv: the file of refusal frames (records of {int32 code, int32 data: 0 null / 1 aligned / 2 misaligned by one, haf_frame}).
 #include "../../haf_grasping_amd/csrc/frame_stage.h"
@@ -91,6 +92,51 @@ static void run_pack(size_t h, size_t w, size_t elem_bytes, size_t elem_stride, 
     check_calls(calls, total, w * elem_bytes);
     EXPECT(calls.size() == 1);                                       // (all of these are shorter than a piece)
     free(src); free(want); free(got); free(got2);
+}
+
+// packed rows through unpack_rows into a target of EXACTLY (h - 1) * stride + row_bytes bytes -- its last row ends at row_bytes, not at the
+// stride -- against a byte-by-byte loop; the bytes between the rows are pre-filled and must be unchanged
+static void run_unpack(size_t h, size_t w, size_t elem_bytes, size_t pad_bytes)
+{
+    const size_t row_bytes = w * elem_bytes, stride = row_bytes + pad_bytes, total = (h - 1) * stride + row_bytes;
+    char *src = (char *)malloc(h * row_bytes), *want = (char *)malloc(total), *got = (char *)malloc(total);
+    for (size_t i = 0; i < h * row_bytes; i++) src[i] = (char)lcg();
+    for (size_t i = 0; i < total; i++) want[i] = got[i] = (char)(0xC3 ^ i);
+    for (size_t v = 0; v < h; v++)
+        for (size_t i = 0; i < row_bytes; i++) want[v * stride + i] = src[v * row_bytes + i];
+    unpack_rows(got, stride, src, h, row_bytes);
+    EXPECT(memcmp(got, want, total) == 0);
+    // the inverse of pack_rows: packing the target again gives the source
+    char *back = (char *)malloc(h * row_bytes);
+    pack_rows(back, got, h, w, elem_bytes, elem_bytes, stride);
+    EXPECT(memcmp(back, src, h * row_bytes) == 0);
+    free(src); free(want); free(got); free(back);
+}
+
+// a side image (a mask, a label image) and an output image as the kernels get them, field by field
+static void run_describe_images()
+{
+    char *image = (char *)malloc(16), *staged = (char *)malloc(16), *own = (char *)malloc(16);
+    for (size_t eb : {1, 2}) {
+        ImageDev d = describe_image(image, 0, 61 * eb + 7, 61, eb, staged);          // host: its packed copy
+        EXPECT(d.src == staged && d.row_stride == 61 * eb);
+        d = describe_image(image, 1, 61 * eb + 7, 61, eb, staged);                   // resident: where it lies, the caller's stride
+        EXPECT(d.src == image && d.row_stride == 61 * eb + 7);
+        for (int on_device = 0; on_device < 2; on_device++) {                        // no image: whatever the other fields say
+            d = describe_image(nullptr, on_device, 61 * eb + 7, 61, eb, staged);
+            EXPECT(d.src == nullptr && d.row_stride == 0);
+        }
+    }
+    for (size_t eb : {1, 2, 4}) {
+        const size_t stride = 61 * eb + 12;
+        OutputDev o = describe_output(image, 0, stride, 61, eb, staged, own);        // host: written packed into the call's block
+        EXPECT(o.dst == staged && o.dst_stride == 61 * eb && o.data == image && o.on_device == 0 && o.row_stride_bytes == stride);
+        o = describe_output(image, 1, stride, 61, eb, staged, own);                  // the caller's device image, its stride
+        EXPECT(o.dst == image && o.dst_stride == stride && o.data == image && o.on_device == 1 && o.row_stride_bytes == stride);
+        o = describe_output(nullptr, 1, 0, 61, eb, staged, own);                     // the engine's own image, packed
+        EXPECT(o.dst == own && o.dst_stride == 61 * eb && o.data == own && o.on_device == 1 && o.row_stride_bytes == 61 * eb);
+    }
+    free(image); free(staged); free(own);
 }
 
 static haf_frame make_frame(int kind, int w, int h, size_t pad_elems, size_t point_stride, int on_device)
@@ -213,6 +259,7 @@ int main(int argc, char **argv)
                 run_pack(h, w, 4, 4, w * 4 + pad * 4);                                   // F32
                 for (size_t ps : {12, 16, 20}) run_pack(h, w, 12, ps, w * ps + pad * 4); // XYZ
                 if (pad == 0) { run_pack(h, w, 1, 1, w); run_pack(h, w, 1, 1, w + 5); }  // masks
+                for (size_t eb : {1, 2, 4}) run_unpack(h, w, eb, pad);                   // output images: labels, depth
                 for (int kind : {HAF_FRAME_DEPTH_U16, HAF_FRAME_DEPTH_F32}) EXPECT(run_pieces(kind, (int)w, (int)h, pad, 0).size() == 1);
                 for (size_t ps : {12, 16, 20}) EXPECT(run_pieces(HAF_FRAME_XYZ_F32, (int)w, (int)h, pad, ps).size() == 1);
             }
@@ -231,6 +278,7 @@ int main(int argc, char **argv)
     run_describe(HAF_FRAME_DEPTH_F32, 0);
     run_describe(HAF_FRAME_XYZ_F32, 12);
     run_describe(HAF_FRAME_XYZ_F32, 20);
+    run_describe_images();
     run_batches(argv[1]);
     if (failures) { fprintf(stderr, "%d expectation(s) failed\n", failures); return 1; }
     printf("stage sanitizer job ok\n");

@@ -1,5 +1,5 @@
-"""CPU test of the sensor-frame staging code that needs no device (csrc/frame_stage.h): the host sanitizer job of pack_rows, stage_rows,
-describe_frame, staged_bytes and check_frame_batch.  The wiring into the engine needs a GPU: tests/test_frame_stage_gpu.py."""
+"""CPU test of the sensor-frame staging code that needs no device (csrc/frame_stage.h): the host sanitizer job of pack_rows, unpack_rows,
+stage_rows, describe_frame, staged_bytes, describe_image, describe_output and check_frame_batch.  The wiring into the engine needs a GPU: tests/test_frame_stage_gpu.py."""
 import ctypes as C
 import os
 import shutil
@@ -17,8 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_stage_paths_under_address_and_ub_sanitizers(tmp_path):
     """frame_stage.cpp + frames_host.cpp + parsers.cpp built with -fsanitize=address,undefined by the ROCm clang and driven by
     tests/sanitize/stage_paths.cpp as a program of its own: every kind, width 1 / 3 / 61 / 64, height 1 / 5, padded rows, point strides
-    12 / 16 / 20 and masks against a byte-by-byte loop in exactly sized heap blocks; the pieces of frames around 256 KB against the upload
-    loop the code replaced; the descriptors; the batch checks over every refusal of frame_cases.refusal_frames().  Any report fails."""
+    12 / 16 / 20 and masks against a byte-by-byte loop in exactly sized heap blocks; unpack_rows of 1 / 2 / 4-byte elements into padded
+    targets whose last row ends at its last element and whose bytes between the rows must stay; the pieces of frames around 256 KB against
+    the upload loop the code replaced; the descriptors of frames, side images and output images; the batch checks over every refusal of frame_cases.refusal_frames().  Any report fails."""
     clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
     if not os.path.exists(clang):
         clang = shutil.which("clang++") or shutil.which("g++")

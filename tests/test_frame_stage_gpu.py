@@ -11,8 +11,11 @@ import pytest
 import frame_cases as fc
 import pcdio
 from haf_grasping_amd import capi
+from test_depth_filter_gpu import fetch
 from test_frames_gpu import C3_IN, K525, TABLE1, assert_same, device_copy, make_engine, render_depth, snapshot
+from test_labels_gpu import device_labels
 from test_roi_gpu import device_mask, strip
+from test_segment_gpu import TABLE1_PARAMS, image_of
 from test_views_gpu import CAM_A, sorted_rows
 
 pytestmark = pytest.mark.gpu
@@ -76,7 +79,10 @@ def roi_state(eng, out):
 def test_staged_host_frame_equals_device_resident_frame_on_every_route(engine, scenes, name):
     """haf_score_frames, haf_score_views (as the only view and as the second of two), haf_score_frames_roi with a host mask of padded rows
     and haf_grasp_map: outputs, the points the kernels read (as a sorted multiset for views), the batch's grids, tier counts and ranked
-    candidates, and the three map images are those of the same call on the device-resident copy"""
+    candidates, and the three map images are those of the same call on the device-resident copy.  So are the stages around a request,
+    each with its host side image in padded rows against the device-resident one: haf_segment_frame into a padded host canvas and into
+    the engine's image, haf_fit_plane under the mask, haf_measure_labels, haf_filter_depth of the frame twice (depth only),
+    haf_grasp_map_best under the mask and haf_grasp_map_labels"""
     eng, inp = engine, capi.default_input(**C3_IN)
     host, _, dev, mask, (dmask, _) = scenes[name]
     other = scenes["xyz" if name == "u16" else "u16"][2]          # device-resident in both calls
@@ -112,6 +118,55 @@ def test_staged_host_frame_equals_device_resident_frame_on_every_route(engine, s
     assert_same(got[0], ref[0])
     assert (got[1] == ref[1]).all() and (got[1] == want_points).all()
     assert 0 < got[0]["out"]["n_evals"]
+
+    h, w = host.height, host.width
+    sp = capi.segment_params(**TABLE1_PARAMS)
+
+    def segment_route(f):
+        canvas = np.full((h, w + 2), 0x5A, np.uint8)
+        labels, infos, stats = eng.segment(f, sp, host_out=canvas[:, :w])
+        assert labels.ctypes.data == canvas.ctypes.data and (canvas[:, w:] == 0x5A).all()
+        img, infos_own, stats_own = eng.segment(f, sp, device_out=True)
+        return labels.tobytes(), infos.tobytes(), stats, image_of(img, f, np.uint8)[0].tobytes(), infos_own.tobytes(), stats_own
+
+    got, ref = segment_route(host), segment_route(dev)
+    assert got == ref and got[0] == got[3] and got[2][3] >= 1                     # (objects were found: not a comparison of empty images)
+    n_labels = min(got[2][3], sp.max_labels)
+    labels = np.full((h, w + 3), 200, np.uint8)                                   # padded rows, the padding a label that must never be read
+    labels[:, :w] = np.frombuffer(got[0], np.uint8).reshape(h, w)
+    labels = labels[:, :w]
+    dlabels, _keep = device_labels(labels, stride_bytes=w + 5)
+
+    def plane_route(f, m):
+        fit = eng.fit_plane(f, mask=m, debug=True)
+        return {k: v.tobytes() if isinstance(v, np.ndarray) else v for k, v in fit.items()}
+
+    got, ref = plane_route(host, mask), plane_route(dev, dmask)
+    assert_same(got, ref)
+    assert got["stats"][1] > 100                                                  # (usable pixels under the mask)
+    got, ref = eng.measure_labels(host, labels, n_labels, plane=[0, 0, 1, 0]), eng.measure_labels(dev, dlabels, n_labels, plane=[0, 0, 1, 0])
+    assert got.tobytes() == ref.tobytes() and len(got) == n_labels
+
+    if name == "u16":
+        def filter_route(frames):
+            f, stats = eng.filter_depth(frames)                                   # (into the engine's image: max_points holds two host frames, not a third image)
+            assert f.on_device == 1 and f.row_stride_bytes == w * 2
+            return fetch(f.data, h * w * 2).tobytes(), stats
+
+        got, ref = filter_route([host, host]), filter_route([dev, dev])
+        assert got == ref and got[1][2] > 1000
+
+    eng.score_frames([dev], [inp])
+    got, ref = eng.best_in_mask(0, host, mask), eng.best_in_mask(0, dev, mask)
+    assert got is not None and got == ref
+
+    def labels_route(f, l):
+        res = eng.best_per_label(0, f, l, n_labels)
+        return dict(res, picks=res["picks"].tobytes())
+
+    got, ref = labels_route(host, labels), labels_route(dev, dlabels)
+    assert_same(got, ref)
+    assert len(got["order"]) >= 1
 
 
 def test_staging_blocks_grow_and_leave_results_as_they_were(data_dir, golden_dir, scenes):
