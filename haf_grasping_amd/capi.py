@@ -231,6 +231,8 @@ def _bind(path, testing):
                                      C.POINTER(LabelImage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.haf_grasp_map_labels.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(C.c_int32)]
+    L.haf_score_objects.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(GraspInput),
+                                    C.c_int32, C.POINTER(GraspOutput), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.haf_roi_cells.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_int32, C.POINTER(Frame), C.c_void_p, C.c_size_t, C.c_void_p,
                                 C.c_void_p]
     L.haf_score_frames_roi.argtypes = [E, C.c_int32, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(GraspInput), C.POINTER(GraspOutput)]
@@ -1211,6 +1213,27 @@ class Engine:
         self._check(self._L.haf_grasp_map_labels(self._h, request, C.byref(frame), C.byref(img), n_labels, min_vote, picks.ctypes.data, poses,
                                                  order.ctypes.data, C.byref(nf)))
         return _label_result(picks[:n_labels], order, nf.value, poses)
+
+    def score_objects(self, frame, labels, n_labels, object_labels, inputs, min_vote=1):
+        """haf_score_objects: every listed object of a label image (label_image(): a numpy uint8 / uint16 array, a device tensor, a device
+        pointer tuple or the LabelImage segment(..., device_out=True) returned) as an ROI request of its own on ONE frame -- request b is
+        inputs[b] under the mask `labels == object_labels[b]` -- and each object's pick from its own request, in one call
+        -> (outputs: a dict per object, picks: LABEL_PICK_DTYPE [n_objects], poses: per object the candidate dict of its pick or None,
+        order: the indices b of the found objects, best pick first).  Afterwards the last batch is those n_objects ROI requests."""
+        img, n_labels = label_image(labels, frame, n_labels)
+        n = len(object_labels)
+        ol = (C.c_int32 * max(1, n))(*[int(l) for l in object_labels])
+        gi = (GraspInput * max(1, n))(*inputs)
+        out = (GraspOutput * max(1, n))()
+        picks = np.zeros(max(1, n), LABEL_PICK_DTYPE)
+        order = np.zeros(max(1, n), np.int32)
+        poses = (GraspCandidate * max(1, n))()
+        nf = C.c_int32(0)
+        self._check(self._L.haf_score_objects(self._h, C.byref(frame), C.byref(img), n_labels, n, ol, gi, min_vote, out, picks.ctypes.data, poses,
+                                              order.ctypes.data, C.byref(nf)))
+        self._last_points = [frame.width * frame.height] * n
+        res = _label_result(picks[:n], order, nf.value, poses)
+        return [output_to_dict(o) for o in out[:n]], res["picks"], res["poses"], res["order"]
 
     def debug_attr(self, cloud, roll):
         """Attribute records of the masked cells of (cloud, roll): cells [n, 2], records [n, 324], computed [n]."""

@@ -36,6 +36,8 @@
 //                                     box with a grasp area that covers it and MARGIN (default 4) more cells (haf_measure_labels,
 //                                     haf_object_input, batched haf_score_frames_roi under the label image); one line "object <label>
 //                                     <u> <v> <hypothesis> width <narrow_width> yaw <deg> height <h>" per object, best first
+//   --segment ... --per-object [MARGIN] --fused   the same lines from ONE haf_score_objects call per chunk of max_clouds objects: the
+//                                     frame is staged and deprojected once and every request evaluates only near its own object
 //   --segment MIN_H,MAX_H,GAP,MIN_PX | default
 //                                     with --depth: no segmenter at hand -- the first view is clustered into objects on the device
 //                                     (haf_segment_frame: pixels MIN_H..MAX_H metres above the support plane, MAX_H <= 0: no upper limit;
@@ -152,7 +154,7 @@ static void usage()
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
             "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
-            "  --labels FILE.pgm --measure [--plane A B C D]     --segment ... --per-object [MARGIN]      (with ONE --depth)\n"
+            "  --labels FILE.pgm --measure [--plane A B C D]     --segment ... --per-object [MARGIN] [--fused]      (with ONE --depth)\n"
             "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D | --plane fit[,TOL,N_HYP] [--plane-mask FILE.pgm]] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
@@ -209,6 +211,7 @@ struct MapOptions {
     float seg_plane[4] = {0, 0, 1, 0};   // the plane the segmentation ran over (filled by run_depth)
     // --per-object [MARGIN]: a request per segmented object; --measure: the shapes of --labels, no request
     bool per_object = false, measure = false;
+    bool fused = false;                  // --per-object --fused: one haf_score_objects call per chunk
     int margin_cells = 4;
 };
 
@@ -458,13 +461,39 @@ static int run_per_object(haf_engine *eng, const haf_config &cfg, const haf_gras
         if (shapes[l].found && haf_object_input(&cfg, &in, &shapes[l], mo.margin_cells, &t.in, &t.fits) == HAF_OK) todo.push_back(t);
     }
     const size_t px = (size_t)f.width * (size_t)f.height;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)cfg.max_clouds, (size_t)cfg.max_points / std::max<size_t>(1, px)));
+    // (--fused: the frame counts once against max_points whatever the chunk holds)
+    const size_t chunk = mo.fused ? std::max<size_t>(1, (size_t)cfg.max_clouds)
+                                  : std::max<size_t>(1, std::min<size_t>((size_t)cfg.max_clouds, (size_t)cfg.max_points / std::max<size_t>(1, px)));
     struct Hit { unsigned long long key; std::string line; };
     std::vector<Hit> hits;
     std::vector<haf_label_pick> picks(n);
     std::vector<haf_grasp_candidate> poses(n);
+    const auto add_hit = [&](int32_t label, const haf_label_pick &p, const haf_grasp_candidate &pose) {
+        const size_t l = (size_t)label - 1;
+        const unsigned i = (unsigned)((size_t)p.v * (size_t)f.width + (size_t)p.u);      // haf_grasp_map_labels' key: vote, then roll, then pixel
+        const unsigned long long key = ((unsigned long long)(unsigned)(p.vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - p.roll) << 32) |
+                                       (unsigned long long)(0xFFFFFFFFu - i);
+        char tail[128];
+        snprintf(tail, sizeof tail, " width %.9g yaw %d height %.9g", shapes[l].narrow_width, (int)shapes[l].narrow_dir * 15, shapes[l].height);
+        hits.push_back(Hit{key, "object " + std::to_string(label) + " " + std::to_string(p.u) + " " + std::to_string(p.v) + " " +
+                                    hafshim::hypothesis_string(pose.grasp, cfg.roll_step_deg) + tail});
+    };
     for (size_t c0 = 0; c0 < todo.size(); c0 += chunk) {
         const size_t k = std::min(chunk, todo.size() - c0);
+        if (mo.fused) {                                   // ONE call: every object of the chunk a request of its own on the shared frame
+            std::vector<int32_t> object_labels(k);
+            std::vector<haf_grasp_input> ins(k);
+            std::vector<haf_grasp_output> outs(k);
+            for (size_t b = 0; b < k; b++) { object_labels[b] = todo[c0 + b].label; ins[b] = todo[c0 + b].in; }
+            if (haf_score_objects(eng, &f, &img, mo.seg_n, (int32_t)k, object_labels.data(), ins.data(), mo.min_vote, outs.data(), picks.data(),
+                                  poses.data(), nullptr, nullptr) != HAF_OK) {
+                fprintf(stderr, "--per-object --fused: %s\n", haf_last_error(eng));
+                return 1;
+            }
+            for (size_t b = 0; b < k; b++)
+                if (picks[b].found) add_hit(object_labels[b], picks[b], poses[b]);
+            continue;
+        }
         std::vector<haf_frame> frames(k, f);
         std::vector<haf_roi> rois(k, haf_roi{mo.seg_labels.data(), (size_t)f.width, 0});
         std::vector<haf_grasp_input> ins(k);
@@ -480,15 +509,7 @@ static int run_per_object(haf_engine *eng, const haf_config &cfg, const haf_gras
                 return 1;
             }
             const size_t l = (size_t)todo[c0 + b].label - 1;
-            const haf_label_pick &p = picks[l];
-            if (!p.found) continue;
-            const unsigned i = (unsigned)((size_t)p.v * (size_t)f.width + (size_t)p.u);      // haf_grasp_map_labels' key: vote, then roll, then pixel
-            const unsigned long long key = ((unsigned long long)(unsigned)(p.vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - p.roll) << 32) |
-                                           (unsigned long long)(0xFFFFFFFFu - i);
-            char tail[128];
-            snprintf(tail, sizeof tail, " width %.9g yaw %d height %.9g", shapes[l].narrow_width, (int)shapes[l].narrow_dir * 15, shapes[l].height);
-            hits.push_back(Hit{key, "object " + std::to_string(todo[c0 + b].label) + " " + std::to_string(p.u) + " " + std::to_string(p.v) + " " +
-                                        hafshim::hypothesis_string(poses[l].grasp, cfg.roll_step_deg) + tail});
+            if (picks[l].found) add_hit(todo[c0 + b].label, picks[l], poses[l]);
         }
     }
     std::sort(hits.begin(), hits.end(), [](const Hit &a, const Hit &b) { return a.key > b.key; });
@@ -738,6 +759,7 @@ int main(int argc, char **argv)
         else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
         else if (a == "--segment") { need(1); if (!parse_segment(argv[++i], &map_opt.segment_params)) { usage(); return 2; } map_opt.segment = true; }
         else if (a == "--segment-roi") map_opt.segment_roi = true;
+        else if (a == "--fused") map_opt.fused = true;
         else if (a == "--per-object") { map_opt.per_object = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') map_opt.margin_cells = atoi(argv[++i]); }
         else if (a == "--measure") map_opt.measure = true;
         else if (a == "--plane" && i + 1 < argc && strncmp(argv[i + 1], "fit", 3) == 0) { if (!parse_plane_fit(argv[++i], &map_opt.plane_params)) { usage(); return 2; } map_opt.fit_plane = true; }
@@ -760,6 +782,7 @@ int main(int argc, char **argv)
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
         (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || (map_opt.have_plane && !map_opt.measure) || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.fused && !map_opt.per_object) ||
         (map_opt.per_object && (!map_opt.segment || views.size() != 1 || map_opt.segment_roi || map_opt.measure || !map_opt.roi_path.empty() || !map_opt.labels_path.empty())) ||
         (map_opt.measure && (map_opt.labels_path.empty() || views.size() != 1 || map_opt.segment || map_opt.fit_plane)) ||
         (map_opt.fit_plane && map_opt.have_plane) || (!map_opt.fit_plane && !map_opt.plane_mask.empty()) ||

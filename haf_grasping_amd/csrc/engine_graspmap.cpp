@@ -127,7 +127,10 @@ int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *
     return HAF_OK;
 }
 
-// a cell's record as a candidate: haf_top_grasps' pose of it, run_length 0 (a cell is not a run).  haf_cell_pose and haf_grasp_map_labels
+}  // namespace
+
+// a cell's record as a candidate: haf_top_grasps' pose of it, run_length 0 (a cell is not a run).  haf_cell_pose, haf_grasp_map_labels
+// and haf_score_objects (engine_objects.cpp)
 int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out)
 {
     haf_roll_record rec;
@@ -141,6 +144,8 @@ int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &
     *out = cand;
     return HAF_OK;
 }
+
+namespace {
 
 int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, haf_grasp_candidate *out)
 {

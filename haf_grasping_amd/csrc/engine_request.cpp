@@ -304,7 +304,7 @@ static int check_request(haf_engine *e, int32_t n_clouds, const haf_cloud *cloud
             if (clouds[b].stride_floats != 3 || (clouds[b].n_points && !inside))
                 return fail(e, HAF_E_ARG, "on_device = 2 needs a packed xyz cloud inside a buffer registered with haf_register_host_cloud");
         }
-        if (clouds[b].on_device != 1) host_pts += clouds[b].n_points;
+        if (clouds[b].on_device != 1 && !(q.from.objects && b > 0)) host_pts += clouds[b].n_points;      // (an objects call: every cloud is frame 0's points)
         q.max_n = std::max(q.max_n, (int)clouds[b].n_points);
     }
     if (host_pts > (size_t)c.max_points) return fail(e, HAF_E_CAPACITY, "more host points than max_points");
@@ -321,7 +321,8 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     const size_t geo_off = up16((size_t)B * sizeof(CloudDev));
     const size_t frames_off = geo_off + up16((size_t)B * R * sizeof(RollGeo));
     q.n_frames = 0;
-    for (int b = 0; frames && b < B; b++) q.n_frames += views ? views[b] : 1;
+    const bool shared = q.from.objects != nullptr;       // haf_score_objects: ONE frame, whose points every cloud of the batch points at
+    for (int b = 0; frames && b < (shared ? 1 : B); b++) q.n_frames += views ? views[b] : 1;
     const size_t roi_off = frames_off + up16((size_t)q.n_frames * sizeof(FrameDev));
     const bool roi_views = views && q.from.roi;
     q.pts_off = roi_off + (roi_views ? up16((size_t)q.n_frames * sizeof(RoiViewDev)) : 0);
@@ -347,7 +348,11 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
         cd.bucket_off = b * e->bkt_ints;
         q.total_n += (long)clouds[b].n_points;
         cd.n = views ? 0 : (int)clouds[b].n_points;      // (views: the kernels count the valid points)
-        if (clouds[b].on_device == 1) {
+        if (shared && b > 0) {
+            cd.xyz = q.h_clouds[0].xyz;
+            cd.stride = 3;
+            q.src[(size_t)b] = q.src[0];
+        } else if (clouds[b].on_device == 1) {
             cd.xyz = clouds[b].xyz;
             cd.stride = (int)clouds[b].stride_floats;
         } else {
@@ -363,7 +368,7 @@ static void pack_headers(haf_engine *e, const haf_cloud *clouds, const haf_grasp
     // Views: compaction writes where other lanes have not read yet, so a host XYZ view is NOT staged in the points area but in a raw
     // area of its own (raw_xyz); the views of a request share its region and its counter
     size_t raw = 0, raw_xyz = 0;
-    for (int b = 0, k = 0; frames && b < B; b++) {
+    for (int b = 0, k = 0; frames && b < (shared ? 1 : B); b++) {
         for (int v = 0; v < (views ? views[b] : 1); v++, k++) {
             const haf_frame &f = frames[k];
             const bool xyz = f.kind == HAF_FRAME_XYZ_F32;
@@ -393,7 +398,7 @@ static int upload_frames(haf_engine *e, const Request &q)
         if (const int rc = upload_frame(e, f, host + at, dev + at, s)) return rc;
     }
     if (!views) {
-        launch_frame_points(q.d_frames, q.h_frames, q.B, s);
+        launch_frame_points(q.d_frames, q.h_frames, q.n_frames, s);      // (a frame per request; one for all of them in an objects call)
         return HAF_OK;
     }
     launch_view_points(q.d_frames, q.h_frames, q.n_frames, s);
@@ -522,7 +527,11 @@ static int run_prestages(haf_engine *e, Request &q)
     const int integral = launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
     e->pre_forms = PrestageForms{bin.form, integral, bin.bucket_refused};
     mark(e, HAF_ST_MASK);
-    if (q.from.roi) {
+    if (q.from.objects) {
+        const int rc = objects_mark_cells(e, *q.from.objects, q.from.frames[0], q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s);
+        if (rc != HAF_OK) return rc;
+        launch_mask_count_roi(e->d_ii.p, q.d_geo, e->d_roi_cells.p, e->d_mask.p, e->d_rowcount.p, d, s);
+    } else if (q.from.roi) {
         const RoiViews rv{q.d_frames, q.h_frames, q.d_roi_views, q.h_roi_views, q.n_frames};
         const int rc = roi_mark_cells(e, *q.from.roi, q.from.frames, q.h_clouds, q.d_geo, d, q.r_row, q.r_col, s, q.from.views ? &rv : nullptr);
         if (rc != HAF_OK) return rc;
@@ -924,7 +933,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     q.s = e->stream;
     mark(e, 0);
     if ((rc = q.from.frames ? upload_frames(e, q) : upload_clouds(e, clouds, q)) != HAF_OK) return rc;
-    if (roi && (rc = roi_upload_masks(e, *roi, q.from.frames, q.n_frames, q.s)) != HAF_OK) return rc;
+    if (roi && !q.from.objects && (rc = roi_upload_masks(e, *roi, q.from.frames, q.n_frames, q.s)) != HAF_OK) return rc;
     classify_request(e, in, q);
     if ((rc = run_prestages(e, q)) != HAF_OK) return rc;
     int mode = contraction_mode(e->cfg);

@@ -12,8 +12,6 @@
 
 namespace haf_host {
 
-namespace {
-
 // the ROI cell sets and the masks' area, on the first call (the precedent: the raw area of host XYZ views, score_views_impl)
 int ensure_roi_buffers(haf_engine *e, const std::string &who)
 {
@@ -26,8 +24,6 @@ int ensure_roi_buffers(haf_engine *e, const std::string &who)
     if (rc == HAF_OK && (rc = ensure_dev(e, e->d_roi_cells, words, who, "the ROI buffers")) != HAF_OK) e->roi_mask.release();      // all or nothing: the next call tries again
     return rc;
 }
-
-}  // namespace
 
 // host masks of the call's views: their rows without the padding into the pinned area, counted on the way (classify_request).
 // first[b]: the flat index of request b's first view, first[n] the number of views

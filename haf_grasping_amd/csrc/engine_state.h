@@ -6,6 +6,7 @@
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
 //   engine_topgrasps.cpp haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch
 //   engine_graspmap.cpp  haf_grasp_map / haf_cell_pose / haf_grasp_map_best: the last batch's votes in a sensor frame's pixels
+//   engine_objects.cpp   haf_score_objects: every object of a label image as a request of its own, on one shared frame (k_roi_mark_objects, k_map_labels_objects)
 //   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
 //   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
 //   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
@@ -211,11 +212,23 @@ struct RoiCall {
     static bool staged(const haf_roi &r) { return r.mask != nullptr && r.on_device != 1; }
 };
 
+// haf_score_objects: the requests of the batch share ONE frame (frames[0]; one upload, one k_frame_points, one set of points that every
+// CloudDev points at, counted once against max_points) and their masks are the instances of one label image: request b's is
+// `labels == the label of object b`.  Filled by engine_objects.cpp, which has uploaded the image and the table before the request path
+// starts; the request path (engine_request.cpp) reads it where an ROI call's masks would be uploaded and marked
+struct ObjectsCall {
+    const void *d_labels = nullptr;      // the label image on the device: the caller's, or the staged copy
+    size_t label_stride = 0;             // bytes between its rows
+    int label_bytes = 1, n_labels = 0;
+    const int *d_req_of_label = nullptr; // [n_labels] on the device: label l -> its request, -1 for none
+};
+
 // Where a request's points come from when not from the caller's clouds (the request path takes a pointer, null for clouds)
 struct FrameSource {
     const haf_frame *frames = nullptr;   // cloud b's points are frame b's, deprojected on the device; clouds[b] only carries its point count
     const int32_t *views = nullptr;      // ... are the valid points of views[b] consecutive frames; clouds[b].n_points is their pixel count
     const RoiCall *roi = nullptr;        // haf_score_frames_roi, haf_score_views_roi (with views): only the cells near the masked pixels' cells are evaluated
+    const ObjectsCall *objects = nullptr;// haf_score_objects (with roi, whose rois is null and whose masked[] counts each object's pixels): frames[0] serves every request
 };
 
 }  // namespace haf_host
@@ -612,6 +625,17 @@ struct RoiViews {
 // views, k_roi_mark_view over every view of the batch, on the raw pixels k_view_points read
 int roi_mark_cells(haf_engine *e, const RoiCall &roi, const haf_frame *frames, const CloudDev *h_clouds, const RollGeo *d_geo, const Dims &d,
                    float r_row, float r_col, hipStream_t s, const RoiViews *views = nullptr);
+// engine_objects.cpp: haf_score_objects.  objects_mark_cells: roi_mark_cells for an objects call -- clears the B * R cell sets and marks
+// them all with ONE launch of k_roi_mark_objects on the points k_frame_points left at h_clouds[0].xyz
+int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, int32_t n_objects,
+                       const int32_t *object_labels, const haf_grasp_input *in, int32_t min_vote, haf_grasp_output *out, haf_label_pick *picks,
+                       haf_grasp_candidate *poses, int32_t *order, int32_t *n_found);
+int objects_mark_cells(haf_engine *e, const ObjectsCall &oc, const haf_frame &frame, const CloudDev *h_clouds, const RollGeo *d_geo, const Dims &d,
+                       float r_row, float r_col, hipStream_t s);
+// engine_roi.cpp: the ROI cell sets and the masks' area, on the first call that needs them
+int ensure_roi_buffers(haf_engine *e, const std::string &who);
+// engine_graspmap.cpp: a cell's record of request `request` of the last batch as a candidate (haf_cell_pose's pose of it)
+int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

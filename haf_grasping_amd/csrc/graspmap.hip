@@ -21,8 +21,9 @@
 // k_cell_record: the record of one arbitrary cell for haf_cell_pose, with the 9 x 8 z window of k_top_grasps.
 // k_map_labels / k_label_records: haf_grasp_map_labels -- the masked best of every label of an instance-label image in one pass over the
 // frame (a segmented arg-max of the same key in a per-workgroup LDS table), then one wave per label for its pick and its record.
-#include "frame_group.h"
-#include "grasp_cells.h"
+// k_map_labels_objects / k_object_records: haf_score_objects -- the same pass ACROSS the requests of a batch that share one frame: a pixel
+// of label l gathers from the grids of the request l belongs to, and the tables are indexed by request.
+#include "object_group.h"
 
 namespace haf {
 
@@ -307,6 +308,40 @@ void launch_map_labels(const FrameDev &f, const CellGeo *geo, int R, int roll_fi
         launch_map_labels_kind<HAF_FRAME_XYZ_F32>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
 }
 
+// What a wave does once its pick is known: `o` without a record = the entry of a label nothing qualifies for, or of a key that decodes
+// to no cell; pick_record = k_cell_record's work at cell ci of the request's roll r (0 <= ci < H * W, 0 <= r < R; ev16 / heights / rec:
+// the request's first roll), written by lane 0.  k_label_records and k_object_records
+__device__ __forceinline__ LabelOutDev label_out_none()
+{
+    LabelOutDev o;
+    o.found = 0; o.u = o.v = o.roll = o.cell = -1; o.vote = haf_cell_math::kNoCellVote; o.n_pixels = 0;
+    o.rec.vote = 0; o.rec.row = o.rec.col = 0; o.rec.h_locmax = 0.0f; o.rec.n_evals = 0;
+    return o;
+}
+__device__ __forceinline__ void pick_record(LabelOutDev o, int ci, int r, const short *__restrict__ ev16, const float *__restrict__ heights,
+                                            const RollRecordDev *__restrict__ rec, int H, int W, LabelOutDev *__restrict__ out)
+{
+    const int row = ci / W, col = ci - row * W;
+    const size_t HW = (size_t)H * W;
+    int zk = f2key(-10.0f);
+    for (int q = threadIdx.x; q < 72; q += 64) {
+        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
+        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
+            const float h = heights[(size_t)r * HW + (size_t)rr * W + cc];
+            if (-10.0f < h) zk = max(zk, f2key(h));
+        }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) zk = max(zk, __shfl_xor(zk, s, 64));
+    if (threadIdx.x == 0) {
+        o.rec.vote = ev16[(size_t)r * HW + (size_t)ci];
+        o.rec.row = (short)row; o.rec.col = (short)col;
+        o.rec.h_locmax = key2f(zk);
+        o.rec.n_evals = rec[r].n_evals;
+        *out = o;
+    }
+}
+
 // k_label_records: one wave per label.  The label's key names its best pixel i and roll r; the pixel's point (frame_points.h) and its
 // cell under roll r (grasp_cells.h) are recomputed -- the arithmetic is deterministic: this is the cell k_map_labels saw -- and the rest
 // is k_cell_record's work at that cell.  out[l] = {the haf_label_pick image, the record}; cell = -2 marks a key that decodes to nothing
@@ -319,9 +354,7 @@ __global__ __launch_bounds__(64) void k_label_records(const FrameDev f, const Ce
 {
     const int l = blockIdx.x;
     const unsigned long long key = g_key[l];
-    LabelOutDev o;
-    o.found = 0; o.u = o.v = o.roll = o.cell = -1; o.vote = haf_cell_math::kNoCellVote; o.n_pixels = 0;
-    o.rec.vote = 0; o.rec.row = o.rec.col = 0; o.rec.h_locmax = 0.0f; o.rec.n_evals = 0;
+    LabelOutDev o = label_out_none();
     if (key == 0ull) {
         if (threadIdx.x == 0) out[l] = o;
         return;
@@ -348,25 +381,7 @@ __global__ __launch_bounds__(64) void k_label_records(const FrameDev f, const Ce
         if (threadIdx.x == 0) out[l] = o;
         return;
     }
-    const int row = ci / W, col = ci - row * W;
-    const size_t HW = (size_t)H * W;
-    int zk = f2key(-10.0f);
-    for (int q = threadIdx.x; q < 72; q += 64) {
-        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
-        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-            const float h = heights[(size_t)r * HW + (size_t)rr * W + cc];
-            if (-10.0f < h) zk = max(zk, f2key(h));
-        }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) zk = max(zk, __shfl_xor(zk, s, 64));
-    if (threadIdx.x == 0) {
-        o.rec.vote = ev16[(size_t)r * HW + (size_t)ci];
-        o.rec.row = (short)row; o.rec.col = (short)col;
-        o.rec.h_locmax = key2f(zk);
-        o.rec.n_evals = rec[r].n_evals;
-        out[l] = o;
-    }
+    pick_record(o, ci, r, ev16, heights, rec, H, W, out + l);
 }
 
 void launch_label_records(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, const float *heights,
@@ -375,6 +390,119 @@ void launch_label_records(const FrameDev &f, const CellGeo *geo, int R, int roll
 {
     hipLaunchKernelGGL(k_label_records, dim3(n_labels), dim3(64), 0, s, f, geo, R, roll_first, ev16, heights, rec, H, W, r_row, r_col, g_key,
                        g_cnt, out);
+}
+
+// ---- the best pixel per object ACROSS the requests of one frame (haf_score_objects) ----
+// k_map_labels_objects<LABEL_BYTES>: what k_map_labels does for one request, for the B requests of a batch that share the frame and whose
+// objects are instances of one label image.  A lane owns four pixels and reads their labels FIRST (object_group.h); a labelled pixel's
+// request is the table's entry for its label (-1: no object of this call, or a request no roll ran for) and its point is read at its
+// pixel index from the shared cloud -- the words k_frame_points wrote, whatever the frame's kind and residence: nothing is deprojected
+// again.  The wave then takes its requests one after the other (next_request): CellGeo and the vote grids of the request in hand are
+// wave-uniform, and (vote, roll, cell) of its pixels are group_best's -- k_map_labels' arithmetic and order.  A qualifying pixel
+// (k_map_best's rule) sends map_key to its REQUEST's slot of the workgroup's LDS table: B keys, then B counts, 12 bytes per request
+// whatever n_labels is; the non-zero slots go on to the global table as in k_map_labels.  Bounds: 0 <= request < B by the host's table.
+template <int LB>
+__global__ __launch_bounds__(kFrameThreads) void k_map_labels_objects(const float *__restrict__ xyz, unsigned width, unsigned n,
+                                                                      const CellGeo *__restrict__ geo, int B, int R, int roll_first,
+                                                                      const short *__restrict__ ev16, int H, int W, float r_row, float r_col,
+                                                                      const void *__restrict__ labels, unsigned long long label_stride,
+                                                                      int n_labels, const int *__restrict__ req_of_label, int min_vote,
+                                                                      unsigned long long *__restrict__ g_key, unsigned *__restrict__ g_cnt)
+{
+    constexpr unsigned G = kObjGroup;
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_okey[];      // [B] keys, then [B] counts
+    unsigned *s_ocnt = reinterpret_cast<unsigned *>(s_okey + B);
+    for (int b = threadIdx.x; b < B; b += kFrameThreads) { s_okey[b] = 0ull; s_ocnt[b] = 0u; }
+    __syncthreads();
+
+    const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;      // (no early return: every lane meets the barrier below)
+    int req[G];
+    unsigned pending = group_requests<LB>(labels, label_stride, width, n, i0, req_of_label, n_labels, req);
+    if (__ballot(pending != 0u) != 0ull) {                // (wave-uniform) a wave of background costs its label loads
+        float p[G * 3];
+        pending = group_cloud_points(xyz, i0, pending, p);
+        const size_t HW = (size_t)H * (size_t)W;
+        unsigned take;
+        for (int b = next_request(req, pending, &take); b >= 0; b = next_request(req, pending, &take)) {
+            bool usable[G];
+            int best[G], best_roll[G], best_cell[G];
+#pragma unroll
+            for (unsigned k = 0; k < G; k++) usable[k] = (take & (1u << k)) != 0u;
+            group_best<G>(p, usable, geo + (size_t)b * R, R, roll_first, ev16 + (size_t)b * R * HW, H, W, r_row, r_col, best, best_roll, best_cell);
+#pragma unroll
+            for (unsigned k = 0; k < G; k++)
+                if (usable[k] && best_roll[k] >= 0 && best[k] >= min_vote && best[k] > haf_cell_math::kNoCellVote) {      // (k_map_best's rule; 0 <= b < B: inside the table)
+                    atomicMax(&s_okey[b], map_key(best[k], best_roll[k], i0 + k));
+                    atomicAdd(&s_ocnt[b], 1u);
+                }
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += kFrameThreads) {
+        const unsigned c = s_ocnt[b];
+        if (c) { atomicMax(&g_key[b], s_okey[b]); atomicAdd(&g_cnt[b], c); }
+    }
+}
+
+void launch_map_labels_objects(const float *xyz, int width, int n, const CellGeo *geo, int B, int R, int roll_first, const short *ev16, int H,
+                               int W, float r_row, float r_col, const void *labels, size_t label_stride, int label_bytes, int n_labels,
+                               const int *req_of_label, int min_vote, unsigned long long *g_key, unsigned *g_cnt, hipStream_t s)
+{
+    const unsigned groups = ((unsigned)std::max(0, n) + kObjGroup - 1) / kObjGroup;
+    if (!groups || B < 1) return;
+    const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
+    const size_t lds = (size_t)B * 12;
+    if (label_bytes == 2)
+        hipLaunchKernelGGL(k_map_labels_objects<2>, grid, block, lds, s, xyz, (unsigned)width, (unsigned)n, geo, B, R, roll_first, ev16, H, W, r_row,
+                           r_col, labels, (unsigned long long)label_stride, n_labels, req_of_label, min_vote, g_key, g_cnt);
+    else
+        hipLaunchKernelGGL(k_map_labels_objects<1>, grid, block, lds, s, xyz, (unsigned)width, (unsigned)n, geo, B, R, roll_first, ev16, H, W, r_row,
+                           r_col, labels, (unsigned long long)label_stride, n_labels, req_of_label, min_vote, g_key, g_cnt);
+}
+
+// k_object_records: one wave per REQUEST.  Its key names the best pixel i of its object and the roll; the pixel's point is read from the
+// shared cloud, its cell under that roll of the request's own CellGeo recomputed (deterministic: the cell k_map_labels_objects saw), and
+// the record is built from the request's own ev16, heights and rec (pick_record)
+__global__ __launch_bounds__(64) void k_object_records(const float *__restrict__ xyz, unsigned width, unsigned n, const CellGeo *__restrict__ geo,
+                                                       int R, int roll_first, const short *__restrict__ ev16, const float *__restrict__ heights,
+                                                       const RollRecordDev *__restrict__ rec, int H, int W, float r_row, float r_col,
+                                                       const unsigned long long *__restrict__ g_key, const unsigned *__restrict__ g_cnt,
+                                                       LabelOutDev *__restrict__ out)
+{
+    const int b = blockIdx.x;
+    const unsigned long long key = g_key[b];
+    LabelOutDev o = label_out_none();
+    if (key == 0ull) {
+        if (threadIdx.x == 0) out[b] = o;
+        return;
+    }
+    const unsigned i = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull), r = roll - roll_first;
+    int ci = -2;
+    unsigned u = 0, v = 0;
+    if (i < n && r >= 0 && r < R) {
+        v = i / width; u = i - v * width;
+        const global_ptr<const float> q = as_global<const float>(xyz + (size_t)i * 3);
+        const float p[3] = {q[0], q[1], q[2]};
+        if (haf_cell_math::point_usable(p)) ci = haf_cell_math::point_cell(geo[(size_t)b * R + r].m, p[0], p[1], p[2], r_row, r_col, H, W);
+        if (ci < 0) ci = -2;
+    }
+    o.found = 1; o.u = (int)u; o.v = (int)v; o.vote = (int)(key >> 48) - 32768; o.roll = roll; o.cell = ci; o.n_pixels = (int)g_cnt[b];
+    if (ci < 0) {
+        if (threadIdx.x == 0) out[b] = o;
+        return;
+    }
+    const size_t HW = (size_t)H * W, br0 = (size_t)b * R;
+    pick_record(o, ci, r, ev16 + br0 * HW, heights + br0 * HW, rec + br0, H, W, out + b);
+}
+
+void launch_object_records(const float *xyz, int width, int n, const CellGeo *geo, int B, int R, int roll_first, const short *ev16,
+                           const float *heights, const RollRecordDev *rec, int H, int W, float r_row, float r_col,
+                           const unsigned long long *g_key, const unsigned *g_cnt, LabelOutDev *out, hipStream_t s)
+{
+    if (B < 1) return;
+    hipLaunchKernelGGL(k_object_records, dim3(B), dim3(64), 0, s, xyz, (unsigned)width, (unsigned)std::max(0, n), geo, R, roll_first, ev16, heights, rec,
+                       H, W, r_row, r_col, g_key, g_cnt, out);
 }
 
 }  // namespace haf

@@ -529,6 +529,18 @@ void launch_map_labels(const FrameDev &f, const haf_cell_math::CellGeo *geo, int
 void launch_label_records(const FrameDev &f, const haf_cell_math::CellGeo *geo, int R, int roll_first, const short *ev16, const float *heights,
                           const RollRecordDev *rec, int H, int W, float r_row, float r_col, int n_labels, const unsigned long long *g_key,
                           const unsigned *g_cnt, LabelOutDev *out, hipStream_t s);
+// haf_score_objects (graspmap.hip): the label pass ACROSS the requests of the last batch, which share one frame.  xyz: the frame's n points
+// in pixel order (what k_frame_points wrote); req_of_label[l - 1] = the request that label l belongs to, -1 for none; geo / ev16 /
+// heights / rec: request 0's first roll, request b's are b * R further.  The tables -- B 64-bit keys (launch_map_best's key), B counts,
+// zeroed by the caller -- and the output are indexed by REQUEST: dynamic LDS 12 bytes per request.  launch_object_records: one wave per
+// request -> out[b] = the haf_label_pick image of its object and the record of its cell
+void launch_map_labels_objects(const float *xyz, int width, int n, const haf_cell_math::CellGeo *geo, int B, int R, int roll_first,
+                               const short *ev16, int H, int W, float r_row, float r_col, const void *labels, size_t label_stride,
+                               int label_bytes, int n_labels, const int *req_of_label, int min_vote, unsigned long long *g_key,
+                               unsigned *g_cnt, hipStream_t s);
+void launch_object_records(const float *xyz, int width, int n, const haf_cell_math::CellGeo *geo, int B, int R, int roll_first,
+                           const short *ev16, const float *heights, const RollRecordDev *rec, int H, int W, float r_row, float r_col,
+                           const unsigned long long *g_key, const unsigned *g_cnt, LabelOutDev *out, hipStream_t s);
 // haf_score_frames_roi (roi.hip; ROI forms in prestages.hip and vote.hip).  The ROI cell set S of a (request, roll) is a bit set of H rows
 // of roi_row_words(W) 64-bit words: cell (row, col) is bit (col & 63) of word (col >> 6) of its row
 __host__ __device__ inline int roi_row_words(int W) { return (W + 63) >> 6; }
@@ -536,6 +548,12 @@ __host__ __device__ inline int roi_row_words(int W) { return (W + 63) >> 6; }
 // packed, pixel order: what k_frame_points wrote) is finite, under the R rolls of geo, OR-ed into S (R grids, zeroed by the caller)
 void launch_roi_mark(const unsigned char *mask, size_t mask_stride, int width, int n, const float *xyz, const RollGeo *geo, int R,
                      unsigned long long *S, int H, int W, float r_row, float r_col, hipStream_t s);
+// haf_score_objects: ONE launch for the B requests of a batch that share one frame.  labels: the instance-label image (label_bytes 1 or 2
+// per pixel, rows label_stride bytes apart, device memory); req_of_label[l - 1] = the request whose cell sets the pixels of label l mark
+// (0 <= it < B), -1 for none; a label above n_labels marks nothing.  geo: B * R transforms, S: B * R grids, zeroed by the caller
+void launch_roi_mark_objects(const void *labels, size_t label_stride, int label_bytes, int width, int n, const float *xyz,
+                             const int *req_of_label, int n_labels, const RollGeo *geo, int R, unsigned long long *S, int H, int W,
+                             float r_row, float r_col, hipStream_t s);
 // haf_score_views_roi: per VIEW of the batch, next to its FrameDev: its mask (device memory; null: the view selects nothing), the bytes
 // between the mask's rows, and its request's first ROI grid and first RollGeo.  One launch per frame kind present marks every view of the
 // batch: the masked pixels are deprojected again from the views' raw pixels (the compacted points have no pixel index)

@@ -28,12 +28,33 @@
 //     is of another kind, has no mask or ends before it returns at once.  The per-view constants (RoiViewDev: mask, stride, the
 //     request's S and RollGeo) are wave-uniform.
 // Bounds: a lane past the view's end marks nothing; a mask byte is read only for a pixel inside the view; point_cell as above.
-#include "frame_group.h"
-#include "grasp_cells.h"
+//
+// k_roi_mark_objects<LABEL_BYTES> (haf_score_objects): the cell sets of ALL requests of a batch whose requests share one frame and whose
+// masks are the instances of one label image -- request b's mask is `labels == the label of its object` -- in ONE launch.
+//   * a lane owns a group of four pixels and reads their labels FIRST (object_group.h: one 4- or 8-byte load where the group is
+//     aligned inside a row); a group of background pixels costs that one load, a wave of them returns before anything else;
+//   * a labelled pixel looks its request up in the label -> request table the host uploaded (n_labels small integers, -1: not an
+//     object of this call; a label above n_labels indexes nothing) and reads its point at its pixel index from the shared cloud, as
+//     k_roi_mark does, with the same finiteness rule;
+//   * the wave then takes the requests its pixels belong to one after the other (next_request): the request in hand is wave-uniform,
+//     so its R RollGeo are scalar loads, and each of its pixels sets its cell's bit in that request's grid of roll r by one 64-bit
+//     atomicOr -- mark_cell below, the device function k_roi_mark sets its bits with.
+// Bounded by the label loads (1 or 2 bytes per pixel) and R atomics per labelled, finite pixel.  Bounds: req is the host's table entry,
+// inside [0, B) by construction (engine_objects.cpp); point_cell as above.  No workgroup waits for another.
+#include "object_group.h"
 
 namespace haf {
 
 constexpr int kRoiThreads = 256;
+
+// the bit of point p's cell under the transform g in the grid Sr (H rows of roi_row_words(W) words); nothing when p has no cell there
+__device__ __forceinline__ void mark_cell(const RollGeo &g, const float *p, unsigned long long *__restrict__ Sr, int H, int W, float r_row, float r_col)
+{
+    const int c = haf_cell_math::point_cell(g.m, p[0], p[1], p[2], r_row, r_col, H, W);
+    if (c < 0) return;
+    const int row = c / W, col = c - row * W;             // (0 <= c < H * W)
+    atomicOr(Sr + (size_t)row * roi_row_words(W) + (col >> 6), 1ull << (col & 63));
+}
 
 __global__ __launch_bounds__(kRoiThreads) void k_roi_mark(const unsigned char *__restrict__ mask, unsigned long long mask_stride, unsigned width,
                                                           unsigned n, const float *__restrict__ xyz, const RollGeo *__restrict__ geo, int R,
@@ -46,12 +67,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_mark(const unsigned char *_
     const float p[3] = {xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2]};
     if (!haf_cell_math::point_usable(p)) return;
     const size_t grid_words = (size_t)H * roi_row_words(W);
-    for (int r = 0; r < R; r++) {
-        const int c = haf_cell_math::point_cell(geo[r].m, p[0], p[1], p[2], r_row, r_col, H, W);   // (r is wave-uniform)
-        if (c < 0) continue;
-        const int row = c / W, col = c - row * W;                                                  // (0 <= c < H * W)
-        atomicOr(S + (size_t)r * grid_words + (size_t)row * roi_row_words(W) + (col >> 6), 1ull << (col & 63));
-    }
+    for (int r = 0; r < R; r++) mark_cell(geo[r], p, S + (size_t)r * grid_words, H, W, r_row, r_col);   // (r is wave-uniform)
 }
 
 void launch_roi_mark(const unsigned char *mask, size_t mask_stride, int width, int n, const float *xyz, const RollGeo *geo, int R,
@@ -60,6 +76,46 @@ void launch_roi_mark(const unsigned char *mask, size_t mask_stride, int width, i
     if (n < 1) return;
     hipLaunchKernelGGL(k_roi_mark, dim3(((unsigned)n + kRoiThreads - 1) / kRoiThreads), dim3(kRoiThreads), 0, s, mask,
                        (unsigned long long)mask_stride, (unsigned)width, (unsigned)n, xyz, geo, R, S, H, W, r_row, r_col);
+}
+
+template <int LB>
+__global__ __launch_bounds__(kRoiThreads) void k_roi_mark_objects(const void *__restrict__ labels, unsigned long long label_stride, unsigned width,
+                                                                  unsigned n, const float *__restrict__ xyz, const int *__restrict__ req_of_label,
+                                                                  int n_labels, const RollGeo *__restrict__ geo, int R,
+                                                                  unsigned long long *__restrict__ S, int H, int W, float r_row, float r_col)
+{
+    const unsigned i0 = (blockIdx.x * (unsigned)kRoiThreads + threadIdx.x) * kObjGroup;      // (n < 2^31 and at most 2^10 points of slack: no wrap)
+    int req[kObjGroup];
+    unsigned pending = group_requests<LB>(labels, label_stride, width, n, i0, req_of_label, n_labels, req);
+    if (__ballot(pending != 0u) == 0ull) return;          // a wave of background: its label loads were all it cost
+    float p[kObjGroup * 3];
+    pending = group_cloud_points(xyz, i0, pending, p);
+    const size_t grid_words = (size_t)H * roi_row_words(W);
+    unsigned take;
+    for (int b = next_request(req, pending, &take); b >= 0; b = next_request(req, pending, &take)) {
+        const RollGeo *const gb = geo + (size_t)b * R;    // (b is wave-uniform: scalar loads)
+        unsigned long long *const Sb = S + (size_t)b * R * grid_words;
+        for (int r = 0; r < R; r++) {
+#pragma unroll
+            for (unsigned k = 0; k < kObjGroup; k++)
+                if (take & (1u << k)) mark_cell(gb[r], p + 3 * k, Sb + (size_t)r * grid_words, H, W, r_row, r_col);
+        }
+    }
+}
+
+void launch_roi_mark_objects(const void *labels, size_t label_stride, int label_bytes, int width, int n, const float *xyz,
+                             const int *req_of_label, int n_labels, const RollGeo *geo, int R, unsigned long long *S, int H, int W,
+                             float r_row, float r_col, hipStream_t s)
+{
+    if (n < 1) return;
+    const unsigned groups = ((unsigned)n + kObjGroup - 1) / kObjGroup;
+    const dim3 grid((groups + kRoiThreads - 1) / kRoiThreads), block(kRoiThreads);
+    if (label_bytes == 2)
+        hipLaunchKernelGGL(k_roi_mark_objects<2>, grid, block, 0, s, labels, (unsigned long long)label_stride, (unsigned)width, (unsigned)n, xyz,
+                           req_of_label, n_labels, geo, R, S, H, W, r_row, r_col);
+    else
+        hipLaunchKernelGGL(k_roi_mark_objects<1>, grid, block, 0, s, labels, (unsigned long long)label_stride, (unsigned)width, (unsigned)n, xyz,
+                           req_of_label, n_labels, geo, R, S, H, W, r_row, r_col);
 }
 
 template <int KIND>

@@ -208,7 +208,7 @@ class CalcGraspPointsServer:
         n = len(self.last_segment_infos)
         return res, (self.best_per_object(frame, img, min_vote=min_vote, n_labels=n) if n else [])
 
-    def execute_frame_per_object(self, goal: GraspInputMsg, frame, params=None, plane=None, min_vote=1, margin_cells=4):
+    def execute_frame_per_object(self, goal: GraspInputMsg, frame, params=None, plane=None, min_vote=1, margin_cells=4, fused=False):
         """execute_frame_segmented() for objects ANYWHERE in the frame: one request per object, each centred on its object, instead of
         the one grid around the goal's grasp_area_center (objects outside that grid have no grasp there: no height grid contains
         them).  The frame is segmented into the engine's device image (params, plane: as execute_frame_segmented takes them), every
@@ -221,8 +221,13 @@ class CalcGraspPointsServer:
         roll, then pixel index ascending); objects without a pixel of vote >= min_vote are left out.  fits is False when the grasp
         area had to be cut to the engine's grid.  self.last_shapes: the capi.LABEL_SHAPE_DTYPE array of all labels; the other last_*
         attributes as execute_frame_segmented leaves them.
-        THE COST: a host frame is staged once per request of a chunk (a device-resident frame is read where it lies), and there is
-        one label call per object; a fused form does not exist."""
+        THE COST of that route: a host frame is staged and deprojected once per request of a chunk (a device-resident frame is read
+        where it lies, and still deprojected per request), every request marks the cells of all objects, and there is one label call
+        per object.
+        fused=True: the same list from ONE haf_score_objects call per chunk of max_clouds objects -- the frame is staged and
+        deprojected once per chunk and counts once against max_points (the chunk rule has no max_points term), request b marks and
+        evaluates only the cells near its own object (mask `labels == label`; the picks are those of `labels != 0`, include/hafgrasp.h),
+        and one label pass serves the chunk."""
         if goal.goal_frame_id:
             self.base_frame_id = goal.goal_frame_id
         p = params if params is not None else self.segment_params_from_goal(goal)
@@ -242,21 +247,34 @@ class CalcGraspPointsServer:
         self.last_shapes = self.engine.measure_labels(frame, img, n_labels=n, plane=list(p.plane))
         cfg, base = self.engine.cfg, goal.to_c()
         todo = [(l + 1,) + capi.object_input(cfg, base, self.last_shapes[l], margin_cells) for l in range(n) if self.last_shapes["found"][l]]
+        hits = []
+
+        def hit(label, fits, pick, c):
+            msg = GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                                 c["approach_vector"], c["roll"])
+            key = (-int(pick["vote"]), int(pick["roll"]), int(pick["v"]) * frame.width + int(pick["u"]))
+            hits.append((key, (label, msg, int(pick["u"]), int(pick["v"]), capi.shape_to_dict(self.last_shapes[label - 1]), fits)))
+
+        if fused:
+            chunk = max(1, int(cfg.max_clouds))
+            for c0 in range(0, len(todo), chunk):
+                part = todo[c0:c0 + chunk]
+                _, picks, poses, _ = self.engine.score_objects(frame, img, n, [label for label, _, _ in part], [inp for _, inp, _ in part],
+                                                               min_vote=min_vote)
+                for b, (label, _, fits) in enumerate(part):
+                    if picks["found"][b]:
+                        hit(label, fits, picks[b], poses[b])
+            return [h for _, h in sorted(hits, key=lambda kh: kh[0])]
         chunk = max(1, min(int(cfg.max_clouds), int(cfg.max_points) // max(1, frame.width * frame.height)))
         mask = (img.data, img.row_stride_bytes)
-        hits = []
         for c0 in range(0, len(todo), chunk):
             part = todo[c0:c0 + chunk]
             self.engine.score_frames_roi([frame] * len(part), [mask] * len(part), [inp for _, inp, _ in part])
             for b, (label, _, fits) in enumerate(part):
                 res = self.engine.best_per_label(b, frame, img, n_labels=n, min_vote=min_vote)
                 pick, c = res["picks"][label - 1], res["poses"][label - 1]
-                if not pick["found"]:
-                    continue
-                msg = GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
-                                     c["approach_vector"], c["roll"])
-                key = (-int(pick["vote"]), int(pick["roll"]), int(pick["v"]) * frame.width + int(pick["u"]))
-                hits.append((key, (label, msg, int(pick["u"]), int(pick["v"]), capi.shape_to_dict(self.last_shapes[label - 1]), fits)))
+                if pick["found"]:
+                    hit(label, fits, pick, c)
         return [h for _, h in sorted(hits, key=lambda kh: kh[0])]
 
     def close(self):

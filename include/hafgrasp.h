@@ -801,6 +801,47 @@ int  haf_measure_labels(haf_engine *e, const haf_frame *frame, const haf_label_i
 int  haf_object_input(const haf_config *cfg, const haf_grasp_input *base, const haf_label_shape *shape, int32_t margin_cells,
                       haf_grasp_input *out, int32_t *fits);
 
+/* ---- every labelled object scored in one call (csrc/engine_objects.cpp, csrc/roi.hip: k_roi_mark_objects, csrc/graspmap.hip:
+ * k_map_labels_objects) --------------------------------------------------------------------------------------------------------
+ * The last link of filter -> plane -> segment -> measure -> one request per object: ONE frame, ONE instance-label image, and per
+ * listed object b its label object_labels[b] and its own request in[b] (haf_object_input's).  The definition of record is a
+ * composition of calls that exist; no new arithmetic is defined:
+ *   request b     haf_score_frames_roi(e, 1, frame, &roi_b, &in[b], &out[b]) with roi_b the 8-bit mask `labels == object_labels[b]`;
+ *   picks[b]      entry object_labels[b] - 1 of haf_grasp_map_labels(e, 0, frame, labels, n_labels, min_vote, ...) after that request,
+ *   poses[b]      and its pose (zeroed when not found);
+ *   order         order[0 .. *n_found) lists the INDICES b of the found objects, best first by haf_grasp_map_labels' key (vote
+ *                 descending, roll ascending, pixel index ascending).
+ * The call equals that composition in every field of out, picks, poses, order and n_found, n_evals of the records included -- which is
+ * why the mask of request b is its own object's label and not `labels != 0`.  The one field that is counted per BATCH, as in every
+ * batched call, is n_rechecked: out[0] carries the batch's, the others 0 (which tier decides an evaluation is no part of any contract
+ * here, see haf_score_frames_roi).  Two further facts:
+ *   * the picks, though not n_evals, also equal those of one request per object under the mask `labels != 0`: every labelled pixel's
+ *     cell lies in S_r under either mask, so V'_r = V_r there (the argument under haf_grasp_map_labels);
+ *   * request b evaluates only the cells near its own object: E_r of request b follows from the pixels of label object_labels[b] alone.
+ * A label of the image that is not listed, and a value above n_labels, select nothing in any request.
+ *
+ * Afterwards the last scored batch is a batch of n_objects ROI requests, exactly as haf_score_frames_roi(e, n_objects, {frame x n},
+ * {roi_b}, in, out) leaves it: haf_top_grasps, haf_grasp_map, haf_cell_pose, haf_get_roll_grid, haf_last_counts,
+ * haf_debug_fetch(HAF_DBG_ROI) and haf_debug_fetch_points describe request b.  Like every ROI call it never re-chooses the form of the
+ * screening pass.
+ *
+ * What is done once instead of n_objects times: a host frame is packed and uploaded once, a device-resident one read where it lies;
+ * the frame is deprojected once and every request reads that one set of points; the frame counts ONCE against max_points (width x
+ * height <= max_points whatever n_objects is); a host label image is uploaded once, a device-resident one -- the image
+ * haf_segment_frame left in the engine included -- is read in place with its stride; one launch marks the cell sets of all requests;
+ * one launch pair, one device-to-host copy and one synchronisation give all picks, behind the request path's own copy and wait.
+ *
+ * Refusals, all before any device work, the engine left as it was -- everything haf_score_frames_roi refuses for a frame and an input;
+ * everything haf_grasp_map_labels refuses for a label image and n_labels (an engine created with HAF_FLAG_PROBABILITY included);
+ * HAF_E_ARG: n_objects < 1, a null object_labels, in, out or picks, an object_labels[b] outside 1..n_labels, a label listed twice;
+ * HAF_E_CAPACITY: n_objects > max_clouds.  A request whose budget is negative finds nothing and the call returns HAF_OK.  Not through
+ * haf_score_rolls or the sharded multi-GPU calls.  Shares the ROI buffers of haf_score_frames_roi and the block of haf_grasp_map. */
+int  haf_score_objects(haf_engine *e, const haf_frame *frame, const haf_label_image *labels, int32_t n_labels, int32_t n_objects,
+                       const int32_t *object_labels /* [n_objects] */, const haf_grasp_input *in /* [n_objects] */, int32_t min_vote,
+                       haf_grasp_output *out /* [n_objects] */, haf_label_pick *picks /* [n_objects] */,
+                       haf_grasp_candidate *poses /* [n_objects], may be NULL */, int32_t *order /* [n_objects], may be NULL */,
+                       int32_t *n_found /* may be NULL */);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
