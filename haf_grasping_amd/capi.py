@@ -91,6 +91,25 @@ SEGMENT_INFO_DTYPE = np.dtype([(f, np.int32) for f in ("n_pixels", "anchor_u", "
 assert SEGMENT_INFO_DTYPE.itemsize == C.sizeof(SegmentInfo) == 28
 
 
+class CellSegmentParams(C.Structure):
+    """haf_cell_segment_params: the parameters of haf_segment_cells"""
+    _fields_ = [("plane", C.c_float * 4), ("min_height", C.c_float), ("max_height", C.c_float), ("cell", C.c_float), ("x0", C.c_float),
+                ("y0", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("connectivity", C.c_int32), ("max_step", C.c_float),
+                ("min_points", C.c_int32), ("max_labels", C.c_int32)]
+
+
+class CellSegmentInfo(C.Structure):
+    """haf_cell_segment_info: point and cell counts, anchor cell, inclusive cell box and largest top of one label"""
+    _fields_ = [(f, C.c_int32) for f in ("n_points", "n_cells", "anchor_ix", "anchor_iy", "ix_min", "iy_min", "ix_max", "iy_max")] + \
+               [("top", C.c_float)]
+
+
+CELL_SEGMENT_INFO_DTYPE = np.dtype([(f, np.int32) for f in ("n_points", "n_cells", "anchor_ix", "anchor_iy", "ix_min", "iy_min", "ix_max",
+                                                             "iy_max")] + [("top", np.float32)])
+assert CELL_SEGMENT_INFO_DTYPE.itemsize == C.sizeof(CellSegmentInfo) == 36
+MAX_CELLS = 1 << 22
+
+
 class PlaneParams(C.Structure):
     """haf_plane_params: the parameters of haf_fit_plane"""
     _fields_ = [("tol", C.c_float), ("min_area2", C.c_float), ("up", C.c_float * 3), ("max_tilt", C.c_float), ("n_hyp", C.c_int32),
@@ -251,6 +270,12 @@ def _bind(path, testing):
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.haf_segment_frame.argtypes = [E, C.POINTER(Frame), C.POINTER(SegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_int32,
                                     C.POINTER(LabelImage), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.haf_cell_segment_default.argtypes = [C.POINTER(CellSegmentParams)]
+    L.haf_cell_segment_default.restype = None
+    L.haf_segment_cells_ref.argtypes = [C.POINTER(Frame), C.POINTER(CellSegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.haf_segment_cells.argtypes = [E, C.POINTER(Frame), C.POINTER(CellSegmentParams), C.c_void_p, C.c_int32, C.c_size_t, C.c_int32,
+                                    C.POINTER(LabelImage), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.haf_plane_default.argtypes = [C.POINTER(PlaneParams)]
     L.haf_plane_default.restype = None
     L.haf_fit_plane_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
@@ -489,6 +514,14 @@ def xyz_frame(array, sensor_to_base=None, width=None, height=None, row_stride_by
     return _frame_of(FRAME_XYZ_F32, ptr, width, height, on_dev, row_stride_bytes, point_stride_bytes, array, **kw)
 
 
+def cloud_frame(xyz):
+    """an unorganised base-frame cloud (float32 [N, >= 3], host) as a haf_frame: N x 1 points of HAF_FRAME_XYZ_F32 under the identity pose,
+    what haf_segment_cells, haf_measure_labels and haf_score_objects take for a cloud; its label image is [1, N]"""
+    xyz = np.asarray(xyz)
+    assert xyz.ndim == 2 and xyz.dtype == np.float32 and xyz.shape[1] >= 3 and xyz.strides[1] == 4
+    return xyz_frame(xyz.reshape(1, xyz.shape[0], xyz.shape[1]), point_stride_bytes=xyz.strides[0])
+
+
 def frame_points(frame):
     """haf_frame_points: the host definition of record -> float32 [height * width, 3]"""
     out = np.empty((max(0, frame.width) * max(0, frame.height), 3), np.float32)
@@ -575,6 +608,38 @@ def segment_ref(frame, params=None, dtype=np.uint8, out=None):
     if rc != HAF_OK:
         raise HafError(rc, "haf_segment_ref refused its arguments")
     return img, info[:n.value].copy(), [int(x) for x in stats]
+
+
+def cell_segment_params(**kw):
+    """haf_cell_segment_params with the library's defaults (plane (0, 0, 1, 0), min_height 0.01, max_height 0 = none, cell 0.01, origin
+    (-5.12, -5.12), 1024 x 1024 cells, connectivity 8, max_step 0 = none, min_points 50, max_labels 255) and `kw` over them"""
+    p = CellSegmentParams()
+    lib().haf_cell_segment_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_cell_segment_params field %r" % k)
+        if k == "plane":
+            v = (C.c_float * 4)(*np.asarray(v, dtype=np.float32).reshape(-1)[:4])
+        setattr(p, k, v)
+    return p
+
+
+def segment_cells_ref(frame, params=None, dtype=np.uint8, out=None, cell_labels=False):
+    """haf_segment_cells_ref: the host definition of record of the top-down cell clustering of a host Frame of any shape -> (labels: uint8
+    / uint16 [height, width], infos: CELL_SEGMENT_INFO_DTYPE [n_labels], stats: [pixels, foreground, foreground outside the grid,
+    occupied cells, components, components that pass the size rule]) and, with cell_labels=True, the uint16 [ny, nx] label grid as a
+    fourth entry.  out: the array to write into (rows may be padded: a view into a wider array)."""
+    p = params if params is not None else cell_segment_params()
+    img, ptr, elem, stride = _label_out(frame, dtype, out)
+    info = np.zeros(max(1, p.max_labels), CELL_SEGMENT_INFO_DTYPE)
+    grid = np.zeros((max(0, p.ny), max(0, p.nx)), np.uint16) if cell_labels else None
+    n, stats = C.c_int32(-1), (C.c_int64 * 6)()
+    rc = lib().haf_segment_cells_ref(C.byref(frame), C.byref(p), ptr, elem, stride, grid.ctypes.data if cell_labels else None, info.ctypes.data,
+                                     C.byref(n), stats)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_segment_cells_ref refused its arguments")
+    res = (img, info[:n.value].copy(), [int(x) for x in stats])
+    return res + (grid,) if cell_labels else res
 
 
 def plane_params(**kw):
@@ -1142,7 +1207,7 @@ class Engine:
     def segment(self, frame, params=None, dtype=np.uint8, device_out=False, host_out=None):
         """haf_segment_frame: a Frame (any kind, host or device-resident) -> (labels, infos, stats) as segment_ref gives them, computed on
         the device.  labels is a new uint8 / uint16 [height, width] array (host_out: the array to write into, rows may be padded).
-        device_out=True: the engine's own packed device image, returned as a LabelImage (valid until the next segment or close(), across
+        device_out=True: the engine's own packed device image, returned as a LabelImage (valid until the next segment, segment_cells or close(), across
         scoring and map calls; as uint8 its data is also a device mask for score_frames_roi); device_out=(pointer, row_stride_bytes) or a
         pointer: the caller's device image, likewise described by the LabelImage returned."""
         p = params if params is not None else segment_params()
@@ -1162,6 +1227,33 @@ class Engine:
             rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), info.ctypes.data, C.byref(n), stats)
         self._check(rc)
         return img, info[:n.value].copy(), [int(x) for x in stats]
+
+    def segment_cells(self, frame, params=None, dtype=np.uint8, device_out=False, host_out=None, cell_labels=False):
+        """haf_segment_cells: a Frame of any kind and shape (host or device-resident) -> what segment_cells_ref gives, computed on the
+        device.  The outputs are segment()'s: a new host array (host_out: the array to write into), device_out=True for the engine's own
+        packed device image -- the same image segment(..., device_out=True) uses -- or device_out=(pointer, row_stride_bytes) for the
+        caller's.  cell_labels=True appends the uint16 [ny, nx] label grid."""
+        p = params if params is not None else cell_segment_params()
+        info = np.zeros(max(1, p.max_labels), CELL_SEGMENT_INFO_DTYPE)
+        grid = np.zeros((max(0, p.ny), max(0, p.nx)), np.uint16) if cell_labels else None
+        gptr = grid.ctypes.data if cell_labels else None
+        n, stats, got = C.c_int32(-1), (C.c_int64 * 6)(), LabelImage()
+        elem = np.dtype(dtype).itemsize
+        if device_out is True:
+            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), None, elem, 0, 1, C.byref(got), gptr, info.ctypes.data, C.byref(n), stats)
+            img = got
+        elif device_out is not False and device_out is not None:
+            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
+            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), int(ptr), elem, stride or frame.width * elem, 1, C.byref(got),
+                                           gptr, info.ctypes.data, C.byref(n), stats)
+            img = got
+        else:
+            img, ptr, elem, stride = _label_out(frame, dtype, host_out)
+            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), gptr, info.ctypes.data,
+                                           C.byref(n), stats)
+        self._check(rc)
+        res = (img, info[:n.value].copy(), [int(x) for x in stats])
+        return res + (grid,) if cell_labels else res
 
     def fit_plane(self, frame, params=None, mask=None, debug=False):
         """haf_fit_plane: a Frame (any kind, host or device-resident) -> the dict fit_plane_ref gives, computed on the device.  mask: a host

@@ -51,6 +51,12 @@
 //                                     is found ("plane none") the default plane stands in.
 //                                     Without --labels the label image feeds the "object" lines; --labels-out FILE.pgm writes it as an
 //                                     8-bit PGM; --segment-roi also scores only under it (with ONE --depth, not with --roi-mask)
+//   --segment-cells MIN_H,MAX_H,CELL,MIN_PTS[,STEP] | default   --segment with haf_segment_cells as the segmenter: the objects are
+//                                     connected occupied cells of the top-down grid (CELL metres; STEP > 0: neighbouring cells whose
+//                                     tops differ by more do not link) instead of neighbouring pixels.  Combines with --plane,
+//                                     --per-object [MARGIN] --fused and --labels-out like --segment and prints the same "object" lines;
+//                                     --cell-labels-out FILE.pgm writes the top-down label grid as an 8-bit PGM.  Works with --depth
+//                                     and, in its place, with ONE .pcd: the cloud as an N x 1 frame in the base frame
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
 //                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
 //                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
@@ -155,6 +161,7 @@ static void usage()
             "  --depth-filter RADIUS,SUPPORT,TOL_ABS,TOL_REL[,MIN_VALID] | default   [--filtered-out FILE.pgm]\n"
             "  --view-roi-mask FILE.pgm                                    (behind a --depth: the mask of that view)\n"
             "  --labels FILE.pgm --measure [--plane A B C D]     --segment ... --per-object [MARGIN] [--fused]      (with ONE --depth)\n"
+            "  --segment-cells MIN_H,MAX_H,CELL,MIN_PTS[,STEP] | default  [--plane ...] [--per-object [MARGIN] [--fused]] [--labels-out FILE.pgm] [--cell-labels-out FILE.pgm]   (with --depth, or with one cloud.pcd)\n"
             "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D | --plane fit[,TOL,N_HYP] [--plane-mask FILE.pgm]] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
@@ -213,6 +220,12 @@ struct MapOptions {
     bool per_object = false, measure = false;
     bool fused = false;                  // --per-object --fused: one haf_score_objects call per chunk
     int margin_cells = 4;
+    // --segment-cells: the segmenter is haf_segment_cells (connected cells of the top-down grid) instead of haf_segment_frame; everything
+    // behind the label image is the same.  It also takes ONE .pcd in place of --depth: the cloud as an N x 1 XYZ frame under the
+    // identity pose.  --cell-labels-out: the top-down label grid as an 8-bit PGM, nx x ny
+    bool cells = false;
+    haf_cell_segment_params cell_params;
+    std::string cell_labels_out;
 };
 
 // --segment MIN_H,MAX_H,GAP,MIN_PX or "default"
@@ -225,6 +238,23 @@ static bool parse_segment(const char *arg, haf_segment_params *p)
     char tail = 0;
     if (sscanf(arg, "%f,%f,%f,%d%c", &min_h, &max_h, &gap, &min_px, &tail) != 4) return false;
     p->min_height = min_h; p->max_height = max_h; p->max_gap = gap; p->min_pixels = min_px;
+    return true;
+}
+
+// --segment-cells MIN_H,MAX_H,CELL,MIN_PTS[,STEP] or "default"
+static bool parse_segment_cells(const char *arg, haf_cell_segment_params *p)
+{
+    haf_cell_segment_default(p);
+    if (strcmp(arg, "default") == 0) return true;
+    float min_h = 0, max_h = 0, cell = 0, step = 0;
+    int min_pts = 0;
+    char tail = 0;
+    int commas = 0;
+    for (const char *c = arg; *c; c++) commas += *c == ',';
+    const int got = sscanf(arg, "%f,%f,%f,%d,%f%c", &min_h, &max_h, &cell, &min_pts, &step, &tail);
+    if ((got != 4 && got != 5) || commas != got - 1) return false;      // ("0.03,0,0.01,50," or "...,50,x")
+    p->min_height = min_h; p->max_height = max_h; p->cell = cell; p->min_points = min_pts;
+    if (got == 5) p->max_step = step;
     return true;
 }
 
@@ -526,6 +556,11 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
     char err[256];
     for (const DepthView &v : views) {
         haf_frame f = v.frame;
+        if (f.kind == HAF_FRAME_XYZ_F32 && f.data) {       // --segment-cells with a .pcd: the cloud as main() wrapped it, its points main()'s
+            images.push_back(nullptr);
+            frames.push_back(f);
+            continue;
+        }
         uint16_t *depth = nullptr;
         if (haf_pgm16_load(v.path.c_str(), &depth, &f.width, &f.height, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", v.path.c_str(), err); release(); return 1; }
         images.push_back(depth);
@@ -609,13 +644,33 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         memcpy(mo.seg_plane, sp.plane, sizeof mo.seg_plane);
         mo.seg_labels.assign((size_t)frames[0].width * (size_t)frames[0].height, 0);
         int64_t stats[4] = {0, 0, 0, 0};
-        if (haf_segment_frame(eng, &frames[0], &sp, mo.seg_labels.data(), 1, (size_t)frames[0].width, 0, nullptr, nullptr, &mo.seg_n, stats) != HAF_OK) {
+        if (mo.cells) {
+            haf_cell_segment_params cp = mo.cell_params;
+            memcpy(cp.plane, sp.plane, sizeof cp.plane);
+            std::vector<uint16_t> grid(mo.cell_labels_out.empty() ? 0 : (size_t)std::max(cp.nx, 0) * (size_t)std::max(cp.ny, 0));
+            int64_t cs[6] = {0, 0, 0, 0, 0, 0};
+            if (haf_segment_cells(eng, &frames[0], &cp, mo.seg_labels.data(), 1, (size_t)frames[0].width, 0, nullptr, grid.empty() ? nullptr : grid.data(),
+                                  nullptr, &mo.seg_n, cs) != HAF_OK) {
+                fprintf(stderr, "%s: --segment-cells: %s\n", views[0].path.c_str(), haf_last_error(eng));
+                release();
+                return 1;
+            }
+            fprintf(stderr, "%s: segmented by cells: %d object(s); %lld of %lld points foreground, %lld outside the grid, %lld cell(s), %lld component(s), %lld pass the size rule\n",
+                    views[0].path.c_str(), (int)mo.seg_n, (long long)cs[1], (long long)cs[0], (long long)cs[2], (long long)cs[3], (long long)cs[4], (long long)cs[5]);
+            std::vector<uint8_t> grid8(grid.begin(), grid.end());      // (a uint8 label image: at most 255 labels)
+            if (!grid.empty() && !write_pgm8(mo.cell_labels_out, grid8.data(), cp.nx, cp.ny)) {
+                fprintf(stderr, "--cell-labels-out: cannot write %s\n", mo.cell_labels_out.c_str());
+                release();
+                return 1;
+            }
+        } else if (haf_segment_frame(eng, &frames[0], &sp, mo.seg_labels.data(), 1, (size_t)frames[0].width, 0, nullptr, nullptr, &mo.seg_n, stats) != HAF_OK) {
             fprintf(stderr, "%s: --segment: %s\n", views[0].path.c_str(), haf_last_error(eng));
             release();
             return 1;
         }
-        fprintf(stderr, "%s: segmented: %d object(s); %lld of %lld pixels foreground, %lld component(s), %lld pass the size rule\n", views[0].path.c_str(),
-                (int)mo.seg_n, (long long)stats[1], (long long)stats[0], (long long)stats[2], (long long)stats[3]);
+        if (!mo.cells)
+            fprintf(stderr, "%s: segmented: %d object(s); %lld of %lld pixels foreground, %lld component(s), %lld pass the size rule\n", views[0].path.c_str(),
+                    (int)mo.seg_n, (long long)stats[1], (long long)stats[0], (long long)stats[2], (long long)stats[3]);
         if (!mo.labels_out.empty() && !write_pgm8(mo.labels_out, mo.seg_labels.data(), frames[0].width, frames[0].height)) {
             fprintf(stderr, "--labels-out: cannot write %s\n", mo.labels_out.c_str());
             release();
@@ -758,6 +813,8 @@ int main(int argc, char **argv)
         else if (a == "--depth-filter") { need(1); if (!parse_depth_filter(argv[++i], &map_opt.filter_params)) { usage(); return 2; } map_opt.filter = true; }
         else if (a == "--filtered-out") { need(1); map_opt.filtered_out = argv[++i]; }
         else if (a == "--segment") { need(1); if (!parse_segment(argv[++i], &map_opt.segment_params)) { usage(); return 2; } map_opt.segment = true; }
+        else if (a == "--segment-cells") { need(1); if (!parse_segment_cells(argv[++i], &map_opt.cell_params)) { usage(); return 2; } map_opt.segment = map_opt.cells = true; }
+        else if (a == "--cell-labels-out") { need(1); map_opt.cell_labels_out = argv[++i]; }
         else if (a == "--segment-roi") map_opt.segment_roi = true;
         else if (a == "--fused") map_opt.fused = true;
         else if (a == "--per-object") { map_opt.per_object = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') map_opt.margin_cells = atoi(argv[++i]); }
@@ -778,11 +835,14 @@ int main(int argc, char **argv)
         else { first_cloud = i; break; }
         if (!views.empty()) views.back().frame = frame;       // (a sensor option applies to the view opened last)
     }
+    // --segment-cells with a .pcd: that one cloud takes the place of the --depth view (wrapped below, once it is loaded)
+    const bool cloud_cells = map_opt.cells && views.empty() && first_cloud + 1 == argc && gpus == 0 && !map_opt.filter && map_opt.plane_mask.empty();
+    if (cloud_cells) { views.push_back(DepthView{argv[first_cloud], frame, "", {}}); first_cloud = argc; have_intrinsics = true; }
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
         (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || (map_opt.have_plane && !map_opt.measure) || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
-        (map_opt.fused && !map_opt.per_object) ||
+        (map_opt.fused && !map_opt.per_object) || (!map_opt.cells && !map_opt.cell_labels_out.empty()) ||
         (map_opt.per_object && (!map_opt.segment || views.size() != 1 || map_opt.segment_roi || map_opt.measure || !map_opt.roi_path.empty() || !map_opt.labels_path.empty())) ||
         (map_opt.measure && (map_opt.labels_path.empty() || views.size() != 1 || map_opt.segment || map_opt.fit_plane)) ||
         (map_opt.fit_plane && map_opt.have_plane) || (!map_opt.fit_plane && !map_opt.plane_mask.empty()) ||
@@ -801,6 +861,17 @@ int main(int argc, char **argv)
     haf_engine *eng = nullptr;
     if (haf_create(&cfg, &eng) != HAF_OK) { fprintf(stderr, "haf_create: %s\n", haf_last_error(nullptr)); return 1; }
     int rc = 0;
+    float *cloud_xyz = nullptr;
+    if (cloud_cells) {
+        size_t n = 0;
+        char err[256];
+        if (haf_pcd_load(views[0].path.c_str(), &cloud_xyz, &n, err, sizeof err) != HAF_OK) { fprintf(stderr, "%s: %s\n", views[0].path.c_str(), err); haf_destroy(eng); return 1; }
+        if (n < 1 || n > (size_t)cfg.max_points) { fprintf(stderr, "%s: %zu points: none, or more than max_points\n", views[0].path.c_str(), n); haf_free(cloud_xyz); haf_destroy(eng); return 1; }
+        haf_frame &f = views[0].frame;
+        haf_frame_default(&f);                             // (the identity pose: the cloud is in the base frame)
+        f.kind = HAF_FRAME_XYZ_F32; f.data = cloud_xyz; f.width = (int32_t)n; f.height = 1;
+        f.point_stride_bytes = 12; f.row_stride_bytes = n * 12;
+    }
     if (from_depth) {
         // (the goal goes through the adapter's fields like every other: goal_to_input rounds the duration through float, 277)
         hafshim::GoalFields goal;
@@ -812,6 +883,7 @@ int main(int argc, char **argv)
         haf_grasp_input gin;
         hafshim::goal_to_input(goal, &gin);
         rc = run_depth(eng, cfg, gin, views, hypotheses, top_k, top_radius, top_rolls, top_dist, map_opt);
+        haf_free(cloud_xyz);
         haf_destroy(eng);
         return rc;
     }

@@ -2,8 +2,8 @@
 // refusal comes before any device work (check_segment of segment_host.cpp, then the capacity); then the frame goes through the
 // single-frame input of engine_stage.cpp, the seven launches of segment.hip run on the engine's stream, ONE copy brings back the counters
 // and the per-label table -- and, for a host `labels`, the packed image behind them -- and ONE synchronisation ends the call.  Nothing of
-// the last scored batch is read or written: the stage timings are not touched, and the engine's own label image is a buffer no other
-// call knows.
+// the last scored batch is read or written: the stage timings are not touched, and the engine's own label image is a buffer only
+// haf_segment_cells shares.
 #include "engine_state.h"
 
 namespace haf_host {

@@ -10,6 +10,7 @@
 //   engine_roi.cpp       haf_score_frames_roi / haf_score_views_roi: the checks, the ROI buffers, the masks' upload, the launch of k_roi_mark / k_roi_mark_view
 //   engine_depthfilter.cpp haf_filter_depth: exposures of one depth camera -> one conditioned depth image (k_depth_filter)
 //   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
+//   engine_cellsegment.cpp haf_segment_cells: one frame of any shape -> object labels by top-down cell clustering (cellsegment.hip)
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
@@ -434,10 +435,15 @@ struct haf_engine {
     DevBuf<char> d_filter_image;
     // haf_segment_frame (engine_segment.cpp), allocated by its first call: the parent and size words (4 bytes x max_points each) with the
     // scan's block totals behind them; the block [counters][per-label table, HAF_MAX_LABELS entries][a host output image, 2 bytes x
-    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which no other call touches
+    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which only haf_segment_cells shares
     DevBuf<int> d_seg_words;
     StageBuf seg_out;
     DevBuf<char> d_seg_image;
+    // haf_segment_cells (engine_cellsegment.cpp), allocated by its first call and grown when the frame or the grid grows: a cell word per
+    // pixel, then count, top, parent and size words per cell and the scan's block totals; the block [counters][per-label cells and tops]
+    // [per-label table][a host output image][the top-down label grid] with its pinned twin.  Its own image is d_seg_image above
+    DevBuf<int> d_cell_words;
+    StageBuf cell_out;
     // haf_fit_plane (engine_plane.cpp), allocated by its first call: the points as three arrays of max_points words, one usable bit per
     // pixel and one count per block of 1024 pixels behind them; the block [counters][moments][counts][hypothesis words][thresholds]
     // [a host mask, max_points bytes] with its pinned twin

@@ -7,6 +7,7 @@
 #include "segment_rules.h"
 #include "plane_rules.h"
 #include "label_shape.h"
+#include "cell_segment_rules.h"
 
 #include <string>
 
@@ -47,6 +48,11 @@ int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, 
 int check_segment(const haf_frame *frame, const haf_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
                   int32_t out_on_device, const int32_t *n_labels, std::string &err);
 haf_segment_math::SegmentRules segment_rules(const haf_segment_params &p);
+// cellsegment_host.cpp, shared by haf_segment_cells_ref and haf_segment_cells: every refusal of a frame, of the parameters and of the
+// label image that needs no engine (check_segment's for the frame and the image); the rules' constants, inv_cell formed here
+int check_cell_segment(const haf_frame *frame, const haf_cell_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
+                       int32_t out_on_device, const int32_t *n_labels, std::string &err);
+haf_cell_math::CellRules cell_rules(const haf_cell_segment_params &p);
 // plane_host.cpp, shared by haf_fit_plane_ref and haf_fit_plane: every refusal of a frame, of the mask and of the parameters that needs
 // no engine; the rules' constants, tol2, cos2 and uu formed here; the winner of a count array (largest count, ties to the lowest k)
 int check_plane(const haf_frame *frame, const haf_roi *mask, const haf_plane_params *p, const haf_plane_result *out, std::string &err);

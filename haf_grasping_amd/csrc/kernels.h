@@ -605,6 +605,34 @@ constexpr int kSegScanPixels = 1024;               // pixels per workgroup of th
 inline size_t segment_scan_blocks(size_t n) { return (n + kSegScanPixels - 1) / kSegScanPixels; }
 // the seven launches of one call, in stream order: tile, seam, flatten, block totals, scan of the totals, numbering, write
 void launch_segment(const SegmentDev &d, hipStream_t s);
+// its launches 4 to 6 on their own: the marks, the ranks and the labels of the roots of ANY flattened parent array of d.f.n words whose
+// roots carry their set's size (cellsegment.hip runs them over the cells of its grid: d.f.width = nx, d.f.n = nx * ny)
+void launch_segment_numbering(const SegmentDev &d, hipStream_t s);
+// haf_segment_cells (cellsegment.hip): one frame and the top-down grid as the kernels read them -- a kernel argument, so every field is
+// a scalar load.  f: the frame (dst and count are not read); cell: f.n words, a pixel's cell index or -1; count / top: a word per
+// cell, zeroed by the caller (top: label_shape.h's shape_enc of the height key); parent / size: a word per cell; totals:
+// segment_scan_blocks(nx * ny) words; counters[8], zeroed by the caller: foreground pixels, components, components that pass the size
+// rule, foreground pixels outside the grid, occupied cells; table: max_labels entries of 7 ints (points, anchor, box: k_segment_number's);
+// extra: max_labels pairs {cells, largest top}, zeroed by the caller; cell_labels: null, or nx * ny uint16 words; out: the label image,
+// elem_bytes 1 or 2 per pixel, rows out_stride bytes apart.  All of it device memory
+struct CellSegDev {
+    FrameDev f;
+    haf_cell_math::CellRules r;
+    int min_points, max_labels;
+    int *cell;
+    unsigned *count, *top;
+    int *parent, *size, *totals;
+    unsigned *counters;
+    int *table;
+    unsigned *extra;
+    uint16_t *cell_labels;
+    void *out;
+    unsigned long long out_stride;
+    int elem_bytes;
+};
+enum { CELL_CNT_FG = 0, CELL_CNT_COMPS = 1, CELL_CNT_KEPT = 2, CELL_CNT_OUTSIDE = 3, CELL_CNT_OCCUPIED = 4, CELL_CNT_WORDS = 8 };
+// the nine launches of one call, in stream order: bin, tile, seam, flatten, block totals, scan, numbering, table, write
+void launch_cell_segment(const CellSegDev &d, hipStream_t s);
 // haf_fit_plane (plane.hip): one frame as the kernels read it -- a kernel argument, so every field is a scalar load.  f: the frame (dst
 // and count are not read); mask: null, or one byte per pixel, rows mask_stride bytes apart; x / y / z: f.n words each, the points with
 // every unusable one as three NaNs; bits: one 64-bit word per 64 pixels of plane_blocks(f.n) blocks, the usable pixels; prefix: a word

@@ -17,7 +17,7 @@
 //   7 k_segment_write       every pixel: label = size[parent[i]], stored in the requested element size; the bounding boxes grow by
 //                           integer atomicMin / atomicMax, one lane per (wave, label), skipped where they would change nothing.
 //
-// The union-find is the lock-free kind: parent[x] <= x always, a root is the lowest index of its set (the component's anchor), and
+// The union-find (wave_union.h, shared with cellsegment.hip) is the lock-free kind: parent[x] <= x always, a root is the lowest index of its set (the component's anchor), and
 // uniting a and b is "find both roots, atomicMin the larger one's parent word with the smaller; if the word held something else, go on
 // with what it held".  Every pass of that loop lowers the larger of its two indices, so a lane's loop ends on its own progress; no lane
 // waits for another lane or workgroup anywhere in this file.  A stale read in a find only yields a former ancestor -- still a member of
@@ -26,46 +26,19 @@
 // a label indexes the table only when it is in 1..max_labels.
 #include "frame_group.h"
 #include "kernels.h"
+#include "wave_union.h"       // uf_find / uf_unite, wave_add_by_key, block_scan
 
 namespace haf {
 
 using namespace haf_segment_math;
 
 constexpr int kSegTileW = 64, kSegTileH = 16, kSegThreads = 256;
+static_assert(kSegThreads == kScanThreads, "block_scan sums over the four waves of a workgroup");
 constexpr int kSegRowsPerLane = kSegTileW * kSegTileH / kSegThreads;      // 4
 constexpr int kSegPW = kSegTileW + 1, kSegPH = kSegTileH + 1;             // the tile with its right and bottom halo
 constexpr int kSegSeamThreads = 128;                                      // 64 pixels of the last row + 16 of the last column
 constexpr int kSegInfoInts = 7;                                           // haf_segment_info
 constexpr int kSegWriteRows = kSegThreads / 64;                           // k_segment_write: a wave per row of 64 pixels
-
-// a parent word as another lane may have just changed it: never kept in a register across a loop
-template <bool LDS> __device__ __forceinline__ int uf_load(const int *p)
-{
-    if constexpr (LDS) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// (parent[x] < x unless x is a root: the walk goes down and ends)
-template <bool LDS> __device__ __forceinline__ int uf_find(const int *parent, int a)
-{
-    for (;;) {
-        const int p = uf_load<LDS>(parent + a);
-        if (p == a) return a;
-        a = p;
-    }
-}
-// a and b are foreground.  Each pass that does not end the loop replaces the larger index by a smaller one
-template <bool LDS> __device__ __forceinline__ void uf_unite(int *parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find<LDS>(parent, a);
-        b = uf_find<LDS>(parent, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(parent + b, a);
-        if (old == b) return;                             // b was a root and now hangs under a
-        b = old;                                          // b had a parent already: that parent and a are still to be united
-    }
-}
 
 __device__ __forceinline__ int seg_tiles_x(int width) { return (width + kSegTileW - 1) / kSegTileW; }
 
@@ -160,20 +133,6 @@ __global__ __launch_bounds__(kSegSeamThreads) void k_segment_seam(const SegmentD
     else if (bits & 1u) uf_unite<false>(d.parent, gi, gi + 1);
 }
 
-// adds `count` of every lane with `active` to word[key] with one atomic per distinct key of the wave.  Called by all lanes of a wave
-__device__ __forceinline__ void wave_add_by_key(int *word, bool active, int key)
-{
-    const int lane = (int)(threadIdx.x & 63u);
-    unsigned long long todo = __ballot(active);
-    while (todo) {                                        // (uniform; every pass retires at least the leader)
-        const int leader = __ffsll((long long)todo) - 1;
-        const int k = __shfl(key, leader);
-        const unsigned long long same = __ballot(active && key == k);
-        if (lane == leader) atomicAdd(word + k, (int)__popcll(same));
-        todo &= ~same;
-    }
-}
-
 __global__ __launch_bounds__(kSegThreads) void k_segment_flatten(const SegmentDev d)
 {
     const unsigned i = blockIdx.x * (unsigned)kSegThreads + threadIdx.x;
@@ -184,30 +143,6 @@ __global__ __launch_bounds__(kSegThreads) void k_segment_flatten(const SegmentDe
         d.parent[i] = root;                               // (a lane whose walk passes here reads the old ancestor or the root: both lead to the root)
     }
     wave_add_by_key(d.size, active, root);
-}
-
-// exclusive prefix sum of x over the workgroup's 256 lanes, and the sum; s_w: one word per wave
-__device__ __forceinline__ int block_scan(int x, int *s_w, int &total)
-{
-    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-    int inc = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(inc, off);
-        if (lane >= off) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kSegThreads / 64; w++) {
-        const int c = s_w[w];
-        if (w < wave) base += c;
-        total += c;
-    }
-    __syncthreads();                                      // (s_w may be written again by the caller's next round)
-    return base + inc - x;
 }
 
 // the marks of a lane's four consecutive pixels from i0: bit k = pixel i0 + k is a root whose size passes the rule; roots: how many are roots
@@ -318,21 +253,27 @@ __global__ __launch_bounds__(kSegThreads) void k_segment_write(const SegmentDev 
     }
 }
 
+void launch_segment_numbering(const SegmentDev &d, hipStream_t s)
+{
+    const unsigned scan_blocks = (unsigned)segment_scan_blocks((unsigned)d.f.n);
+    hipLaunchKernelGGL(k_segment_totals, dim3(scan_blocks), dim3(kSegThreads), 0, s, d);
+    hipLaunchKernelGGL(k_segment_scan, dim3(1), dim3(kSegThreads), 0, s, d, (int)scan_blocks);
+    hipLaunchKernelGGL(k_segment_number, dim3(scan_blocks), dim3(kSegThreads), 0, s, d);
+}
+
 void launch_segment(const SegmentDev &d, hipStream_t s)
 {
     // (width * height < 2^31, so the tiles of the image are fewer than 2^31 / 64 + 2^31 / 16, and the rows' segments fewer than 2^31 / 4
     // + 2^31 / 64: they fit grid.x)
     const unsigned tiles_x = (unsigned)((d.f.width + kSegTileW - 1) / kSegTileW);
     const unsigned tiles = tiles_x * (unsigned)((d.height + kSegTileH - 1) / kSegTileH);
-    const unsigned n = (unsigned)d.f.n, scan_blocks = (unsigned)segment_scan_blocks(n);
+    const unsigned n = (unsigned)d.f.n;
     if (d.f.kind == HAF_FRAME_DEPTH_U16) hipLaunchKernelGGL((k_segment_tile<HAF_FRAME_DEPTH_U16>), dim3(tiles), dim3(kSegThreads), 0, s, d);
     else if (d.f.kind == HAF_FRAME_DEPTH_F32) hipLaunchKernelGGL((k_segment_tile<HAF_FRAME_DEPTH_F32>), dim3(tiles), dim3(kSegThreads), 0, s, d);
     else hipLaunchKernelGGL((k_segment_tile<HAF_FRAME_XYZ_F32>), dim3(tiles), dim3(kSegThreads), 0, s, d);
     hipLaunchKernelGGL(k_segment_seam, dim3(tiles), dim3(kSegSeamThreads), 0, s, d);
     hipLaunchKernelGGL(k_segment_flatten, dim3((n + kSegThreads - 1) / kSegThreads), dim3(kSegThreads), 0, s, d);
-    hipLaunchKernelGGL(k_segment_totals, dim3(scan_blocks), dim3(kSegThreads), 0, s, d);
-    hipLaunchKernelGGL(k_segment_scan, dim3(1), dim3(kSegThreads), 0, s, d, (int)scan_blocks);
-    hipLaunchKernelGGL(k_segment_number, dim3(scan_blocks), dim3(kSegThreads), 0, s, d);
+    launch_segment_numbering(d, s);
     const unsigned segs = tiles_x * (unsigned)((d.height + kSegWriteRows - 1) / kSegWriteRows);
     hipLaunchKernelGGL(k_segment_write, dim3(segs), dim3(kSegThreads), 0, s, d);
 }

@@ -208,7 +208,13 @@ class CalcGraspPointsServer:
         n = len(self.last_segment_infos)
         return res, (self.best_per_object(frame, img, min_vote=min_vote, n_labels=n) if n else [])
 
-    def execute_frame_per_object(self, goal: GraspInputMsg, frame, params=None, plane=None, min_vote=1, margin_cells=4, fused=False):
+    @staticmethod
+    def cell_segment_params_from_goal(goal: GraspInputMsg, **kw):
+        """capi.cell_segment_params() with segment_params_from_goal()'s support plane; kw: the other fields over the library's defaults"""
+        return capi.cell_segment_params(plane=list(CalcGraspPointsServer.segment_params_from_goal(goal).plane), **kw)
+
+    def execute_frame_per_object(self, goal: GraspInputMsg, frame, params=None, plane=None, min_vote=1, margin_cells=4, fused=False,
+                                 segmenter="pixels"):
         """execute_frame_segmented() for objects ANYWHERE in the frame: one request per object, each centred on its object, instead of
         the one grid around the goal's grasp_area_center (objects outside that grid have no grasp there: no height grid contains
         them).  The frame is segmented into the engine's device image (params, plane: as execute_frame_segmented takes them), every
@@ -227,19 +233,30 @@ class CalcGraspPointsServer:
         fused=True: the same list from ONE haf_score_objects call per chunk of max_clouds objects -- the frame is staged and
         deprojected once per chunk and counts once against max_points (the chunk rule has no max_points term), request b marks and
         evaluates only the cells near its own object (mask `labels == label`; the picks are those of `labels != 0`, include/hafgrasp.h),
-        and one label pass serves the chunk."""
+        and one label pass serves the chunk.
+        segmenter="cells": the objects come from haf_segment_cells -- connected occupied cells of the top-down grid instead of
+        neighbouring pixels, so an object cut in two in the image stays one object and the frame may have any shape (an N x 1 cloud:
+        execute_cloud_per_object).  params is then a capi.cell_segment_params() (None: cell_segment_params_from_goal(goal)), and
+        self.last_segment_infos / self.last_segment_stats are that call's."""
+        if segmenter not in ("pixels", "cells"):
+            raise ValueError("segmenter: \"pixels\" or \"cells\"")
+        cells = segmenter == "cells"
         if goal.goal_frame_id:
             self.base_frame_id = goal.goal_frame_id
-        p = params if params is not None else self.segment_params_from_goal(goal)
+        if params is not None:
+            p = params
+        else:
+            p = self.cell_segment_params_from_goal(goal) if cells else self.segment_params_from_goal(goal)
         self.last_plane_fit = None
         if plane is not None:
             if isinstance(plane, str) and plane != "fit":
                 raise ValueError("plane: None, \"fit\" or a capi.plane_params()")
             self.last_plane_fit = self.engine.fit_plane(frame, None if isinstance(plane, str) else plane)
             if self.last_plane_fit["found"]:
-                p = capi.SegmentParams.from_buffer_copy(p)
+                p = type(p).from_buffer_copy(p)
                 p.plane = (C.c_float * 4)(*self.last_plane_fit["plane"])
-        img, self.last_segment_infos, self.last_segment_stats = self.engine.segment(frame, p, np.uint8, device_out=True)
+        segment = self.engine.segment_cells if cells else self.engine.segment
+        img, self.last_segment_infos, self.last_segment_stats = segment(frame, p, np.uint8, device_out=True)
         n = len(self.last_segment_infos)
         self.last_shapes = np.zeros(0, capi.LABEL_SHAPE_DTYPE)
         if not n:
@@ -276,6 +293,16 @@ class CalcGraspPointsServer:
                 if pick["found"]:
                     hit(label, fits, pick, c)
         return [h for _, h in sorted(hits, key=lambda kh: kh[0])]
+
+    def execute_cloud_per_object(self, goal: GraspInputMsg, xyz, params=None, plane=None, min_vote=1, margin_cells=4):
+        """execute_frame_per_object() for an UNORGANISED base-frame cloud (float32 [N, >= 3]: a PointCloud2 goal's points), which has no
+        image for haf_segment_frame: the cloud is wrapped as an N x 1 XYZ frame under the identity pose (capi.cloud_frame), clustered
+        by haf_segment_cells, and measured and scored as a frame is -- haf_measure_labels, haf_object_input, one haf_score_objects
+        call per chunk of max_clouds objects.  params: a capi.cell_segment_params(); plane: as execute_frame_segmented takes it.
+        -> the list execute_frame_per_object gives, with u = the index of the pick's point in `xyz` and v = 0."""
+        frame = capi.cloud_frame(np.ascontiguousarray(xyz, np.float32))
+        return self.execute_frame_per_object(goal, frame, params=params, plane=plane, min_vote=min_vote, margin_cells=margin_cells, fused=True,
+                                             segmenter="cells")
 
     def close(self):
         self.engine.close()

@@ -646,8 +646,8 @@ int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
  * haf_segment_ref: the host definition of record -- no device, no engine, a host frame and a host output only.
  * haf_segment_frame: equal to it in every label word, every info field, n_labels and stats.  out_on_device = 1: labels is the caller's
  * device memory, written on the engine's stream and complete when the call returns; labels == NULL with out_on_device = 1: a packed
- * image the engine owns (2 bytes x max_points, allocated by the first call that asks for it), valid until the next haf_segment_frame
- * or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
+ * image the engine owns (2 bytes x max_points, allocated by the first call that asks for it), valid until the next haf_segment_frame,
+ * haf_segment_cells or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
  * haf_grasp_map_labels; its data as a uint8 image is a haf_roi mask.  The first call allocates the scratch: 8 bytes x max_points of
  * parent and size words, the per-label table and the copy-back block.  Like haf_filter_depth the call neither reads nor changes
  * last-batch state or stage timings, and works before any request and with HAF_FLAG_PROBABILITY.
@@ -841,6 +841,72 @@ int  haf_score_objects(haf_engine *e, const haf_frame *frame, const haf_label_im
                        haf_grasp_output *out /* [n_objects] */, haf_label_pick *picks /* [n_objects] */,
                        haf_grasp_candidate *poses /* [n_objects], may be NULL */, int32_t *order /* [n_objects], may be NULL */,
                        int32_t *n_found /* may be NULL */);
+
+/* ---- objects of any cloud by top-down cell clustering (csrc/cellsegment.hip) -------------------------------------------------------
+ * haf_segment_frame links neighbouring PIXELS, so it needs an image: an unorganised cloud has none, an object cut in two in the image
+ * becomes two labels, and neighbours of clearly different height are one.  This segmenter's neighbourhood is the scene's: it clusters
+ * the occupied cells of the top-down grid, the view a height-accumulated feature has of the world.  A frame of any shape is accepted
+ * -- an N x 1 HAF_FRAME_XYZ_F32 frame with the identity pose is an unorganised cloud -- and the label image has the frame's shape, so
+ * haf_measure_labels and haf_score_objects follow as they follow haf_segment_frame.  The rules are csrc/cell_segment_rules.h's; every
+ * floating-point step is ONE correctly rounded fp32 operation in the stated order, never fused.
+ *
+ *   point       pixel i = v * width + u has haf_frame_points' three words; any kind and shape of frame.
+ *   foreground  each word finite and |w| <= 16 m (haf_fit_plane's usable point) and haf_segment_frame's height band: plane,
+ *               min_height and max_height have exactly its meaning.
+ *   cell        fx = (x - x0) * inv_cell, fy = (y - y0) * inv_cell, inv_cell = 1.0f / cell formed once on the host.  The point is in
+ *               the grid when fx >= 0 && fx < (float)nx and likewise fy; then ix = (int)floorf(fx), iy = (int)floorf(fy) and the cell
+ *               index is iy * nx + ix.  A point just below x0 is outside the grid, never cell 0.
+ *   per cell    count = the number of its foreground points; top = their largest h; occupied when count > 0.
+ *   link        two occupied cells that share an edge -- or also a corner with connectivity 8 -- are linked when max_step <= 0 or
+ *               fabsf(top_a - top_b) <= max_step; the difference is one subtraction, so the rule is symmetric.
+ *   component   a connected component of the link graph; its ANCHOR is its lowest cell index.
+ *   labels      components whose summed count is below min_points are background; the others are numbered 1, 2, ... in ascending
+ *               order of anchor; those numbered above max_labels are background too.  *n_labels = min(kept, max_labels).  A pixel
+ *               carries its cell's number when it is foreground and in the grid, 0 otherwise.
+ *   info[l - 1] n_points, n_cells, the anchor cell, the inclusive box of its cells and top, the largest top of its cells (first
+ *               *n_labels entries written).
+ *   stats       [0] pixels, [1] foreground, [2] foreground outside the grid, [3] occupied cells, [4] components, [5] components that
+ *               pass the size rule, before the cap.
+ *   cell_labels may be NULL; host memory, uint16 [ny][nx] packed: the top-down label grid.
+ *   labels      as haf_segment_frame's: elem_bytes 1 or 2, strides, alignment, bytes between rows not written, no overlap.
+ * Counts are integer sums, heights maxima through an ordered key, unions minima: nothing depends on an order of arrival.
+ *
+ * haf_segment_cells_ref: the host definition of record -- no device, no engine, a host frame and host outputs only.
+ * haf_segment_cells: equal to it in every label word, info field, cell_labels word, n_labels and stat.  The output conventions are
+ * exactly haf_segment_frame's, the engine's own image (labels == NULL with out_on_device = 1) is the SAME image for both segmenters.
+ * Scratch is allocated at first use and grown when nx * ny or the frame grows: one int32 cell word per pixel; count, top key, parent
+ * and size / label words per cell; the per-label tables and the copy-back block.  The call neither reads nor changes last-batch
+ * state or stage timings, and works before any request and with HAF_FLAG_PROBABILITY.
+ * Refusals, all before any device work, nothing written -- everything haf_segment_frame refuses for its frame and its label output;
+ * HAF_E_ARG: a plane entry, height or max_step that is not finite, cell outside 0.001..1, |x0| or |y0| > 64 (or not finite), nx or
+ * ny outside 1..4096, nx * ny > 2^22, connectivity not 4 or 8, min_points < 1, max_labels as haf_segment_params, for the _ref form
+ * a device-resident frame; HAF_E_CAPACITY: width * height > max_points. */
+#define HAF_MAX_CELLS (1 << 22)
+typedef struct haf_cell_segment_params {
+    float   plane[4];      /* as haf_segment_params.plane                                              */
+    float   min_height;    /* as haf_segment_params                                                    */
+    float   max_height;    /* as haf_segment_params: <= 0 is no upper limit                            */
+    float   cell;          /* metres, 0.001..1: the edge of a grid cell                                */
+    float   x0, y0;        /* base frame, |.| <= 64: the corner of cell (0, 0)                         */
+    int32_t nx, ny;        /* 1..4096 each, nx * ny <= HAF_MAX_CELLS                                   */
+    int32_t connectivity;  /* 4 or 8                                                                   */
+    float   max_step;      /* metres, finite; > 0: neighbours whose tops differ by more do not link    */
+    int32_t min_points;    /* >= 1: components of fewer foreground points become background            */
+    int32_t max_labels;    /* 1..HAF_MAX_LABELS (1..255 when the output is uint8)                      */
+} haf_cell_segment_params;
+typedef struct haf_cell_segment_info {   /* label l is entry l - 1 */
+    int32_t n_points, n_cells, anchor_ix, anchor_iy, ix_min, iy_min, ix_max, iy_max;
+    float   top;
+} haf_cell_segment_info;
+void haf_cell_segment_default(haf_cell_segment_params *p);   /* (0,0,1,0), 0.01f, 0, 0.01f, (-5.12f, -5.12f), 1024 x 1024, 8, 0, 50, 255 */
+int  haf_segment_cells_ref(const haf_frame *frame, const haf_cell_segment_params *p, void *labels, int32_t elem_bytes,
+                           size_t row_stride_bytes, uint16_t *cell_labels /* [ny][nx], may be NULL */,
+                           haf_cell_segment_info *info /* [max_labels], may be NULL */, int32_t *n_labels,
+                           int64_t *stats /* [6], may be NULL */);
+int  haf_segment_cells(haf_engine *e, const haf_frame *frame, const haf_cell_segment_params *p, void *labels, int32_t elem_bytes,
+                       size_t row_stride_bytes, int32_t out_on_device, haf_label_image *out_image /* may be NULL */,
+                       uint16_t *cell_labels /* [ny][nx], host, may be NULL */, haf_cell_segment_info *info /* [max_labels], may be NULL */,
+                       int32_t *n_labels, int64_t *stats /* [6], may be NULL */);
 
 int haf_abi_version(void);
 
