@@ -135,6 +135,17 @@ class LabelImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("elem_bytes", C.c_int32), ("on_device", C.c_int32), ("row_stride_bytes", C.c_size_t)]
 
 
+class Camera(C.Structure):
+    """haf_camera: the rectified pinhole camera a label image belongs to, and the transform from the base frame into its frame"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("base_to_camera", C.c_float * 12)]
+
+
+class TransferParams(C.Structure):
+    """haf_transfer_params: the parameters of haf_transfer_labels"""
+    _fields_ = [("near_m", C.c_float), ("tol_abs", C.c_float), ("tol_rel", C.c_float), ("splat", C.c_int32)]
+
+
 class LabelPick(C.Structure):
     """haf_label_pick: the best pixel of one label and its grasp-map values"""
     _fields_ = [("found", C.c_int32), ("u", C.c_int32), ("v", C.c_int32), ("vote", C.c_int32), ("roll", C.c_int32), ("cell", C.c_int32),
@@ -283,6 +294,13 @@ def _bind(path, testing):
     L.haf_measure_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_measure_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_object_input.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_void_p, C.c_int32, C.POINTER(GraspInput), C.POINTER(C.c_int32)]
+    L.haf_transfer_default.argtypes = [C.POINTER(TransferParams)]
+    L.haf_transfer_default.restype = None
+    L.haf_invert_pose.argtypes = [C.c_void_p, C.c_void_p]
+    L.haf_transfer_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(Camera), C.POINTER(LabelImage), C.c_int32, C.POINTER(TransferParams),
+                                          C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.POINTER(C.c_int64)]
+    L.haf_transfer_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(Camera), C.POINTER(LabelImage), C.c_int32, C.POINTER(TransferParams),
+                                      C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.POINTER(LabelImage), C.c_void_p, C.POINTER(C.c_int64)]
     # several GPUs in one process (csrc/multi.cpp)
     L.haf_create_multi.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(E)]
     L.haf_destroy_multi.argtypes = [E]
@@ -709,6 +727,56 @@ def measure_labels_ref(frame, labels, n_labels=None, plane=None):
     if rc != HAF_OK:
         raise HafError(rc, "haf_measure_labels_ref refused its arguments")
     return shapes[:n_labels]
+
+
+def camera(width, height, fx, fy, cx, cy, base_to_camera=None, sensor_to_base=None):
+    """haf_camera: the camera a label image belongs to.  base_to_camera: a 3x4 or 4x4 matrix, base frame -> the camera's frame (default:
+    identity); or sensor_to_base, the camera's pose as a Frame carries it, which invert_pose() turns into it."""
+    if sensor_to_base is not None:
+        assert base_to_camera is None
+        base_to_camera = invert_pose(sensor_to_base)
+    m = np.eye(4, dtype=np.float32)[:3] if base_to_camera is None else np.asarray(base_to_camera, dtype=np.float32).reshape(-1)[:12]
+    return Camera(width, height, fx, fy, cx, cy, (C.c_float * 12)(*np.asarray(m, dtype=np.float32).reshape(-1)))
+
+
+def transfer_params(**kw):
+    """haf_transfer_params with the library's defaults (near_m 0.05, tol_abs 0.01, tol_rel 0.01, splat 1) and `kw` over them"""
+    p = TransferParams()
+    lib().haf_transfer_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_transfer_params field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def invert_pose(pose):
+    """haf_invert_pose: the inverse of a 3x4 (or the first three rows of a 4x4) affine, in double, rounded once -> float32 [3, 4]"""
+    m = np.ascontiguousarray(np.asarray(pose, dtype=np.float32).reshape(-1)[:12])
+    assert m.size == 12
+    out = np.zeros(12, np.float32)
+    rc = lib().haf_invert_pose(m.ctypes.data, out.ctypes.data)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_invert_pose refused the pose (an entry that is not finite, or a singular matrix)")
+    return out.reshape(3, 4)
+
+
+def transfer_labels_ref(depth, cam, cam_labels, n_labels=None, params=None, dtype=np.uint8, out=None, zbuffer=False):
+    """haf_transfer_labels_ref: the host definition of record of a camera's label image carried over to a depth frame.  depth: a host
+    Frame of any kind; cam: a Camera; cam_labels: a host uint8 / uint16 [cam.height, cam.width] array (label_image()) -> (labels:
+    uint8 / uint16 [height, width] on the depth frame, stats: [pixels, in front of the camera, projecting, visible, labelled]);
+    zbuffer=True appends the int32 [cam.height, cam.width] z-buffer.  out: the array to write into (rows may be padded)."""
+    img, n_labels = label_image(cam_labels, cam, n_labels)
+    p = params if params is not None else transfer_params()
+    lab, ptr, elem, stride = _label_out(depth, dtype, out)
+    z = np.zeros((max(0, cam.height), max(0, cam.width)), np.int32) if zbuffer else None
+    stats = (C.c_int64 * 5)()
+    rc = lib().haf_transfer_labels_ref(C.byref(depth), C.byref(cam), C.byref(img), n_labels, C.byref(p), ptr, elem, stride,
+                                       z.ctypes.data if zbuffer else None, stats)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_transfer_labels_ref refused its arguments")
+    res = (lab, [int(x) for x in stats])
+    return res + (z,) if zbuffer else res
 
 
 def shape_to_dict(shape):
@@ -1274,6 +1342,34 @@ class Engine:
         shapes = np.zeros(max(1, n_labels), LABEL_SHAPE_DTYPE)
         self._check(self._L.haf_measure_labels(self._h, C.byref(frame), C.byref(img), n_labels, ptr, shapes.ctypes.data))
         return shapes[:n_labels]
+
+    def transfer_labels(self, depth, cam, cam_labels, n_labels=None, params=None, dtype=np.uint8, device_out=False, host_out=None,
+                        zbuffer=False):
+        """haf_transfer_labels: a depth Frame (any kind, host or device-resident), a Camera and its label image (label_image(): a numpy
+        uint8 / uint16 [cam.height, cam.width] array, a device tensor, a device pointer tuple or a LabelImage) -> (labels, stats) as
+        transfer_labels_ref gives them, computed on the device; zbuffer=True appends the int32 [cam.height, cam.width] z-buffer.  The
+        outputs are segment()'s: a new host array (host_out: the array to write into), device_out=True for the engine's own packed
+        device image -- the same image segment(..., device_out=True) uses -- or device_out=(pointer, row_stride_bytes) for the caller's."""
+        img, n_labels = label_image(cam_labels, cam, n_labels)
+        p = params if params is not None else transfer_params()
+        z = np.zeros((max(0, cam.height), max(0, cam.width)), np.int32) if zbuffer else None
+        zptr = z.ctypes.data if zbuffer else None
+        stats, got = (C.c_int64 * 5)(), LabelImage()
+        elem = np.dtype(dtype).itemsize
+        head = (self._h, C.byref(depth), C.byref(cam), C.byref(img), n_labels, C.byref(p))
+        if device_out is True:
+            rc = self._L.haf_transfer_labels(*head, None, elem, 0, 1, C.byref(got), zptr, stats)
+            lab = got
+        elif device_out is not False and device_out is not None:
+            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
+            rc = self._L.haf_transfer_labels(*head, int(ptr), elem, stride or depth.width * elem, 1, C.byref(got), zptr, stats)
+            lab = got
+        else:
+            lab, ptr, elem, stride = _label_out(depth, dtype, host_out)
+            rc = self._L.haf_transfer_labels(*head, ptr, elem, stride, 0, C.byref(got), zptr, stats)
+        self._check(rc)
+        res = (lab, [int(x) for x in stats])
+        return res + (z,) if zbuffer else res
 
     def cell_pose(self, request, roll, row, col):
         """haf_cell_pose: the pose of cell (row, col) of roll `roll` (global index) of request `request` of the last batch -> candidate dict"""

@@ -57,6 +57,14 @@
 //                                     --per-object [MARGIN] --fused and --labels-out like --segment and prints the same "object" lines;
 //                                     --cell-labels-out FILE.pgm writes the top-down label grid as an 8-bit PGM.  Works with --depth
 //                                     and, in its place, with ONE .pcd: the cloud as an N x 1 frame in the base frame
+//   --labels FILE.pgm --labels-camera FX FY CX CY [--labels-pose <12 floats>] [--transfer NEAR,TOL_ABS,TOL_REL,SPLAT]
+//                                     the label image is ANOTHER camera's (the colour camera an instance segmenter ran on): any size,
+//                                     that camera's intrinsics, --labels-pose the rows 0..2 of ITS sensor-to-base matrix (default
+//                                     identity).  haf_transfer_labels carries it over to the first view's pixels behind a z-buffer
+//                                     (--transfer: its parameters, default 0.05,0.01,0.01,1) in front of the plain --labels pick, of
+//                                     --measure, and of --per-object [MARGIN] --fused (then without --segment: the objects are the
+//                                     image's; --plane A B C D gives their heights); --labels-out FILE.pgm writes the transferred
+//                                     image.  Without --labels-camera every option behaves as before
 //   --roi-mask FILE.pgm               with ONE --depth: an 8-bit binary PGM of the image's size; only the cells near the cells of the
 //                                     pixels under its non-zero samples are scored (haf_score_frames_roi) and the grasp printed is the
 //                                     best one there; --hypotheses, --top-k and --map-out work behind it on the restricted request
@@ -163,6 +171,8 @@ static void usage()
             "  --labels FILE.pgm --measure [--plane A B C D]     --segment ... --per-object [MARGIN] [--fused]      (with ONE --depth)\n"
             "  --segment-cells MIN_H,MAX_H,CELL,MIN_PTS[,STEP] | default  [--plane ...] [--per-object [MARGIN] [--fused]] [--labels-out FILE.pgm] [--cell-labels-out FILE.pgm]   (with --depth, or with one cloud.pcd)\n"
             "  --segment MIN_H,MAX_H,GAP,MIN_PX | default  [--plane A B C D | --plane fit[,TOL,N_HYP] [--plane-mask FILE.pgm]] [--labels-out FILE.pgm] [--segment-roi]   (with --depth)\n"
+            "  --labels FILE.pgm --labels-camera FX FY CX CY [--labels-pose m00 m01 ... m23] [--transfer NEAR,TOL_ABS,TOL_REL,SPLAT] [--labels-out FILE.pgm]\n"
+            "                     (with --depth: the labels are ANOTHER camera's; alone, with --measure, or with --per-object [MARGIN] --fused)\n"
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
@@ -226,7 +236,28 @@ struct MapOptions {
     bool cells = false;
     haf_cell_segment_params cell_params;
     std::string cell_labels_out;
+    // --labels-camera FX FY CX CY [--labels-pose 12 floats] [--transfer NEAR,TOL_ABS,TOL_REL,SPLAT]: --labels is ANOTHER camera's image (any
+    // size); haf_transfer_labels carries it over to the first view before --measure, --per-object --fused or the plain --labels pick
+    // read it, and --labels-out writes the transferred image
+    bool labels_camera = false;
+    haf_camera camera;
+    float labels_pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    haf_transfer_params transfer_params;
+    std::vector<uint8_t> xfer8;          // the transferred image (filled by run_depth): uint8 up to 255 labels, uint16 above
+    std::vector<uint16_t> xfer16;
+    int32_t xfer_n = 0;
 };
+
+// --transfer NEAR,TOL_ABS,TOL_REL,SPLAT
+static bool parse_transfer(const char *arg, haf_transfer_params *p)
+{
+    float a = 0, b = 0, c = 0;
+    int s = 0;
+    char tail = 0;
+    if (sscanf(arg, "%f,%f,%f,%d%c", &a, &b, &c, &s, &tail) != 4) return false;
+    p->near_m = a; p->tol_abs = b; p->tol_rel = c; p->splat = s;
+    return true;
+}
 
 // --segment MIN_H,MAX_H,GAP,MIN_PX or "default"
 static bool parse_segment(const char *arg, haf_segment_params *p)
@@ -399,7 +430,17 @@ static int run_map(haf_engine *eng, const haf_config &cfg, const haf_frame &f, c
         if (found) printf("mask %d %d %s\n", u, v, hafshim::hypothesis_string(best.grasp, cfg.roll_step_deg).c_str());
         else printf("mask none\n");
     }
-    if (!mo.labels_path.empty()) {
+    if (mo.labels_camera) {                               // --labels through --labels-camera: the transferred image, already on this frame
+        const bool wide = !mo.xfer16.empty();
+        const haf_label_image img = {wide ? (const void *)mo.xfer16.data() : (const void *)mo.xfer8.data(), wide ? 2 : 1, 0, (size_t)f.width * (wide ? 2 : 1)};
+        std::vector<std::string> lines;
+        std::string serr;
+        if (hafshim::label_hypotheses(eng, cfg, f, img, mo.xfer_n, mo.min_vote, &lines, &serr) != HAF_OK) {
+            fprintf(stderr, "--labels: %s\n", serr.c_str());
+            return 1;
+        }
+        for (const std::string &l : lines) printf("object %s\n", l.c_str());
+    } else if (!mo.labels_path.empty()) {
         // 8-bit samples as they are, 16-bit ones through the library's reader; labels above HAF_MAX_LABELS are ignored like background
         std::vector<uint8_t> lab8;
         uint16_t *lab16 = nullptr;
@@ -459,7 +500,11 @@ static int run_measure(haf_engine *eng, const haf_frame &f, const MapOptions &mo
     uint16_t *lab16 = nullptr;
     haf_label_image img;
     unsigned top = 0;
-    if (!load_labels(mo.labels_path, f.width, f.height, lab8, &lab16, &img, &top)) { if (lab16) haf_free(lab16); return 1; }
+    if (mo.labels_camera) {                               // the transferred image, already on this frame
+        const bool wide = !mo.xfer16.empty();
+        img = haf_label_image{wide ? (const void *)mo.xfer16.data() : (const void *)mo.xfer8.data(), wide ? 2 : 1, 0, (size_t)f.width * (wide ? 2 : 1)};
+        top = (unsigned)mo.xfer_n;
+    } else if (!load_labels(mo.labels_path, f.width, f.height, lab8, &lab16, &img, &top)) { if (lab16) haf_free(lab16); return 1; }
     const int32_t n = (int32_t)std::min(std::max(top, 1u), (unsigned)HAF_MAX_LABELS);
     std::vector<haf_label_shape> shapes((size_t)n);
     const int rc = haf_measure_labels(eng, &f, &img, n, mo.have_plane ? mo.plane : nullptr, shapes.data());
@@ -604,6 +649,57 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
         fprintf(stderr, "--filtered-out: cannot write %s\n", mo.filtered_out.c_str());
         release();
         return 1;
+    }
+    // --labels-camera: the other camera's label image onto the first view (filtered or not), before anything reads labels
+    if (mo.labels_camera) {
+        std::vector<uint8_t> lab8;
+        uint16_t *lab16 = nullptr;
+        int w8 = 0, h8 = 0;
+        int32_t wc = 0, hc = 0;
+        if (read_pgm8(mo.labels_path, lab8, w8, h8)) { wc = w8; hc = h8; }
+        else if (haf_pgm16_load(mo.labels_path.c_str(), &lab16, &wc, &hc, err, sizeof err) != HAF_OK) {
+            fprintf(stderr, "%s: not a binary 8- or 16-bit PGM (%s)\n", mo.labels_path.c_str(), err);
+            release();
+            return 1;
+        }
+        unsigned top = 0;
+        for (size_t i = 0; i < (size_t)wc * (size_t)hc; i++) top = std::max(top, lab16 ? (unsigned)lab16[i] : (unsigned)lab8[i]);
+        mo.xfer_n = (int32_t)std::min(std::max(top, 1u), (unsigned)HAF_MAX_LABELS);
+        const bool wide = mo.xfer_n > 255;
+        const size_t px = (size_t)frames[0].width * (size_t)frames[0].height;
+        if (wide) mo.xfer16.assign(px, 0); else mo.xfer8.assign(px, 0);
+        haf_camera cam = mo.camera;
+        cam.width = wc; cam.height = hc;
+        const haf_label_image cl = {lab16 ? (const void *)lab16 : (const void *)lab8.data(), lab16 ? 2 : 1, 0, (size_t)wc * (lab16 ? 2 : 1)};
+        int64_t ts[5] = {0, 0, 0, 0, 0};
+        int trc = haf_invert_pose(mo.labels_pose, cam.base_to_camera);
+        if (trc != HAF_OK) fprintf(stderr, "--labels-pose: not finite, or singular\n");
+        else if ((trc = haf_transfer_labels(eng, &frames[0], &cam, &cl, mo.xfer_n, &mo.transfer_params, wide ? (void *)mo.xfer16.data() : (void *)mo.xfer8.data(),
+                                            wide ? 2 : 1, (size_t)frames[0].width * (wide ? 2 : 1), 0, nullptr, nullptr, ts)) != HAF_OK)
+            fprintf(stderr, "%s: --labels-camera: %s\n", mo.labels_path.c_str(), haf_last_error(eng));
+        if (lab16) haf_free(lab16);
+        if (trc != HAF_OK) { release(); return 1; }
+        fprintf(stderr, "%s: %d x %d labels transferred: %lld of %lld pixels in front of the camera, %lld project, %lld visible, %lld labelled\n",
+                mo.labels_path.c_str(), (int)wc, (int)hc, (long long)ts[1], (long long)ts[0], (long long)ts[2], (long long)ts[3], (long long)ts[4]);
+        if (!mo.labels_out.empty() && !(wide ? write_depth_pgm16(mo.labels_out, mo.xfer16.data(), frames[0].width, frames[0].height)
+                                             : write_pgm8(mo.labels_out, mo.xfer8.data(), frames[0].width, frames[0].height))) {
+            fprintf(stderr, "--labels-out: cannot write %s\n", mo.labels_out.c_str());
+            release();
+            return 1;
+        }
+        if (mo.per_object) {                              // the objects of --per-object --fused are the transferred image's
+            if (wide) { fprintf(stderr, "--per-object: more than 255 labels\n"); release(); return 1; }
+            mo.seg_labels = mo.xfer8;
+            mo.seg_n = mo.xfer_n;
+            if (mo.have_plane) memcpy(mo.seg_plane, mo.plane, sizeof mo.seg_plane);
+            else {
+                hafshim::GoalFields g;
+                haf_segment_params from_goal;
+                for (int k = 0; k < 3; k++) { g.center[k] = in.grasp_area_center[k]; g.approach_vector[k] = in.approach_vector[k]; }
+                hafshim::segment_params_from_goal(g, &from_goal);
+                memcpy(mo.seg_plane, from_goal.plane, sizeof mo.seg_plane);
+            }
+        }
     }
     if (mo.measure) {
         const int mrc = run_measure(eng, frames[0], mo);
@@ -774,8 +870,10 @@ int main(int argc, char **argv)
     std::string shard = "rolls";
     std::string features, range, model;
     std::vector<DepthView> views;                  // --depth: 16-bit PGMs in place of the .pcd arguments, the views of one request
-    bool have_intrinsics = false;
+    bool have_intrinsics = false, have_labels_pose = false, have_transfer = false;
     MapOptions map_opt;
+    haf_transfer_default(&map_opt.transfer_params);
+    memset(&map_opt.camera, 0, sizeof map_opt.camera);
     haf_frame frame;                               // the sensor options as they stand: what the next view opened inherits
     haf_frame_default(&frame);
     int first_cloud = argc;
@@ -823,6 +921,13 @@ int main(int argc, char **argv)
         else if (a == "--plane-mask") { need(1); map_opt.plane_mask = argv[++i]; }
         else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) map_opt.plane[k] = (float)atof(argv[++i]); map_opt.have_plane = true; }
         else if (a == "--labels-out") { need(1); map_opt.labels_out = argv[++i]; }
+        else if (a == "--labels-camera") {
+            need(4);
+            map_opt.camera.fx = (float)atof(argv[++i]); map_opt.camera.fy = (float)atof(argv[++i]); map_opt.camera.cx = (float)atof(argv[++i]); map_opt.camera.cy = (float)atof(argv[++i]);
+            map_opt.labels_camera = true;
+        }
+        else if (a == "--labels-pose") { need(12); for (int k = 0; k < 12; k++) map_opt.labels_pose[k] = (float)atof(argv[++i]); have_labels_pose = true; }
+        else if (a == "--transfer") { need(1); if (!parse_transfer(argv[++i], &map_opt.transfer_params)) { usage(); return 2; } have_transfer = true; }
         else if (a == "--intrinsics") { need(4); frame.fx = (float)atof(argv[++i]); frame.fy = (float)atof(argv[++i]); frame.cx = (float)atof(argv[++i]); frame.cy = (float)atof(argv[++i]); have_intrinsics = true; }
         else if (a == "--depth-scale") { need(1); frame.depth_scale = (float)atof(argv[++i]); }
         else if (a == "--depth-range") { need(2); frame.min_depth = (float)atof(argv[++i]); frame.max_depth = (float)atof(argv[++i]); }
@@ -841,9 +946,11 @@ int main(int argc, char **argv)
     const bool from_depth = !views.empty();
     if (features.empty() || range.empty() || model.empty() || (!from_depth && (!map_opt.out_prefix.empty() || !map_opt.mask_path.empty() || !map_opt.labels_path.empty())) ||
         (!map_opt.roi_path.empty() && (views.size() != 1 || !views[0].roi_path.empty())) ||
-        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || (map_opt.have_plane && !map_opt.measure) || map_opt.fit_plane || !map_opt.labels_out.empty())) ||
+        (map_opt.segment && !from_depth) || (!map_opt.segment && (map_opt.segment_roi || (map_opt.have_plane && !map_opt.measure && !map_opt.labels_camera) || map_opt.fit_plane || (!map_opt.labels_out.empty() && !map_opt.labels_camera))) ||
+        (map_opt.labels_camera ? (map_opt.labels_path.empty() || map_opt.segment || (map_opt.per_object && !map_opt.fused)) : (have_labels_pose || have_transfer)) ||
         (map_opt.fused && !map_opt.per_object) || (!map_opt.cells && !map_opt.cell_labels_out.empty()) ||
-        (map_opt.per_object && (!map_opt.segment || views.size() != 1 || map_opt.segment_roi || map_opt.measure || !map_opt.roi_path.empty() || !map_opt.labels_path.empty())) ||
+        (map_opt.per_object && ((!map_opt.segment && !map_opt.labels_camera) || views.size() != 1 || map_opt.segment_roi || map_opt.measure || !map_opt.roi_path.empty() ||
+                                (!map_opt.labels_path.empty() && !map_opt.labels_camera))) ||
         (map_opt.measure && (map_opt.labels_path.empty() || views.size() != 1 || map_opt.segment || map_opt.fit_plane)) ||
         (map_opt.fit_plane && map_opt.have_plane) || (!map_opt.fit_plane && !map_opt.plane_mask.empty()) ||
         (map_opt.segment_roi && (views.size() != 1 || !views[0].roi_path.empty() || !map_opt.roi_path.empty())) ||

@@ -3,7 +3,7 @@
 // single-frame input of engine_stage.cpp, the seven launches of segment.hip run on the engine's stream, ONE copy brings back the counters
 // and the per-label table -- and, for a host `labels`, the packed image behind them -- and ONE synchronisation ends the call.  Nothing of
 // the last scored batch is read or written: the stage timings are not touched, and the engine's own label image is a buffer only
-// haf_segment_cells shares.
+// haf_segment_cells and haf_transfer_labels share.
 #include "engine_state.h"
 
 namespace haf_host {

@@ -13,6 +13,7 @@
 //   engine_cellsegment.cpp haf_segment_cells: one frame of any shape -> object labels by top-down cell clustering (cellsegment.hip)
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
+//   engine_transfer.cpp  haf_transfer_labels: another camera's label image onto a depth frame's pixels, behind a z-buffer (transfer.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
 //   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
@@ -435,7 +436,7 @@ struct haf_engine {
     DevBuf<char> d_filter_image;
     // haf_segment_frame (engine_segment.cpp), allocated by its first call: the parent and size words (4 bytes x max_points each) with the
     // scan's block totals behind them; the block [counters][per-label table, HAF_MAX_LABELS entries][a host output image, 2 bytes x
-    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which only haf_segment_cells shares
+    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which haf_segment_cells and haf_transfer_labels share
     DevBuf<int> d_seg_words;
     StageBuf seg_out;
     DevBuf<char> d_seg_image;
@@ -452,6 +453,11 @@ struct haf_engine {
     // haf_measure_labels (engine_labelshape.cpp), allocated by its first call: the block [per-label table, HAF_MAX_LABELS rows of 160 bytes]
     // [a host label image, 2 bytes x max_points] with its pinned twin
     StageBuf shape_io;
+    // haf_transfer_labels (engine_transfer.cpp), allocated by its first call: the z-buffer, a word per pixel of the label camera, grown to
+    // the largest camera seen; the block [counters][a host output image, 2 bytes x max_points][a host camera label image, 2 bytes x
+    // max_points] with its pinned twin.  Its own image is d_seg_image above
+    DevBuf<int> d_transfer_z;
+    StageBuf transfer_io;
 };
 
 namespace haf_host {

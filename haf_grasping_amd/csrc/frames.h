@@ -8,6 +8,7 @@
 #include "plane_rules.h"
 #include "label_shape.h"
 #include "cell_segment_rules.h"
+#include "transfer_rules.h"
 
 #include <string>
 
@@ -73,5 +74,12 @@ int check_measure(const haf_frame *frame, const haf_label_image *labels, int32_t
 void shape_finish(haf_label_shape *s);
 // a label's row of the device table (label_shape.h: kShapeRowWords words, as copied back) -> its integers and h_max, then shape_finish
 void shape_from_row(const uint32_t *row, haf_label_shape *s);
+// transfer_host.cpp, shared by haf_transfer_labels_ref and haf_transfer_labels: every refusal of the depth frame, the camera, its label
+// image, the parameters and the label output that needs no engine (check_segment's for the frame and the output; labels may be null only
+// with out_on_device = 1); THE constants of a call, formed here in double
+int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_label_image *cam_labels, int32_t n_labels,
+                   const haf_transfer_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device,
+                   std::string &err);
+haf_transfer_math::TransferRules transfer_rules(const haf_camera &cam, const haf_transfer_params &p);
 
 }  // namespace haf

@@ -670,6 +670,26 @@ struct ShapeDev {
     unsigned *table;
 };
 void launch_label_shape(const ShapeDev &d, hipStream_t s);
+// haf_transfer_labels (transfer.hip): the depth frame, the camera and its label image as the kernels read them -- a kernel argument, so
+// every field is a scalar load.  f: the depth frame (dst and count are not read); r: the call's constants (transfer_rules.h); z: the
+// z-buffer, r.width * r.height words; labels: the CAMERA's label image, label_bytes 1 or 2 per pixel, rows label_stride bytes apart;
+// out: the label image on the depth frame, elem_bytes 1 or 2 per pixel, rows out_stride bytes apart; counters[4], zeroed by the caller:
+// pixels in front of the camera, projecting, visible, labelled.  All of it device memory
+struct TransferDev {
+    FrameDev f;
+    haf_transfer_math::TransferRules r;
+    int *z;
+    const void *labels;
+    unsigned long long label_stride;
+    int label_bytes, n_labels;
+    void *out;
+    unsigned long long out_stride;
+    int elem_bytes;
+    unsigned *counters;
+};
+enum { TRANSFER_CNT_FRONT = 0, TRANSFER_CNT_PROJECTS = 1, TRANSFER_CNT_VISIBLE = 2, TRANSFER_CNT_LABELLED = 3, TRANSFER_CNT_WORDS = 4 };
+// the fill and the two launches of one call, in stream order: z-buffer to INT32_MAX, splat, gather.  hipSuccess, or the fill's error
+hipError_t launch_transfer(const TransferDev &d, hipStream_t s);
 void launch_mfma_accum_test(const void *a, const void *b, const float *c0, float *out, int trials, hipStream_t s);   // testkernels.hip (testing build)
 void launch_mfma_rate_test(const void *in, float *out, int blocks, int iters, hipStream_t s);                       // testkernels.hip (testing build)
 void launch_mfma_model_test(const void *in, float *out, int mb, int blocks, int tiles, hipStream_t s);             // testkernels.hip (testing build)

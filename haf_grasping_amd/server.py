@@ -304,5 +304,45 @@ class CalcGraspPointsServer:
         return self.execute_frame_per_object(goal, frame, params=params, plane=plane, min_vote=min_vote, margin_cells=margin_cells, fused=True,
                                              segmenter="cells")
 
+    def execute_frame_labelled(self, goal: GraspInputMsg, frame, camera, cam_labels, n_labels=None, params=None, plane=None, min_vote=1,
+                               margin_cells=4):
+        """execute_frame_per_object(fused=True) with the objects of a LEARNED instance segmenter in place of the engine's own: cam_labels
+        is the label image of another camera (the colour camera the segmenter ran on; `camera`: a capi.camera() with that camera's
+        intrinsics and its base -> camera transform, cam_labels: what capi.label_image() takes, n_labels: its largest label).  The
+        image is carried over to the depth frame's pixels behind a z-buffer (haf_transfer_labels; params: a capi.transfer_params()) into
+        the engine's device image; from there the chain is the fused one: haf_measure_labels, haf_object_input per found object, one
+        haf_score_objects call per chunk of max_clouds objects.  plane: None (the shapes carry no height), four floats, "fit" or a
+        capi.plane_params() (haf_fit_plane on the frame; without a plane found, no height).
+        -> the list execute_frame_per_object gives.  self.last_transfer_stats: [pixels, in front of the camera, projecting, visible,
+        labelled]; self.last_shapes and self.last_plane_fit as execute_frame_per_object leaves them."""
+        if goal.goal_frame_id:
+            self.base_frame_id = goal.goal_frame_id
+        _, n = capi.label_image(cam_labels, camera, n_labels)
+        self.last_plane_fit = None
+        if isinstance(plane, str) and plane != "fit":
+            raise ValueError("plane: None, four floats, \"fit\" or a capi.plane_params()")
+        if isinstance(plane, (str, capi.PlaneParams)):
+            self.last_plane_fit = self.engine.fit_plane(frame, None if isinstance(plane, str) else plane)
+            plane = list(self.last_plane_fit["plane"]) if self.last_plane_fit["found"] else None
+        img, self.last_transfer_stats = self.engine.transfer_labels(frame, camera, cam_labels, n, params, np.uint8 if n <= 255 else np.uint16,
+                                                                    device_out=True)
+        self.last_shapes = self.engine.measure_labels(frame, img, n_labels=n, plane=plane)
+        cfg, base = self.engine.cfg, goal.to_c()
+        todo = [(l + 1,) + capi.object_input(cfg, base, self.last_shapes[l], margin_cells) for l in range(n) if self.last_shapes["found"][l]]
+        hits = []
+        chunk = max(1, int(cfg.max_clouds))
+        for c0 in range(0, len(todo), chunk):
+            part = todo[c0:c0 + chunk]
+            _, picks, poses, _ = self.engine.score_objects(frame, img, n, [label for label, _, _ in part], [inp for _, inp, _ in part],
+                                                           min_vote=min_vote)
+            for b, (label, _, fits) in enumerate(part):
+                if picks["found"][b]:
+                    pick, c = picks[b], poses[b]
+                    msg = GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
+                                         c["approach_vector"], c["roll"])
+                    key = (-int(pick["vote"]), int(pick["roll"]), int(pick["v"]) * frame.width + int(pick["u"]))
+                    hits.append((key, (label, msg, int(pick["u"]), int(pick["v"]), capi.shape_to_dict(self.last_shapes[label - 1]), fits)))
+        return [h for _, h in sorted(hits, key=lambda kh: kh[0])]
+
     def close(self):
         self.engine.close()

@@ -647,7 +647,7 @@ int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
  * haf_segment_frame: equal to it in every label word, every info field, n_labels and stats.  out_on_device = 1: labels is the caller's
  * device memory, written on the engine's stream and complete when the call returns; labels == NULL with out_on_device = 1: a packed
  * image the engine owns (2 bytes x max_points, allocated by the first call that asks for it), valid until the next haf_segment_frame,
- * haf_segment_cells or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
+ * haf_segment_cells, haf_transfer_labels or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
  * haf_grasp_map_labels; its data as a uint8 image is a haf_roi mask.  The first call allocates the scratch: 8 bytes x max_points of
  * parent and size words, the per-label table and the copy-back block.  Like haf_filter_depth the call neither reads nor changes
  * last-batch state or stage timings, and works before any request and with HAF_FLAG_PROBABILITY.
@@ -907,6 +907,71 @@ int  haf_segment_cells(haf_engine *e, const haf_frame *frame, const haf_cell_seg
                        size_t row_stride_bytes, int32_t out_on_device, haf_label_image *out_image /* may be NULL */,
                        uint16_t *cell_labels /* [ny][nx], host, may be NULL */, haf_cell_segment_info *info /* [max_labels], may be NULL */,
                        int32_t *n_labels, int64_t *stats /* [6], may be NULL */);
+
+/* ---- another camera's label image on a depth frame (csrc/transfer.hip) -------------------------------------------------------------
+ * Every object-level call above takes a label image that lies on the depth frame's pixels.  An instance segmenter runs on the COLOUR
+ * image: another camera, with its own intrinsics, a baseline of some centimetres against the depth sensor, often another resolution.
+ * This call carries such an image over, and it is not a nearest-pixel lookup: a depth pixel the colour camera cannot see, because an
+ * object stands in front of it, must not take that object's label (the table behind a mug would become "mug").  So it is the classic
+ * two passes: a z-buffer of the depth frame's points in the camera's image, then a gather that keeps a label only where the point is
+ * the one the camera sees.  The rules are csrc/transfer_rules.h's.  Only the transform into the camera's frame is floating point --
+ * ONE correctly rounded fp32 operation per step, never fused; everything behind it is integer arithmetic, so no result depends on a
+ * division unit or on the order in which atomics arrive.
+ *
+ * Constants, formed once on the host in double (rne: round to nearest even): FX = rne(fx * 256), FY, CX, CY likewise, as int32;
+ * NEAR = max(1, rne(near_m * 65536)); TA = rne(tol_abs * 65536) clamped to int32; TR = rne(tol_rel * 65536).
+ * Per pixel i = v * width + u of the DEPTH frame, which may be of any kind:
+ *   point       p = haf_frame_points' three words; the pixel is unlabelled (output 0) unless all three are finite.
+ *   camera      q[r] = ((m[r][0] p0 + m[r][1] p1) + m[r][2] p2) + m[r][3], m = base_to_camera, left to right.  Unlabelled unless every
+ *               q[r] is finite and |q[r]| <= 16.  Q[r] = rne(q[r] * 65536) as int32 (the product is exact, |Q| <= 2^20).  Unlabelled
+ *               unless Qz >= NEAR; the pixels that pass are stats[1].
+ *   projection  in int64: d = 256 Qz, nu = FX Qx + (CX + 128) Qz, nv = FY Qy + (CY + 128) Qz.  The point PROJECTS when
+ *               0 <= nu < width_c d and 0 <= nv < height_c d; then uc = nu div d, vc = nv div d -- the nearest pixel to fx x / z + cx.
+ *               Projecting pixels are stats[2].
+ *   z-buffer    Z[vc'][uc'] = the minimum of Qz over all projecting pixels and all (uc', vc') with |uc' - uc| <= splat and
+ *               |vc' - vc| <= splat inside the camera image; a word no point reached holds INT32_MAX.
+ *   visible     Qz - Z[vc][uc] <= TA + ((int64)TR * Z[vc][uc] >> 16).  Visible pixels are stats[3].
+ *   label       L = the camera label image's value at (uc, vc), read as haf_grasp_map_labels reads a haf_label_image (0 and values
+ *               above n_labels count as 0).  The output pixel is L when visible, else 0; non-zero outputs are stats[4].  stats[0] is
+ *               the number of pixels.
+ * Outputs: the label image on the depth frame with exactly haf_segment_frame's conventions -- uint8 (n_labels <= 255) or uint16; a
+ * host image with a stride, the caller's device image, or (labels == NULL with out_on_device = 1) the engine's own image, which is the
+ * SAME one image the two segmenters use, valid until the next call of any of the three; out_image describes the result.  zbuffer (may
+ * be NULL): host memory, int32 [height_c][width_c], the words of Z.
+ *
+ * haf_invert_pose: pure host.  The inverse of the general 3x4 affine, in double by the adjugate, rounded once to float; HAF_E_ARG for
+ * an entry that is not finite or a determinant whose magnitude is below 1e-12.  base_to_camera = the inverse of the camera's
+ * sensor_to_base.
+ * haf_transfer_labels_ref: the host definition of record -- no device, no engine, a host frame, host images and host outputs only.
+ * haf_transfer_labels: equal to it in every label word, every zbuffer word and every stat.  The depth frame and the camera label image
+ * may each be host or device resident; a device-resident one is read where it lies, with its strides.  A fill, two launches and one
+ * copy back on the engine's stream.  Like the segmenters the call neither reads nor changes last-batch state or stage timings, and
+ * works before any request and with HAF_FLAG_PROBABILITY.  Scratch, allocated on first use: 4 bytes per camera pixel, grown on
+ * demand, and the copy-back block (a host output image and a host camera label image, 2 bytes x max_points each).
+ * Refusals, all before any device work, nothing written -- everything haf_segment_frame refuses for its frame and its label output;
+ * everything haf_grasp_map_labels refuses for a label image and n_labels (and n_labels > 255 with a uint8 output); HAF_E_ARG: a null
+ * cam, cam_labels or p, a camera or parameter field outside the ranges below or not finite, the camera label image overlapping the
+ * output in the same residence (the engine's own image given as BOTH included), for the _ref form anything device-resident;
+ * HAF_E_CAPACITY: width * height of the depth frame or of the camera > max_points. */
+typedef struct haf_camera {            /* the camera the label image belongs to: a rectified pinhole image */
+    int32_t width, height;             /* 1..32768 each */
+    float   fx, fy, cx, cy;            /* pixels; fx, fy in [1/256, 32768], |cx|, |cy| <= 32768, all finite */
+    float   base_to_camera[12];        /* rows 0..2 of the 4x4, row-major: base frame -> this camera's frame */
+} haf_camera;
+typedef struct haf_transfer_params {
+    float   near_m;                    /* metres, finite, in [0.001, 16]: points nearer to the camera plane are not projected */
+    float   tol_abs, tol_rel;          /* metres, and per metre of the z-buffer's value; finite, >= 0, tol_rel <= 1 */
+    int32_t splat;                     /* 0..2: a point enters the z-buffer in the (2 splat + 1)^2 pixels around its own */
+} haf_transfer_params;
+void haf_transfer_default(haf_transfer_params *p);      /* 0.05f, 0.01f, 0.01f, 1 */
+int  haf_invert_pose(const float pose[12], float inverse[12]);
+int  haf_transfer_labels_ref(const haf_frame *depth, const haf_camera *cam, const haf_label_image *cam_labels, int32_t n_labels,
+                             const haf_transfer_params *p, void *labels, int32_t elem_bytes, size_t row_stride_bytes,
+                             int32_t *zbuffer /* [height_c][width_c], may be NULL */, int64_t *stats /* [5], may be NULL */);
+int  haf_transfer_labels(haf_engine *e, const haf_frame *depth, const haf_camera *cam, const haf_label_image *cam_labels, int32_t n_labels,
+                         const haf_transfer_params *p, void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device,
+                         haf_label_image *out_image /* may be NULL */, int32_t *zbuffer /* host, may be NULL */,
+                         int64_t *stats /* [5], may be NULL */);
 
 int haf_abi_version(void);
 
