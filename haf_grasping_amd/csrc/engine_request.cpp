@@ -62,30 +62,33 @@ static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool
 {
     *changed = false;
     *resolved = 0;
-    const int n2 = std::min(std::min(e->h_counters[CNT_FLAGGED2], e->list_cap), e->flag_cap);     // (one window of the attribute image)
+    const int n2 = std::min(e->h_counters[CNT_FLAGGED2], e->list_cap);
     if (n2 <= 0 || e->prob_mode) return HAF_OK;
     std::vector<double> dec((size_t)n2);
     std::vector<int> ev((size_t)n2);
     HIPCHK(e, hipMemcpyAsync(dec.data(), e->d_dec_exact2.p, (size_t)n2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(ev.data(), e->d_flag2_list.p, (size_t)n2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
-    std::vector<int> cand;
-    for (int i = 0; i < n2; i++) if (!(std::fabs(dec[(size_t)i]) > e->host_exp_thr)) cand.push_back(i);
-    if (cand.empty()) return HAF_OK;
     std::vector<double> x64;
-    const int rc = fetch_attributes64(e, d, s, e->d_flag2_list.p, CNT_FLAGGED2, 0, n2, x64);
-    if (rc != HAF_OK) return rc;
-    for (int i : cand) {
-        const double dv = host_decision(e->model, attr_column(x64, i), e->kx);
-        const int8_t lab = (int8_t)(dv > 0.0 ? e->gv0 : e->gv1);
-        int cell = 0;
-        int8_t old = 0;
-        HIPCHK(e, hipMemcpy(&cell, e->d_evalcell.p + ev[(size_t)i], sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(&old, e->d_labels.p + cell, 1, hipMemcpyDeviceToHost));
-        if (old != lab) *changed = true;
-        HIPCHK(e, hipMemcpy(e->d_labels.p + cell, &lab, 1, hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(e->d_dec_exact2.p + i, &dv, sizeof(double), hipMemcpyHostToDevice));
-        (*resolved)++;
+    for (int off = 0; off < n2; off += e->flag_cap) {            // (the attribute image holds one window of the list at a time)
+        const int nw = std::min(e->flag_cap, n2 - off);
+        std::vector<int> cand;
+        for (int i = off; i < off + nw; i++) if (!(std::fabs(dec[(size_t)i]) > e->host_exp_thr)) cand.push_back(i);
+        if (cand.empty()) continue;
+        const int rc = fetch_attributes64(e, d, s, e->d_flag2_list.p, CNT_FLAGGED2, off, nw, x64);
+        if (rc != HAF_OK) return rc;
+        for (int i : cand) {
+            const double dv = host_decision(e->model, attr_column(x64, i - off), e->kx);
+            const int8_t lab = (int8_t)(dv > 0.0 ? e->gv0 : e->gv1);
+            int cell = 0;
+            int8_t old = 0;
+            HIPCHK(e, hipMemcpy(&cell, e->d_evalcell.p + ev[(size_t)i], sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(e, hipMemcpy(&old, e->d_labels.p + cell, 1, hipMemcpyDeviceToHost));
+            if (old != lab) *changed = true;
+            HIPCHK(e, hipMemcpy(e->d_labels.p + cell, &lab, 1, hipMemcpyHostToDevice));
+            HIPCHK(e, hipMemcpy(e->d_dec_exact2.p + i, &dv, sizeof(double), hipMemcpyHostToDevice));
+            (*resolved)++;
+        }
     }
     return HAF_OK;
 }

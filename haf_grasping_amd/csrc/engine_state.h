@@ -50,6 +50,14 @@ inline const char *test_env(const char *name) { return getenv(name); }
 #else
 inline const char *test_env(const char *) { return nullptr; }
 #endif
+// A guard-band scale from the testing build's environment (HAF_GUARD0_REL, HAF_GUARD_REL, HAF_GUARD_I8_REL, HAF_GUARD2_REL).  A value
+// below 1e30 scales the band, as the diagnosis tools pass it.  1e30 AND BEYOND IS NOT A SCALE: it means "wide open", every evaluation
+// goes on to the next tier, and becomes an infinity.  A finite scale cannot do that: the band of an evaluation whose sum|coef|K is
+// exactly 0 (every kernel value underflows) is relative to that 0.  With an infinite scale its band is inf * 0 = NaN, and this
+// relies on every tier deciding by the form !(|dec| > band), which a NaN band leaves undecided (screen.hip screen_tail_vals,
+// contraction.hip, exact8.hip k_recheck_i8_combine, recheck.hip, features.hip k_small_direct): a tier written as |dec| <= band
+// would decide such an evaluation.  The product library never gets here (test_env returns nullptr).
+inline double guard_knob(const char *v) { const double g = atof(v); return g >= 1e30 ? (double)INFINITY : g; }
 
 constexpr double kPi = 3.141592653;   // server.cpp:94 -- the reference's truncated constant, NOT M_PI
 

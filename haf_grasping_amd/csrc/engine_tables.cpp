@@ -986,8 +986,8 @@ int build_tables(haf_engine *e)
             e->i8.dq_scale = -2.0 * std::ldexp(1.0, 14 - kI8Q - qs);
             e->i8.s_max = std::sqrt(s_max2) * (1.0 + 1e-12);
             e->i8.guard_scale = 1.0;
-            if (const char *g = test_env("HAF_GUARD_I8_REL")) e->i8.guard_scale = atof(g);
-            else if (test_env("HAF_GUARD2_REL")) e->i8.guard_scale = 1e30;      // a test that forces the fp64 / strict tiers means all of them
+            if (const char *g = test_env("HAF_GUARD_I8_REL")) e->i8.guard_scale = guard_knob(g);
+            else if (test_env("HAF_GUARD2_REL")) e->i8.guard_scale = INFINITY;  // a test that forces the fp64 / strict tiers means all of them
             e->i8.n_sv_pad = e->n_sv_pad;
         }
     }
@@ -995,7 +995,7 @@ int build_tables(haf_engine *e)
     e->exact.as_max1 = 1.0 + m.gamma * log2e * ss_max;
     // fp64 GEMM-form tier: worst-case error ~ 324 * 2^-53 per unit of (a_x + a_s) * sum|coef|K, i.e. < 2^-44; 2^-40 leaves 16x
     e->exact.guard2 = std::ldexp(1.0, -40);
-    if (const char *g = test_env("HAF_GUARD2_REL")) e->exact.guard2 = atof(g);
+    if (const char *g = test_env("HAF_GUARD2_REL")) e->exact.guard2 = guard_knob(g);
 
     e->gv0 = label_grid_value(m.label[0]);
     e->gv1 = label_grid_value(m.label[1]);
@@ -1022,7 +1022,7 @@ int build_tables(haf_engine *e)
     //   guard_acc: the fp32 part of the sum of coef*K (below), v_exp_f32 and the coefficient product (3 * 2^-23).
     // tests/diag_guard.py measures the actual error with the band disabled: 20-30x smaller.  HAF_GUARD_REL scales the band.
     double guard_scale = 1.0;
-    if (const char *g = test_env("HAF_GUARD_REL")) guard_scale = atof(g);
+    if (const char *g = test_env("HAF_GUARD_REL")) guard_scale = guard_knob(g);
     const double u = std::ldexp(1.0, -24);
     e->svm.guard_dot = (float)(guard_scale * (0.6932 * 324.0 * u + 8.0 * u));
     // PRECISE form of the three-pass kernel (k_svm_rbf_h<true>): every instruction of the main pass starts from zero and is off by
@@ -1052,7 +1052,7 @@ int build_tables(haf_engine *e)
     // class split, v_exp_f32 and the coefficient product; the band is ~3e-4, so nothing is gained by a two-level sum.
     // HAF_GUARD0_REL scales the whole screening band (this term and the per-evaluation one) for experiments.
     double guard0_scale = 1.0;
-    if (const char *g = test_env("HAF_GUARD0_REL")) guard0_scale = atof(g);
+    if (const char *g = test_env("HAF_GUARD0_REL")) guard0_scale = guard_knob(g);
     // (plain variant: two levels -- a term passes through at most 16 fmas of the lower level, one fold, and the folds of its
     // sweep, <= tiles/8 + 1; then the final fma and add, the 4-step lane reduction, the class split, exp2 + product, the two
     // products with the common factor.  SUMSQ variant: one level, 2 fmas per tile.)
