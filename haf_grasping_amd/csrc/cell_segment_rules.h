@@ -22,7 +22,8 @@ struct CellRules {
     int nx, ny, connectivity;
 };
 
-HAF_FRAME_HD bool cell_foreground(const float *p, const CellRules &r) { return point_usable(p) && foreground(p, r.band); }
+// (plane_rules.h's range rule, said by name: grasp_cells.h has a point_usable of its own in THIS namespace, which would win unqualified)
+HAF_FRAME_HD bool cell_foreground(const float *p, const CellRules &r) { return haf_plane_math::point_usable(p) && foreground(p, r.band); }
 
 // f = (w - w0) * inv_cell; inside when 0 <= f < n.  A usable w, |w0| <= 64 and inv_cell <= 1000 keep f finite.  (int)f truncates,
 // which is floorf for the f >= 0 that pass; -0.0f passes and gives 0; a w just below w0 gives f < 0 and is outside, never cell 0

@@ -23,6 +23,33 @@ __device__ __forceinline__ float key2f(int k)
     return __int_as_float(k >= 0 ? k : (k ^ 0x7FFFFFFF));
 }
 
+// The z window of cell (row, col) of one roll's height grid (pick_rules.h) by ONE WHOLE WAVE: lane l takes slots l and l + 64, a
+// butterfly leaves the maximum in every lane -> the ordered key; key2f of it is the record's h_locmax.  Every lane of the wave calls it
+__device__ __forceinline__ int wave_z_window(const float *__restrict__ heights_of_roll, int row, int col, int H, int W)
+{
+    int zk = haf_pick_math::z_window_start();
+    for (int q = threadIdx.x & 63; q < haf_pick_math::kZWindowSlots; q += 64) {
+        int rr, cc;
+        if (haf_pick_math::z_window_slot(q, row, col, H, W, &rr, &cc)) zk = haf_pick_math::z_window_fold(zk, heights_of_roll[(size_t)rr * W + cc]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) zk = max(zk, __shfl_xor(zk, o, 64));
+    return zk;
+}
+
+// The record of cell (row, col) of one roll by one whole wave: the cell's vote, the cell, its z window and the roll's n_evals.  ev16_roll
+// / heights_roll: that roll's grids; 0 <= row < H, 0 <= col < W.  Every lane gets the record, lane 0 is the one that stores it
+__device__ __forceinline__ RollRecordDev cell_record(const short *__restrict__ ev16_roll, const float *__restrict__ heights_roll, int n_evals,
+                                                     int row, int col, int H, int W)
+{
+    RollRecordDev q;
+    q.vote = ev16_roll[(size_t)row * W + col];
+    q.row = (short)row; q.col = (short)col;
+    q.h_locmax = key2f(wave_z_window(heights_roll, row, col, H, W));
+    q.n_evals = n_evals;
+    return q;
+}
+
 // entries of a list of `total` that fall into the window [off, off + cap)
 __device__ __forceinline__ int window_count(int total, int off, int cap) { return max(0, min(total - off, cap)); }
 

@@ -89,7 +89,8 @@ int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const 
     int rc;
     if ((rc = stage_map(e, request, rolls, f, l, &fd)) != HAF_OK) return rc;
     const int H = c.grid_h, W = c.grid_w;
-    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    float r_row, r_col;
+    haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     const short *ev = e->d_ev16.p + (size_t)request * last.R * (size_t)H * W;
     launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(e->map.dev.p + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll,
                      d_cell, s);
@@ -129,9 +130,8 @@ int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *
 
 }  // namespace
 
-// a cell's record as a candidate: haf_top_grasps' pose of it, run_length 0 (a cell is not a run).  haf_cell_pose, haf_grasp_map_labels
-// and haf_score_objects (engine_objects.cpp)
-int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out)
+// a cell's record as a candidate: haf_top_grasps' pose of it, run_length 0 (a cell is not a run)
+static int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out)
 {
     haf_roll_record rec;
     rec.vote = q.vote; rec.row = q.row; rec.col = q.col; rec.h_locmax = q.h_locmax; rec.n_evals = q.n_evals;
@@ -142,6 +142,30 @@ int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &
     cand.run_length = 0;
     cand.h_locmax = rec.h_locmax;
     *out = cand;
+    return HAF_OK;
+}
+
+int hand_over_picks(haf_engine *e, const std::string &who, const LabelOutDev *got, int32_t n, const std::function<int(int32_t)> &request_of,
+                    const std::function<int32_t(int32_t)> &id_of, int32_t width, haf_label_pick *picks, haf_grasp_candidate *poses,
+                    int32_t *order, int32_t *n_found)
+{
+    const int cells = e->cfg.grid_h * e->cfg.grid_w;
+    // every entry is checked before the first one is handed over
+    for (int32_t k = 0; k < n; k++) {
+        const LabelOutDev &o = got[k];
+        if (!o.found) continue;
+        if (o.cell < 0 || o.cell >= cells || o.n_pixels < 1) return fail(e, HAF_E_INTERNAL, who + "malformed key");
+        if (o.rec.vote != o.vote) return fail(e, HAF_E_INTERNAL, who + "the record's vote is not the key's");
+    }
+    for (int32_t k = 0; k < n; k++) {
+        const LabelOutDev &o = got[k];
+        if (!o.found) continue;
+        haf_label_pick &p = picks[k];
+        p.found = 1; p.u = o.u; p.v = o.v; p.vote = o.vote; p.roll = o.roll; p.cell = o.cell; p.n_pixels = o.n_pixels;
+        int rc;
+        if (poses && (rc = record_candidate(e, request_of(k), o.roll, o.rec, &poses[k])) != HAF_OK) return rc;
+    }
+    label_order(picks, n, id_of, width, order, n_found);
     return HAF_OK;
 }
 
@@ -203,8 +227,8 @@ int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint
     unsigned long long key;
     memcpy(&key, e->map.host, 8);
     if (key == 0ull) { *found = 0; return HAF_OK; }
-    const size_t i = (size_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull);
+    const size_t i = (size_t)haf_pick_math::pick_key_pixel(key);
+    const int roll = haf_pick_math::pick_key_roll(key);
     if (i >= n || roll < e->last.roll_first || roll >= e->last.roll_first + e->last.R) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed key");
     int32_t ci = -1;
     HIPCHK(e, hipMemcpyAsync(e->map.host + 8, dc + i, 4, hipMemcpyDeviceToHost, e->stream));
@@ -251,7 +275,8 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     HIPCHK(e, hipMemsetAsync(d + l.ltab, 0, nl * 12, s));
     const int H = c.grid_h, W = c.grid_w;
     const size_t HW = (size_t)H * W, br0 = (size_t)request * last.R;
-    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    float r_row, r_col;
+    haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     const CellGeo *d_geo = reinterpret_cast<const CellGeo *>(d + l.geo);
     const short *ev = e->d_ev16.p + br0 * HW;
     launch_map_labels(fd, d_geo, rolls, last.roll_first, ev, H, W, r_row, r_col, ld.src, (size_t)ld.row_stride, (int)eb, n_labels, min_vote, d_key, d_cnt, s);
@@ -262,23 +287,8 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     HIPCHK(e, hipMemcpyAsync(e->map.host + l.lout, d_out, nl * sizeof(LabelOutDev), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    const LabelOutDev *got = reinterpret_cast<const LabelOutDev *>(e->map.host + l.lout);
-    // every entry is checked before the first one is handed over
-    for (size_t k = 0; k < nl; k++) {
-        const LabelOutDev &o = got[k];
-        if (!o.found) continue;
-        if (o.cell < 0 || o.cell >= H * W || o.n_pixels < 1) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_labels: malformed key");
-        if (o.rec.vote != o.vote) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_labels: the record's vote is not the key's");
-    }
-    for (size_t k = 0; k < nl; k++) {
-        const LabelOutDev &o = got[k];
-        if (!o.found) continue;
-        haf_label_pick &p = picks[k];
-        p.found = 1; p.u = o.u; p.v = o.v; p.vote = o.vote; p.roll = o.roll; p.cell = o.cell; p.n_pixels = o.n_pixels;
-        if (poses && (rc = record_candidate(e, request, o.roll, o.rec, &poses[k])) != HAF_OK) return rc;
-    }
-    label_order(picks, n_labels, f->width, order, n_found);
-    return HAF_OK;
+    return hand_over_picks(e, "haf_grasp_map_labels: ", reinterpret_cast<const LabelOutDev *>(e->map.host + l.lout), n_labels,
+                           [&](int32_t) { return (int)request; }, [](int32_t k) { return k + 1; }, f->width, picks, poses, order, n_found);
 }
 
 }  // namespace

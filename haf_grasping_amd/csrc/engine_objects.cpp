@@ -135,7 +135,8 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     if (last.B != B || last.R != R || last.clouds.empty() || !last.clouds[0].staged) return fail(e, HAF_E_INTERNAL, who + "the scored batch is not the call's");
     const float *xyz = reinterpret_cast<const float *>(e->in_block.dev.p) + last.clouds[0].float_off;
     const int H = c.grid_h, W = c.grid_w;
-    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    float r_row, r_col;
+    haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     const CellGeo *d_geo = reinterpret_cast<const CellGeo *>(d + l.geo);
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d + l.keys);
     unsigned *d_cnt = reinterpret_cast<unsigned *>(d + l.cnt);
@@ -149,28 +150,9 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     HIPCHK(e, hipMemcpyAsync(e->map.host + l.out, d_out, (size_t)B * sizeof(LabelOutDev), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    const LabelOutDev *got = reinterpret_cast<const LabelOutDev *>(e->map.host + l.out);
-    // every entry is checked before the first one is handed over
-    for (int b = 0; b < B; b++) {
-        const LabelOutDev &o = got[b];
-        if (!o.found) continue;
-        if (o.cell < 0 || o.cell >= H * W || o.n_pixels < 1) return fail(e, HAF_E_INTERNAL, who + "malformed key");
-        if (o.rec.vote != o.vote) return fail(e, HAF_E_INTERNAL, who + "the record's vote is not the key's");
-    }
-    std::vector<std::pair<unsigned long long, int32_t>> keys;
-    for (int b = 0; b < B; b++) {
-        const LabelOutDev &o = got[b];
-        if (!o.found) continue;
-        haf_label_pick &p = picks[b];
-        p.found = 1; p.u = o.u; p.v = o.v; p.vote = o.vote; p.roll = o.roll; p.cell = o.cell; p.n_pixels = o.n_pixels;
-        if (poses && (rc = record_candidate(e, b, o.roll, o.rec, &poses[b])) != HAF_OK) return rc;
-        keys.emplace_back(label_pick_key(p, frame->width), (int32_t)b);
-    }
     // best first by haf_grasp_map_labels' key (pixel indices differ between objects: the order is total)
-    std::sort(keys.begin(), keys.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-    for (size_t k = 0; order && k < keys.size(); k++) order[k] = keys[k].second;
-    if (n_found) *n_found = (int32_t)keys.size();
-    return HAF_OK;
+    return hand_over_picks(e, who, reinterpret_cast<const LabelOutDev *>(e->map.host + l.out), B, [](int32_t b) { return (int)b; },
+                           [](int32_t b) { return b; }, frame->width, picks, poses, order, n_found);
 }
 
 }  // namespace haf_host

@@ -464,8 +464,7 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
     const int B = q.B, R = q.R, H = e->cfg.grid_h, W = e->cfg.grid_w;
     Dims &d = q.d;
     d.H = H; d.W = W; d.R = R; d.B = B; d.nf = e->nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->n_sv_tiles; d.sv_tile_neg = e->sv_tile_neg;
-    q.r_row = (float)((0.5 * (float)H) / 100.0);   // server.cpp:410-411
-    q.r_col = (float)((0.5 * (float)W) / 100.0);
+    haf_pick_math::cell_reach(H, W, &q.r_row, &q.r_col);
     q.evals_cap = (long)B * R * (H - 14) * (W - 14);
     // For choosing between the feature kernels only: the masked cells of a roll lie inside the rotated search rectangle of
     // half sizes sx/2 - 7, sy/2 - 7 (pnt_in_box 687-688), at most (a + 2)(b + 2) lattice points for sides a, b -- usually far

@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -87,11 +88,13 @@ bool invert(const Mat4 &m, Mat4 &inv);
 // graspmap_host.cpp: rows 0..2 of the transforms of rolls roll_first .. roll_first + roll_count - 1 (fill_roll_geo's), 64 bytes each
 void fill_cell_geo(const haf_config &cfg, const haf_grasp_input &in, int roll_first, int roll_count, haf_cell_math::CellGeo *geo);
 // graspmap_host.cpp, shared by haf_label_best_ref and haf_grasp_map_labels: every refusal of a label image that goes with a frame `width`
-// pixels wide; the not-found pick; a pick's key (k_map_best's: its maximum is the best pick); the found labels, best pick first
+// pixels wide; the not-found pick; a pick's key (pick_rules.h: its maximum is the best pick); the ids id_of(k) of the found ones among
+// picks[0..n), best pick first
 int check_label_image(const haf_label_image *l, int32_t width, int32_t n_labels, const void *picks, std::string &err);
 void label_pick_none(haf_label_pick *p);
 unsigned long long label_pick_key(const haf_label_pick &p, int32_t width);
-void label_order(const haf_label_pick *picks, int32_t n_labels, int32_t width, int32_t *order, int32_t *n_found);
+void label_order(const haf_label_pick *picks, int32_t n, const std::function<int32_t(int32_t)> &id_of, int32_t width, int32_t *order,
+                 int32_t *n_found);
 
 // Testing build: every device buffer lies between two guard zones filled with kCanaryByte -- kCanaryGuard bytes in front, and from
 // the buffer's last byte to the next multiple of kCanaryGuard plus kCanaryGuard behind -- and is registered with the source line that
@@ -654,8 +657,13 @@ int objects_mark_cells(haf_engine *e, const ObjectsCall &oc, const haf_frame &fr
                        float r_row, float r_col, hipStream_t s);
 // engine_roi.cpp: the ROI cell sets and the masks' area, on the first call that needs them
 int ensure_roi_buffers(haf_engine *e, const std::string &who);
-// engine_graspmap.cpp: a cell's record of request `request` of the last batch as a candidate (haf_cell_pose's pose of it)
-int record_candidate(haf_engine *e, int request, int roll, const RollRecordDev &q, haf_grasp_candidate *out);
+// engine_graspmap.cpp: the host tail of a label pass (haf_grasp_map_labels, haf_score_objects).  got[k], k < n: what the record kernel
+// left for entry k, which belongs to request request_of(k) of the last batch and is listed in `order` as id_of(k).  EVERY entry is
+// checked before the first one is handed over (HAF_E_INTERNAL, `who` in front of the text); then picks[k], poses[k] (null: not wanted;
+// the cell's record as a candidate, haf_cell_pose's pose of it) and the found ids, best pick first (label_order)
+int hand_over_picks(haf_engine *e, const std::string &who, const LabelOutDev *got, int32_t n, const std::function<int(int32_t)> &request_of,
+                    const std::function<int32_t(int32_t)> &id_of, int32_t width, haf_label_pick *picks, haf_grasp_candidate *poses,
+                    int32_t *order, int32_t *n_found);
 // engine_geometry.cpp
 int finalize_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, haf_grasp_output *out, std::string &error);
 int roll_pose_impl(const haf_config &c, const haf_grasp_input *in, const haf_roll_record *rec, int roll, haf_grasp_output *out,

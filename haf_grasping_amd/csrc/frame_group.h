@@ -13,11 +13,20 @@ using namespace haf_frame_math;
 constexpr int kFrameThreads = 256;
 // the frame's two pointers come out of the descriptor, where the compiler cannot see their address space: said here, so that the
 // accesses are global_load / global_store and not flat ones
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 template <class T> using global_ptr = __attribute__((address_space(1))) T *;
 template <class T> __device__ __forceinline__ global_ptr<T> as_global(const void *p) { return (global_ptr<T>)(uintptr_t)p; }
 template <int KIND> constexpr unsigned frame_group() { return KIND == HAF_FRAME_DEPTH_U16 ? 8u : 4u; }
+// a launcher's switch over the frame kind, once: call(K) with K a std::integral_constant whose ::value is the kind (a checked frame has
+// one of the three); the caller names its kernel instance as decltype(K)::value
+template <class F> inline void with_frame_kind(int kind, F &&call)
+{
+    if (kind == HAF_FRAME_DEPTH_U16) call(std::integral_constant<int, HAF_FRAME_DEPTH_U16>{});
+    else if (kind == HAF_FRAME_DEPTH_F32) call(std::integral_constant<int, HAF_FRAME_DEPTH_F32>{});
+    else call(std::integral_constant<int, HAF_FRAME_XYZ_F32>{});
+}
 
 // the points of the group that starts at flat index i0 of frame f (n pixels): p[3k..3k+2] = point i0 + k; what lies beyond the frame's
 // end is computed from zero words and never stored

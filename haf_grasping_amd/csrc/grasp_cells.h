@@ -24,7 +24,7 @@ struct CellGeo {
     float pad[4];
 };
 
-// row * W + col of point (x, y, z) under the roll whose transform is m, or -1.  r_row = (float)((0.5 * (float)H) / 100.0), r_col likewise
+// row * W + col of point (x, y, z) under the roll whose transform is m, or -1.  r_row, r_col: pick_rules.h's cell_reach(H, W)
 HAF_FRAME_HD int32_t point_cell(const float *m, float x, float y, float z, float r_row, float r_col, int H, int W)
 {
     const float px = f_add(f_add(f_add(f_mul(m[0], x), f_mul(m[1], y)), f_mul(m[2], z)), m[3]);

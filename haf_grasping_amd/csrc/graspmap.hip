@@ -16,9 +16,9 @@
 // Floor per pixel: 2-12 bytes read, 8 written, R two-byte gathers.  It reads the vote grids and nothing else of the request.
 //
 // k_map_best: the masked best pixel of haf_grasp_map_best -- a wave-level maximum of a packed 64-bit key over the pixels whose mask
-// byte is not zero and whose vote is >= min_vote, then one 64-bit atomicMax per wave.  Key, most significant first: vote + 32768
-// (16 bits), 65535 - roll (16), 2^32 - 1 - pixel index (32): its maximum is vote descending, roll ascending, then v, then u ascending.
-// k_cell_record: the record of one arbitrary cell for haf_cell_pose, with the 9 x 8 z window of k_top_grasps.
+// byte is not zero and that qualify (pick_rules.h: pick_qualifies), then one 64-bit atomicMax per wave.  The key is pick_rules.h's
+// pick_key: its maximum is vote descending, roll ascending, then v, then u ascending.
+// k_cell_record: the record of one arbitrary cell for haf_cell_pose (device_common.h: cell_record), with the 9 x 8 z window of k_top_grasps.
 // k_map_labels / k_label_records: haf_grasp_map_labels -- the masked best of every label of an instance-label image in one pass over the
 // frame (a segmented arg-max of the same key in a per-workgroup LDS table), then one wave per label for its pick and its record.
 // k_map_labels_objects / k_object_records: haf_score_objects -- the same pass ACROSS the requests of a batch that share one frame: a pixel
@@ -28,8 +28,8 @@
 namespace haf {
 
 using haf_cell_math::CellGeo;
-
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
+using haf_pick_math::pick_key;
+using haf_pick_math::pick_qualifies;
 
 // The roll loop of a group: for each of its G points that takes part (usable[k]) the best vote over the R rolls, that roll (global index)
 // and that cell; kNoCellVote, -1, -1 where no roll has a cell.  k_grasp_map and k_map_labels both call it: one arithmetic, one order
@@ -122,24 +122,15 @@ void launch_grasp_map(const FrameDev &f, const CellGeo *geo, int R, int roll_fir
     const unsigned groups = ((unsigned)f.n + G - 1) / G;
     if (!groups) return;
     const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
-    if (f.kind == HAF_FRAME_DEPTH_U16)
-        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_DEPTH_U16>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
-    else if (f.kind == HAF_FRAME_DEPTH_F32)
-        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_DEPTH_F32>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
-    else
-        hipLaunchKernelGGL(k_grasp_map<HAF_FRAME_XYZ_F32>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
+    with_frame_kind(f.kind, [&](auto K) {
+        hipLaunchKernelGGL(k_grasp_map<decltype(K)::value>, grid, block, 0, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, vote, roll, cell);
+    });
 }
 
 // ---- the masked best pixel ----
 constexpr int kBestThreads = 256;
 
-__device__ __forceinline__ unsigned long long map_key(int vote, int roll, unsigned i)
-{
-    return ((unsigned long long)(unsigned)(vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - roll) << 32) | (unsigned long long)(0xFFFFFFFFu - i);
-}
-
 // mask: n packed bytes (the host's rows without their padding), or null for every pixel.  *best starts as 0, which no pixel's key is
-// (a pixel with a roll has a vote above HAF_MAP_NO_CELL: its top 16 bits are not zero)
 __global__ __launch_bounds__(kBestThreads) void k_map_best(const short *__restrict__ vote, const short *__restrict__ roll,
                                                            const unsigned char *__restrict__ mask, unsigned n, int min_vote,
                                                            unsigned long long *__restrict__ best)
@@ -147,8 +138,8 @@ __global__ __launch_bounds__(kBestThreads) void k_map_best(const short *__restri
     unsigned long long key = 0ull;
     for (unsigned i = blockIdx.x * (unsigned)kBestThreads + threadIdx.x; i < n; i += gridDim.x * (unsigned)kBestThreads) {
         const int r = roll[i], v = vote[i];
-        if (r >= 0 && v >= min_vote && v > haf_cell_math::kNoCellVote && (!mask || mask[i] != 0)) {
-            const unsigned long long k = map_key(v, r, i);
+        if (pick_qualifies(v, r, min_vote) && (!mask || mask[i] != 0)) {
+            const unsigned long long k = pick_key(v, r, i);
             key = k > key ? k : key;
         }
     }
@@ -168,31 +159,15 @@ void launch_map_best(const short *vote, const short *roll, const unsigned char *
 }
 
 // ---- the record of one cell ----
-// rec[br] as k_top_grasps reads it (the roll's n_evals); out = {vote at the cell, row, col, max height of rows row-4..row+4, cols
-// col-4..col+3 as an ordered-key maximum above -10 (k_vote_record; server.cpp:1342-1351), n_evals}.  One wave.
+// rec[br] as k_top_grasps reads it (the roll's n_evals); out = cell_record (device_common.h) of cell (row, col) of (cloud, roll) br:
+// {vote at the cell, row, col, its z window (pick_rules.h), n_evals}.  One wave.
 __global__ __launch_bounds__(64) void k_cell_record(const short *__restrict__ ev16, const float *__restrict__ heights,
                                                     const RollRecordDev *__restrict__ rec, int br, int row, int col, int H, int W,
                                                     RollRecordDev *__restrict__ out)
 {
     const size_t HW = (size_t)H * W;
-    int zk = f2key(-10.0f);
-    for (int q = threadIdx.x; q < 72; q += 64) {
-        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
-        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-            const float h = heights[(size_t)br * HW + (size_t)rr * W + cc];
-            if (-10.0f < h) zk = max(zk, f2key(h));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) zk = max(zk, __shfl_xor(zk, o, 64));
-    if (threadIdx.x == 0) {
-        RollRecordDev q;
-        q.vote = ev16[(size_t)br * HW + (size_t)row * W + col];
-        q.row = (short)row; q.col = (short)col;
-        q.h_locmax = key2f(zk);
-        q.n_evals = rec[br].n_evals;
-        *out = q;
-    }
+    const RollRecordDev q = cell_record(ev16 + (size_t)br * HW, heights + (size_t)br * HW, rec[br].n_evals, row, col, H, W);
+    if (threadIdx.x == 0) *out = q;
 }
 
 void launch_cell_record(const short *ev16, const float *heights, const RollRecordDev *rec, int br, int row, int col, int H, int W,
@@ -204,7 +179,7 @@ void launch_cell_record(const short *ev16, const float *heights, const RollRecor
 // ---- the best pixel per instance label (haf_grasp_map_labels) ----
 // k_map_labels<KIND, LABEL_BYTES>: a lane owns the group of G pixels k_grasp_map gives it and reads the group's labels FIRST: a group
 // without a label in 1..n_labels is done before the deprojection and the R gathers (a background wave costs its label load).  A labelled
-// pixel's (vote, roll, cell) is group_best's, the map's own; a qualifying one (k_map_best's rule: a roll, vote >= min_vote) sends map_key(vote, roll, i) to
+// pixel's (vote, roll, cell) is group_best's, the map's own; a qualifying one (pick_rules.h: pick_qualifies) sends pick_key(vote, roll, i) to
 // its label's slot of the workgroup's table in dynamic LDS -- n_labels 64-bit keys, then n_labels 32-bit counts: 12 bytes per label, at
 // most 48 KB -- with one LDS atomicMax and one atomicAdd.  At the end the workgroup walks its table and sends the non-zero slots on to
 // the global table (zeroed by the caller): one 64-bit atomicMax and one atomicAdd each.  A label outside 1..n_labels indexes nothing.
@@ -223,38 +198,11 @@ __global__ __launch_bounds__(kFrameThreads) void k_map_labels(const FrameDev f, 
     const unsigned n = (unsigned)f.n;
     const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;
     if (i0 < n) {                                         // (no early return: every lane meets the barrier below)
-        const unsigned Wf = (unsigned)f.width;
-        const unsigned v0 = i0 / Wf, u0 = i0 - v0 * Wf;
-        unsigned lab[G] = {};
-        const char *a = static_cast<const char *>(labels) + (size_t)v0 * label_stride + (size_t)u0 * LB;
-        if (i0 + G <= n && u0 + G <= Wf && (reinterpret_cast<uintptr_t>(a) & (G * LB - 1u)) == 0) {
-            unsigned w[G * LB / 4];                       // the group's labels in one load of G * LB bytes: inside one row
-            if constexpr (G * LB == 16) { const v4u q = *as_global<const v4u>(a); w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w; }
-            else if constexpr (G * LB == 8) { const v2u q = *as_global<const v2u>(a); w[0] = q.x; w[1] = q.y; }
-            else w[0] = *as_global<const unsigned>(a);
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) {
-                if constexpr (LB == 2) lab[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-                else lab[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-            }
-        } else {
-            unsigned u = u0, v = v0;
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) {
-                if (i0 + k < n) {                         // (v < height: inside the label image)
-                    const char *s = static_cast<const char *>(labels) + (size_t)v * label_stride + (size_t)u * LB;
-                    if constexpr (LB == 2) lab[k] = *as_global<const uint16_t>(s);
-                    else lab[k] = *as_global<const unsigned char>(s);
-                }
-                if (++u == Wf) { u = 0; v++; }
-            }
-        }
+        unsigned lab[G];
+        group_labels<G, LB>(labels, label_stride, (unsigned)f.width, n, i0, n_labels, lab);      // (0, or 1..n_labels)
         bool any = false;
 #pragma unroll
-        for (unsigned k = 0; k < G; k++) {
-            if (lab[k] > (unsigned)n_labels) lab[k] = 0u;      // ignored like background, before it indexes anything
-            any |= lab[k] != 0u;
-        }
+        for (unsigned k = 0; k < G; k++) any |= lab[k] != 0u;
         if (any) {
             float p[G * 3];
             group_points<KIND>(f, i0, n, p);
@@ -265,8 +213,8 @@ __global__ __launch_bounds__(kFrameThreads) void k_map_labels(const FrameDev f, 
             group_best<G>(p, usable, geo, R, roll_first, ev16, H, W, r_row, r_col, best, best_roll, best_cell);
 #pragma unroll
             for (unsigned k = 0; k < G; k++)
-                if (lab[k] != 0u && best_roll[k] >= 0 && best[k] >= min_vote && best[k] > haf_cell_math::kNoCellVote) {      // (k_map_best's rule; 1 <= lab <= n_labels: inside the table)
-                    atomicMax(&s_key[lab[k] - 1u], map_key(best[k], best_roll[k], i0 + k));
+                if (lab[k] != 0u && pick_qualifies(best[k], best_roll[k], min_vote)) {      // (1 <= lab <= n_labels: inside the table)
+                    atomicMax(&s_key[lab[k] - 1u], pick_key(best[k], best_roll[k], i0 + k));
                     atomicAdd(&s_cnt[lab[k] - 1u], 1u);
                 }
         }
@@ -278,39 +226,32 @@ __global__ __launch_bounds__(kFrameThreads) void k_map_labels(const FrameDev f, 
     }
 }
 
-template <int KIND>
-static void launch_map_labels_kind(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row,
-                                   float r_col, const void *labels, size_t label_stride, int label_bytes, int n_labels, int min_vote,
-                                   unsigned long long *g_key, unsigned *g_cnt, hipStream_t s)
-{
-    constexpr unsigned G = frame_group<KIND>();
-    const unsigned groups = ((unsigned)f.n + G - 1) / G;
-    if (!groups) return;
-    const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
-    const size_t lds = (size_t)n_labels * 12;
-    if (label_bytes == 2)
-        hipLaunchKernelGGL((k_map_labels<KIND, 2>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
-                           (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
-    else
-        hipLaunchKernelGGL((k_map_labels<KIND, 1>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
-                           (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
-}
-
 void launch_map_labels(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row, float r_col,
                        const void *labels, size_t label_stride, int label_bytes, int n_labels, int min_vote, unsigned long long *g_key,
                        unsigned *g_cnt, hipStream_t s)
 {
-    if (f.kind == HAF_FRAME_DEPTH_U16)
-        launch_map_labels_kind<HAF_FRAME_DEPTH_U16>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
-    else if (f.kind == HAF_FRAME_DEPTH_F32)
-        launch_map_labels_kind<HAF_FRAME_DEPTH_F32>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
-    else
-        launch_map_labels_kind<HAF_FRAME_XYZ_F32>(f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels, label_stride, label_bytes, n_labels, min_vote, g_key, g_cnt, s);
+    with_frame_kind(f.kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        constexpr unsigned G = frame_group<KIND>();
+        const unsigned groups = ((unsigned)f.n + G - 1) / G;
+        if (!groups) return;
+        const dim3 grid((groups + kFrameThreads - 1) / kFrameThreads), block(kFrameThreads);
+        const size_t lds = (size_t)n_labels * 12;
+        if (label_bytes == 2)
+            hipLaunchKernelGGL((k_map_labels<KIND, 2>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
+                               (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
+        else
+            hipLaunchKernelGGL((k_map_labels<KIND, 1>), grid, block, lds, s, f, geo, R, roll_first, ev16, H, W, r_row, r_col, labels,
+                               (unsigned long long)label_stride, n_labels, min_vote, g_key, g_cnt);
+    });
 }
 
-// What a wave does once its pick is known: `o` without a record = the entry of a label nothing qualifies for, or of a key that decodes
-// to no cell; pick_record = k_cell_record's work at cell ci of the request's roll r (0 <= ci < H * W, 0 <= r < R; ev16 / heights / rec:
-// the request's first roll), written by lane 0.  k_label_records and k_object_records
+// What a wave does once its table holds its key: k_label_records and k_object_records.  The key names the best pixel i and the roll; the
+// pixel's point (point_of(i, u, v, p)) and its cell under that roll of the request's CellGeo (grasp_cells.h) are recomputed -- the
+// arithmetic is deterministic: this is the cell the pass over the frame saw -- and the rest is cell_record at that cell.  *out = {the
+// haf_label_pick image, the record}, written by lane 0: without a record for a key of 0 (nothing qualifies: label_out_none) and for a key
+// that decodes to nothing, which cell = -2 marks (the host answers HAF_E_INTERNAL).  n: the frame's pixels, `width` to a row; geo / ev16 /
+// heights / rec: the request's first roll of the last batch
 __device__ __forceinline__ LabelOutDev label_out_none()
 {
     LabelOutDev o;
@@ -318,34 +259,38 @@ __device__ __forceinline__ LabelOutDev label_out_none()
     o.rec.vote = 0; o.rec.row = o.rec.col = 0; o.rec.h_locmax = 0.0f; o.rec.n_evals = 0;
     return o;
 }
-__device__ __forceinline__ void pick_record(LabelOutDev o, int ci, int r, const short *__restrict__ ev16, const float *__restrict__ heights,
-                                            const RollRecordDev *__restrict__ rec, int H, int W, LabelOutDev *__restrict__ out)
+template <class PointOf>
+__device__ __forceinline__ void finish_pick(unsigned long long key, unsigned count, unsigned n, unsigned width, const PointOf &point_of,
+                                            const CellGeo *__restrict__ geo, int R, int roll_first, const short *__restrict__ ev16,
+                                            const float *__restrict__ heights, const RollRecordDev *__restrict__ rec, int H, int W, float r_row,
+                                            float r_col, LabelOutDev *__restrict__ out)
 {
-    const int row = ci / W, col = ci - row * W;
-    const size_t HW = (size_t)H * W;
-    int zk = f2key(-10.0f);
-    for (int q = threadIdx.x; q < 72; q += 64) {
-        const int rr = row + q / 8 - 4, cc = col + q % 8 - 4;
-        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-            const float h = heights[(size_t)r * HW + (size_t)rr * W + cc];
-            if (-10.0f < h) zk = max(zk, f2key(h));
-        }
+    LabelOutDev o = label_out_none();
+    if (key == 0ull) {
+        if (threadIdx.x == 0) *out = o;
+        return;
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) zk = max(zk, __shfl_xor(zk, s, 64));
-    if (threadIdx.x == 0) {
-        o.rec.vote = ev16[(size_t)r * HW + (size_t)ci];
-        o.rec.row = (short)row; o.rec.col = (short)col;
-        o.rec.h_locmax = key2f(zk);
-        o.rec.n_evals = rec[r].n_evals;
-        *out = o;
+    const unsigned i = haf_pick_math::pick_key_pixel(key);
+    const int roll = haf_pick_math::pick_key_roll(key), r = roll - roll_first;
+    int ci = -2;
+    unsigned u = 0, v = 0;
+    if (i < n && r >= 0 && r < R) {
+        v = i / width; u = i - v * width;
+        float p[3];
+        point_of(i, u, v, p);
+        if (haf_cell_math::point_usable(p)) ci = haf_cell_math::point_cell(geo[r].m, p[0], p[1], p[2], r_row, r_col, H, W);
+        if (ci < 0) ci = -2;
     }
+    o.found = 1; o.u = (int)u; o.v = (int)v; o.vote = haf_pick_math::pick_key_vote(key); o.roll = roll; o.cell = ci; o.n_pixels = (int)count;
+    if (ci >= 0) {                                        // (0 <= ci < H * W, 0 <= r < R)
+        const size_t HW = (size_t)H * W;
+        const int row = ci / W;
+        o.rec = cell_record(ev16 + (size_t)r * HW, heights + (size_t)r * HW, rec[r].n_evals, row, ci - row * W, H, W);
+    }
+    if (threadIdx.x == 0) *out = o;
 }
 
-// k_label_records: one wave per label.  The label's key names its best pixel i and roll r; the pixel's point (frame_points.h) and its
-// cell under roll r (grasp_cells.h) are recomputed -- the arithmetic is deterministic: this is the cell k_map_labels saw -- and the rest
-// is k_cell_record's work at that cell.  out[l] = {the haf_label_pick image, the record}; cell = -2 marks a key that decodes to nothing
-// (the host answers HAF_E_INTERNAL).  ev16 / heights / rec: the request's first roll of the last batch
+// k_label_records: one wave per label; the pixel's point is deprojected again from the frame (frame_points.h).  out[l]: label l + 1
 __global__ __launch_bounds__(64) void k_label_records(const FrameDev f, const CellGeo *__restrict__ geo, int R, int roll_first,
                                                       const short *__restrict__ ev16, const float *__restrict__ heights,
                                                       const RollRecordDev *__restrict__ rec, int H, int W, float r_row, float r_col,
@@ -353,35 +298,16 @@ __global__ __launch_bounds__(64) void k_label_records(const FrameDev f, const Ce
                                                       LabelOutDev *__restrict__ out)
 {
     const int l = blockIdx.x;
-    const unsigned long long key = g_key[l];
-    LabelOutDev o = label_out_none();
-    if (key == 0ull) {
-        if (threadIdx.x == 0) out[l] = o;
-        return;
-    }
-    const unsigned i = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull), r = roll - roll_first;
-    int ci = -2;
-    unsigned u = 0, v = 0;
-    if (i < (unsigned)f.n && r >= 0 && r < R) {
-        v = i / (unsigned)f.width; u = i - v * (unsigned)f.width;
+    const auto point_of = [&](unsigned, unsigned u, unsigned v, float *p) {
         const char *src = static_cast<const char *>(f.src) + (size_t)v * f.row_stride;
-        float p[3];
         if (f.kind == HAF_FRAME_DEPTH_U16) point_u16(f.m, u, v, *as_global<const uint16_t>(src + (size_t)u * 2), p);
         else if (f.kind == HAF_FRAME_DEPTH_F32) point_f32(f.m, u, v, *as_global<const float>(src + (size_t)u * 4), p);
         else {
             const global_ptr<const float> q = as_global<const float>(src + (size_t)u * f.point_stride);
             point_xyz(f.m, q[0], q[1], q[2], p);
         }
-        if (haf_cell_math::point_usable(p)) ci = haf_cell_math::point_cell(geo[r].m, p[0], p[1], p[2], r_row, r_col, H, W);
-        if (ci < 0) ci = -2;
-    }
-    o.found = 1; o.u = (int)u; o.v = (int)v; o.vote = (int)(key >> 48) - 32768; o.roll = roll; o.cell = ci; o.n_pixels = (int)g_cnt[l];
-    if (ci < 0) {
-        if (threadIdx.x == 0) out[l] = o;
-        return;
-    }
-    pick_record(o, ci, r, ev16, heights, rec, H, W, out + l);
+    };
+    finish_pick(g_key[l], g_cnt[l], (unsigned)f.n, (unsigned)f.width, point_of, geo, R, roll_first, ev16, heights, rec, H, W, r_row, r_col, out + l);
 }
 
 void launch_label_records(const FrameDev &f, const CellGeo *geo, int R, int roll_first, const short *ev16, const float *heights,
@@ -399,7 +325,7 @@ void launch_label_records(const FrameDev &f, const CellGeo *geo, int R, int roll
 // pixel index from the shared cloud -- the words k_frame_points wrote, whatever the frame's kind and residence: nothing is deprojected
 // again.  The wave then takes its requests one after the other (next_request): CellGeo and the vote grids of the request in hand are
 // wave-uniform, and (vote, roll, cell) of its pixels are group_best's -- k_map_labels' arithmetic and order.  A qualifying pixel
-// (k_map_best's rule) sends map_key to its REQUEST's slot of the workgroup's LDS table: B keys, then B counts, 12 bytes per request
+// (pick_qualifies) sends its pick_key to its REQUEST's slot of the workgroup's LDS table: B keys, then B counts, 12 bytes per request
 // whatever n_labels is; the non-zero slots go on to the global table as in k_map_labels.  Bounds: 0 <= request < B by the host's table.
 template <int LB>
 __global__ __launch_bounds__(kFrameThreads) void k_map_labels_objects(const float *__restrict__ xyz, unsigned width, unsigned n,
@@ -431,8 +357,8 @@ __global__ __launch_bounds__(kFrameThreads) void k_map_labels_objects(const floa
             group_best<G>(p, usable, geo + (size_t)b * R, R, roll_first, ev16 + (size_t)b * R * HW, H, W, r_row, r_col, best, best_roll, best_cell);
 #pragma unroll
             for (unsigned k = 0; k < G; k++)
-                if (usable[k] && best_roll[k] >= 0 && best[k] >= min_vote && best[k] > haf_cell_math::kNoCellVote) {      // (k_map_best's rule; 0 <= b < B: inside the table)
-                    atomicMax(&s_okey[b], map_key(best[k], best_roll[k], i0 + k));
+                if (usable[k] && pick_qualifies(best[k], best_roll[k], min_vote)) {      // (0 <= b < B: inside the table)
+                    atomicMax(&s_okey[b], pick_key(best[k], best_roll[k], i0 + k));
                     atomicAdd(&s_ocnt[b], 1u);
                 }
         }
@@ -460,9 +386,8 @@ void launch_map_labels_objects(const float *xyz, int width, int n, const CellGeo
                            r_col, labels, (unsigned long long)label_stride, n_labels, req_of_label, min_vote, g_key, g_cnt);
 }
 
-// k_object_records: one wave per REQUEST.  Its key names the best pixel i of its object and the roll; the pixel's point is read from the
-// shared cloud, its cell under that roll of the request's own CellGeo recomputed (deterministic: the cell k_map_labels_objects saw), and
-// the record is built from the request's own ev16, heights and rec (pick_record)
+// k_object_records: one wave per REQUEST; the pixel's point is read from the shared cloud, and finish_pick gets the request's own
+// CellGeo, ev16, heights and rec.  out[b]: request b
 __global__ __launch_bounds__(64) void k_object_records(const float *__restrict__ xyz, unsigned width, unsigned n, const CellGeo *__restrict__ geo,
                                                        int R, int roll_first, const short *__restrict__ ev16, const float *__restrict__ heights,
                                                        const RollRecordDev *__restrict__ rec, int H, int W, float r_row, float r_col,
@@ -470,30 +395,13 @@ __global__ __launch_bounds__(64) void k_object_records(const float *__restrict__
                                                        LabelOutDev *__restrict__ out)
 {
     const int b = blockIdx.x;
-    const unsigned long long key = g_key[b];
-    LabelOutDev o = label_out_none();
-    if (key == 0ull) {
-        if (threadIdx.x == 0) out[b] = o;
-        return;
-    }
-    const unsigned i = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-    const int roll = 65535 - (int)((key >> 32) & 0xFFFFull), r = roll - roll_first;
-    int ci = -2;
-    unsigned u = 0, v = 0;
-    if (i < n && r >= 0 && r < R) {
-        v = i / width; u = i - v * width;
+    const auto point_of = [&](unsigned i, unsigned, unsigned, float *p) {
         const global_ptr<const float> q = as_global<const float>(xyz + (size_t)i * 3);
-        const float p[3] = {q[0], q[1], q[2]};
-        if (haf_cell_math::point_usable(p)) ci = haf_cell_math::point_cell(geo[(size_t)b * R + r].m, p[0], p[1], p[2], r_row, r_col, H, W);
-        if (ci < 0) ci = -2;
-    }
-    o.found = 1; o.u = (int)u; o.v = (int)v; o.vote = (int)(key >> 48) - 32768; o.roll = roll; o.cell = ci; o.n_pixels = (int)g_cnt[b];
-    if (ci < 0) {
-        if (threadIdx.x == 0) out[b] = o;
-        return;
-    }
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+    };
     const size_t HW = (size_t)H * W, br0 = (size_t)b * R;
-    pick_record(o, ci, r, ev16 + br0 * HW, heights + br0 * HW, rec + br0, H, W, out + b);
+    finish_pick(g_key[b], g_cnt[b], n, width, point_of, geo + br0, R, roll_first, ev16 + br0 * HW, heights + br0 * HW, rec + br0, H, W, r_row, r_col,
+                out + b);
 }
 
 void launch_object_records(const float *xyz, int width, int n, const CellGeo *geo, int B, int R, int roll_first, const short *ev16,

@@ -9,8 +9,6 @@ namespace haf_host {
 
 using haf_cell_math::CellGeo;
 
-static float half_extent(int cells) { return (float)((0.5 * (float)cells) / 100.0); }      // server.cpp:410-411 (engine_request.cpp: r_row)
-
 void fill_cell_geo(const haf_config &cfg, const haf_grasp_input &in, int roll_first, int roll_count, CellGeo *geo)
 {
     const NormalisedInput n = normalise(in);
@@ -35,7 +33,8 @@ static int point_cells_impl(const haf_config *cfg, const haf_grasp_input *in, in
     if (n > (size_t)INT32_MAX) return HAF_E_CAPACITY;
     CellGeo g;
     fill_cell_geo(*cfg, *in, roll, 1, &g);
-    const float r_row = half_extent(cfg->grid_h), r_col = half_extent(cfg->grid_w);
+    float r_row, r_col;
+    haf_pick_math::cell_reach(cfg->grid_h, cfg->grid_w, &r_row, &r_col);
     for (size_t i = 0; i < n; i++) {
         const float *p = xyz + i * stride_floats;
         cell[i] = haf_cell_math::point_cell(g.m, p[0], p[1], p[2], r_row, r_col, cfg->grid_h, cfg->grid_w);
@@ -52,7 +51,8 @@ static int map_pixels(const haf_config *cfg, const haf_grasp_input *in, int32_t 
     fill_cell_geo(*cfg, *in, roll_first, roll_count, geo.data());
     const int H = cfg->grid_h, W = cfg->grid_w;
     const size_t HW = (size_t)H * W;
-    const float r_row = half_extent(H), r_col = half_extent(W);
+    float r_row, r_col;
+    haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     const haf_frame_math::FrameMath m = frame_math(*f);
     const char *base = static_cast<const char *>(f->data);
     for (uint32_t v = 0; v < (uint32_t)f->height; v++) {
@@ -131,15 +131,15 @@ void label_pick_none(haf_label_pick *p)
 
 unsigned long long label_pick_key(const haf_label_pick &p, int32_t width)
 {
-    const unsigned i = (unsigned)((size_t)p.v * (size_t)width + (size_t)p.u);
-    return ((unsigned long long)(unsigned)(p.vote + 32768) << 48) | ((unsigned long long)(unsigned)(65535 - p.roll) << 32) | (unsigned long long)(0xFFFFFFFFu - i);
+    return haf_pick_math::pick_key(p.vote, p.roll, (unsigned)((size_t)p.v * (size_t)width + (size_t)p.u));
 }
 
-void label_order(const haf_label_pick *picks, int32_t n_labels, int32_t width, int32_t *order, int32_t *n_found)
+void label_order(const haf_label_pick *picks, int32_t n, const std::function<int32_t(int32_t)> &id_of, int32_t width, int32_t *order,
+                 int32_t *n_found)
 {
     std::vector<std::pair<unsigned long long, int32_t>> keys;
-    for (int32_t l = 0; l < n_labels; l++)
-        if (picks[l].found) keys.emplace_back(label_pick_key(picks[l], width), l + 1);
+    for (int32_t k = 0; k < n; k++)
+        if (picks[k].found) keys.emplace_back(label_pick_key(picks[k], width), id_of(k));
     std::sort(keys.begin(), keys.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
     if (order)
         for (size_t k = 0; k < keys.size(); k++) order[k] = keys[k].second;
@@ -165,7 +165,7 @@ static int label_best_ref_impl(const haf_config *cfg, const haf_grasp_input *in,
         unsigned lab;
         if (labels->elem_bytes == 1) lab = *reinterpret_cast<const uint8_t *>(at);
         else { uint16_t w; memcpy(&w, at, 2); lab = w; }
-        if (lab < 1u || lab > (unsigned)n_labels || br < 0 || (int)bv < min_vote || (int)bv <= HAF_MAP_NO_CELL) return;
+        if (lab < 1u || lab > (unsigned)n_labels || !haf_pick_math::pick_qualifies(bv, br, min_vote)) return;
         haf_label_pick cand;
         cand.found = 1; cand.u = (int32_t)u; cand.v = (int32_t)v; cand.vote = bv; cand.roll = br; cand.cell = bc;
         haf_label_pick &p = picks[lab - 1];
@@ -175,7 +175,7 @@ static int label_best_ref_impl(const haf_config *cfg, const haf_grasp_input *in,
         else p.n_pixels = cand.n_pixels;
     });
     if (rc != HAF_OK) return rc;
-    label_order(picks, n_labels, f->width, order, n_found);
+    label_order(picks, n_labels, [](int32_t l) { return l + 1; }, f->width, order, n_found);
     return HAF_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "frame_points.h"
 #include "frames.h"           // FrameDev
 #include "grasp_cells.h"
+#include "pick_rules.h"
 
 namespace haf {
 
@@ -510,8 +511,8 @@ void launch_top_grasps(const short *ev16, const float *heights, const RollRecord
 // vote grids (ev16 = its first grid) -> packed width * height images, any of them null; f.dst and f.count are not read
 void launch_grasp_map(const FrameDev &f, const haf_cell_math::CellGeo *geo, int R, int roll_first, const short *ev16, int H, int W, float r_row,
                       float r_col, short *vote, short *roll, int *cell, hipStream_t s);
-// *best (zeroed by the caller) = the largest key of the n pixels whose mask byte (null: all) is not zero and whose vote is >= min_vote:
-// (vote + 32768) << 48 | (65535 - roll) << 32 | (2^32 - 1 - pixel index); still 0 when none qualifies
+// *best (zeroed by the caller) = the largest key (pick_rules.h: pick_key) of the n pixels whose mask byte (null: all) is not zero and
+// that qualify (pick_qualifies); still 0 when none does
 void launch_map_best(const short *vote, const short *roll, const unsigned char *mask, unsigned n, int min_vote, unsigned long long *best,
                      hipStream_t s);
 // the record of cell (row, col) of (cloud, roll) br of the last batch: its vote, the 9x8 z window of k_top_grasps, the roll's n_evals

@@ -14,17 +14,16 @@
 // extent and for the height key (label_shape.h: a minimum travels as the maximum of its complement, so that zero is the empty value).
 // Compact objects cost a wave a few passes; an image whose every pixel differs costs a pass per pixel, 64 G at most, each without the
 // shuffles: the loop is bounded by the pixels a wave owns.
-// Bounds: a label is loaded only for a pixel i < n, at its own (row, column) or by one aligned load inside a row; a pixel's words by
+// Bounds: a label is loaded only for a pixel i < n, at its own (row, column) or by one aligned load inside a row (label_group.h); a pixel's words by
 // group_points, which k_grasp_map bounds the same way; a value above n_labels is cleared before it names a row, so a row index is in
 // [0, n_labels).
-#include "frame_group.h"
+#include "label_group.h"
 #include "kernels.h"
 
 namespace haf {
 
 using namespace haf_shape_math;
 
-typedef unsigned v2u_shape __attribute__((ext_vector_type(2)));
 typedef ShapeAcc<int> WaveAcc;
 
 __device__ __forceinline__ int wave_sum(int x)
@@ -86,39 +85,11 @@ __global__ __launch_bounds__(kFrameThreads) void k_label_shape(const ShapeDev d)
     const unsigned n = (unsigned)d.f.n, Wf = (unsigned)d.f.width;
     const unsigned lane = threadIdx.x & 63u;
     const unsigned i0 = (blockIdx.x * (unsigned)kFrameThreads + threadIdx.x) * G;
-    unsigned lab[G] = {};
-    if (i0 < n) {
-        const unsigned v0 = i0 / Wf, u0 = i0 - v0 * Wf;
-        const char *a = static_cast<const char *>(d.labels) + (size_t)v0 * d.label_stride + (size_t)u0 * LB;
-        if (i0 + G <= n && u0 + G <= Wf && (reinterpret_cast<uintptr_t>(a) & (G * LB - 1u)) == 0) {
-            unsigned w[G * LB / 4];                       // the group's labels in one load of G * LB bytes: inside one row
-            if constexpr (G * LB == 16) { const v4u q = *as_global<const v4u>(a); w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w; }
-            else if constexpr (G * LB == 8) { const v2u_shape q = *as_global<const v2u_shape>(a); w[0] = q.x; w[1] = q.y; }
-            else w[0] = *as_global<const unsigned>(a);
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) {
-                if constexpr (LB == 2) lab[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-                else lab[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-            }
-        } else {
-            unsigned u = u0, v = v0;
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) {
-                if (i0 + k < n) {                         // (v < height: inside the label image)
-                    const char *s = static_cast<const char *>(d.labels) + (size_t)v * d.label_stride + (size_t)u * LB;
-                    if constexpr (LB == 2) lab[k] = *as_global<const uint16_t>(s);
-                    else lab[k] = *as_global<const unsigned char>(s);
-                }
-                if (++u == Wf) { u = 0; v++; }
-            }
-        }
-    }
+    unsigned lab[G];                                      // (0, or 1..n_labels: a label above n_labels is ignored like background)
+    group_labels<G, LB>(d.labels, d.label_stride, Wf, n, i0, d.n_labels, lab);
     unsigned pending = 0;                                 // bit k: pixel i0 + k carries a label and is not folded yet
 #pragma unroll
-    for (unsigned k = 0; k < G; k++) {
-        if (lab[k] > (unsigned)d.n_labels) lab[k] = 0u;   // ignored like background, before it names a row
-        pending |= lab[k] != 0u ? 1u << k : 0u;
-    }
+    for (unsigned k = 0; k < G; k++) pending |= lab[k] != 0u ? 1u << k : 0u;
     unsigned long long todo = __ballot(pending != 0u);
     if (!todo) return;                                    // (wave-uniform; the kernel has no barrier)
     float p[G * 3] = {};

@@ -4,7 +4,7 @@
 // CellGeo, vote grids, cell sets), so a wave handles them one after the other: the request in hand is wave-uniform and its transforms
 // stay scalar loads, as in the single-request kernels.  A wave of background pixels takes no turn, most labelled waves one or two.
 #pragma once
-#include "frame_group.h"
+#include "label_group.h"
 #include "grasp_cells.h"
 
 namespace haf {
@@ -12,47 +12,18 @@ namespace haf {
 constexpr unsigned kObjGroup = 4;
 
 // req[k] = the request of pixel i0 + k: req_of_label[label - 1] for a label in 1..n_labels, -1 for the background, a label above
-// n_labels and a pixel past the frame's end.  The labels first, in one load of 4 * LB bytes where the group lies inside one row at an
-// aligned address, element by element elsewhere; a group without a label reads nothing of the table.  Returns the bits of the k with
-// req[k] >= 0.  Bounds: a label is read for a pixel inside the frame only, the table at an index below n_labels only
+// n_labels and a pixel past the frame's end.  The labels first (label_group.h: group_labels); a group without a label reads nothing of
+// the table.  Returns the bits of the k with req[k] >= 0.  Bounds: the table is read at an index below n_labels only
 template <int LB>
 __device__ __forceinline__ unsigned group_requests(const void *__restrict__ labels, unsigned long long label_stride, unsigned width, unsigned n,
                                                    unsigned i0, const int *__restrict__ req_of_label, int n_labels, int (&req)[kObjGroup])
 {
-    constexpr unsigned G = kObjGroup;
-#pragma unroll
-    for (unsigned k = 0; k < G; k++) req[k] = -1;
-    if (i0 >= n) return 0u;
-    const unsigned v0 = i0 / width, u0 = i0 - v0 * width;
-    unsigned lab[G] = {};
-    const char *a = static_cast<const char *>(labels) + (size_t)v0 * label_stride + (size_t)u0 * LB;
-    if (i0 + G <= n && u0 + G <= width && (reinterpret_cast<uintptr_t>(a) & (G * LB - 1u)) == 0) {
-        if constexpr (LB == 2) {
-            const unsigned long long w = *as_global<const unsigned long long>(a);
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) lab[k] = (unsigned)(w >> (16 * k)) & 0xFFFFu;
-        } else {
-            const unsigned w = *as_global<const unsigned>(a);
-#pragma unroll
-            for (unsigned k = 0; k < G; k++) lab[k] = (w >> (8 * k)) & 0xFFu;
-        }
-    } else {
-        unsigned u = u0, v = v0;
-#pragma unroll
-        for (unsigned k = 0; k < G; k++) {
-            if (i0 + k < n) {                             // (v < height: inside the label image)
-                const char *s = static_cast<const char *>(labels) + (size_t)v * label_stride + (size_t)u * LB;
-                if constexpr (LB == 2) lab[k] = *as_global<const uint16_t>(s);
-                else lab[k] = *as_global<const unsigned char>(s);
-            }
-            if (++u == width) { u = 0; v++; }
-        }
-    }
+    unsigned lab[kObjGroup];
+    group_labels<kObjGroup, LB>(labels, label_stride, width, n, i0, n_labels, lab);
     unsigned sel = 0;
 #pragma unroll
-    for (unsigned k = 0; k < G; k++) {
-        if (lab[k] == 0u || lab[k] > (unsigned)n_labels) continue;      // ignored like background, before it indexes anything
-        req[k] = req_of_label[lab[k] - 1u];
+    for (unsigned k = 0; k < kObjGroup; k++) {
+        req[k] = lab[k] != 0u ? req_of_label[lab[k] - 1u] : -1;      // (1 <= lab <= n_labels)
         if (req[k] >= 0) sel |= 1u << k;
     }
     return sel;

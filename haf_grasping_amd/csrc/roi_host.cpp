@@ -42,7 +42,8 @@ static int roi_cells_impl(const haf_config *cfg, const haf_grasp_input *in, int3
     if (rp != HAF_OK) return rp;
     haf_cell_math::CellGeo g;
     fill_cell_geo(*cfg, *in, roll, 1, &g);
-    const float r_row = (float)((0.5 * (float)H) / 100.0), r_col = (float)((0.5 * (float)W) / 100.0);      // server.cpp:410-411
+    float r_row, r_col;
+    haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     std::vector<uint8_t> S(HW, 0);
     for (size_t v = 0; v < (size_t)f->height; v++)
         for (size_t u = 0; u < (size_t)f->width; u++) {

@@ -217,16 +217,13 @@ __global__ __launch_bounds__(kTopThreads) void k_top_grasps(const short *__restr
             __syncthreads();
         }
         const int nk = s_nk;
-        // z window rows row-4..row+4, cols col-4..col+3 of every kept entry (k_vote_record; 1342-1351), as an ordered-key max
+        // the z window of every kept entry (pick_rules.h; k_vote_record's, 1342-1351): a lane owns an entry and walks its slots itself
         for (int j = t; j < nk; j += kTopThreads) {
             const int r = out[j].row, c = out[j].col;
-            int zk = f2key(-10.0f);
-            for (int q = 0; q < 72; q++) {
-                const int rr = r + q / 8 - 4, cc = c + q % 8 - 4;
-                if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-                    const float h = heights[(size_t)br * HW + (size_t)rr * W + cc];
-                    if (-10.0f < h) zk = max(zk, f2key(h));
-                }
+            int zk = haf_pick_math::z_window_start();
+            for (int q = 0; q < haf_pick_math::kZWindowSlots; q++) {
+                int rr, cc;
+                if (haf_pick_math::z_window_slot(q, r, c, H, W, &rr, &cc)) zk = haf_pick_math::z_window_fold(zk, heights[(size_t)br * HW + (size_t)rr * W + cc]);
             }
             out[j].h_locmax = key2f(zk);
         }

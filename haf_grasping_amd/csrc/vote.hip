@@ -192,17 +192,7 @@ __global__ __launch_bounds__(64) void k_vote_record(const float *__restrict__ he
     const int top = (int)(keys3[br] >> 32) - 32768;
     const unsigned long long best = keys3[BR + br];
     const int brow = 0xFFFF - (int)((best >> 20) & 0xFFFFF), bcol = (int)(best & 0xFFFFF);
-    // z estimate window rows brow-4..brow+4, cols bcol-4..bcol+3 (1342-1351), as an ordered-key max
-    int zk = f2key(-10.0f);
-    for (int t = lane; t < 72; t += 64) {
-        const int rr = brow + (t / 8) - 4, cc = bcol + (t % 8) - 4;
-        if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-            const float h = heights[(size_t)br * HW + rr * W + cc];
-            if (-10.0f < h) zk = max(zk, f2key(h));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) zk = max(zk, __shfl_xor(zk, o, 64));
+    const int zk = wave_z_window(heights + (size_t)br * HW, brow, bcol, H, W);      // the z window of a11 (1342-1351)
     if (lane == 0) {
         RollRecordDev r;
         r.vote = top; r.row = (short)brow; r.col = (short)bcol;
@@ -281,18 +271,8 @@ __global__ __launch_bounds__(256) void k_vote_small(const int8_t *__restrict__ l
     if (t == 0) { s_row = 0xFFFF - (int)((red[0] >> 20) & 0xFFFFF); s_col = (int)(red[0] & 0xFFFFF); }
     __syncthreads();
     const int brow = s_row, bcol = s_col;
-    // z estimate window rows brow-4..brow+4, cols bcol-4..bcol+3 (1342-1351), as an ordered-key max
-    if (t < 64) {
-        int zk = f2key(-10.0f);
-        for (int q = t; q < 72; q += 64) {
-            const int rr = brow + (q / 8) - 4, cc = bcol + (q % 8) - 4;
-            if (rr >= 0 && cc >= 0 && rr < H && cc < W) {
-                const float h = heights[(size_t)br * HW + rr * W + cc];
-                if (-10.0f < h) zk = max(zk, f2key(h));
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) zk = max(zk, __shfl_xor(zk, o, 64));
+    if (t < 64) {                                         // (wave 0 as a whole) the z window of a11 (1342-1351)
+        const int zk = wave_z_window(heights + (size_t)br * HW, brow, bcol, H, W);
         if (t == 0) {
             RollRecordDev r;
             r.vote = top; r.row = (short)brow; r.col = (short)bcol;

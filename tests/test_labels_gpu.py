@@ -15,6 +15,7 @@ import frame_cases as fc
 import grasp_map_cases as gm
 import label_cases as lc
 import pcdio
+import vote_cases as vc
 from haf_grasping_amd import capi
 from test_frames_gpu import C3_CFG, C3_IN, K525, TABLE1, _files, device_copy, make_engine, render_depth
 from test_grasp_map_cpu import scene_frames
@@ -199,26 +200,44 @@ def test_small_frames_partial_groups_and_one_pixel(c3, table1):
 
 def test_synthetic_grids_negative_votes_and_the_order_by_pixel(c3):
     """Three rolls, grids installed through the re-vote hook, a frame with one point in the middle of every cell.  (a) votes that are
-    nowhere positive: the label over the negative pixels is found with min_vote = -100 and not with 1; (b) a uniform grid: labels whose
-    picks share vote and roll are ranked by v, then u."""
+    nowhere positive: the label over the negative pixels is found with min_vote = -100 and not with 1; a label of ONE pixel whose cell
+    is a corner of the grid: its pose's h_locmax is the clipped 9 x 8 window of the re-voted heights by the independent mirror
+    vote_cases.z_key, bit for bit (the pose and haf_cell_pose share their device code: their equality says nothing about the window);
+    (b) a uniform grid: labels whose picks share vote and roll are ranked by v, then u."""
     eng, inp = c3["eng"], c3["inp"]
     gi = capi.default_input(grasp_area_length_x=54, grasp_area_length_y=54)
     eng.score_rolls([TINY], [gi], 0, 3)
     frame, img = cell_centre_frame(56)
     rows = np.zeros((56, 56), np.int8)
     rows[::3] = -1                                           # every third row -1: no vote is positive, the rows' own votes are negative
-    eng.revote(labels=np.stack([rows, np.roll(rows, 1, axis=0), rows.T.copy()]).reshape(1, 3, 56, 56))
+    rng = np.random.RandomState(7)                           # heights around -10 and 0, another grid per roll, zeros of both signs
+    heights = rng.uniform(-11.0, 1.0, size=(1, 3, 56, 56)).astype(np.float32)
+    heights[rng.uniform(size=heights.shape) < 0.03] = 0.0
+    heights[rng.uniform(size=heights.shape) < 0.03] = -0.0
+    eng.revote(labels=np.stack([rows, np.roll(rows, 1, axis=0), rows.T.copy()]).reshape(1, 3, 56, 56), heights=heights)
     maps = eng.grasp_map(0, frame)
-    vote, roll = maps["vote"], maps["roll"]
+    vote, roll, cell = maps["vote"], maps["roll"], maps["cell"]
     neg = (vote < 0) & (roll >= 0)
     assert vote[roll >= 0].max() <= 0 and neg.sum() > 50 and vote[neg].min() >= -100
     labels = np.where(neg, 1, 2).astype(np.uint8)
     labels[roll < 0] = 0
+    corners = (0, 55, 55 * 56, 56 * 56 - 1)
+    at_corner = np.argwhere((roll >= 0) & np.isin(cell, corners))
+    assert len(at_corner) >= 1                               # (a corner cell scores 0, the border's vote: found with min_vote = -100 only)
+    cv, cu = (int(x) for x in at_corner[0])
+    labels[cv, cu] = 3
     for mv in (1, -100):
-        r = check_labels(eng, 0, gi, 0, 3, frame, img, labels, 2, mv, "negative votes, min_vote %d" % mv, maps=maps)
+        r = check_labels(eng, 0, gi, 0, 3, frame, img, labels, 3, mv, "negative votes, min_vote %d" % mv, maps=maps)
         check_poses(eng, 0, r)
         assert (1 in r["order"]) == bool(r["picks"]["found"][0]) == (mv == -100) and (mv == -100 or r["order"] == []), (mv, r["order"])
         assert r["order"][-1:] == ([1] if mv == -100 else [])                 # behind the label of the zero votes, when that one has pixels
+        if mv == -100:
+            p = r["picks"][2]
+            assert p["found"] and (int(p["u"]), int(p["v"]), int(p["cell"])) == (cu, cv, int(cell[cv, cu])) and int(p["roll"]) == int(roll[cv, cu])
+            want = vc.z_key(heights[0, int(p["roll"])], int(p["cell"]) // 56, int(p["cell"]) % 56)
+            got = np.float32(r["poses"][2]["h_locmax"])
+            print("corner cell %d of roll %d: h_locmax %r, the mirror %r" % (p["cell"], p["roll"], got, want))
+            assert want > -10.0 and got.view(np.uint32) == np.float32(want).view(np.uint32)
     assert eng.best_per_label(0, frame, labels, min_vote=-100)["picks"]["vote"][0] < 0
     # (b)
     eng.revote(labels=np.ones((1, 3, 56, 56), np.int8))
