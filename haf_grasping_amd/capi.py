@@ -614,6 +614,20 @@ def _label_out(frame, dtype, out):
     return out, out.ctypes.data, dt.itemsize, out.strides[0] if frame.height > 1 else frame.width * dt.itemsize
 
 
+def _label_target(frame, dtype, device_out, host_out, got):
+    """where a label-writing engine call for `frame` writes, from the arguments of Engine.segment: -> (labels pointer, element size, row
+    stride, out_on_device, what the method returns as its labels): device_out=True the engine's own image, device_out a pointer or
+    (pointer, row_stride_bytes) the caller's -- both returned as `got`, the LabelImage the call fills -- else the host array of _label_out"""
+    if device_out is True:
+        return None, np.dtype(dtype).itemsize, 0, 1, got
+    if device_out is not False and device_out is not None:
+        ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
+        elem = np.dtype(dtype).itemsize
+        return int(ptr), elem, stride or frame.width * elem, 1, got
+    img, ptr, elem, stride = _label_out(frame, dtype, host_out)
+    return ptr, elem, stride, 0, img
+
+
 def segment_ref(frame, params=None, dtype=np.uint8, out=None):
     """haf_segment_ref: the host definition of record of the tabletop segmentation of a host Frame -> (labels: uint8 / uint16 [height,
     width], infos: SEGMENT_INFO_DTYPE [n_labels], stats: [pixels, foreground, components, components that pass the size rule]).
@@ -1281,19 +1295,9 @@ class Engine:
         p = params if params is not None else segment_params()
         info = np.zeros(max(1, p.max_labels), SEGMENT_INFO_DTYPE)
         n, stats, got = C.c_int32(-1), (C.c_int64 * 4)(), LabelImage()
-        elem = np.dtype(dtype).itemsize
-        if device_out is True:
-            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), None, elem, 0, 1, C.byref(got), info.ctypes.data, C.byref(n), stats)
-            img = got
-        elif device_out is not False and device_out is not None:
-            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
-            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), int(ptr), elem, stride or frame.width * elem, 1, C.byref(got),
-                                           info.ctypes.data, C.byref(n), stats)
-            img = got
-        else:
-            img, ptr, elem, stride = _label_out(frame, dtype, host_out)
-            rc = self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), info.ctypes.data, C.byref(n), stats)
-        self._check(rc)
+        ptr, elem, stride, on_device, img = _label_target(frame, dtype, device_out, host_out, got)
+        self._check(self._L.haf_segment_frame(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, on_device, C.byref(got), info.ctypes.data,
+                                              C.byref(n), stats))
         return img, info[:n.value].copy(), [int(x) for x in stats]
 
     def segment_cells(self, frame, params=None, dtype=np.uint8, device_out=False, host_out=None, cell_labels=False):
@@ -1306,20 +1310,9 @@ class Engine:
         grid = np.zeros((max(0, p.ny), max(0, p.nx)), np.uint16) if cell_labels else None
         gptr = grid.ctypes.data if cell_labels else None
         n, stats, got = C.c_int32(-1), (C.c_int64 * 6)(), LabelImage()
-        elem = np.dtype(dtype).itemsize
-        if device_out is True:
-            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), None, elem, 0, 1, C.byref(got), gptr, info.ctypes.data, C.byref(n), stats)
-            img = got
-        elif device_out is not False and device_out is not None:
-            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
-            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), int(ptr), elem, stride or frame.width * elem, 1, C.byref(got),
-                                           gptr, info.ctypes.data, C.byref(n), stats)
-            img = got
-        else:
-            img, ptr, elem, stride = _label_out(frame, dtype, host_out)
-            rc = self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, 0, C.byref(got), gptr, info.ctypes.data,
-                                           C.byref(n), stats)
-        self._check(rc)
+        ptr, elem, stride, on_device, img = _label_target(frame, dtype, device_out, host_out, got)
+        self._check(self._L.haf_segment_cells(self._h, C.byref(frame), C.byref(p), ptr, elem, stride, on_device, C.byref(got), gptr,
+                                              info.ctypes.data, C.byref(n), stats))
         res = (img, info[:n.value].copy(), [int(x) for x in stats])
         return res + (grid,) if cell_labels else res
 
@@ -1355,19 +1348,9 @@ class Engine:
         z = np.zeros((max(0, cam.height), max(0, cam.width)), np.int32) if zbuffer else None
         zptr = z.ctypes.data if zbuffer else None
         stats, got = (C.c_int64 * 5)(), LabelImage()
-        elem = np.dtype(dtype).itemsize
-        head = (self._h, C.byref(depth), C.byref(cam), C.byref(img), n_labels, C.byref(p))
-        if device_out is True:
-            rc = self._L.haf_transfer_labels(*head, None, elem, 0, 1, C.byref(got), zptr, stats)
-            lab = got
-        elif device_out is not False and device_out is not None:
-            ptr, stride = device_out if isinstance(device_out, tuple) else (device_out, 0)
-            rc = self._L.haf_transfer_labels(*head, int(ptr), elem, stride or depth.width * elem, 1, C.byref(got), zptr, stats)
-            lab = got
-        else:
-            lab, ptr, elem, stride = _label_out(depth, dtype, host_out)
-            rc = self._L.haf_transfer_labels(*head, ptr, elem, stride, 0, C.byref(got), zptr, stats)
-        self._check(rc)
+        ptr, elem, stride, on_device, lab = _label_target(depth, dtype, device_out, host_out, got)
+        self._check(self._L.haf_transfer_labels(self._h, C.byref(depth), C.byref(cam), C.byref(img), n_labels, C.byref(p), ptr, elem, stride,
+                                                on_device, C.byref(got), zptr, stats))
         res = (lab, [int(x) for x in stats])
         return res + (z,) if zbuffer else res
 

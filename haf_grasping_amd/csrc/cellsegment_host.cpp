@@ -2,7 +2,7 @@
 // checks of the frame, the parameters and the label image (both entry points apply them), and haf_segment_cells_ref, the definition of
 // record of cell_segment_rules.h's rules and of the integer rules behind them (counts, components, anchors, numbering); the device
 // kernels of cellsegment.hip are tested against it word for word.  Built with -ffp-contract=off like every unit (build.py: FLAGS).
-#include "frames.h"
+#include "frame_stage.h"
 
 #include <cmath>
 #include <cstring>
@@ -17,17 +17,16 @@ int check_cell_segment(const haf_frame *frame, const haf_cell_segment_params *p,
                        int32_t out_on_device, const int32_t *n_labels, std::string &err)
 {
     if (!frame || !p || !n_labels) { err = "null frame, parameters or n_labels"; return HAF_E_ARG; }
-    // the frame, the plane, the heights, the size rule, the cap and the label image: haf_segment_frame's checks, with a gap they pass
-    haf_segment_params sp;
-    memcpy(sp.plane, p->plane, sizeof sp.plane);
-    sp.min_height = p->min_height; sp.max_height = p->max_height; sp.max_gap = 1.0f;
-    sp.min_pixels = p->min_points; sp.max_labels = p->max_labels;
-    const int rc = check_segment(frame, &sp, labels, elem_bytes, row_stride_bytes, out_on_device, n_labels, err);
-    if (rc != HAF_OK) {
-        const std::string theirs = "haf_segment_params: ";
-        if (err.compare(0, theirs.size(), theirs) == 0) err = "haf_cell_segment_params: " + err.substr(theirs.size());
-        if (err == "haf_cell_segment_params: min_pixels < 1") err = "haf_cell_segment_params: min_points < 1";
-        return rc;
+    int rc = check_frame(*frame, err);
+    if (rc != HAF_OK) return rc;
+    if ((rc = check_label_output(*frame, labels, elem_bytes, row_stride_bytes, out_on_device, err)) != HAF_OK) return rc;
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(p->plane[i])) { err = "haf_cell_segment_params: plane has an entry that is not finite"; return HAF_E_ARG; }
+    if (!std::isfinite(p->min_height) || !std::isfinite(p->max_height)) { err = "haf_cell_segment_params: min_height and max_height must be finite"; return HAF_E_ARG; }
+    if (p->min_points < 1) { err = "haf_cell_segment_params: min_points < 1"; return HAF_E_ARG; }
+    if (p->max_labels < 1 || p->max_labels > (elem_bytes == 1 ? 255 : HAF_MAX_LABELS)) {
+        err = "haf_cell_segment_params: max_labels outside 1..HAF_MAX_LABELS (1..255 for a uint8 image)";
+        return HAF_E_ARG;
     }
     if (!std::isfinite(p->cell) || p->cell < 0.001f || p->cell > 1.0f) { err = "haf_cell_segment_params: cell outside 0.001 .. 1"; return HAF_E_ARG; }
     if (!(std::fabs(p->x0) <= 64.0f) || !(std::fabs(p->y0) <= 64.0f)) { err = "haf_cell_segment_params: x0 or y0 not finite or beyond 64 m"; return HAF_E_ARG; }
@@ -156,9 +155,7 @@ int segment_cells_ref_impl(const haf_frame *frame, const haf_cell_segment_params
         for (size_t u = 0; u < W; u++) {
             const int32_t c = cell[v * W + u];
             const int32_t l = c >= 0 ? number[(size_t)parent[(size_t)c]] : 0;
-            char *d = static_cast<char *>(labels) + v * row_stride_bytes + u * (size_t)elem_bytes;
-            if (elem_bytes == 1) { const uint8_t b = (uint8_t)l; memcpy(d, &b, 1); }
-            else { const uint16_t s = (uint16_t)l; memcpy(d, &s, 2); }
+            store_label(labels, row_stride_bytes, elem_bytes, u, v, (uint32_t)l);
         }
     *n_labels = (int32_t)(kept < (int64_t)p->max_labels ? kept : (int64_t)p->max_labels);
     if (stats) { stats[0] = (int64_t)n; stats[1] = fg; stats[2] = outside; stats[3] = occupied; stats[4] = comps; stats[5] = kept; }

@@ -2,7 +2,7 @@
 // checks of an exposure stack, of the filter's parameters and of the output image (both entry points apply them), and
 // haf_filter_depth_ref, the definition of record of depth_filter.h's rules; the device kernel of depthfilter.hip is tested against it
 // word for word.  Built with -ffp-contract=off like every unit (build.py: FLAGS).
-#include "frames.h"
+#include "frame_stage.h"
 #include "depth_filter.h"
 
 #include <cmath>
@@ -45,21 +45,13 @@ int check_depth_stack(const haf_frame *frames, int32_t n_frames, const haf_depth
 
 int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, size_t out_row_stride_bytes, int32_t out_on_device, std::string &err)
 {
-    if (out_on_device != 0 && out_on_device != 1) { err = "out_on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
-    if (!out) {
-        if (out_on_device == 0) { err = "null out in host memory"; return HAF_E_ARG; }
-        return HAF_OK;                                    // (the engine's own image: packed)
-    }
-    const size_t elem = frame_elem_bytes(frames[0]), row = (size_t)frames[0].width * elem, h = (size_t)frames[0].height;
-    if (out_row_stride_bytes < row) { err = "out_row_stride_bytes smaller than a row"; return HAF_E_ARG; }
-    if (out_row_stride_bytes % elem != 0) { err = "out_row_stride_bytes is not a multiple of the element size"; return HAF_E_ARG; }
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (h - 1) * out_row_stride_bytes + row;
-    if (o0 % elem != 0) { err = "out is not aligned to its element size"; return HAF_E_ARG; }
-    for (int k = 0; k < n_frames; k++) {
-        if (frames[k].on_device != out_on_device) continue;
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(frames[k].data), i1 = i0 + (h - 1) * frames[k].row_stride_bytes + row;
-        if (o0 < i1 && i0 < o1) { err = "out overlaps frame " + std::to_string(k); return HAF_E_ARG; }
-    }
+    const haf_frame &f0 = frames[0];
+    const size_t elem = frame_elem_bytes(f0);
+    if (check_output_image(out, out_on_device, out_row_stride_bytes, f0.width, elem, "out", err) != HAF_OK) return HAF_E_ARG;
+    if (!out) return HAF_OK;
+    const ByteSpan o = image_span(out, (size_t)f0.height, out_row_stride_bytes, (size_t)f0.width * elem);
+    for (int k = 0; k < n_frames; k++)
+        if (frames[k].on_device == out_on_device && spans_overlap(o, frame_span(frames[k]))) { err = "out overlaps frame " + std::to_string(k); return HAF_E_ARG; }
     return HAF_OK;
 }
 

@@ -37,9 +37,10 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     const size_t extra_at = kCellCounterBytes, tab_at = up16(extra_at + nl * kCellExtraBytes), img_at = up16(tab_at + nl * kCellTableBytes);
     const size_t grid_at = up16(img_at + (host_out ? px * elem : 0)), end_at = grid_at + (cell_labels ? nc * 2 : 0);
     if ((rc = ensure_stage(e, e->cell_out, end_at, who, "the copy-back block")) != HAF_OK) return rc;
-    if (!labels && (rc = ensure_dev(e, e->d_seg_image, (size_t)e->cfg.max_points * 2, who, "the engine's label image")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->cell_out.dev.p, *const host = e->cell_out.host;
+    OutputDev o;
+    if ((rc = label_output_prepare(e, f, labels, elem_bytes, row_stride_bytes, out_on_device, dev + img_at, who, &o)) != HAF_OK) return rc;
 
     CellSegDev d;
     memset(&d, 0, sizeof d);
@@ -56,7 +57,6 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     d.extra = reinterpret_cast<unsigned *>(dev + extra_at);
     d.table = reinterpret_cast<int *>(dev + tab_at);
     d.cell_labels = cell_labels ? reinterpret_cast<uint16_t *>(dev + grid_at) : nullptr;
-    const OutputDev o = describe_output(labels, out_on_device, row_stride_bytes, (size_t)f.width, elem, dev + img_at, e->d_seg_image.p);
     d.out = o.dst; d.out_stride = o.dst_stride;
     d.elem_bytes = elem_bytes;
     HIPCHK(e, hipMemsetAsync(dev, 0, tab_at, s));                                     // the counters, and every label's cells and top
@@ -66,7 +66,7 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     HIPCHK(e, hipMemcpyAsync(host, dev, cell_labels ? end_at : img_at + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    if (host_out) unpack_rows(static_cast<char *>(labels), row_stride_bytes, host + img_at, (size_t)f.height, (size_t)f.width * elem);
+    label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     if (cell_labels) memcpy(cell_labels, host + grid_at, nc * 2);
     unsigned cnt[CELL_CNT_WORDS];
     memcpy(cnt, host, sizeof cnt);
@@ -85,10 +85,6 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     if (stats) {
         stats[0] = (int64_t)px; stats[1] = (int64_t)cnt[CELL_CNT_FG]; stats[2] = (int64_t)cnt[CELL_CNT_OUTSIDE];
         stats[3] = (int64_t)cnt[CELL_CNT_OCCUPIED]; stats[4] = (int64_t)cnt[CELL_CNT_COMPS]; stats[5] = (int64_t)cnt[CELL_CNT_KEPT];
-    }
-    if (out_image) {
-        out_image->data = o.data; out_image->on_device = o.on_device; out_image->row_stride_bytes = o.row_stride_bytes;
-        out_image->elem_bytes = elem_bytes;
     }
     return HAF_OK;
 }

@@ -253,7 +253,7 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     if ((rc = check_last(e, "haf_grasp_map_labels", request, &rolls)) != HAF_OK) return rc;
     if ((rc = check_map_frame(e, "haf_grasp_map_labels", f)) != HAF_OK) return rc;
     std::string why;
-    if ((rc = check_label_image(labels, f->width, n_labels, picks, why)) != HAF_OK) return fail(e, rc, "haf_grasp_map_labels: " + why);
+    if (!picks || check_label_image(labels, f->width, n_labels, why) != HAF_OK) return fail(e, HAF_E_ARG, "haf_grasp_map_labels: " + (picks ? why : "null picks"));
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
     for (int32_t l = 0; l < n_labels; l++) label_pick_none(&picks[l]);

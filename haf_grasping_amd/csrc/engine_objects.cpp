@@ -81,7 +81,7 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     if (chk.code != HAF_OK) return fail(e, chk.code, who + (chk.text.empty() ? "more pixels than max_points" : chk.text));
     std::string why;
     int rc;
-    if ((rc = check_label_image(labels, frame->width, n_labels, picks, why)) != HAF_OK) return fail(e, rc, who + why);
+    if (!picks || check_label_image(labels, frame->width, n_labels, why) != HAF_OK) return fail(e, HAF_E_ARG, who + (picks ? why : "null picks"));
     const int B = n_objects, R = e->cfg.n_rolls;
     std::vector<int> mark((size_t)n_labels, -1);
     for (int b = 0; b < B; b++) {

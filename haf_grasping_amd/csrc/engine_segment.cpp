@@ -30,11 +30,12 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     const size_t mp = (size_t)e->cfg.max_points;
     if ((rc = ensure_dev(e, e->d_seg_words, 2 * mp + segment_scan_blocks(mp), who, "the parent and size words")) != HAF_OK) return rc;
     if ((rc = ensure_stage(e, e->seg_out, up16(kSegCounterBytes + (size_t)HAF_MAX_LABELS * kSegInfoBytes) + mp * 2, who, "the copy-back block")) != HAF_OK) return rc;
-    if (!labels && (rc = ensure_dev(e, e->d_seg_image, mp * 2, who, "the engine's label image")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->seg_out.dev.p, *const host = e->seg_out.host;
     // the copy-back block of this call: [counters][max_labels table entries][a host output image, packed]
     const size_t tab_at = kSegCounterBytes, img_at = up16(tab_at + (size_t)p->max_labels * kSegInfoBytes);
+    OutputDev o;
+    if ((rc = label_output_prepare(e, f, labels, elem_bytes, row_stride_bytes, out_on_device, dev + img_at, who, &o)) != HAF_OK) return rc;
 
     SegmentDev d;
     memset(&d, 0, sizeof d);
@@ -47,7 +48,6 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     d.totals = d.size + px;
     d.counters = reinterpret_cast<unsigned *>(dev);
     d.table = reinterpret_cast<int *>(dev + tab_at);
-    const OutputDev o = describe_output(labels, out_on_device, row_stride_bytes, (size_t)f.width, elem, dev + img_at, e->d_seg_image.p);
     d.out = o.dst; d.out_stride = o.dst_stride;
     d.elem_bytes = elem_bytes;
     HIPCHK(e, hipMemsetAsync(d.counters, 0, kSegCounterBytes, s));
@@ -56,17 +56,13 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     HIPCHK(e, hipMemcpyAsync(host, dev, img_at + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    if (host_out) unpack_rows(static_cast<char *>(labels), row_stride_bytes, host + img_at, (size_t)f.height, (size_t)f.width * elem);
+    label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     unsigned cnt[4];
     memcpy(cnt, host, sizeof cnt);
     const int32_t n = (int32_t)std::min<unsigned>(cnt[2], (unsigned)p->max_labels);
     *n_labels = n;
     if (info && n > 0) memcpy(info, host + tab_at, (size_t)n * kSegInfoBytes);
     if (stats) { stats[0] = (int64_t)px; stats[1] = (int64_t)cnt[0]; stats[2] = (int64_t)cnt[1]; stats[3] = (int64_t)cnt[2]; }
-    if (out_image) {
-        out_image->data = o.data; out_image->on_device = o.on_device; out_image->row_stride_bytes = o.row_stride_bytes;
-        out_image->elem_bytes = elem_bytes;
-    }
     return HAF_OK;
 }
 

@@ -7,8 +7,10 @@
 //     frame through that of haf_score_views, allocated on first need.  Two steps, so that every refusal comes before any stream operation
 //     and the call's own buffers exist before the upload is enqueued.  The raw areas are only read inside the call that filled them;
 //   * a side image's way to the kernels (upload_image): a host one's rows packed into the pinned half of the call's block and sent with
-//     ONE copy, the bytes between the caller's rows not read; a device-resident one is read where it lies (describe_image).
-// An output image leaves through describe_output and unpack_rows (frame_stage.h).
+//     ONE copy, the bytes between the caller's rows not read; a device-resident one is read where it lies (describe_image);
+//   * a label image's way out (label_output_prepare, label_output_finish): the engine's own image on first need and where the kernels
+//     write (describe_output); behind the call's one copy back, a host image's rows to the caller's (unpack_rows) and the descriptor handed
+//     back.  The block's layout stays with the call.  haf_filter_depth's image leaves through describe_output and unpack_rows itself.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -62,6 +64,19 @@ int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_dev
     pack_rows(block.host + at, static_cast<const char *>(data), h, w, elem_bytes, elem_bytes, row_stride_bytes);
     HIPCHK(e, hipMemcpyAsync(block.dev.p + at, block.host + at, h * w * elem_bytes, hipMemcpyHostToDevice, s));
     return HAF_OK;
+}
+
+int label_output_prepare(haf_engine *e, const haf_frame &f, void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device, void *packed_at, const std::string &who, OutputDev *o)
+{
+    if (const int rc = labels ? HAF_OK : ensure_dev(e, e->d_seg_image, (size_t)e->cfg.max_points * 2, who, "the engine's label image")) return rc;
+    *o = describe_output(labels, out_on_device, row_stride_bytes, (size_t)f.width, (size_t)elem_bytes, packed_at, e->d_seg_image.p);
+    return HAF_OK;
+}
+
+void label_output_finish(const OutputDev &o, const haf_frame &f, int32_t elem_bytes, const char *host_packed_at, haf_label_image *out_image)
+{
+    if (o.on_device == 0) unpack_rows(static_cast<char *>(o.data), o.row_stride_bytes, host_packed_at, (size_t)f.height, (size_t)f.width * (size_t)elem_bytes);
+    if (out_image) *out_image = o.label_image(elem_bytes);
 }
 
 }  // namespace haf_host

@@ -15,8 +15,8 @@
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_transfer.cpp  haf_transfer_labels: another camera's label image onto a depth frame's pixels, behind a z-buffer (transfer.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
-//   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input
-//   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h)
+//   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input, a label image's way out
+//   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h, which also holds the checks of label and output images)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
 #pragma once
@@ -87,10 +87,8 @@ void fill_roll_geo(const haf_config &cfg, const haf_grasp_input &in, const Norma
 bool invert(const Mat4 &m, Mat4 &inv);
 // graspmap_host.cpp: rows 0..2 of the transforms of rolls roll_first .. roll_first + roll_count - 1 (fill_roll_geo's), 64 bytes each
 void fill_cell_geo(const haf_config &cfg, const haf_grasp_input &in, int roll_first, int roll_count, haf_cell_math::CellGeo *geo);
-// graspmap_host.cpp, shared by haf_label_best_ref and haf_grasp_map_labels: every refusal of a label image that goes with a frame `width`
-// pixels wide; the not-found pick; a pick's key (pick_rules.h: its maximum is the best pick); the ids id_of(k) of the found ones among
-// picks[0..n), best pick first
-int check_label_image(const haf_label_image *l, int32_t width, int32_t n_labels, const void *picks, std::string &err);
+// graspmap_host.cpp, shared by haf_label_best_ref and haf_grasp_map_labels: the not-found pick; a pick's key (pick_rules.h: its maximum
+// is the best pick); the ids id_of(k) of the found ones among picks[0..n), best pick first
 void label_pick_none(haf_label_pick *p);
 unsigned long long label_pick_key(const haf_label_pick &p, int32_t width);
 void label_order(const haf_label_pick *picks, int32_t n, const std::function<int32_t(int32_t)> &id_of, int32_t width, int32_t *order,
@@ -629,6 +627,11 @@ int frame_input_prepare(haf_engine *e, const haf_frame &f, const std::string &wh
 int frame_input_upload(haf_engine *e, const haf_frame &f, StageBuf &area, hipStream_t s, FrameDev *fd);
 // a side image of frame f (f.height x f.width elements): a host one through `block` at `at`, one copy; *id = where the kernels read it
 int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, StageBuf &block, size_t at, hipStream_t s, ImageDev *id);
+// the label image a call writes for frame f.  prepare, before the call's first stream operation: the engine's own image on its first use
+// when `labels` is null; *o = where the kernels write, a host image packed at packed_at inside the block the call copies back.  finish, after
+// the call's ONE copy back and ONE synchronisation: a host image's rows from host_packed_at, packed_at's pinned twin, to the caller's; *out_image (may be null) filled
+int label_output_prepare(haf_engine *e, const haf_frame &f, void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device, void *packed_at, const std::string &who, OutputDev *o);
+void label_output_finish(const OutputDev &o, const haf_frame &f, int32_t elem_bytes, const char *host_packed_at, haf_label_image *out_image);
 // engine_roi.cpp
 int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, const haf_roi *rois, const haf_grasp_input *in, haf_grasp_output *out);
 int score_views_roi_impl(haf_engine *e, int32_t n, const int32_t *views_per_request, const haf_frame *frames, const haf_roi *rois,

@@ -27,11 +27,9 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     const size_t px = (size_t)f.width * (size_t)f.height, elem = (size_t)elem_bytes, mp = (size_t)e->cfg.max_points;
     const size_t cam_px = (size_t)cam->width * (size_t)cam->height, ceb = (size_t)cl.elem_bytes;
     const bool host_out = out_on_device == 0;
-    if (!labels && cl.on_device == 1 && e->d_seg_image.p) {       // (the engine's own image as the camera's AND as the output)
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(e->d_seg_image.p), o1 = o0 + px * elem;
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(cl.data), i1 = i0 + (size_t)(cam->height - 1) * cl.row_stride_bytes + (size_t)cam->width * ceb;
-        if (o0 < i1 && i0 < o1) return fail(e, HAF_E_ARG, who + "the engine's own image is both the camera's label image and the output");
-    }
+    // (the engine's own image, packed, as the camera's AND as the output)
+    if (!labels && cl.on_device == 1 && e->d_seg_image.p && spans_overlap(image_span(e->d_seg_image.p, 1, 0, px * elem), label_span(cl, cam->width, cam->height)))
+        return fail(e, HAF_E_ARG, who + "the engine's own image is both the camera's label image and the output");
     if (cam_px > mp) return fail(e, HAF_E_CAPACITY, who + "more camera pixels than max_points");
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
@@ -39,9 +37,10 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     // the call's block, device and pinned: [counters][a host output image, packed][a host camera label image, packed]
     const size_t img_at = kTransferCounterBytes, cam_at = up16(img_at + mp * 2);
     if ((rc = ensure_stage(e, e->transfer_io, cam_at + mp * 2, who, "the copy-back block")) != HAF_OK) return rc;
-    if (!labels && (rc = ensure_dev(e, e->d_seg_image, mp * 2, who, "the engine's label image")) != HAF_OK) return rc;
     const hipStream_t s = e->stream;
     char *const dev = e->transfer_io.dev.p, *const host = e->transfer_io.host;
+    OutputDev o;
+    if ((rc = label_output_prepare(e, f, labels, elem_bytes, row_stride_bytes, out_on_device, dev + img_at, who, &o)) != HAF_OK) return rc;
 
     TransferDev d;
     memset(&d, 0, sizeof d);
@@ -55,7 +54,6 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     d.labels = ld.src; d.label_stride = ld.row_stride;
     d.label_bytes = cl.elem_bytes;
     d.n_labels = n_labels;
-    const OutputDev o = describe_output(labels, out_on_device, row_stride_bytes, (size_t)f.width, elem, dev + img_at, e->d_seg_image.p);
     d.out = o.dst; d.out_stride = o.dst_stride;
     d.elem_bytes = elem_bytes;
     d.counters = reinterpret_cast<unsigned *>(dev);
@@ -66,16 +64,12 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     if (zbuffer) HIPCHK(e, hipMemcpyAsync(zbuffer, d.z, cam_px * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     if ((rc = check_guards(e)) != HAF_OK) return rc;
-    if (host_out) unpack_rows(static_cast<char *>(labels), row_stride_bytes, host + img_at, (size_t)f.height, (size_t)f.width * elem);
+    label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     unsigned cnt[TRANSFER_CNT_WORDS];
     memcpy(cnt, host, sizeof cnt);
     if (stats) {
         stats[0] = (int64_t)px; stats[1] = (int64_t)cnt[TRANSFER_CNT_FRONT]; stats[2] = (int64_t)cnt[TRANSFER_CNT_PROJECTS];
         stats[3] = (int64_t)cnt[TRANSFER_CNT_VISIBLE]; stats[4] = (int64_t)cnt[TRANSFER_CNT_LABELLED];
-    }
-    if (out_image) {
-        out_image->data = o.data; out_image->on_device = o.on_device; out_image->row_stride_bytes = o.row_stride_bytes;
-        out_image->elem_bytes = elem_bytes;
     }
     return HAF_OK;
 }

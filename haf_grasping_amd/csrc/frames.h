@@ -41,16 +41,17 @@ haf_frame_math::FrameMath frame_math(const haf_frame &f);
 int view_points_impl(const haf_frame *frames, int32_t n_views, float *xyz, size_t cap_points, size_t *n_valid, std::string &err);
 // depthfilter_host.cpp, shared by haf_filter_depth_ref and haf_filter_depth: every refusal of an exposure stack and of the filter's
 // parameters that needs no engine (the text names the frame), and every refusal of the output image that goes with a checked stack
-// (out may be null only with out_on_device = 1)
+// (frame_stage.h: check_output_image, then no byte shared with an exposure; out may be null only with out_on_device = 1)
 int check_depth_stack(const haf_frame *frames, int32_t n_frames, const haf_depth_filter *p, std::string &err);
 int check_depth_out(const haf_frame *frames, int32_t n_frames, const void *out, size_t out_row_stride_bytes, int32_t out_on_device, std::string &err);
 // segment_host.cpp, shared by haf_segment_ref and haf_segment_frame: every refusal of a frame, of the parameters and of the label image
-// that needs no engine (labels may be null only with out_on_device = 1); the predicates' constants, gap2 formed here
+// that needs no engine (the image's: frame_stage.h's check_label_output; labels may be null only with out_on_device = 1); the
+// predicates' constants, gap2 formed here
 int check_segment(const haf_frame *frame, const haf_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
                   int32_t out_on_device, const int32_t *n_labels, std::string &err);
 haf_segment_math::SegmentRules segment_rules(const haf_segment_params &p);
 // cellsegment_host.cpp, shared by haf_segment_cells_ref and haf_segment_cells: every refusal of a frame, of the parameters and of the
-// label image that needs no engine (check_segment's for the frame and the image); the rules' constants, inv_cell formed here
+// label image that needs no engine (check_frame, check_label_output); the rules' constants, inv_cell formed here
 int check_cell_segment(const haf_frame *frame, const haf_cell_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
                        int32_t out_on_device, const int32_t *n_labels, std::string &err);
 haf_cell_math::CellRules cell_rules(const haf_cell_segment_params &p);
@@ -75,8 +76,8 @@ void shape_finish(haf_label_shape *s);
 // a label's row of the device table (label_shape.h: kShapeRowWords words, as copied back) -> its integers and h_max, then shape_finish
 void shape_from_row(const uint32_t *row, haf_label_shape *s);
 // transfer_host.cpp, shared by haf_transfer_labels_ref and haf_transfer_labels: every refusal of the depth frame, the camera, its label
-// image, the parameters and the label output that needs no engine (check_segment's for the frame and the output; labels may be null only
-// with out_on_device = 1); THE constants of a call, formed here in double
+// image, the parameters and the label output that needs no engine (check_frame, check_label_output, and check_label_image with the
+// CAMERA's width; labels may be null only with out_on_device = 1); THE constants of a call, formed here in double
 int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_label_image *cam_labels, int32_t n_labels,
                    const haf_transfer_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device,
                    std::string &err);

@@ -112,18 +112,6 @@ static int grasp_map_ref_impl(const haf_config *cfg, const haf_grasp_input *in, 
     });
 }
 
-int check_label_image(const haf_label_image *l, int32_t width, int32_t n_labels, const void *picks, std::string &err)
-{
-    if (!l || !l->data || !picks) { err = "null labels, label data or picks"; return HAF_E_ARG; }
-    if (l->elem_bytes != 1 && l->elem_bytes != 2) { err = "label elem_bytes must be 1 or 2"; return HAF_E_ARG; }
-    if (l->on_device != 0 && l->on_device != 1) { err = "label on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
-    const size_t eb = (size_t)l->elem_bytes;
-    if (l->row_stride_bytes < (size_t)std::max(0, width) * eb || l->row_stride_bytes % eb != 0) { err = "label row stride too small or misaligned"; return HAF_E_ARG; }
-    if (reinterpret_cast<uintptr_t>(l->data) % eb != 0) { err = "label data not aligned to its element"; return HAF_E_ARG; }
-    if (n_labels < 1 || n_labels > HAF_MAX_LABELS) { err = "n_labels outside 1..HAF_MAX_LABELS"; return HAF_E_ARG; }
-    return HAF_OK;
-}
-
 void label_pick_none(haf_label_pick *p)
 {
     p->found = 0; p->u = p->v = p->roll = p->cell = -1; p->vote = HAF_MAP_NO_CELL; p->n_pixels = 0;
@@ -153,18 +141,14 @@ static int label_best_ref_impl(const haf_config *cfg, const haf_grasp_input *in,
     int rc = check_map_ref_args(cfg, in, roll_first, roll_count, eval_grids, f);
     if (rc != HAF_OK) return rc;
     std::string err;
-    if ((rc = check_label_image(labels, f->width, n_labels, picks, err)) != HAF_OK) return rc;
+    if (!picks || check_label_image(labels, f->width, n_labels, err) != HAF_OK) return HAF_E_ARG;
     if (labels->on_device != 0) return HAF_E_ARG;           // (host memory only)
     for (int32_t l = 0; l < n_labels; l++) label_pick_none(&picks[l]);
     std::vector<unsigned long long> best((size_t)n_labels, 0ull);
-    const char *lbase = static_cast<const char *>(labels->data);
     const size_t width = (size_t)f->width;
     rc = map_pixels(cfg, in, roll_first, roll_count, eval_grids, f, [&](size_t i, int16_t bv, int16_t br, int32_t bc) {
         const size_t v = i / width, u = i - v * width;
-        const char *at = lbase + v * labels->row_stride_bytes + u * (size_t)labels->elem_bytes;
-        unsigned lab;
-        if (labels->elem_bytes == 1) lab = *reinterpret_cast<const uint8_t *>(at);
-        else { uint16_t w; memcpy(&w, at, 2); lab = w; }
+        const uint32_t lab = load_label(*labels, u, v);
         if (lab < 1u || lab > (unsigned)n_labels || !haf_pick_math::pick_qualifies(bv, br, min_vote)) return;
         haf_label_pick cand;
         cand.found = 1; cand.u = (int32_t)u; cand.v = (int32_t)v; cand.vote = bv; cand.roll = br; cand.cell = bc;

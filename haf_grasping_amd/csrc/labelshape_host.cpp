@@ -3,7 +3,7 @@
 // integers, which both entry points call -- haf_measure_labels_ref, the definition of record of label_shape.h's rules (the device
 // kernel of labelshape.hip is tested against it word for word), and haf_object_input.  Built with -ffp-contract=off like every unit
 // (build.py: FLAGS).
-#include "frames.h"
+#include "frame_stage.h"
 
 #include <cmath>
 #include <cstring>
@@ -24,16 +24,10 @@ int check_measure(const haf_frame *frame, const haf_label_image *l, int32_t n_la
                   std::string &err)
 {
     if (!frame) { err = "null frame"; return HAF_E_ARG; }
-    const int rc = check_frame(*frame, err);
+    int rc = check_frame(*frame, err);
     if (rc != HAF_OK) return rc;
-    // (the label image: what haf_grasp_map_labels refuses of one, with shapes in the place of its picks)
-    if (!l || !l->data || !shapes) { err = "null labels, label data or shapes"; return HAF_E_ARG; }
-    if (l->elem_bytes != 1 && l->elem_bytes != 2) { err = "label elem_bytes must be 1 or 2"; return HAF_E_ARG; }
-    if (l->on_device != 0 && l->on_device != 1) { err = "label on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
-    const size_t eb = (size_t)l->elem_bytes;
-    if (l->row_stride_bytes < (size_t)frame->width * eb || l->row_stride_bytes % eb != 0) { err = "label row stride too small or misaligned"; return HAF_E_ARG; }
-    if (reinterpret_cast<uintptr_t>(l->data) % eb != 0) { err = "label data not aligned to its element"; return HAF_E_ARG; }
-    if (n_labels < 1 || n_labels > HAF_MAX_LABELS) { err = "n_labels outside 1..HAF_MAX_LABELS"; return HAF_E_ARG; }
+    if (!shapes) { err = "null shapes"; return HAF_E_ARG; }
+    if ((rc = check_label_image(l, frame->width, n_labels, err)) != HAF_OK) return rc;
     if (plane)
         for (int i = 0; i < 4; i++)
             if (!std::isfinite(plane[i])) { err = "a plane entry is not finite"; return HAF_E_ARG; }
@@ -111,13 +105,9 @@ int measure_labels_ref_impl(const haf_frame *frame, const haf_label_image *label
     if ((rc = haf_frame_points(frame, xyz.data())) != HAF_OK) return rc;
     std::vector<ShapeAcc<int64_t>> acc((size_t)n_labels);
     for (auto &a : acc) shape_clear(a);
-    const char *lbase = static_cast<const char *>(labels->data);
     for (size_t v = 0; v < H; v++)
         for (size_t u = 0; u < W; u++) {
-            const char *at = lbase + v * labels->row_stride_bytes + u * (size_t)labels->elem_bytes;
-            unsigned lab;
-            if (labels->elem_bytes == 1) lab = *reinterpret_cast<const uint8_t *>(at);
-            else { uint16_t w; memcpy(&w, at, 2); lab = w; }
+            const uint32_t lab = load_label(*labels, u, v);
             if (lab < 1u || lab > (unsigned)n_labels) continue;
             shape_add_pixel(acc[lab - 1], &xyz[3 * (v * W + u)], plane, plane != nullptr);
         }

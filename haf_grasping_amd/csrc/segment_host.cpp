@@ -2,7 +2,7 @@
 // the frame, the parameters and the label image (both entry points apply them), and haf_segment_ref, the definition of record of
 // segment_rules.h's predicates and of the integer rules behind them (components, anchors, numbering); the device kernels of
 // segment.hip are tested against it word for word.  Built with -ffp-contract=off like every unit (build.py: FLAGS).
-#include "frames.h"
+#include "frame_stage.h"
 
 #include <cmath>
 #include <cstring>
@@ -13,38 +13,29 @@ namespace haf {
 
 using namespace haf_segment_math;
 
+// every refusal of the parameters; elem_bytes: the label image's, which bounds max_labels
+static int check_segment_params(const haf_segment_params &p, int32_t elem_bytes, std::string &err)
+{
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(p.plane[i])) { err = "haf_segment_params: plane has an entry that is not finite"; return HAF_E_ARG; }
+    if (!std::isfinite(p.min_height) || !std::isfinite(p.max_height)) { err = "haf_segment_params: min_height and max_height must be finite"; return HAF_E_ARG; }
+    if (!std::isfinite(p.max_gap) || !(p.max_gap > 0.0f)) { err = "haf_segment_params: max_gap must be finite and positive"; return HAF_E_ARG; }
+    if (p.min_pixels < 1) { err = "haf_segment_params: min_pixels < 1"; return HAF_E_ARG; }
+    if (p.max_labels < 1 || p.max_labels > (elem_bytes == 1 ? 255 : HAF_MAX_LABELS)) {
+        err = "haf_segment_params: max_labels outside 1..HAF_MAX_LABELS (1..255 for a uint8 image)";
+        return HAF_E_ARG;
+    }
+    return HAF_OK;
+}
+
 int check_segment(const haf_frame *frame, const haf_segment_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes,
                   int32_t out_on_device, const int32_t *n_labels, std::string &err)
 {
     if (!frame || !p || !n_labels) { err = "null frame, parameters or n_labels"; return HAF_E_ARG; }
-    const int rc = check_frame(*frame, err);
+    int rc = check_frame(*frame, err);
     if (rc != HAF_OK) return rc;
-    for (int i = 0; i < 4; i++)
-        if (!std::isfinite(p->plane[i])) { err = "haf_segment_params: plane has an entry that is not finite"; return HAF_E_ARG; }
-    if (!std::isfinite(p->min_height) || !std::isfinite(p->max_height)) { err = "haf_segment_params: min_height and max_height must be finite"; return HAF_E_ARG; }
-    if (!std::isfinite(p->max_gap) || !(p->max_gap > 0.0f)) { err = "haf_segment_params: max_gap must be finite and positive"; return HAF_E_ARG; }
-    if (p->min_pixels < 1) { err = "haf_segment_params: min_pixels < 1"; return HAF_E_ARG; }
-    if (elem_bytes != 1 && elem_bytes != 2) { err = "elem_bytes must be 1 or 2"; return HAF_E_ARG; }
-    if (p->max_labels < 1 || p->max_labels > (elem_bytes == 1 ? 255 : HAF_MAX_LABELS)) {
-        err = "haf_segment_params: max_labels outside 1..HAF_MAX_LABELS (1..255 for a uint8 image)";
-        return HAF_E_ARG;
-    }
-    if (out_on_device != 0 && out_on_device != 1) { err = "out_on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
-    if (!labels) {
-        if (out_on_device == 0) { err = "null labels in host memory"; return HAF_E_ARG; }
-        return HAF_OK;                                    // (the engine's own image: packed)
-    }
-    const size_t elem = (size_t)elem_bytes, row = (size_t)frame->width * elem, h = (size_t)frame->height;
-    if (row_stride_bytes < row) { err = "row_stride_bytes smaller than a row"; return HAF_E_ARG; }
-    if (row_stride_bytes % elem != 0) { err = "row_stride_bytes is not a multiple of the element size"; return HAF_E_ARG; }
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(labels), o1 = o0 + (h - 1) * row_stride_bytes + row;
-    if (o0 % elem != 0) { err = "labels is not aligned to its element size"; return HAF_E_ARG; }
-    if (frame->on_device == out_on_device) {
-        const size_t last = (size_t)(frame->width - 1) * frame_elem_bytes(*frame) + frame_pixel_bytes(frame->kind);
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(frame->data), i1 = i0 + (h - 1) * frame->row_stride_bytes + last;
-        if (o0 < i1 && i0 < o1) { err = "labels overlaps the frame"; return HAF_E_ARG; }
-    }
-    return HAF_OK;
+    if ((rc = check_segment_params(*p, elem_bytes, err)) != HAF_OK) return rc;
+    return check_label_output(*frame, labels, elem_bytes, row_stride_bytes, out_on_device, err);
 }
 
 SegmentRules segment_rules(const haf_segment_params &p)
@@ -122,9 +113,7 @@ int segment_ref_impl(const haf_frame *frame, const haf_segment_params *p, void *
         for (size_t u = 0; u < W; u++) {
             const size_t i = v * W + u;
             const int32_t l = parent[i] >= 0 ? number[(size_t)parent[i]] : 0;      // (every path was shortened to its root above)
-            char *d = static_cast<char *>(labels) + v * row_stride_bytes + u * (size_t)elem_bytes;
-            if (elem_bytes == 1) { const uint8_t b = (uint8_t)l; memcpy(d, &b, 1); }
-            else { const uint16_t s = (uint16_t)l; memcpy(d, &s, 2); }
+            store_label(labels, row_stride_bytes, elem_bytes, u, v, (uint32_t)l);
             if (l > 0 && info) {
                 haf_segment_info &s = info[l - 1];
                 if ((int32_t)u < s.u_min) s.u_min = (int32_t)u;

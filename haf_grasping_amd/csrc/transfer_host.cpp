@@ -3,7 +3,7 @@
 // apply them), transfer_rules -- THE constants of a call, which both entry points form here -- and haf_transfer_labels_ref, the
 // definition of record of transfer_rules.h's rules; the device kernels of transfer.hip are tested against it word for word.  Built with
 // -ffp-contract=off like every unit (build.py: FLAGS).
-#include "frames.h"
+#include "frame_stage.h"
 
 #include <cmath>
 #include <cstring>
@@ -32,12 +32,9 @@ int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_labe
                    const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device, std::string &err)
 {
     if (!depth || !cam || !l || !p) { err = "null depth frame, camera, camera labels or parameters"; return HAF_E_ARG; }
-    // the frame and the label output: haf_segment_frame's refusals, under its default parameters
-    haf_segment_params seg;
-    haf_segment_default(&seg);
-    int32_t unused = 0;
-    const int rc = check_segment(depth, &seg, labels, elem_bytes, row_stride_bytes, out_on_device, &unused, err);
+    int rc = check_frame(*depth, err);
     if (rc != HAF_OK) return rc;
+    if ((rc = check_label_output(*depth, labels, elem_bytes, row_stride_bytes, out_on_device, err)) != HAF_OK) return rc;
     if (cam->width < 1 || cam->width > kMaxCameraSide || cam->height < 1 || cam->height > kMaxCameraSide) {
         err = "haf_camera: width or height outside 1..32768";
         return HAF_E_ARG;
@@ -50,20 +47,13 @@ int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_labe
     if (!std::isfinite(p->tol_abs) || !(p->tol_abs >= 0.0f)) { err = "haf_transfer_params: tol_abs must be finite and not negative"; return HAF_E_ARG; }
     if (!in_range(p->tol_rel, 0.0f, 1.0f)) { err = "haf_transfer_params: tol_rel outside 0..1"; return HAF_E_ARG; }
     if (p->splat < 0 || p->splat > kMaxSplat) { err = "haf_transfer_params: splat outside 0..2"; return HAF_E_ARG; }
-    // (the camera's label image: what haf_grasp_map_labels refuses of one)
-    if (!l->data) { err = "null camera label data"; return HAF_E_ARG; }
-    if (l->elem_bytes != 1 && l->elem_bytes != 2) { err = "label elem_bytes must be 1 or 2"; return HAF_E_ARG; }
-    if (l->on_device != 0 && l->on_device != 1) { err = "label on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
-    const size_t eb = (size_t)l->elem_bytes, cam_row = (size_t)cam->width * eb;
-    if (l->row_stride_bytes < cam_row || l->row_stride_bytes % eb != 0) { err = "label row stride too small or misaligned"; return HAF_E_ARG; }
-    if (reinterpret_cast<uintptr_t>(l->data) % eb != 0) { err = "label data not aligned to its element"; return HAF_E_ARG; }
-    if (n_labels < 1 || n_labels > HAF_MAX_LABELS) { err = "n_labels outside 1..HAF_MAX_LABELS"; return HAF_E_ARG; }
+    if ((rc = check_label_image(l, cam->width, n_labels, err)) != HAF_OK) return rc;      // (the CAMERA's width: its image is the camera's)
     if (elem_bytes == 1 && n_labels > 255) { err = "n_labels above 255 with a uint8 output"; return HAF_E_ARG; }
-    if (labels && l->on_device == out_on_device) {
-        const size_t row = (size_t)depth->width * (size_t)elem_bytes;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(labels), o1 = o0 + (size_t)(depth->height - 1) * row_stride_bytes + row;
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(l->data), i1 = i0 + (size_t)(cam->height - 1) * l->row_stride_bytes + cam_row;
-        if (o0 < i1 && i0 < o1) { err = "labels overlaps the camera's label image"; return HAF_E_ARG; }
+    if (labels && l->on_device == out_on_device &&
+        spans_overlap(image_span(labels, (size_t)depth->height, row_stride_bytes, (size_t)depth->width * (size_t)elem_bytes),
+                      label_span(*l, cam->width, cam->height))) {
+        err = "labels overlaps the camera's label image";
+        return HAF_E_ARG;
     }
     return HAF_OK;
 }
@@ -85,15 +75,6 @@ TransferRules transfer_rules(const haf_camera &cam, const haf_transfer_params &p
 }
 
 namespace {
-
-uint32_t read_label(const haf_label_image &l, size_t u, size_t v)
-{
-    const char *at = static_cast<const char *>(l.data) + v * l.row_stride_bytes + u * (size_t)l.elem_bytes;
-    if (l.elem_bytes == 1) return *reinterpret_cast<const uint8_t *>(at);
-    uint16_t w;
-    memcpy(&w, at, 2);
-    return w;
-}
 
 int transfer_ref_impl(const haf_frame *depth, const haf_camera *cam, const haf_label_image *cam_labels, int32_t n_labels,
                       const haf_transfer_params *p, void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t *zbuffer, int64_t *stats)
@@ -130,12 +111,10 @@ int transfer_ref_impl(const haf_frame *depth, const haf_camera *cam, const haf_l
             if (transfer_project(r, &xyz[3 * (v * W + u)], Qz, uc, vc) == TRANSFER_PROJECTS &&
                 transfer_visible(r, Qz, Z[(size_t)vc * Wc + (size_t)uc])) {
                 visible++;
-                l = transfer_label(read_label(*cam_labels, (size_t)uc, (size_t)vc), n_labels);
+                l = transfer_label(load_label(*cam_labels, (size_t)uc, (size_t)vc), n_labels);
             }
             labelled += l != 0;
-            char *d = static_cast<char *>(labels) + v * row_stride_bytes + u * (size_t)elem_bytes;
-            if (elem_bytes == 1) { const uint8_t b = (uint8_t)l; memcpy(d, &b, 1); }
-            else { const uint16_t s = (uint16_t)l; memcpy(d, &s, 2); }
+            store_label(labels, row_stride_bytes, elem_bytes, u, v, (uint32_t)l);
         }
     if (zbuffer) memcpy(zbuffer, Z.data(), Z.size() * sizeof(int32_t));
     if (stats) { stats[0] = (int64_t)n; stats[1] = front; stats[2] = projects; stats[3] = visible; stats[4] = labelled; }

@@ -1,7 +1,9 @@
 // stage_paths.cpp -- sanitizer driver of the sensor-frame staging code that needs no device (csrc/frame_stage.h; tests/test_frame_stage_cpu.py
 // builds it with -fsanitize=address,undefined, host only): pack_rows and stage_rows over frames and masks of every kind, shape and stride
 // against a byte-by-byte loop, unpack_rows into padded targets whose bytes between the rows must stay, the pieces stage_rows sends against
-// the upload loop it replaced, describe_frame / staged_bytes / describe_image / describe_output field by field, check_frame_batch over the
+// the upload loop it replaced, describe_frame / staged_bytes / describe_image / describe_output and the label image an OutputDev hands
+// back field by field, image_span / frame_span / label_span and spans_overlap at their edges, store_label / load_label round trips,
+// check_label_image / check_output_image / check_label_output over one accepted case and every refusal, check_frame_batch over the
 // refusals of tests/frame_cases.py.  Every source and destination is a heap block of EXACTLY the bytes
 // the frame describes -- the last source row ends at its last kept element -- so one byte read or written past either is a report.
 // argv: the file of refusal frames (records of {int32 code, int32 data: 0 null / 1 aligned / 2 misaligned by one, haf_frame}).
@@ -136,7 +138,148 @@ static void run_describe_images()
         o = describe_output(nullptr, 1, 0, 61, eb, staged, own);                     // the engine's own image, packed
         EXPECT(o.dst == own && o.dst_stride == 61 * eb && o.data == own && o.on_device == 1 && o.row_stride_bytes == 61 * eb);
     }
+    for (int32_t eb : {1, 2}) {                                                      // the descriptor handed back, for the three residences
+        const size_t stride = 61 * (size_t)eb + 12;
+        haf_label_image l = describe_output(image, 0, stride, 61, (size_t)eb, staged, own).label_image(eb);
+        EXPECT(l.data == image && l.elem_bytes == eb && l.on_device == 0 && l.row_stride_bytes == stride);
+        l = describe_output(image, 1, stride, 61, (size_t)eb, staged, own).label_image(eb);
+        EXPECT(l.data == image && l.elem_bytes == eb && l.on_device == 1 && l.row_stride_bytes == stride);
+        l = describe_output(nullptr, 1, 0, 61, (size_t)eb, staged, own).label_image(eb);
+        EXPECT(l.data == own && l.elem_bytes == eb && l.on_device == 1 && l.row_stride_bytes == 61 * (size_t)eb);
+    }
     free(image); free(staged); free(own);
+}
+
+static haf_frame make_frame(int kind, int w, int h, size_t pad_elems, size_t point_stride, int on_device);
+
+// the bytes an image and a frame span, and whether two spans share one
+static void run_spans()
+{
+    char *block = (char *)malloc(8192);                                              // (only its addresses are used)
+    // 5 rows of 61 uint16, packed: ends at its last element; the next byte starts the second image
+    const size_t a_bytes = 4 * 122 + 122;
+    ByteSpan a = image_span(block, 5, 122, 122);
+    EXPECT(a.begin == (uintptr_t)block && a.end == a.begin + a_bytes);
+    EXPECT(!spans_overlap(a, image_span(block + a_bytes, 5, 122, 122)) && !spans_overlap(image_span(block + a_bytes, 5, 122, 122), a));
+    EXPECT(spans_overlap(a, image_span(block + a_bytes - 1, 5, 122, 122)) && spans_overlap(image_span(block + a_bytes - 1, 5, 122, 122), a));
+    EXPECT(spans_overlap(a, a));
+    // padded rows (stride 160): the span ends at the last element, not at height * stride, so an image inside the padding behind the
+    // last row shares nothing with it; one inside the padding of an earlier row does
+    a = image_span(block, 5, 160, 122);
+    EXPECT(a.end == a.begin + 4 * 160 + 122);
+    EXPECT(!spans_overlap(a, image_span(block + 4 * 160 + 122, 1, 38, 38)) && !spans_overlap(image_span(block + 4 * 160 + 122, 1, 38, 38), a));
+    EXPECT(spans_overlap(a, image_span(block + 3 * 160 + 122, 1, 38, 38)));
+    // height 1: the stride does not count
+    a = image_span(block + 100, 1, 4000, 7);
+    EXPECT(a.begin == (uintptr_t)block + 100 && a.end == a.begin + 7);
+    EXPECT(!spans_overlap(a, image_span(block + 107, 1, 0, 1)) && spans_overlap(a, image_span(block + 106, 1, 0, 1)) && !spans_overlap(a, image_span(block, 1, 0, 100)));
+    // frames: a depth row ends at its last sample; an XYZ frame 12 bytes into its last point whatever lies between two points
+    haf_frame f = make_frame(HAF_FRAME_DEPTH_U16, 61, 5, 7, 0, 0);
+    f.data = block;
+    EXPECT(frame_span(f).begin == (uintptr_t)block && frame_span(f).end == (uintptr_t)block + 4 * (122 + 14) + 122);
+    f = make_frame(HAF_FRAME_DEPTH_F32, 3, 1, 7, 0, 1);
+    f.data = block;
+    EXPECT(frame_span(f).end == (uintptr_t)block + 12);
+    f = make_frame(HAF_FRAME_XYZ_F32, 61, 5, 2, 20, 0);
+    f.data = block;
+    a = frame_span(f);
+    EXPECT(f.row_stride_bytes == 61 * 20 + 8 && a.end == a.begin + 4 * f.row_stride_bytes + 60 * 20 + 12);
+    EXPECT(!spans_overlap(a, image_span((const char *)a.end, 1, 0, 8)) && spans_overlap(a, image_span((const char *)a.end - 1, 1, 0, 8)));
+    // a label image's span
+    const haf_label_image l = {block + 2, 2, 0, 20};
+    a = label_span(l, 7, 3);
+    EXPECT(a.begin == (uintptr_t)block + 2 && a.end == a.begin + 2 * 20 + 14);
+    free(block);
+}
+
+// labels through store_label and load_label in a heap block of EXACTLY (h - 1) * stride + w * elem bytes; the bytes between the rows
+// are pre-filled and must be unchanged
+static void run_labels(size_t h, size_t w, int32_t elem, size_t pad_bytes)
+{
+    const size_t row_bytes = w * (size_t)elem, stride = row_bytes + pad_bytes, total = (h - 1) * stride + row_bytes;
+    char *block = (char *)malloc(total);
+    const uint32_t values[5] = {0, 1, 255, 256, 65535};
+    const size_t n_values = elem == 1 ? 3 : 5;
+    for (size_t first = 0; first < n_values; first++) {
+        for (size_t i = 0; i < total; i++) block[i] = (char)(0xC3 ^ i);
+        for (size_t v = 0; v < h; v++)
+            for (size_t u = 0; u < w; u++) store_label(block, stride, elem, u, v, values[(first + v * w + u) % n_values]);
+        const haf_label_image l = {block, elem, 0, stride};
+        for (size_t v = 0; v < h; v++) {
+            for (size_t u = 0; u < w; u++) {
+                const uint32_t want = values[(first + v * w + u) % n_values];
+                EXPECT(load_label(l, u, v) == want);
+                if (elem == 1) EXPECT((uint8_t)block[v * stride + u] == want);
+                else { uint16_t word; memcpy(&word, block + v * stride + u * 2, 2); EXPECT(word == want); }
+            }
+            for (size_t i = v * stride + row_bytes; v + 1 < h && i < (v + 1) * stride; i++) EXPECT(block[i] == (char)(0xC3 ^ i));
+        }
+    }
+    free(block);
+}
+
+// check_label_image: one accepted image and every refusal of its list; check_output_image and check_label_output likewise
+static void run_image_checks()
+{
+    char *block = (char *)malloc(8192);                                              // (only its addresses are used)
+    std::string err;
+    for (int32_t eb : {1, 2}) {
+        const size_t row = 61 * (size_t)eb;
+        const haf_label_image good = {block, eb, 0, row};                            // a stride of exactly a row
+        EXPECT(check_label_image(&good, 61, 1, err) == HAF_OK && check_label_image(&good, 61, HAF_MAX_LABELS, err) == HAF_OK);
+        haf_label_image l = good;
+        l.on_device = 1; l.row_stride_bytes = row + 8;
+        EXPECT(check_label_image(&l, 61, 7, err) == HAF_OK);
+        const auto refused = [&](const haf_label_image *p, int32_t width, int32_t n_labels) {
+            err.clear();
+            return check_label_image(p, width, n_labels, err) == HAF_E_ARG && !err.empty();
+        };
+        EXPECT(refused(nullptr, 61, 1));
+        l = good; l.data = nullptr; EXPECT(refused(&l, 61, 1));
+        for (int32_t bad : {0, 3, 4, -1}) { l = good; l.elem_bytes = bad; l.row_stride_bytes = 1024; EXPECT(refused(&l, 61, 1)); }
+        for (int32_t bad : {2, -1}) { l = good; l.on_device = bad; EXPECT(refused(&l, 61, 1)); }
+        l = good; l.row_stride_bytes = row - 1; EXPECT(refused(&l, 61, 1));          // one byte short
+        EXPECT(refused(&good, 62, 1));                                               // (the same image against a wider frame)
+        EXPECT(refused(&good, 61, 0) && refused(&good, 61, HAF_MAX_LABELS + 1) && refused(&good, 61, -1));
+        if (eb == 2) {
+            l = good; l.row_stride_bytes = row + 1; EXPECT(refused(&l, 61, 1));      // no multiple of the element
+            l = good; l.data = block + 1; EXPECT(refused(&l, 61, 1));                // misaligned
+        }
+    }
+    for (size_t eb : {1, 2, 4}) {
+        const size_t row = 61 * eb;
+        EXPECT(check_output_image(block, 0, row, 61, eb, "out", err) == HAF_OK);     // a stride of exactly a row
+        EXPECT(check_output_image(block, 1, row + 4 * eb, 61, eb, "out", err) == HAF_OK);
+        EXPECT(check_output_image(nullptr, 1, 0, 61, eb, "out", err) == HAF_OK);     // the engine's own: nothing more is looked at
+        const auto refused = [&](const void *out, int32_t on_device, size_t stride, const char *name) {
+            err.clear();
+            return check_output_image(out, on_device, stride, 61, eb, name, err) == HAF_E_ARG && !err.empty();
+        };
+        EXPECT(refused(block, 2, row, "out") && refused(block, -1, row, "out") && refused(nullptr, 2, row, "out"));
+        EXPECT(refused(nullptr, 0, row, "labels") && err.find("labels") != std::string::npos);
+        EXPECT(refused(block, 0, row - 1, "labels") && err.find("labels") != std::string::npos);
+        EXPECT(refused(block, 1, row - 1, "out") && err.find("out") != std::string::npos);
+        if (eb > 1) {
+            EXPECT(refused(block, 0, row + 1, "out"));                               // no multiple of the element
+            EXPECT(refused(block + 1, 0, row, "out") && refused(block + 1, 1, row, "out"));
+        }
+    }
+    // a label output of a frame: the element size, check_output_image's list, and no byte shared with a frame of the same residence
+    haf_frame f = make_frame(HAF_FRAME_XYZ_F32, 61, 5, 2, 20, 0);
+    f.data = block;
+    const ByteSpan fs = frame_span(f);
+    char *behind = (char *)fs.end + (fs.end & 1);
+    for (int32_t eb : {1, 2}) {
+        const size_t row = 61 * (size_t)eb;
+        EXPECT(check_label_output(f, behind, eb, row, 0, err) == HAF_OK && check_label_output(f, nullptr, eb, 0, 1, err) == HAF_OK);
+        EXPECT(check_label_output(f, (char *)fs.end - eb, eb, row, 0, err) == HAF_E_ARG);        // the frame's last bytes
+        EXPECT(check_label_output(f, (char *)fs.end - eb, eb, row, 1, err) == HAF_OK);           // (another residence: another memory)
+        EXPECT(check_label_output(f, block, eb, row, 0, err) == HAF_E_ARG);
+        EXPECT(check_label_output(f, behind, eb, row - 1, 0, err) == HAF_E_ARG && check_label_output(f, nullptr, eb, row, 0, err) == HAF_E_ARG);
+        EXPECT(check_label_output(f, behind, eb, row, 2, err) == HAF_E_ARG);
+    }
+    for (int32_t bad : {0, 3, 4, -1}) EXPECT(check_label_output(f, behind, bad, 1024, 0, err) == HAF_E_ARG);
+    free(block);
 }
 
 static haf_frame make_frame(int kind, int w, int h, size_t pad_elems, size_t point_stride, int on_device)
@@ -279,6 +422,12 @@ int main(int argc, char **argv)
     run_describe(HAF_FRAME_XYZ_F32, 12);
     run_describe(HAF_FRAME_XYZ_F32, 20);
     run_describe_images();
+    run_spans();
+    for (size_t w : {1, 3, 61})
+        for (size_t h : {1, 5})
+            for (int32_t elem : {1, 2})
+                for (size_t pad : {0, 7}) run_labels(h, w, elem, pad * (size_t)elem);
+    run_image_checks();
     run_batches(argv[1]);
     if (failures) { fprintf(stderr, "%d expectation(s) failed\n", failures); return 1; }
     printf("stage sanitizer job ok\n");

@@ -1,7 +1,8 @@
 """The wiring of the sensor-frame staging code (csrc/frame_stage.h, StageBuf in csrc/engine_state.h) into the engine on the MI355X: host
 frames large enough to go to the device in several pieces, through every entry point that takes a haf_frame, against the same call on the
 same pixels handed over device-resident -- the route that stages nothing.  Every comparison is an equality.  The staging arithmetic itself
-is tested without a device (tests/test_frame_stage_cpu.py).  Testing build; the guard zones around every device buffer are checked after
+is tested without a device (tests/test_frame_stage_cpu.py).  And the way out of a label image: every call that writes one, into every
+residence of its output, against its host definition, with the descriptor handed back.  Testing build; the guard zones around every device buffer are checked after
 every request and after each test."""
 import os
 
@@ -10,8 +11,10 @@ import pytest
 
 import frame_cases as fc
 import pcdio
+import segment_cases as sc
+import transfer_cases as tc
 from haf_grasping_amd import capi
-from test_depth_filter_gpu import fetch
+from test_depth_filter_gpu import SENTINEL, device_image, fetch
 from test_frames_gpu import C3_IN, K525, TABLE1, assert_same, device_copy, make_engine, render_depth, snapshot
 from test_labels_gpu import device_labels
 from test_roi_gpu import device_mask, strip
@@ -167,6 +170,69 @@ def test_staged_host_frame_equals_device_resident_frame_on_every_route(engine, s
     got, ref = labels_route(host, labels), labels_route(dev, dlabels)
     assert_same(got, ref)
     assert len(got["order"]) >= 1
+
+
+def label_writers():
+    """-> [(name, frame, image, call(eng, frame, dtype, **output) -> labels, ref(frame, dtype) -> labels)] for haf_segment_frame,
+    haf_segment_cells and haf_transfer_labels, each on a 61 x 5 frame (no multiple of the kernels' 4 or 8 pixel groups: head and tail
+    stores run) and on a 1 x 1 frame ((h - 1) * stride vanishes), from the small synthetic scenes of segment_cases, cell_segment_cases
+    and transfer_cases"""
+    out = []
+    n_of = lambda dt: 255 if dt == np.uint8 else 300                               # (a uint8 output holds 255 labels)
+    for w, h in ((61, 5), (1, 1)):
+        size = "_%dx%d" % (w, h)
+        frame, image, kw = sc.make_case("random", "u16", (w, h), False)
+        p = capi.segment_params(**kw)
+        out.append(("segment" + size, frame, image, lambda eng, f, dt, p=p, **o: eng.segment(f, p, dt, **o)[0],
+                    lambda f, dt, p=p: capi.segment_ref(f, p, dt)[0]))
+        frame, image, kw = sc.make_case("random", "xyz", (w, h), True)
+        p = capi.cell_segment_params(plane=kw["plane"], min_height=0.01, max_height=0.2, min_points=2, max_step=0.03)
+        out.append(("cells" + size, frame, image, lambda eng, f, dt, p=p, **o: eng.segment_cells(f, p, dt, **o)[0],
+                    lambda f, dt, p=p: capi.segment_cells_ref(f, p, dt)[0]))
+        rng = np.random.default_rng([61, w, h])
+        frame, image = tc.depth_case_frame(capi.FRAME_DEPTH_F32, w, h, rng, pad=3 if h > 1 else 0, holes=h > 1)
+        cam, labels = tc.label_camera(17, 9), tc.label_image(17, 9, np.uint16, rng, 300, pad=5)
+        out.append(("transfer" + size, frame, image, lambda eng, f, dt, c=cam, l=labels, **o: eng.transfer_labels(f, c, l, n_of(dt), None, dt, **o)[0],
+                    lambda f, dt, c=cam, l=labels: capi.transfer_labels_ref(f, c, l, n_of(dt), None, dt)[0]))
+    return out
+
+
+def test_label_outputs_of_every_residence_and_what_is_handed_back(data_dir, golden_dir):
+    """Engine.segment, Engine.segment_cells and Engine.transfer_labels on one small engine (max_points just above 61 x 5), uint8 and
+    uint16, into a host canvas whose rows are 80 elements apart, into the caller's device image of the same stride and into the engine's
+    own image: the image is the *_ref image, every canvas byte outside it is untouched, and the LabelImage handed back has exactly the
+    data, on_device, row_stride_bytes and elem_bytes of where the image lies.  For the 1 x 1 frame the caller's device image is a bare
+    pointer, whose stride capi substitutes.  The guard zones are checked inside every call and after the test."""
+    eng = make_engine(data_dir, os.path.join(golden_dir, "surrogate.model"), n_rolls=1, max_points=320)
+    own, nonzero = set(), 0
+    for name, frame, image, call, ref in label_writers():
+        h, w = frame.height, frame.width
+        dev = device_copy(frame, image)
+        for dtype in (np.uint8, np.uint16):
+            e, at = np.dtype(dtype).itemsize, (name, dtype.__name__)
+            want = ref(frame, dtype)
+            assert want.shape == (h, w) and want.dtype == dtype, at
+            nonzero += int((want != 0).sum())
+            # a host canvas, rows 80 elements apart; a host and a device-resident frame
+            for f in (frame, dev):
+                canvas = np.full((h, 80), 0x5A, dtype)
+                got = call(eng, f, dtype, host_out=canvas[:, :w])
+                assert got.ctypes.data == canvas.ctypes.data and (got == want).all() and (canvas[:, w:] == 0x5A).all(), at
+            # the caller's device image of the same stride
+            keep, ptr, stride, nbytes = device_image(frame, dtype, pad_elems=80 - w)
+            img = call(eng, frame, dtype, device_out=(ptr, stride) if h > 1 else ptr)
+            assert (img.data, img.on_device, img.row_stride_bytes, img.elem_bytes) == (ptr, 1, 80 * e if h > 1 else w * e, e), at
+            labels, pad = image_of(img, frame, dtype)
+            whole, off = keep.cpu().numpy(), ptr - keep.data_ptr()
+            assert (labels == want).all() and (pad == SENTINEL).all() and (whole[:off] == SENTINEL).all() and (whole[off + nbytes:] == SENTINEL).all(), at
+            # the engine's own image, packed
+            img = call(eng, dev, dtype, device_out=True)
+            assert img.data and (img.on_device, img.row_stride_bytes, img.elem_bytes) == (1, w * e, e), at
+            assert (image_of(img, frame, dtype)[0] == want).all(), at
+            own.add(img.data)
+    assert len(own) == 1                                                           # one image: the three calls share it
+    assert nonzero > 100                                                           # (not a comparison of empty images)
+    eng.close()
 
 
 def test_staging_blocks_grow_and_leave_results_as_they_were(data_dir, golden_dir, scenes):
