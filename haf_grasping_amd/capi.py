@@ -125,6 +125,27 @@ class PlaneResult(C.Structure):
 MAX_PLANE_HYP = 1024
 
 
+class Gripper(C.Structure):
+    """haf_gripper: one parallel-jaw gripper of haf_check_grasps, metres; the library's defaults are nominal figures, no real gripper's"""
+    _fields_ = [("opening", C.c_float), ("finger_thickness", C.c_float), ("finger_breadth", C.c_float), ("tip_depth", C.c_float),
+                ("finger_length", C.c_float), ("palm_width", C.c_float), ("palm_breadth", C.c_float), ("palm_height", C.c_float),
+                ("max_hits", C.c_int32), ("min_between", C.c_int32)]
+
+
+class GraspClearance(C.Structure):
+    """haf_grasp_clearance: a grasp's integer row and what clearance_finish derives from it"""
+    _fields_ = [("free", C.c_int32), ("n_near", C.c_int32), ("n_finger", C.c_int32 * 2), ("n_palm", C.c_int32), ("n_between", C.c_int32),
+                ("s_min", C.c_int32), ("s_max", C.c_int32), ("u_max", C.c_int32), ("reserved", C.c_int32), ("width_m", C.c_double),
+                ("offset_m", C.c_double), ("top_m", C.c_double)]
+
+
+CLEARANCE_DTYPE = np.dtype([("free", np.int32), ("n_near", np.int32), ("n_finger", np.int32, 2), ("n_palm", np.int32), ("n_between", np.int32),
+                            ("s_min", np.int32), ("s_max", np.int32), ("u_max", np.int32), ("reserved", np.int32), ("width_m", np.float64),
+                            ("offset_m", np.float64), ("top_m", np.float64)])
+assert CLEARANCE_DTYPE.itemsize == C.sizeof(GraspClearance) == 64
+MAX_CHECK_GRASPS = 4096              # HAF_MAX_CHECK_GRASPS: grasps of one haf_check_grasps call
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -291,6 +312,12 @@ def _bind(path, testing):
     L.haf_plane_default.restype = None
     L.haf_fit_plane_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
     L.haf_fit_plane.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.c_void_p, C.c_void_p]
+    L.haf_gripper_default.argtypes = [C.POINTER(Gripper)]
+    L.haf_gripper_default.restype = None
+    L.haf_check_grasps_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_int32)]
+    L.haf_check_grasps.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_void_p, C.POINTER(C.c_int32)]
     L.haf_measure_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_measure_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_object_input.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_void_p, C.c_int32, C.POINTER(GraspInput), C.POINTER(C.c_int32)]
@@ -719,6 +746,50 @@ def fit_plane_ref(frame, params=None, mask=None, debug=False):
     if rc != HAF_OK:
         raise HafError(rc, "haf_fit_plane_ref refused its arguments")
     return _plane_result(res, p.n_hyp, counts, hyps, debug)
+
+
+def gripper(**kw):
+    """haf_gripper with the library's defaults (opening 0.08, finger_thickness 0.01, finger_breadth 0.02, tip_depth 0.03, finger_length
+    0.06, palm 0.12 x 0.04 x 0.04, max_hits 0, min_between 1 -- nominal figures, no real gripper's) and `kw` over them"""
+    g = Gripper()
+    lib().haf_gripper_default(C.byref(g))
+    for k, v in kw.items():
+        if not hasattr(g, k):
+            raise TypeError("unknown haf_gripper field %r" % k)
+        setattr(g, k, v)
+    return g
+
+
+def _grasp_array(grasps):
+    """a list of the dicts top_grasps / best_per_label / score give (the four pose fields are read), or a ctypes array of GraspOutput or
+    GraspCandidate -> (ctypes array, count, stride in bytes)"""
+    if isinstance(grasps, C.Array):
+        return grasps, len(grasps), C.sizeof(grasps._type_)
+    arr = (GraspOutput * max(1, len(grasps)))()
+    for o, g in zip(arr, grasps):
+        for f in ("grasp_point1", "grasp_point2", "averaged_grasp_point", "approach_vector"):
+            setattr(o, f, (C.c_double * 3)(*[float(x) for x in g[f]]))
+    return arr, len(grasps), C.sizeof(GraspOutput)
+
+
+def _check_grasps(call, frame, grasps, grip, mask):
+    g = grip if grip is not None else gripper()
+    roi, keep = _plane_mask(frame, mask)
+    arr, n, stride = _grasp_array(grasps)
+    out, order, nf = np.zeros(max(1, n), CLEARANCE_DTYPE), np.zeros(max(1, n), np.int32), C.c_int32(0)
+    rc = call(C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(g), n, arr, stride, out.ctypes.data, order.ctypes.data, C.byref(nf))
+    return rc, out[:n], order[:nf.value].copy()
+
+
+def check_grasps_ref(frame, grasps, gripper=None, mask=None):
+    """haf_check_grasps_ref: the host definition of record of the gripper's clearance at every grasp against the points of a host Frame
+    -> (CLEARANCE_DTYPE [n_grasps], order: the indices of the free grasps in input order).  grasps: a list of grasp dicts or a ctypes
+    array of GraspOutput / GraspCandidate; gripper: gripper(...), default the library's nominal one; mask: uint8 [height, width], a
+    non-zero byte admits the pixel."""
+    rc, out, order = _check_grasps(lib().haf_check_grasps_ref, frame, grasps, gripper, mask)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_check_grasps_ref refused its arguments")
+    return out, order
 
 
 def _shape_plane(plane):
@@ -1325,6 +1396,13 @@ class Engine:
         self._check(self._L.haf_fit_plane(self._h, C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(p), C.byref(res),
                                           counts.ctypes.data if debug else None, hyps.ctypes.data if debug else None))
         return _plane_result(res, p.n_hyp, counts, hyps, debug)
+
+    def check_grasps(self, frame, grasps, gripper=None, mask=None):
+        """haf_check_grasps: a Frame (any kind, host or device-resident) and grasps -> what check_grasps_ref gives, computed on the
+        device.  mask: a host uint8 [height, width] array or (device_ptr, row_stride_bytes)."""
+        rc, out, order = _check_grasps(lambda *a: self._L.haf_check_grasps(self._h, *a), frame, grasps, gripper, mask)
+        self._check(rc)
+        return out, order
 
     def measure_labels(self, frame, labels, n_labels=None, plane=None):
         """haf_measure_labels: a Frame (any kind, host or device-resident) and its label image (label_image(): a numpy uint8 / uint16

@@ -19,6 +19,11 @@
 //   --top-k N                         after the normal output, "top <rank> <hypothesis>" for the N best distinct candidates of the
 //                                     goal (haf_top_grasps); --top-radius cells, --top-rolls steps, --top-dist metres set its suppression
 //                                     (server.cpp:962-969), in its string format
+//   --gripper default|OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H   with --top-k: after the "top" lines one line per candidate,
+//                                     "clear <rank> <free> fingers <n0> <n1> palm <n> between <n> width <w> offset <o> top <t>": the
+//                                     scene's points inside the boxes of that parallel-jaw gripper (metres; the default is nominal, no
+//                                     real gripper's) placed at the candidate (haf_check_grasps).  The scene is the --depth frame, or
+//                                     the .pcd cloud as an N x 1 frame.  Without it no output line changes
 //   --map-out PREFIX                  with --depth: the goal's votes in the pixels of the (first) depth image (haf_grasp_map), written as
 //                                     PREFIX.vote.pgm and PREFIX.roll.pgm: 16-bit binary PGMs of the image's size, sample = value + 32768
 //                                     (a pixel without a cell: vote -32768 -> 0, roll -1 -> 32767)
@@ -162,7 +167,7 @@ static void usage()
             "                     [--depth FILE2.pgm [its --intrinsics, --depth-scale, --depth-range, --sensor-pose] ...]\n"
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
-            "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m]\n"
+            "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m] [--gripper default|OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H]\n"
             "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
@@ -176,7 +181,24 @@ static void usage()
             "  --gpus N [--shard rolls|clouds] [--shards-per-gpu K]\n");
 }
 
-static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, int top_k, int top_radius, int top_rolls, double top_dist, int *rc)
+// --gripper: the clearance of the ranked candidates (haf_check_grasps) against `scene`
+struct ClearOptions { bool on = false; haf_gripper gripper; };
+
+// --gripper default | OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H (metres; max_hits and min_between stay the library's)
+static bool parse_gripper(const char *arg, haf_gripper *g)
+{
+    haf_gripper_default(g);
+    if (strcmp(arg, "default") == 0) return true;
+    float v[8];
+    char tail = 0;
+    if (sscanf(arg, "%f,%f,%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &tail) != 8) return false;
+    g->opening = v[0]; g->finger_thickness = v[1]; g->finger_breadth = v[2]; g->tip_depth = v[3]; g->finger_length = v[4];
+    g->palm_width = v[5]; g->palm_breadth = v[6]; g->palm_height = v[7];
+    return true;
+}
+
+static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, int top_k, int top_radius, int top_rolls, double top_dist, int *rc,
+                      const ClearOptions *clear = nullptr, const haf_frame *scene = nullptr)
 {
     haf_top_params tp;
     haf_top_params_default(eng, &tp);
@@ -191,6 +213,24 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
         *rc = 1;
     }
     for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
+    if (!clear || !clear->on || !scene) return;
+    // the same candidates once more, as poses: "clear <rank> <free> fingers <n0> <n1> palm <n> between <n> width <w> offset <o> top <t>"
+    std::vector<haf_grasp_candidate> cand((size_t)std::max(1, cfg.max_clouds) * (size_t)std::max(1, tp.k));
+    std::vector<int32_t> found((size_t)std::max(1, cfg.max_clouds), 0);
+    if (haf_top_grasps(eng, &tp, cand.data(), found.data()) != HAF_OK) { fprintf(stderr, "%s: --gripper: %s\n", what, haf_last_error(eng)); *rc = 1; return; }
+    const int32_t n = found[0];
+    if (n < 1) return;
+    std::vector<haf_grasp_clearance> rows((size_t)n);
+    if (haf_check_grasps(eng, scene, nullptr, &clear->gripper, n, cand.data(), sizeof(haf_grasp_candidate), rows.data(), nullptr, nullptr) != HAF_OK) {
+        fprintf(stderr, "%s: --gripper: %s\n", what, haf_last_error(eng));
+        *rc = 1;
+        return;
+    }
+    for (int32_t t = 0; t < n; t++) {
+        const haf_grasp_clearance &c = rows[(size_t)t];
+        printf("clear %d %d fingers %d %d palm %d between %d width %.9g offset %.9g top %.9g\n", t + 1, c.free, c.n_finger[0], c.n_finger[1], c.n_palm,
+               c.n_between, c.width_m, c.offset_m, c.top_m);
+    }
 }
 
 // --depth: one goal whose cloud is a depth image, deprojected on the device.  stdout as for a .pcd: with --hypotheses every roll's own
@@ -207,6 +247,7 @@ struct DepthView { std::string path; haf_frame frame; std::string roi_path; std:
 // --depth-filter: every view's exposures (its --depth and its --stack files) through haf_filter_depth before the view is scored;
 // --filtered-out: the filtered image of the first view
 struct MapOptions {
+    ClearOptions clear;            // --gripper: with --top-k, the candidates' clearance against the (first) frame
     std::string out_prefix, mask_path, roi_path, labels_path;
     int min_vote = 1;
     bool filter = false;
@@ -843,7 +884,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
             if (cand[(size_t)i].grasp.best_roll < out.rolls_done) printf("hypothesis %s\n", hafshim::hypothesis_string(cand[(size_t)i].grasp, cfg.roll_step_deg).c_str());
     }
     printf("%s\n", hafshim::hypothesis_string(out, cfg.roll_step_deg).c_str());
-    if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc);
+    if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc, &mo.clear, &frames[0]);
     if (run_map(eng, cfg, frames[0], mo) != 0) rc = 1;
     char size[96];
     if (n_views == 1) snprintf(size, sizeof size, "%d x %d pixels", frames[0].width, frames[0].height);
@@ -897,6 +938,7 @@ int main(int argc, char **argv)
         else if (a == "--hypotheses") hypotheses = true;
         else if (a == "--grid-out") { need(1); grid_out = argv[++i]; }
         else if (a == "--top-k") { need(1); top_k = atoi(argv[++i]); }
+        else if (a == "--gripper") { need(1); if (!parse_gripper(argv[++i], &map_opt.clear.gripper)) { usage(); return 2; } map_opt.clear.on = true; }
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }
         else if (a == "--top-dist") { need(1); top_dist = atof(argv[++i]); }
@@ -1031,7 +1073,11 @@ int main(int argc, char **argv)
             if (hypotheses) printf("hypothesis %s\n", lines[l].c_str());
         printf("%s\n", lines.back().c_str());
         (void)res;
-        if (top_k > 0) print_top(eng, cfg, argv[i], top_k, top_radius, top_rolls, top_dist, &rc);
+        haf_frame scene;                                  // --gripper: the cloud as an N x 1 frame in the base frame
+        haf_frame_default(&scene);
+        scene.data = xyz; scene.kind = HAF_FRAME_XYZ_F32; scene.width = (int32_t)n; scene.height = 1;
+        scene.row_stride_bytes = n * 12; scene.point_stride_bytes = 12;
+        if (top_k > 0) print_top(eng, cfg, argv[i], top_k, top_radius, top_rolls, top_dist, &rc, &map_opt.clear, &scene);
         fprintf(stderr, "%s: %zu points, %lld evaluations (%lld re-evaluated in fp64), best vote %d at row %d col %d roll %d\n", argv[i], n,
                 (long long)out.n_evals, (long long)out.n_rechecked, out.best_vote, out.best_row, out.best_col, out.best_roll);
         if (per_roll) {

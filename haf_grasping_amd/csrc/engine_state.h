@@ -12,6 +12,7 @@
 //   engine_segment.cpp   haf_segment_frame: one frame -> an image of object labels (segment.hip)
 //   engine_cellsegment.cpp haf_segment_cells: one frame of any shape -> object labels by top-down cell clustering (cellsegment.hip)
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
+//   engine_clearance.cpp haf_check_grasps: one frame, one gripper, n grasp poses -> the points in the gripper's boxes (clearance.hip)
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_transfer.cpp  haf_transfer_labels: another camera's label image onto a depth frame's pixels, behind a z-buffer (transfer.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
@@ -459,6 +460,11 @@ struct haf_engine {
     // [a host mask, max_points bytes] with its pinned twin
     DevBuf<char> d_plane_scratch;
     StageBuf plane_io;
+    // haf_check_grasps (engine_clearance.cpp), allocated by its first call: the points' coordinate words as three arrays of max_points
+    // words; the block [HAF_MAX_CHECK_GRASPS rows of 32 bytes][as many grasps of 64 bytes][a host mask, max_points bytes] with its
+    // pinned twin
+    DevBuf<char> d_clear_scratch;
+    StageBuf clear_io;
     // haf_measure_labels (engine_labelshape.cpp), allocated by its first call: the block [per-label table, HAF_MAX_LABELS rows of 160 bytes]
     // [a host label image, 2 bytes x max_points] with its pinned twin
     StageBuf shape_io;

@@ -9,6 +9,7 @@
 #include "label_shape.h"
 #include "cell_segment_rules.h"
 #include "transfer_rules.h"
+#include "clearance_rules.h"
 
 #include <string>
 
@@ -82,5 +83,18 @@ int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_labe
                    const haf_transfer_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device,
                    std::string &err);
 haf_transfer_math::TransferRules transfer_rules(const haf_camera &cam, const haf_transfer_params &p);
+// clearance_host.cpp, shared by haf_check_grasps_ref and haf_check_grasps: every refusal of the frame, the mask, the gripper and the
+// grasp list that needs no engine (*bounds filled when the gripper passes); THE integer bounds and the reach of a gripper, false for one
+// the call refuses; THE twelve words of a grasp, in double (reach_q = -1 for a void one); the words of n grasps read at a stride
+int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripper *gripper, int32_t n_grasps, const void *grasps,
+                    size_t grasp_stride_bytes, const haf_grasp_clearance *out, haf_clear_math::ClearBounds *bounds, std::string &err);
+bool gripper_rules(const haf_gripper &g, haf_clear_math::ClearBounds *b);
+void grasp_frame(const haf_grasp_output &g, int32_t reach_q, haf_clear_math::GraspWords *w);
+void grasp_frames(const void *grasps, size_t stride, int32_t n, int32_t reach_q, haf_clear_math::GraspWords *w);
+// a grasp's row of the device table (clearance_rules.h: kClearRowWords words, as copied back) -> the plain integers of the host's row
+void clearance_row_decode(const uint32_t *dev_row, int32_t *row);
+// THE derived fields of every grasp from its integer row (rows: n x kClearRowWords host words), order and n_free (either may be null)
+void clearance_finish(const haf_gripper &g, const haf_clear_math::GraspWords *w, const int32_t *rows, int32_t n, haf_grasp_clearance *out,
+                      int32_t *order, int32_t *n_free);
 
 }  // namespace haf

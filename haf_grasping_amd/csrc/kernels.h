@@ -657,6 +657,23 @@ constexpr int kPlaneBlockPixels = 1024;            // pixels per workgroup of th
 inline size_t plane_blocks(size_t n) { return (n + kPlaneBlockPixels - 1) / kPlaneBlockPixels; }
 // the five launches of one call, in stream order: points and usable bits, scan of the block counts, hypotheses, score, moments
 void launch_plane(const PlaneDev &d, hipStream_t s);
+// haf_check_grasps (clearance.hip): one frame, the gripper and the grasps as the kernels read them -- a kernel argument, so every field
+// is a scalar load.  f: the frame (dst and count are not read); mask: null, or one byte per pixel, rows mask_stride bytes apart; b: the
+// gripper's bounds; qx / qy / qz: f.n words each, the points' coordinate words (qx = 2^30 for an unusable or masked-out pixel), each
+// array 16-byte aligned; grasps: n_grasps x haf_clear_math::kClearGraspWords words (GraspWords); rows: n_grasps x kClearRowWords words,
+// zeroed by the caller.  All of it device memory
+struct ClearDev {
+    FrameDev f;
+    const unsigned char *mask;
+    unsigned long long mask_stride;
+    haf_clear_math::ClearBounds b;
+    int n_grasps;
+    int *qx, *qy, *qz;
+    const int *grasps;
+    unsigned *rows;
+};
+// the two launches of one call, in stream order: the points' words, then grasps x points
+void launch_clearance(const ClearDev &d, hipStream_t s);
 // haf_measure_labels (labelshape.hip): one frame and its label image as the kernel reads them -- a kernel argument, so every field is a
 // scalar load.  f: the frame (dst and count are not read); labels: label_bytes 1 or 2 per pixel, rows label_stride bytes apart; plane:
 // read when use_plane is set; table: n_labels rows of haf_shape_math::kShapeRowWords words (label_shape.h), zeroed by the caller.  All

@@ -132,6 +132,23 @@ class CalcGraspPointsServer:
         return [GraspOutputMsg(self.base_frame_id, c["eval"], c["grasp_point1"], c["grasp_point2"], c["averaged_grasp_point"],
                                c["approach_vector"], c["roll"]) for c in cands]
 
+    def free_grasps(self, frame, k=None, gripper=None, mask=None, **top_params):
+        """The ranked candidates of the last execute*() at which the gripper FITS (haf_check_grasps on haf_top_grasps' output): the
+        scene's points in `frame` (any Frame, e.g. the one just scored; capi.cloud_frame(xyz) for a cloud) are counted inside the boxes of
+        one parallel-jaw gripper (capi.gripper(...); the default is a nominal figure, no real gripper's) placed at every candidate, and
+        those with no point in the fingers or the palm and at least one between the fingers are returned as (GraspOutputMsg, clearance)
+        pairs, best first; clearance: one capi.CLEARANCE_DTYPE record (counts, width_m, offset_m, top_m).  mask: uint8 [height, width]
+        or (device_ptr, row_stride_bytes), a non-zero byte admits the pixel -- e.g. to keep the robot's own arm out.  top_params: min_vote,
+        cell_radius, roll_window, min_dist_m (haf_top_params).  The ranking itself is top_grasps()', unchanged."""
+        if k is not None:
+            top_params["k"] = k
+        cands = self.engine.top_grasps(**top_params)[0]
+        if not cands:
+            return []
+        rows, order = self.engine.check_grasps(frame, cands, gripper, mask)
+        return [(GraspOutputMsg(self.base_frame_id, cands[i]["eval"], cands[i]["grasp_point1"], cands[i]["grasp_point2"],
+                                cands[i]["averaged_grasp_point"], cands[i]["approach_vector"], cands[i]["roll"]), rows[i].copy()) for i in order]
+
     def grasp_map(self, frame, want=("vote", "roll")):
         """The last execute*()'s votes in the pixels of `frame` (haf_grasp_map): any capi.depth_frame / capi.xyz_frame -- the scored
         view, another camera, the registered RGB view -- -> dict of [height, width] images: vote int16 (capi.MAP_NO_CELL where no roll

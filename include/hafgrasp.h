@@ -973,6 +973,83 @@ int  haf_transfer_labels(haf_engine *e, const haf_frame *depth, const haf_camera
                          haf_label_image *out_image /* may be NULL */, int32_t *zbuffer /* host, may be NULL */,
                          int64_t *stats /* [5], may be NULL */);
 
+/* ---- does the gripper fit at a grasp pose: clearance against the scene's points, on the device (csrc/clearance.hip) ----------------
+ * haf_score*, haf_top_grasps, haf_grasp_map_labels and haf_score_objects hand out grasp POSES; a vote says the height profile around a
+ * cell resembles the graspable examples.  It does not say how far the object extends between the fingers, whether the fingertips land
+ * in the table or in a neighbour, or whether the palm hits something taller beside the grasp.  This call counts the scene's points
+ * inside the boxes of ONE parallel-jaw gripper placed at each of n_grasps poses.  Integers throughout: no result depends on an order
+ * of evaluation.
+ *
+ *   scene point   pixel i of one haf_frame of any kind (an N x 1 HAF_FRAME_XYZ_F32 frame under the identity pose is an unorganised
+ *                 cloud) has haf_frame_points' three words.  It is usable by haf_fit_plane's rule -- all three finite, magnitudes <= 16 m,
+ *                 and the mask, a haf_roi over the frame (NULL or a NULL mask pointer: every pixel), non-zero there -- and enters as
+ *                 its three words q = round-to-nearest-even(coordinate * 4096), haf_fit_plane's refit word.
+ *   grasp         read from four fields of a haf_grasp_output, in double: a = approach_vector / |a|; g = grasp_point2 - grasp_point1;
+ *                 c = g - (g . a) a, normalised: the closing axis; b = a x c.  Nine axis words A, B, C = lrint(16384 component), three
+ *                 origin words o = lrint(4096 averaged_grasp_point).  VOID when any of the twelve doubles is not finite, |a| < 1e-6,
+ *                 |g| < 1e-6, |c| < 1e-3 |g| or an |averaged_grasp_point_j| > 16: a void grasp counts nothing and comes back with free =
+ *                 -1 and zeros elsewhere (the "nothing found" output of a request is one); it does not refuse the call.
+ *   gripper       metres.  Along c: the fingers' inner faces at +-opening / 2, each finger_thickness thick.  Along b: finger_breadth,
+ *                 centred.  Along a (u grows with approach_vector, which points from the scene toward the palm): the tips reach
+ *                 tip_depth BELOW the grasp point, the fingers run finger_length from the tips up to the palm, a box of palm_width (c)
+ *                 x palm_breadth (b) x palm_height (a) on top of them.  Bounds W(x) = llrint(x 2^26), formed once per call in double;
+ *                 U0 = -W(tip_depth), U1 = W(finger_length - tip_depth).
+ *   near          d = q - o.  A point is NEAR a grasp when |d_j| <= reach_q for j = 0, 1, 2; reach_q = ceil(4096 r) + 3 with r the
+ *                 radius about the grasp point of the box that bounds all four regions.  Only near points are counted; no point inside
+ *                 a region fails the test (csrc/clearance_rules.h has the proof).
+ *   regions       of a near point: s = C . d, t = B . d, u = A . d, int32 dot products in units of 2^-26 m.  At most one of
+ *                   between   -W(opening/2) < s < W(opening/2),  |t| <= W(finger_breadth/2),  U0 <= u < U1
+ *                   finger 0  -W(opening/2 + finger_thickness) <= s <= -W(opening/2),  t and u as between
+ *                   finger 1   W(opening/2) <= s <= W(opening/2 + finger_thickness),   t and u as between
+ *                   palm      |s| <= W(palm_width/2),  |t| <= W(palm_breadth/2),  U1 <= u <= U1 + W(palm_height)
+ *                 (tested in this order: it matters only for an opening below 2^-26 m.)
+ *   row           n_near, n_finger[2], n_palm, n_between, and s_min, s_max, u_max over the between points (0 without one).
+ *   derived       by ONE host function both entry points call: width_m = (s_max - s_min) 2^-26, the object's extent along the closing
+ *                 axis; offset_m = (s_max + s_min) 2^-27, its centre's offset from the grasp point; top_m = u_max 2^-26, how far it
+ *                 rises toward the palm; all 0 without a between point.  free = 1 when n_finger[0] + n_finger[1] + n_palm <= max_hits
+ *                 and n_between >= min_between, else 0.  order (may be NULL): the indices of the grasps with free = 1, in input order;
+ *                 *n_free (may be NULL) their number.
+ * The defaults of haf_gripper_default are NOMINAL figures, no real gripper's drawing.  Not modelled: other gripper shapes, an opening
+ * per grasp, the search for the smallest free opening, the arm behind the palm.  Points are tested, not surfaces: a sparse cloud can
+ * let a finger through.
+ *
+ * grasps points at the first haf_grasp_output; grasp i is read at grasps + i * grasp_stride_bytes, so a haf_grasp_candidate[] of
+ * haf_top_grasps or haf_grasp_map_labels goes in as it is with its sizeof as the stride.
+ * haf_check_grasps_ref: the host definition of record -- no device, no engine, a host frame and a host mask only.
+ * haf_check_grasps: equal to it in every word of every entry, of order and of n_free; a host or device-resident frame, a host or
+ * device-resident mask; two launches, ONE copy back and ONE synchronisation.  Like haf_fit_plane the call neither reads nor changes
+ * last-batch state or stage timings, works before any request and with HAF_FLAG_PROBABILITY, and allocates its scratch (12 bytes x
+ * max_points, the copy-back block) on first use.
+ * Refusals, all before any device work, nothing written -- HAF_E_ARG: everything haf_fit_plane refuses for a frame and a mask, a null
+ * frame, gripper, grasps or out, a gripper dimension that is negative or not finite, opening <= 0, a reach r above 1 m, n_grasps
+ * outside 1..HAF_MAX_CHECK_GRASPS, a stride below sizeof(haf_grasp_output) or not a multiple of 8, for the _ref form a device-resident
+ * frame or mask; HAF_E_CAPACITY: a frame of more than 2^28 pixels, width * height > max_points. */
+#define HAF_MAX_CHECK_GRASPS 4096
+typedef struct haf_gripper {
+    float   opening;            /* > 0: between the fingers' inner faces                                          */
+    float   finger_thickness;   /* along the closing axis                                                        */
+    float   finger_breadth;     /* across the closing axis and the approach vector                               */
+    float   tip_depth;          /* how far the tips reach below the grasp point, against the approach vector     */
+    float   finger_length;      /* from the tips up to the palm                                                  */
+    float   palm_width, palm_breadth, palm_height;   /* along the closing axis, across it, along the approach vector */
+    int32_t max_hits;           /* free: at most this many points in the fingers and the palm together           */
+    int32_t min_between;        /* free: at least this many points between the fingers                           */
+} haf_gripper;
+typedef struct haf_grasp_clearance {
+    int32_t free;               /* 1 free, 0 not, -1 a void grasp */
+    int32_t n_near, n_finger[2], n_palm, n_between;
+    int32_t s_min, s_max, u_max;   /* units of 2^-26 m, over the between points */
+    int32_t reserved;
+    double  width_m, offset_m, top_m;
+} haf_grasp_clearance;
+void haf_gripper_default(haf_gripper *g);   /* 0.08f, 0.01f, 0.02f, 0.03f, 0.06f, palm 0.12f x 0.04f x 0.04f, 0, 1 */
+int  haf_check_grasps_ref(const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_gripper *gripper, int32_t n_grasps,
+                          const void *grasps, size_t grasp_stride_bytes, haf_grasp_clearance *out /* [n_grasps] */,
+                          int32_t *order /* [n_grasps], may be NULL */, int32_t *n_free /* may be NULL */);
+int  haf_check_grasps(haf_engine *e, const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_gripper *gripper,
+                      int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes, haf_grasp_clearance *out /* [n_grasps] */,
+                      int32_t *order /* [n_grasps], may be NULL */, int32_t *n_free /* may be NULL */);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus
