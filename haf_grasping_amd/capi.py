@@ -1540,7 +1540,14 @@ class Engine:
         self._check(self._L.haf_test_set_screen_inactive(self._h))
 
     def set_stream(self, hip_stream_ptr):
-        self._check(self._L.haf_set_stream(self._h, C.c_void_p(hip_stream_ptr)))
+        """haf_set_stream: every later call enqueues all its work on this hipStream_t (an int: torch's stream.cuda_stream; 0 or None is
+        HIP's default stream, torch.cuda.default_stream()).  The caller keeps the stream alive while it is current; the handle
+        get_stream() gave before the first switch is the engine's own stream and switches back to it."""
+        self._check(self._L.haf_set_stream(self._h, C.c_void_p(hip_stream_ptr or None)))
+
+    def get_stream(self):
+        """haf_get_stream: the current stream's handle as an int (0: HIP's default stream)"""
+        return int(self._L.haf_get_stream(self._h) or 0)
 
     def stage_ms(self):
         ms = (C.c_float * len(STAGES))()

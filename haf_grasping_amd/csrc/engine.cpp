@@ -61,11 +61,11 @@ const char *haf_last_error(const haf_engine *e) { return e ? e->error.c_str() : 
 void haf_destroy(haf_engine *e)
 {
     if (!e) return;
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    if (e->has_own_stream) (void)hipStreamSynchronize(e->stream); // (a half-built engine touches no device; a null handle is HIP's default stream, not "no stream")
     for (auto &r : e->host_regs) (void)hipHostUnregister((void *)r.first);
     e->host_regs.clear();
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
+    if (e->has_own_stream) (void)hipStreamDestroy(e->own_stream);   // (idle: haf_set_stream synchronised it when it switched away)
     delete e;      // frees every DevBuf and StageBuf member: the stream was synchronised above, so nothing still runs on them
 }
 // Default mode: which screening variant serves this MODEL is found out here, at creation, not on the first goals of a fresh
@@ -244,8 +244,9 @@ static int create_impl(const haf_config *cfg, haf_engine **out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) { e->error = "hipGetDeviceProperties failed"; return bail(HAF_E_DEVICE); }
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) { e->error = std::string("device is ") + prop.gcnArchName + ", the kernels are built for gfx950 only"; return bail(HAF_E_DEVICE); }
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { e->error = "hipStreamCreate failed"; return bail(HAF_E_DEVICE); }
-    e->own_stream = true;
+    if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) { e->error = "hipStreamCreate failed"; return bail(HAF_E_DEVICE); }
+    e->has_own_stream = true;
+    e->stream = e->own_stream;
     for (auto &ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { e->error = "hipEventCreate failed"; return bail(HAF_E_DEVICE); }
 
 #ifndef HAF_FLUSH_F16_SUBNORMALS
@@ -350,7 +351,7 @@ int haf_unregister_host_cloud(haf_engine *e, const void *ptr)
     if (!e) return HAF_E_ARG;
     for (size_t i = 0; i < e->host_regs.size(); i++)
         if (e->host_regs[i].first == ptr) {
-            if (e->stream) (void)hipStreamSynchronize(e->stream);
+            (void)hipStreamSynchronize(e->stream);
             HIPCHK(e, hipHostUnregister(const_cast<void *>(ptr)));
             e->host_regs.erase(e->host_regs.begin() + (long)i);
             return HAF_OK;
@@ -420,10 +421,12 @@ int haf_last_prestage(const haf_engine *e, int64_t *n_inexact_grids)
 int haf_set_stream(haf_engine *e, void *s)
 {
     if (!e) return HAF_E_ARG;
-    if (e->stream) (void)hipStreamSynchronize(e->stream);          // (the counters of the next request are zeroed on the old stream)
-    if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
-    e->stream = (hipStream_t)s;
-    e->own_stream = false;
+    if ((hipStream_t)s == e->stream) return HAF_OK;                // the current stream: nothing to order
+    // every request leaves, unsynchronised, the memset that zeroes the next request's counters on the old stream: the new stream
+    // must not start before it.  A null handle is HIP's default stream and is synchronised like any other
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    (void)hipStreamSynchronize(e->stream);
+    e->stream = (hipStream_t)s;                                    // (the engine's own stream lives until haf_destroy: its handle switches back)
     return HAF_OK;
 }
 

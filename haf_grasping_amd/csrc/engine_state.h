@@ -260,8 +260,10 @@ struct haf_engine {
     ExactParams exact{};
     std::string error;
 
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // stream: the CURRENT stream, on which every operation of every call is enqueued (haf_set_stream; null is HIP's default stream).
+    // own_stream: the one the engine created, alive from haf_create to haf_destroy whichever stream is current
+    hipStream_t stream = nullptr, own_stream = nullptr;
+    bool has_own_stream = false;    // creation got as far as a device and its stream (haf_destroy of a half-built engine touches no device)
     hipEvent_t ev[HAF_ST_COUNT + 1] = {};
     float stage_ms[HAF_ST_COUNT] = {};
 

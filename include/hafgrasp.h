@@ -124,8 +124,8 @@ typedef struct haf_cloud {
     const float *xyz;        /* x,y,z fp32 triples                                                        */
     size_t       n_points;
     size_t       stride_floats; /* 3 for packed xyz, 4 for pcl::PointXYZ                                  */
-    int32_t      on_device;  /* 0: host memory (copied over PCIe inside the call); 1: HBM resident: the caller has
-                                synchronised the stream that wrote it (the engine reads it on its own stream);
+    int32_t      on_device;  /* 0: host memory (copied over PCIe inside the call); 1: HBM resident: ordered on the engine's
+                                current stream before the call, or finished (the stream contract at haf_set_stream);
                                 2: host memory inside a buffer registered with haf_register_host_cloud (packed xyz, stride 3):
                                 the DMA engine reads it where it lies -- no staging copy on the host (a 1.2 MB cloud: 30 us
                                 instead of 75); anything else about it as for 0                                        */
@@ -276,11 +276,34 @@ typedef struct haf_attr_record { float feature; float pad; double q4; double sca
 int haf_debug_fetch_attr(haf_engine *e, int32_t cloud, int32_t roll, int32_t max_cells, int32_t *cells /* [max_cells][2] */,
                          haf_attr_record *attr /* [max_cells][324] */, uint8_t *computed /* [max_cells] */, int32_t *n_cells);
 
-/* Launch everything on this hipStream_t (default: a stream the engine creates).  The caller keeps ownership. */
+/* THE STREAM CONTRACT (every on_device and out_on_device comment in this header points here).
+ *
+ * An engine has one CURRENT stream.  haf_create makes a non-blocking stream of the engine's own and makes it current; the engine
+ * keeps that stream until haf_destroy, whichever stream is current.  haf_set_stream makes the caller's hipStream_t current; NULL is
+ * HIP's default (legacy null) stream -- a stream like any other, what torch.cuda.default_stream() is -- not "no stream".  The caller
+ * keeps ownership of a stream it hands over and keeps it alive for as long as it is current.  haf_get_stream returns the current
+ * handle (NULL for the default stream, and for a null engine), so
+ *     void *old = haf_get_stream(e);  haf_set_stream(e, mine);  ...;  haf_set_stream(e, old);
+ * switches to the caller's stream and back to the engine's own.  Handing over the current handle does nothing.  Any other switch
+ * first synchronises the stream it leaves (the engine leaves work of its own there: the clear of the next request's counters), so
+ * nothing of the engine is left running on a stream once haf_set_stream has returned and the caller may destroy it.
+ *
+ * What a caller may rely on, on whichever stream is current:
+ *   - every kernel, copy and fill of every call that touches a caller's device memory or depends on it is enqueued on the current
+ *     stream, and on no other;
+ *   - a device-resident input (on_device = 1: clouds, frames, masks, label images) need only be ORDERED on that stream before the
+ *     call, or finished: work the caller enqueued on the stream before the call -- a kernel that renders the frame, a copy that has
+ *     not completed -- is seen by the call, and no host synchronisation is needed.  Memory written on ANOTHER stream must be finished,
+ *     or that stream joined to the current one (an event wait), before the call;
+ *   - a device output (out_on_device = 1, the engine's own images) is written on the current stream, behind whatever the caller
+ *     enqueued there before the call, and is complete when the call returns: every call synchronises the current stream before it
+ *     returns, so host outputs are complete then too.
+ * The getters of the last batch (haf_get_roll_grid, haf_debug_fetch*) read state that a finished call left, with blocking copies.
+ * HAF_E_ARG for a null engine. */
 int haf_set_stream(haf_engine *e, void *hip_stream);
 void *haf_get_stream(haf_engine *e);
 
-/* Stage timings of the last call in milliseconds (HAF_FLAG_PROFILE): HIP events on the engine's stream. */
+/* Stage timings of the last call in milliseconds (HAF_FLAG_PROFILE): HIP events on the current stream. */
 enum { HAF_ST_UPLOAD = 0, HAF_ST_BIN, HAF_ST_INTEGRAL, HAF_ST_MASK, HAF_ST_FEATURES, HAF_ST_SVM, HAF_ST_REFINE,
        HAF_ST_RECHECK, HAF_ST_VOTE, HAF_ST_DOWNLOAD, HAF_ST_COUNT };   /* REFINE: three-pass kernel on the screened-out rest */
 int haf_get_stage_ms(haf_engine *e, float *ms /* HAF_ST_COUNT */);
@@ -351,7 +374,7 @@ enum { HAF_FRAME_DEPTH_U16 = 0, HAF_FRAME_DEPTH_F32 = 1, HAF_FRAME_XYZ_F32 = 2 }
 typedef struct haf_frame {
     const void *data;
     int32_t kind, width, height;
-    int32_t on_device;           /* 0 host, 1 device-resident (caller has synchronised its writer); 2 is HAF_E_ARG */
+    int32_t on_device;           /* 0 host, 1 device-resident (ordered on the current stream or finished: haf_set_stream); 2 is HAF_E_ARG */
     size_t  row_stride_bytes;    /* >= width * element size, a multiple of the element size */
     size_t  point_stride_bytes;  /* XYZ only: >= 12, multiple of 4 (16 = pcl::PointXYZ, 32 = PointXYZRGB) */
     float   fx, fy, cx, cy;      /* pinhole intrinsics in pixels; depth kinds only */
@@ -437,7 +460,7 @@ int  haf_grasp_map_ref(const haf_config *cfg, const haf_grasp_input *in, int32_t
                        const haf_frame *frame, int16_t *vote, int16_t *roll, int32_t *cell);
 /* The map of request `request` of the LAST scored batch for `frame` (host or device-resident, any kind), computed on the device from
  * the vote grids that batch left there: equal to haf_grasp_map_ref on the request's haf_get_roll_grid grids in every pixel.  vote, roll,
- * cell: width * height packed images in host memory, or in device memory when out_on_device = 1 (written on the engine's stream and
+ * cell: width * height packed images in host memory, or in device memory when out_on_device = 1 (written on the current stream, haf_set_stream, and
  * complete when the call returns); any of them may be NULL.  A request whose budget was negative (no roll ran) yields HAF_MAP_NO_CELL
  * everywhere.  Leaves all last-batch state as it was (records, grids, counters, debug data), like haf_top_grasps.
  * HAF_E_ARG: a null frame, no scored batch, request out of range, out_on_device not 0 or 1, an engine created with
@@ -485,7 +508,7 @@ int  haf_grasp_map_best(haf_engine *e, int32_t request, const haf_frame *frame, 
 typedef struct haf_label_image {   /* goes with a haf_frame of the same width x height */
     const void *data;              /* 0 = background; 1..n_labels = instance; anything larger is ignored like background */
     int32_t elem_bytes;            /* 1 (uint8) or 2 (uint16, host byte order) */
-    int32_t on_device;             /* 0 host, 1 device-resident (caller has synchronised its writer) */
+    int32_t on_device;             /* 0 host, 1 device-resident (ordered on the current stream or finished: haf_set_stream) */
     size_t  row_stride_bytes;      /* >= width * elem_bytes, a multiple of elem_bytes; data aligned to elem_bytes */
 } haf_label_image;
 typedef struct haf_label_pick {    /* label l is entry l - 1 */
@@ -526,7 +549,7 @@ int  haf_grasp_map_labels(haf_engine *e, int32_t request, const haf_frame *frame
 typedef struct haf_roi {
     const uint8_t *mask;      /* width x height of the frame it goes with; != 0 selects the pixel */
     size_t  row_stride_bytes; /* >= width */
-    int32_t on_device;        /* 0 host, 1 device-resident (caller has synchronised its writer) */
+    int32_t on_device;        /* 0 host, 1 device-resident (ordered on the current stream or finished: haf_set_stream) */
 } haf_roi;
 int  haf_roi_cells(const haf_config *cfg, const haf_grasp_input *in, int32_t roll, const haf_frame *frame, const uint8_t *mask,
                    size_t mask_row_stride, uint8_t *roi, uint8_t *eval);
@@ -594,7 +617,7 @@ int  haf_roi_cells_views(const haf_config *cfg, const haf_grasp_input *in, int32
  *
  * haf_filter_depth_ref: the host definition of record -- no device, no engine, host frames and host output only.
  * haf_filter_depth: equal to it in every word and in stats.  out_on_device = 1: out is the caller's device memory, written on the
- * engine's stream and complete when the call returns; out == NULL with out_on_device = 1: the engine writes a packed image of its own
+ * current stream (haf_set_stream) and complete when the call returns; out == NULL with out_on_device = 1: the engine writes a packed image of its own
  * (4 bytes x max_points, allocated by the first call that asks for it, valid until the next haf_filter_depth or haf_destroy).
  * out_frame (may be NULL): a copy of frames[0] whose data, on_device and row_stride_bytes describe the output.  The call neither reads
  * nor changes last-batch state or stage timings, and works with HAF_FLAG_PROBABILITY and before any request.
@@ -645,7 +668,7 @@ int  haf_filter_depth(haf_engine *e, const haf_frame *frames, int32_t n_frames, 
  *
  * haf_segment_ref: the host definition of record -- no device, no engine, a host frame and a host output only.
  * haf_segment_frame: equal to it in every label word, every info field, n_labels and stats.  out_on_device = 1: labels is the caller's
- * device memory, written on the engine's stream and complete when the call returns; labels == NULL with out_on_device = 1: a packed
+ * device memory, written on the current stream (haf_set_stream) and complete when the call returns; labels == NULL with out_on_device = 1: a packed
  * image the engine owns (2 bytes x max_points, allocated by the first call that asks for it), valid until the next haf_segment_frame,
  * haf_segment_cells, haf_transfer_labels or haf_destroy -- ACROSS scoring and map calls, which is its purpose.  out_image (may be NULL) describes the result for
  * haf_grasp_map_labels; its data as a uint8 image is a haf_roi mask.  The first call allocates the scratch: 8 bytes x max_points of
@@ -945,7 +968,7 @@ int  haf_segment_cells(haf_engine *e, const haf_frame *frame, const haf_cell_seg
  * haf_transfer_labels_ref: the host definition of record -- no device, no engine, a host frame, host images and host outputs only.
  * haf_transfer_labels: equal to it in every label word, every zbuffer word and every stat.  The depth frame and the camera label image
  * may each be host or device resident; a device-resident one is read where it lies, with its strides.  A fill, two launches and one
- * copy back on the engine's stream.  Like the segmenters the call neither reads nor changes last-batch state or stage timings, and
+ * copy back on the current stream.  Like the segmenters the call neither reads nor changes last-batch state or stage timings, and
  * works before any request and with HAF_FLAG_PROBABILITY.  Scratch, allocated on first use: 4 bytes per camera pixel, grown on
  * demand, and the copy-back block (a host output image and a host camera label image, 2 bytes x max_points each).
  * Refusals, all before any device work, nothing written -- everything haf_segment_frame refuses for its frame and its label output;

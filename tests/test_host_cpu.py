@@ -57,6 +57,14 @@ def test_create_fails_loudly_without_gpu(data_dir, golden_dir):
     assert ei.value.code == capi.HAF_E_DEVICE and "no CPU fallback" in str(ei.value)
 
 
+def test_stream_entry_points_refuse_a_null_engine():
+    """haf_set_stream(NULL engine, ...) is HAF_E_ARG whatever the handle, haf_get_stream(NULL) is null; neither touches a device"""
+    for L in (capi.lib(), capi.testlib()):
+        assert L.haf_set_stream(None, None) == capi.HAF_E_ARG
+        assert L.haf_set_stream(None, C.c_void_p(0x1000)) == capi.HAF_E_ARG
+        assert L.haf_get_stream(None) is None
+
+
 def _glibc_q(x, digits):
     return float(("%." + str(digits) + "g") % x)      # CPython: PyOS_double_to_string -> correctly rounded, == glibc
 
