@@ -3,7 +3,8 @@
 // the capacity); then the frame goes through the single-frame input of engine_stage.cpp, the nine launches of cellsegment.hip run on the
 // engine's stream, ONE copy brings back the counters and the per-label tables -- and, behind them, a host `labels` image and the
 // top-down grid when they were asked for -- and ONE synchronisation ends the call.  Nothing of the last scored batch is read or
-// written: the stage timings are not touched; the engine's own label image is haf_segment_frame's.
+// written: the stage timings are not touched; the block and the scratch are the ones every such call shares (call_io, call_scratch);
+// the engine's own label image is haf_segment_frame's.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -30,15 +31,16 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     const bool host_out = out_on_device == 0;
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
-    // the words: [a cell word per pixel, whole 16-byte pieces][count][top][parent][size: a word per cell each][the scan's block totals]
+    // the scratch: [a cell word per pixel, whole 16-byte pieces: k_cell_bin stores them so][count][top][parent][size: a word per cell
+    // each][the scan's block totals]; px4 words keep everything behind the cell words at a multiple of 16 bytes
     const size_t px4 = (px + 3) / 4 * 4;
-    if ((rc = ensure_dev(e, e->d_cell_words, px4 + 4 * nc + segment_scan_blocks(nc), who, "the cell words")) != HAF_OK) return rc;
     // the copy-back block of this call: [counters][cells and top per label][table entries][a host output image, packed][the top-down grid]
     const size_t extra_at = kCellCounterBytes, tab_at = up16(extra_at + nl * kCellExtraBytes), img_at = up16(tab_at + nl * kCellTableBytes);
     const size_t grid_at = up16(img_at + (host_out ? px * elem : 0)), end_at = grid_at + (cell_labels ? nc * 2 : 0);
-    if ((rc = ensure_stage(e, e->cell_out, end_at, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->cell_out.dev.p, *const host = e->cell_out.host;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, end_at, "the copy-back block", (px4 + 4 * nc + segment_scan_blocks(nc)) * sizeof(int), "the cell words", &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host;
     OutputDev o;
     if ((rc = label_output_prepare(e, f, labels, elem_bytes, row_stride_bytes, out_on_device, dev + img_at, who, &o)) != HAF_OK) return rc;
 
@@ -47,7 +49,7 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
     d.r = cell_rules(*p);
     d.min_points = p->min_points; d.max_labels = p->max_labels;
-    d.cell = e->d_cell_words.p;
+    d.cell = reinterpret_cast<int *>(cb.scratch);
     d.count = reinterpret_cast<unsigned *>(d.cell + px4);
     d.top = d.count + nc;
     d.parent = reinterpret_cast<int *>(d.top + nc);
@@ -62,10 +64,7 @@ int segment_cells_impl(haf_engine *e, const haf_frame *frame, const haf_cell_seg
     HIPCHK(e, hipMemsetAsync(dev, 0, tab_at, s));                                     // the counters, and every label's cells and top
     HIPCHK(e, hipMemsetAsync(d.count, 0, 2 * nc * sizeof(unsigned), s));            // every cell's count and top
     launch_cell_segment(d, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, cell_labels ? end_at : img_at + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, cell_labels ? end_at : img_at + (host_out ? px * elem : 0))) != HAF_OK) return rc;
     label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     if (cell_labels) memcpy(cell_labels, host + grid_at, nc * 2);
     unsigned cnt[CELL_CNT_WORDS];

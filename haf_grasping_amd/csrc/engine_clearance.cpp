@@ -4,8 +4,8 @@
 // through the single-frame input of engine_stage.cpp and a host mask through its upload_image, the grasps' words go up in one copy, the
 // rows are zeroed, the two launches of clearance.hip run on the engine's stream, ONE copy brings back the rows and ONE synchronisation
 // ends the call.  The derived fields, order and n_free are clearance_finish's (clearance_host.cpp) -- the code haf_check_grasps_ref
-// ends with, on the same integers.  Nothing of the last scored batch is read or written: the stage timings are not touched, and the
-// scratch is this call's own.
+// ends with, on the same integers.  Nothing of the last scored batch is read or written: the stage timings are not touched; the
+// block and the scratch are the ones every such call shares (call_io, call_scratch).
 #include "engine_state.h"
 
 #include <vector>
@@ -37,16 +37,17 @@ int check_grasps_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
     const size_t mp = (size_t)e->cfg.max_points, words = up16(mp * 4);
-    if ((rc = ensure_dev(e, e->d_clear_scratch, 3 * words, who, "the points' coordinate words")) != HAF_OK) return rc;
-    if ((rc = ensure_stage(e, e->clear_io, kClearMaskAt + mp, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->clear_io.dev.p, *const host = e->clear_io.host, *const scratch = e->d_clear_scratch.p;
+    // the scratch: [qx][qy][qz], max_points words each, every array at a multiple of 16 bytes (k_clear_points stores 16-byte pieces)
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, kClearMaskAt + mp, "the copy-back block", 3 * words, "the points' coordinate words", &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host, *const scratch = cb.scratch;
 
     GraspWords *const gw = reinterpret_cast<GraspWords *>(host + kClearGraspsAt);
     grasp_frames(grasps, stride, n_grasps, d.b.reach_q, gw);
     if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
     ImageDev md;
-    if ((rc = upload_image(e, f, m.mask, m.on_device, m.row_stride_bytes, 1, e->clear_io, kClearMaskAt, s, &md)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, f, m.mask, m.on_device, m.row_stride_bytes, 1, cb, kClearMaskAt, &md)) != HAF_OK) return rc;
     d.mask = static_cast<const unsigned char *>(md.src); d.mask_stride = md.row_stride;
     d.n_grasps = n_grasps;
     d.qx = reinterpret_cast<int *>(scratch);
@@ -55,12 +56,9 @@ int check_grasps_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask
     d.grasps = reinterpret_cast<const int *>(dev + kClearGraspsAt);
     d.rows = reinterpret_cast<unsigned *>(dev);
     HIPCHK(e, hipMemcpyAsync(dev + kClearGraspsAt, gw, K * kClearGraspBytes, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemsetAsync(dev, 0, K * kClearRowBytes, s));        // a reused block must not carry the last call's rows
+    HIPCHK(e, hipMemsetAsync(dev, 0, K * kClearRowBytes, s));        // the rows are accumulated into: the block carries some earlier call's bytes
     launch_clearance(d, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, K * kClearRowBytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, K * kClearRowBytes)) != HAF_OK) return rc;
     std::vector<int32_t> rows(K * kClearRowWords);
     for (size_t k = 0; k < K; k++) clearance_row_decode(reinterpret_cast<const uint32_t *>(host + k * kClearRowBytes), &rows[k * kClearRowWords]);
     clearance_finish(*gripper, gw, rows.data(), n_grasps, out, order, n_free);

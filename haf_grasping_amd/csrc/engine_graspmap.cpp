@@ -1,8 +1,10 @@
 // engine_graspmap.cpp -- haf_grasp_map, haf_cell_pose, haf_grasp_map_best and haf_grasp_map_labels: the votes of the last scored batch in the pixels of a
 // sensor frame (include/hafgrasp.h).  The device pass (graspmap.hip) reads the vote grids that batch left on the device and, for
 // haf_cell_pose, its height grids and records; nothing here writes to any of them, to the request's input block or to the raw areas
-// of haf_score_frames / haf_score_views: the frame's pixels, the roll transforms, the images and the mask live in one block of their
-// own (haf_engine::map).  The roll transforms are recomputed from the inputs the batch was scored with (LastCall::inputs) through
+// of haf_score_frames / haf_score_views: the frame's pixels, the roll transforms, the images and the mask live in the call's block
+// (call_io, the one every call outside the request path shares), laid out here as [best key + cell record: 64 bytes][R x CellGeo]
+// [vote | roll | cell images][mask bytes][a host frame's pixels][a host label image][label table: keys, counts][label output entries].
+// The roll transforms are recomputed from the inputs the batch was scored with (LastCall::inputs) through
 // fill_roll_geo: the header of the request's input block may have been overwritten since.  Built with -ffp-contract=off.
 #include "engine_state.h"
 
@@ -37,13 +39,6 @@ MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t ra
     return l;
 }
 
-int ensure_map(haf_engine *e, size_t bytes)
-{
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, e->map.ensure(bytes));
-    return HAF_OK;
-}
-
 // what every entry point here asks of the last batch; *rolls = the rolls that ran for the request (0: its budget was negative)
 int check_last(haf_engine *e, const char *who, int32_t request, int *rolls)
 {
@@ -67,33 +62,31 @@ int check_map_frame(haf_engine *e, const char *who, const haf_frame *f)
 
 // What every device pass over one checked frame starts with: the zeroed header and the roll transforms go up, a host frame's pixels are
 // staged (upload_frame, engine_stage.cpp); *fd = the frame as the kernels read it.  No synchronisation.
-int stage_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, FrameDev *fd_out)
+int stage_map(haf_engine *e, const CallBuffers &cb, int request, int rolls, const haf_frame &f, const MapLayout &l, FrameDev *fd_out)
 {
-    const haf_config &c = e->cfg;
     const LastCall &last = e->last;
-    const hipStream_t s = e->stream;
-    memset(e->map.host, 0, kMapHdr);
-    fill_cell_geo(c, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(e->map.host + l.geo));
-    HIPCHK(e, hipMemcpyAsync(e->map.dev.p, e->map.host, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, s));
-    *fd_out = describe_frame(f, e->map.dev.p + l.raw);
-    return f.on_device == 1 ? HAF_OK : upload_frame(e, f, e->map.host + l.raw, e->map.dev.p + l.raw, s);
+    memset(cb.host, 0, kMapHdr);
+    fill_cell_geo(e->cfg, last.inputs[(size_t)request], last.roll_first, rolls, reinterpret_cast<CellGeo *>(cb.host + l.geo));
+    HIPCHK(e, hipMemcpyAsync(cb.dev, cb.host, l.geo + (size_t)rolls * sizeof(CellGeo), hipMemcpyHostToDevice, cb.stream));
+    *fd_out = describe_frame(f, cb.dev + l.raw);
+    return f.on_device == 1 ? HAF_OK : upload_frame(e, f, cb.host + l.raw, cb.dev + l.raw, cb.stream);
 }
 
 // stage_map, then k_grasp_map on the engine's stream.  d_vote / d_roll / d_cell: where the images go (null: not wanted).  No synchronisation.
-int launch_map(haf_engine *e, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll, int *d_cell)
+int launch_map(haf_engine *e, const CallBuffers &cb, int request, int rolls, const haf_frame &f, const MapLayout &l, short *d_vote, short *d_roll,
+               int *d_cell)
 {
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
-    const hipStream_t s = e->stream;
     FrameDev fd;
     int rc;
-    if ((rc = stage_map(e, request, rolls, f, l, &fd)) != HAF_OK) return rc;
+    if ((rc = stage_map(e, cb, request, rolls, f, l, &fd)) != HAF_OK) return rc;
     const int H = c.grid_h, W = c.grid_w;
     float r_row, r_col;
     haf_pick_math::cell_reach(H, W, &r_row, &r_col);
     const short *ev = e->d_ev16.p + (size_t)request * last.R * (size_t)H * W;
-    launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(e->map.dev.p + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll,
-                     d_cell, s);
+    launch_grasp_map(fd, reinterpret_cast<const CellGeo *>(cb.dev + l.geo), rolls, last.roll_first, ev, H, W, r_row, r_col, d_vote, d_roll, d_cell,
+                     cb.stream);
     HIPCHK(e, hipGetLastError());
     return HAF_OK;
 }
@@ -107,24 +100,21 @@ int grasp_map_impl(haf_engine *e, int32_t request, const haf_frame *f, int16_t *
     const size_t n = (size_t)f->width * (size_t)f->height;
     // (device outputs: the images are the caller's, the block only holds the header, the transforms and a host frame's pixels)
     const MapLayout use = map_layout(e, out_on_device ? 0 : n, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
-    if ((rc = ensure_map(e, use.total)) != HAF_OK) return rc;
-    char *d = e->map.dev.p;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, "haf_grasp_map: ", use.total, "the map block", 0, nullptr, &cb)) != HAF_OK) return rc;
+    char *d = cb.dev;
     short *dv = !vote ? nullptr : out_on_device ? vote : reinterpret_cast<short *>(d + use.vote);
     short *dr = !roll ? nullptr : out_on_device ? roll : reinterpret_cast<short *>(d + use.roll);
     int *dc = !cell ? nullptr : out_on_device ? cell : reinterpret_cast<int *>(d + use.cell);
-    if ((rc = launch_map(e, request, rolls, *f, use, dv, dr, dc)) != HAF_OK) return rc;
-    if (!out_on_device) {
-        if (vote) HIPCHK(e, hipMemcpyAsync(e->map.host + use.vote, d + use.vote, n * 2, hipMemcpyDeviceToHost, e->stream));
-        if (roll) HIPCHK(e, hipMemcpyAsync(e->map.host + use.roll, d + use.roll, n * 2, hipMemcpyDeviceToHost, e->stream));
-        if (cell) HIPCHK(e, hipMemcpyAsync(e->map.host + use.cell, d + use.cell, n * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
-    if (!out_on_device) {
-        if (vote) memcpy(vote, e->map.host + use.vote, n * 2);
-        if (roll) memcpy(roll, e->map.host + use.roll, n * 2);
-        if (cell) memcpy(cell, e->map.host + use.cell, n * 4);
-    }
+    if ((rc = launch_map(e, cb, request, rolls, *f, use, dv, dr, dc)) != HAF_OK) return rc;
+    // (host outputs: three images, three copies; the last one is call_finish's)
+    const bool back = !out_on_device;
+    if (back && vote) HIPCHK(e, hipMemcpyAsync(cb.host + use.vote, d + use.vote, n * 2, hipMemcpyDeviceToHost, cb.stream));
+    if (back && roll) HIPCHK(e, hipMemcpyAsync(cb.host + use.roll, d + use.roll, n * 2, hipMemcpyDeviceToHost, cb.stream));
+    if ((rc = call_finish(e, cb, back && cell ? n * 4 : 0, use.cell)) != HAF_OK) return rc;
+    if (back && vote) memcpy(vote, cb.host + use.vote, n * 2);
+    if (back && roll) memcpy(roll, cb.host + use.roll, n * 2);
+    if (back && cell) memcpy(cell, cb.host + use.cell, n * 4);
     return HAF_OK;
 }
 
@@ -176,17 +166,14 @@ int cell_pose_checked(haf_engine *e, int request, int roll, int row, int col, ha
     const haf_config &c = e->cfg;
     const LastCall &last = e->last;
     int rc;
-    if (e->map.dev.n < kMapHdr && (rc = ensure_map(e, map_layout(e, 0, 0, 0).total)) != HAF_OK) return rc;
-    HIPCHK(e, hipSetDevice(c.device));
+    CallBuffers cb;                                         // (inside haf_grasp_map_best: the block is there and larger, nothing moves)
+    if ((rc = call_buffers(e, "haf_cell_pose: ", kMapHdr, "the record's block", 0, nullptr, &cb)) != HAF_OK) return rc;
     const int br = request * last.R + (roll - last.roll_first);
-    RollRecordDev *d_rec = reinterpret_cast<RollRecordDev *>(e->map.dev.p + kMapRecOff);
-    launch_cell_record(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, br, row, col, c.grid_h, c.grid_w, d_rec, e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->map.host + kMapRecOff, d_rec, sizeof(RollRecordDev), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    RollRecordDev *d_rec = reinterpret_cast<RollRecordDev *>(cb.dev + kMapRecOff);
+    launch_cell_record(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, br, row, col, c.grid_h, c.grid_w, d_rec, cb.stream);
+    if ((rc = call_finish(e, cb, sizeof(RollRecordDev), kMapRecOff)) != HAF_OK) return rc;
     RollRecordDev q;
-    memcpy(&q, e->map.host + kMapRecOff, sizeof q);
+    memcpy(&q, cb.host + kMapRecOff, sizeof q);
     return record_candidate(e, request, roll, q, out);
 }
 
@@ -211,29 +198,27 @@ int map_best_impl(haf_engine *e, int32_t request, const haf_frame *f, const uint
     if (mask && mask_row_stride < (size_t)f->width) return fail(e, HAF_E_ARG, "haf_grasp_map_best: mask_row_stride smaller than a row");
     const size_t n = (size_t)f->width * (size_t)f->height;
     const MapLayout l = map_layout(e, n, mask ? n : 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind));
-    if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
-    char *d = e->map.dev.p;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, "haf_grasp_map_best: ", l.total, "the map block", 0, nullptr, &cb)) != HAF_OK) return rc;
+    char *d = cb.dev;
     short *dv = reinterpret_cast<short *>(d + l.vote), *dr = reinterpret_cast<short *>(d + l.roll);
     int *dc = reinterpret_cast<int *>(d + l.cell);
-    if ((rc = launch_map(e, request, rolls, *f, l, dv, dr, dc)) != HAF_OK) return rc;
+    if ((rc = launch_map(e, cb, request, rolls, *f, l, dv, dr, dc)) != HAF_OK) return rc;
     ImageDev md;                                            // (a host mask; k_map_best reads it packed)
-    if ((rc = upload_image(e, *f, mask, 0, mask_row_stride, 1, e->map, l.mask, e->stream, &md)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, *f, mask, 0, mask_row_stride, 1, cb, l.mask, &md)) != HAF_OK) return rc;
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d);      // (zeroed by launch_map's header copy)
-    launch_map_best(dv, dr, static_cast<const unsigned char *>(md.src), (unsigned)n, min_vote, d_key, e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->map.host, d_key, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    launch_map_best(dv, dr, static_cast<const unsigned char *>(md.src), (unsigned)n, min_vote, d_key, cb.stream);
+    if ((rc = call_finish(e, cb, 8)) != HAF_OK) return rc;
     unsigned long long key;
-    memcpy(&key, e->map.host, 8);
+    memcpy(&key, cb.host, 8);
     if (key == 0ull) { *found = 0; return HAF_OK; }
     const size_t i = (size_t)haf_pick_math::pick_key_pixel(key);
     const int roll = haf_pick_math::pick_key_roll(key);
     if (i >= n || roll < e->last.roll_first || roll >= e->last.roll_first + e->last.R) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed key");
     int32_t ci = -1;
-    HIPCHK(e, hipMemcpyAsync(e->map.host + 8, dc + i, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    memcpy(&ci, e->map.host + 8, 4);
+    HIPCHK(e, hipMemcpyAsync(cb.host + 8, dc + i, 4, hipMemcpyDeviceToHost, cb.stream));      // (the best pixel's cell: a second, 4-byte round trip)
+    HIPCHK(e, hipStreamSynchronize(cb.stream));
+    memcpy(&ci, cb.host + 8, 4);
     const int W = e->cfg.grid_w;
     if (ci < 0 || ci >= e->cfg.grid_h * W) return fail(e, HAF_E_INTERNAL, "haf_grasp_map_best: malformed cell");
     haf_grasp_candidate cand;
@@ -262,13 +247,14 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     if (rolls == 0) return HAF_OK;                          // (a negative budget: no roll ran, no pixel has a roll)
     const size_t n = (size_t)f->width * (size_t)f->height, eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
     const MapLayout l = map_layout(e, 0, 0, f->on_device == 1 ? 0 : n * frame_pixel_bytes(f->kind), labels->on_device != 1 ? n * eb : 0, nl);
-    if ((rc = ensure_map(e, l.total)) != HAF_OK) return rc;
-    char *d = e->map.dev.p;
-    const hipStream_t s = e->stream;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, "haf_grasp_map_labels: ", l.total, "the map block", 0, nullptr, &cb)) != HAF_OK) return rc;
+    char *d = cb.dev;
+    const hipStream_t s = cb.stream;
     FrameDev fd;
-    if ((rc = stage_map(e, request, rolls, *f, l, &fd)) != HAF_OK) return rc;
+    if ((rc = stage_map(e, cb, request, rolls, *f, l, &fd)) != HAF_OK) return rc;
     ImageDev ld;
-    if ((rc = upload_image(e, *f, labels->data, labels->on_device, labels->row_stride_bytes, eb, e->map, l.labels, s, &ld)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, *f, labels->data, labels->on_device, labels->row_stride_bytes, eb, cb, l.labels, &ld)) != HAF_OK) return rc;
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(d + l.ltab);
     unsigned *d_cnt = reinterpret_cast<unsigned *>(d + l.ltab + nl * 8);
     LabelOutDev *d_out = reinterpret_cast<LabelOutDev *>(d + l.lout);
@@ -283,11 +269,8 @@ int map_labels_impl(haf_engine *e, int32_t request, const haf_frame *f, const ha
     HIPCHK(e, hipGetLastError());
     launch_label_records(fd, d_geo, rolls, last.roll_first, ev, reinterpret_cast<const float *>(e->d_heights.p) + br0 * HW, e->d_rec.p + br0, H, W,
                          r_row, r_col, n_labels, d_key, d_cnt, d_out, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->map.host + l.lout, d_out, nl * sizeof(LabelOutDev), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
-    return hand_over_picks(e, "haf_grasp_map_labels: ", reinterpret_cast<const LabelOutDev *>(e->map.host + l.lout), n_labels,
+    if ((rc = call_finish(e, cb, nl * sizeof(LabelOutDev), l.lout)) != HAF_OK) return rc;
+    return hand_over_picks(e, "haf_grasp_map_labels: ", reinterpret_cast<const LabelOutDev *>(cb.host + l.lout), n_labels,
                            [&](int32_t) { return (int)request; }, [](int32_t k) { return k + 1; }, f->width, picks, poses, order, n_found);
 }
 

@@ -3,7 +3,7 @@
 // input of engine_stage.cpp and a host label image through its upload_image, the table is zeroed, the one launch of labelshape.hip runs
 // on the engine's stream, ONE copy brings back the n_labels rows and ONE synchronisation ends the call.  The shapes are shape_from_row's
 // (labelshape_host.cpp) -- the code haf_measure_labels_ref ends with, on the same integers.  Nothing of the last scored batch is read or
-// written: the stage timings are not touched, and the block is this call's own.
+// written: the stage timings are not touched; the block is the one every such call shares (call_io).
 #include "engine_state.h"
 
 namespace haf_host {
@@ -27,27 +27,25 @@ int measure_labels_impl(haf_engine *e, const haf_frame *frame, const haf_label_i
     const size_t eb = (size_t)labels->elem_bytes, nl = (size_t)n_labels;
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
-    if ((rc = ensure_stage(e, e->shape_io, kShapeLabelsAt + (size_t)e->cfg.max_points * 2, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->shape_io.dev.p, *const host = e->shape_io.host;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, kShapeLabelsAt + (size_t)e->cfg.max_points * 2, "the copy-back block", 0, nullptr, &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host;
 
     ShapeDev d;
     memset(&d, 0, sizeof d);
     if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
     ImageDev ld;
-    if ((rc = upload_image(e, f, labels->data, labels->on_device, labels->row_stride_bytes, eb, e->shape_io, kShapeLabelsAt, s, &ld)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, f, labels->data, labels->on_device, labels->row_stride_bytes, eb, cb, kShapeLabelsAt, &ld)) != HAF_OK) return rc;
     d.labels = ld.src; d.label_stride = ld.row_stride;
     d.label_bytes = labels->elem_bytes;
     d.n_labels = n_labels;
     if (plane) memcpy(d.plane, plane, sizeof d.plane);
     d.use_plane = plane ? 1 : 0;
     d.table = reinterpret_cast<unsigned *>(dev);
-    HIPCHK(e, hipMemsetAsync(dev, 0, nl * kShapeRowBytes, s));      // a reused table must not carry the last call's rows
+    HIPCHK(e, hipMemsetAsync(dev, 0, nl * kShapeRowBytes, s));      // the rows are accumulated into: the block carries some earlier call's bytes
     launch_label_shape(d, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, nl * kShapeRowBytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, nl * kShapeRowBytes)) != HAF_OK) return rc;
     for (size_t l = 0; l < nl; l++) shape_from_row(reinterpret_cast<const uint32_t *>(host + l * kShapeRowBytes), &shapes[l]);
     return HAF_OK;
 }

@@ -8,7 +8,8 @@
 //   * ONE launch of k_roi_mark_objects marks the cell sets of all requests, where the composition has a mask upload and a launch each;
 //   * ONE launch pair (k_map_labels_objects, k_object_records), one copy back and one synchronisation give every object's pick, behind
 //     the request path's own copy back and wait.
-// Every refusal comes before the first stream operation and before any buffer is touched.  The call's block is haf_engine::map, laid
+// Every refusal comes before the first stream operation and before any buffer is touched.  The call's block (call_io, the one every call
+// outside the request path shares; this call HOLDS it across the request path, which therefore never asks for it: call_buffers) is laid
 // out here as [64 bytes unused][B * R x CellGeo][label -> request, for the cell sets][label -> request, for the picks][B keys][B counts]
 // [B x LabelOutDev][a host label image]: everything up to the keys goes up with one copy.  Built with -ffp-contract=off.
 #include "engine_state.h"
@@ -95,8 +96,8 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     const bool host_labels = labels->on_device != 1;
     const ObjLayout l = obj_layout((size_t)B, (size_t)R, (size_t)n_labels, host_labels ? n * eb : 0);
     if ((rc = ensure_roi_buffers(e, who)) != HAF_OK) return rc;
-    HIPCHK(e, hipSetDevice(c.device));
-    if ((rc = ensure_stage(e, e->map, l.total, who, "the call's block")) != HAF_OK) return rc;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, l.total, "the call's block", 0, nullptr, &cb)) != HAF_OK) return rc;
 
     for (int b = 0; b < B; b++) label_pick_none(&picks[b]);
     if (poses) memset(poses, 0, (size_t)B * sizeof *poses);
@@ -111,17 +112,17 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     RoiCall call;
     call.masked.assign((size_t)B, host_labels ? 0 : -1);
     ObjectsCall oc;
-    const hipStream_t s = e->stream;
-    char *d = e->map.dev.p;
+    const hipStream_t s = cb.stream;
+    char *d = cb.dev;
     if (any_runs) {                                       // (a batch whose every budget is negative runs nothing on the device)
         if (host_labels) count_object_pixels(*labels, frame->width, frame->height, n_labels, mark, call.masked);
-        for (int b = 0; b < B; b++) fill_cell_geo(c, in[b], 0, R, reinterpret_cast<CellGeo *>(e->map.host + l.geo) + (size_t)b * R);
-        memcpy(e->map.host + l.mark, mark.data(), (size_t)n_labels * sizeof(int));
-        memcpy(e->map.host + l.pick, pick.data(), (size_t)n_labels * sizeof(int));
-        HIPCHK(e, hipMemcpyAsync(d + l.geo, e->map.host + l.geo, l.keys - l.geo, hipMemcpyHostToDevice, s));
+        for (int b = 0; b < B; b++) fill_cell_geo(c, in[b], 0, R, reinterpret_cast<CellGeo *>(cb.host + l.geo) + (size_t)b * R);
+        memcpy(cb.host + l.mark, mark.data(), (size_t)n_labels * sizeof(int));
+        memcpy(cb.host + l.pick, pick.data(), (size_t)n_labels * sizeof(int));
+        HIPCHK(e, hipMemcpyAsync(d + l.geo, cb.host + l.geo, l.keys - l.geo, hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemsetAsync(d + l.keys, 0, l.out - l.keys, s));
         ImageDev ld;
-        if ((rc = upload_image(e, *frame, labels->data, labels->on_device, labels->row_stride_bytes, eb, e->map, l.labels, s, &ld)) != HAF_OK) return rc;
+        if ((rc = upload_image(e, *frame, labels->data, labels->on_device, labels->row_stride_bytes, eb, cb, l.labels, &ld)) != HAF_OK) return rc;
         oc.d_labels = ld.src; oc.label_stride = (size_t)ld.row_stride; oc.label_bytes = (int)eb; oc.n_labels = n_labels;
         oc.d_req_of_label = reinterpret_cast<const int *>(d + l.mark);
     }
@@ -146,12 +147,9 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     HIPCHK(e, hipGetLastError());
     launch_object_records(xyz, frame->width, (int)n, d_geo, B, R, last.roll_first, e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p),
                           e->d_rec.p, H, W, r_row, r_col, d_key, d_cnt, d_out, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->map.host + l.out, d_out, (size_t)B * sizeof(LabelOutDev), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, (size_t)B * sizeof(LabelOutDev), l.out)) != HAF_OK) return rc;
     // best first by haf_grasp_map_labels' key (pixel indices differ between objects: the order is total)
-    return hand_over_picks(e, who, reinterpret_cast<const LabelOutDev *>(e->map.host + l.out), B, [](int32_t b) { return (int)b; },
+    return hand_over_picks(e, who, reinterpret_cast<const LabelOutDev *>(cb.host + l.out), B, [](int32_t b) { return (int)b; },
                            [](int32_t b) { return b; }, frame->width, picks, poses, order, n_found);
 }
 

@@ -3,7 +3,7 @@
 // engine_stage.cpp and a host mask through its upload_image, the five launches of plane.hip run on the engine's stream, ONE copy brings
 // back the counters, the moments, the counts and the hypothesis words, and ONE synchronisation ends the call.  The plane itself is
 // plane_finish's (plane_host.cpp) -- the code haf_fit_plane_ref runs on the same integers.  Nothing of the last scored batch is read or
-// written: the stage timings are not touched, and the scratch is this call's own.
+// written: the stage timings are not touched; the block and the scratch are the ones every such call shares (call_io, call_scratch).
 #include "engine_state.h"
 
 namespace haf_host {
@@ -33,17 +33,18 @@ int fit_plane_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask, c
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
     const size_t hyps_at = plane_hyps_at(K), thr_at = plane_thr_at(K), mp = (size_t)e->cfg.max_points, blocks = plane_blocks(mp);
-    if ((rc = ensure_dev(e, e->d_plane_scratch, up16(mp * 12) + blocks * (kPlaneBlockPixels / 64) * 8 + blocks * 4, who,
-                         "the points, the usable bits and the block counts")) != HAF_OK) return rc;
-    if ((rc = ensure_stage(e, e->plane_io, kPlaneMaskAt + mp, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->plane_io.dev.p, *const host = e->plane_io.host, *const scratch = e->d_plane_scratch.p;
+    // the scratch: [x][y][z: max_points words each][a usable bit per pixel, 64-bit words][a count per block of 1024 pixels]
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, kPlaneMaskAt + mp, "the copy-back block", up16(mp * 12) + blocks * (kPlaneBlockPixels / 64) * 8 + blocks * 4,
+                           "the points, the usable bits and the block counts", &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host, *const scratch = cb.scratch;
 
     PlaneDev d;
     memset(&d, 0, sizeof d);
     if ((rc = frame_input_upload(e, f, *in, s, &d.f)) != HAF_OK) return rc;
     ImageDev md;
-    if ((rc = upload_image(e, f, m.mask, m.on_device, m.row_stride_bytes, 1, e->plane_io, kPlaneMaskAt, s, &md)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, f, m.mask, m.on_device, m.row_stride_bytes, 1, cb, kPlaneMaskAt, &md)) != HAF_OK) return rc;
     d.height = f.height;
     d.mask = static_cast<const unsigned char *>(md.src); d.mask_stride = md.row_stride;
     d.r = plane_rules(*p);
@@ -57,12 +58,9 @@ int fit_plane_impl(haf_engine *e, const haf_frame *frame, const haf_roi *mask, c
     d.counts = reinterpret_cast<int *>(dev + kPlaneCountsAt);
     d.hyps = reinterpret_cast<float *>(dev + hyps_at);
     d.thr = reinterpret_cast<float *>(dev + thr_at);
-    HIPCHK(e, hipMemsetAsync(dev, 0, hyps_at, s));         // counters, moments, counts: a reused block must not carry the last call's sums
+    HIPCHK(e, hipMemsetAsync(dev, 0, hyps_at, s));         // counters, moments, counts: the block carries some earlier call's bytes
     launch_plane(d, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, thr_at, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, thr_at)) != HAF_OK) return rc;
     unsigned cnt[4];
     memcpy(cnt, host, sizeof cnt);
     const int32_t *h_counts = reinterpret_cast<const int32_t *>(host + kPlaneCountsAt);

@@ -2,8 +2,8 @@
 // refusal comes before any device work (check_segment of segment_host.cpp, then the capacity); then the frame goes through the
 // single-frame input of engine_stage.cpp, the seven launches of segment.hip run on the engine's stream, ONE copy brings back the counters
 // and the per-label table -- and, for a host `labels`, the packed image behind them -- and ONE synchronisation ends the call.  Nothing of
-// the last scored batch is read or written: the stage timings are not touched, and the engine's own label image is a buffer only
-// haf_segment_cells and haf_transfer_labels share.
+// the last scored batch is read or written: the stage timings are not touched; the block and the scratch are the ones every such call
+// shares (call_io, call_scratch), and the engine's own label image is a buffer only haf_segment_cells and haf_transfer_labels share.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -28,10 +28,12 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
     const size_t mp = (size_t)e->cfg.max_points;
-    if ((rc = ensure_dev(e, e->d_seg_words, 2 * mp + segment_scan_blocks(mp), who, "the parent and size words")) != HAF_OK) return rc;
-    if ((rc = ensure_stage(e, e->seg_out, up16(kSegCounterBytes + (size_t)HAF_MAX_LABELS * kSegInfoBytes) + mp * 2, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->seg_out.dev.p, *const host = e->seg_out.host;
+    // the scratch: [parent][size: a word per pixel each][the scan's block totals], all read and written word by word
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, up16(kSegCounterBytes + (size_t)HAF_MAX_LABELS * kSegInfoBytes) + mp * 2, "the copy-back block",
+                           (2 * mp + segment_scan_blocks(mp)) * sizeof(int), "the parent and size words", &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host;
     // the copy-back block of this call: [counters][max_labels table entries][a host output image, packed]
     const size_t tab_at = kSegCounterBytes, img_at = up16(tab_at + (size_t)p->max_labels * kSegInfoBytes);
     OutputDev o;
@@ -43,7 +45,7 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     d.height = f.height;
     d.r = segment_rules(*p);
     d.min_pixels = p->min_pixels; d.max_labels = p->max_labels;
-    d.parent = e->d_seg_words.p;
+    d.parent = reinterpret_cast<int *>(cb.scratch);
     d.size = d.parent + px;
     d.totals = d.size + px;
     d.counters = reinterpret_cast<unsigned *>(dev);
@@ -52,10 +54,7 @@ int segment_frame_impl(haf_engine *e, const haf_frame *frame, const haf_segment_
     d.elem_bytes = elem_bytes;
     HIPCHK(e, hipMemsetAsync(d.counters, 0, kSegCounterBytes, s));
     launch_segment(d, s);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, img_at + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, img_at + (host_out ? px * elem : 0))) != HAF_OK) return rc;
     label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     unsigned cnt[4];
     memcpy(cnt, host, sizeof cnt);

@@ -1,6 +1,9 @@
 // engine_stage.cpp -- what the calls that take a haf_frame share on the engine's side (the device-free half: frame_stage.h):
 //   * a buffer on a call's first use (ensure_dev, ensure_stage, ensure_raw_xyz): allocated, or grown, before the call's first stream
 //     operation; a failure is HAF_E_DEVICE and leaves a StageBuf as it was and a DevBuf empty, so the next call tries again;
+//   * the way in and the way out of the calls that run outside the request path (call_buffers, call_finish): ONE block with its pinned
+//     twin and ONE device-only scratch serve them all, since each is live only inside one call and the calls run on one stream; the
+//     layout of both stays with the call, and so does writing every region before reading it;
 //   * a host frame's way up (upload_frame): its rows packed into the pinned half of a block and sent in pieces of kStagePiece, the DMA
 //     engine moving one while the host packs the next;
 //   * the single-frame input (frame_input_prepare, frame_input_upload): a depth frame through the raw area of haf_score_frames, an XYZ
@@ -30,6 +33,25 @@ int ensure_raw_xyz(haf_engine *e, const std::string &who)
     return ensure_stage(e, e->raw_xyz, (size_t)e->cfg.max_points * 12 + (size_t)e->cfg.max_clouds * HAF_MAX_VIEWS * 16, who, "the raw area of host XYZ views");
 }
 
+int call_buffers(haf_engine *e, const std::string &who, size_t io_bytes, const char *what_io, size_t scratch_bytes, const char *what_scratch,
+                 CallBuffers *out)
+{
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc;
+    if ((rc = ensure_dev(e, e->call_scratch, scratch_bytes, who, what_scratch)) != HAF_OK) return rc;
+    if ((rc = ensure_stage(e, e->call_io, io_bytes, who, what_io)) != HAF_OK) return rc;
+    *out = CallBuffers{e->stream, e->call_io.dev.p, e->call_io.host, e->call_scratch.p};
+    return HAF_OK;
+}
+
+int call_finish(haf_engine *e, const CallBuffers &cb, size_t back_bytes, size_t back_at)
+{
+    HIPCHK(e, hipGetLastError());
+    if (back_bytes) HIPCHK(e, hipMemcpyAsync(cb.host + back_at, cb.dev + back_at, back_bytes, hipMemcpyDeviceToHost, cb.stream));
+    HIPCHK(e, hipStreamSynchronize(cb.stream));
+    return check_guards(e);
+}
+
 int upload_frame(haf_engine *e, const haf_frame &f, char *host_at, char *dev_at, hipStream_t s)
 {
     const auto send = [&](size_t o, size_t bytes) { return hipMemcpyAsync(dev_at + o, host_at + o, bytes, hipMemcpyHostToDevice, s); };
@@ -56,13 +78,13 @@ int frame_input_upload(haf_engine *e, const haf_frame &f, StageBuf &area, hipStr
     return HAF_OK;
 }
 
-int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, StageBuf &block, size_t at, hipStream_t s, ImageDev *id)
+int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, const CallBuffers &cb, size_t at, ImageDev *id)
 {
     const size_t w = (size_t)f.width, h = (size_t)f.height;
-    *id = describe_image(data, on_device, row_stride_bytes, w, elem_bytes, block.dev.p + at);
+    *id = describe_image(data, on_device, row_stride_bytes, w, elem_bytes, cb.dev + at);
     if (!data || on_device == 1) return HAF_OK;
-    pack_rows(block.host + at, static_cast<const char *>(data), h, w, elem_bytes, elem_bytes, row_stride_bytes);
-    HIPCHK(e, hipMemcpyAsync(block.dev.p + at, block.host + at, h * w * elem_bytes, hipMemcpyHostToDevice, s));
+    pack_rows(cb.host + at, static_cast<const char *>(data), h, w, elem_bytes, elem_bytes, row_stride_bytes);
+    HIPCHK(e, hipMemcpyAsync(cb.dev + at, cb.host + at, h * w * elem_bytes, hipMemcpyHostToDevice, cb.stream));
     return HAF_OK;
 }
 

@@ -16,7 +16,8 @@
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_transfer.cpp  haf_transfer_labels: another camera's label image onto a depth frame's pixels, behind a z-buffer (transfer.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
-//   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input, a label image's way out
+//   engine_stage.cpp     what the calls that take a haf_frame share: first-use buffers, a host frame's and a side image's upload, the single-frame input, a label image's way out;
+//                        and the one block and one scratch of every call outside the request path: call_buffers, call_finish
 //   frame_stage.cpp      a haf_frame on its way to the device: descriptor, row packing, upload pieces, batch checks (no device: frame_stage.h, which also holds the checks of label and output images)
 // Private to csrc/: not installed, nothing here is part of the ABI (include/hafgrasp.h).  Every engine*.cpp unit above is
 // compiled twice, without and with -DHAF_TESTING (test_env below), for the product and the testing library.
@@ -429,14 +430,13 @@ struct haf_engine {
     long snap_cap = 0;              // evaluation slots the last snapshot covers
     DevBuf<char> snap_X;
     DevBuf<float> snap_gband, snap_ax;
-    // haf_top_grasps (engine_topgrasps.cpp), allocated on its first call: run-list scratch of its slots, the output block
-    // [hdr: 4 ints per (cloud, roll)][TopCandDev x depth per (cloud, roll)] and its pinned host copy
-    DevBuf<unsigned long long> d_top_scratch;
-    StageBuf top_out;
-    // haf_grasp_map (engine_graspmap.cpp), allocated on its first call and grown to the largest frame seen: the device block
-    // [best key + cell record: 64 bytes][R x CellGeo][vote | roll | cell images][mask bytes][a host frame's pixels][a host label image]
-    // [label table: keys, counts][label output entries] and its pinned host copy
-    StageBuf map;
+    // The calls that run outside the request path -- haf_segment_frame, haf_segment_cells, haf_fit_plane, haf_check_grasps,
+    // haf_measure_labels, haf_transfer_labels, the haf_grasp_map family with haf_cell_pose, haf_score_objects and haf_top_grasps -- share
+    // ONE block with its pinned twin and ONE device-only scratch (call_buffers, engine_stage.cpp): allocated by the first call that needs
+    // them, grown to the largest need seen, laid out by the call that is running, and nobody's once it has returned.  A call writes every
+    // region before it reads it (DESIGN.md 4 has the table): what it finds there is any other call's leftovers
+    StageBuf call_io;
+    DevBuf<char> call_scratch;
     // haf_score_frames_roi (engine_roi.cpp), allocated on its first call: the ROI cell sets -- one bit per cell, max_clouds x max_rolls
     // grids of H x roi_row_words(W) 64-bit words (roi.hip) -- and the area of uploaded host masks (max_points bytes and 16 bytes of slack
     // per view, every mask at a multiple of 16 bytes) with its pinned twin.  haf_score_views_roi shares both
@@ -446,35 +446,9 @@ struct haf_engine {
     // first call that asks for it.  Everything else of that call -- staged host exposures, the counters, a host output image -- passes
     // through the raw area above
     DevBuf<char> d_filter_image;
-    // haf_segment_frame (engine_segment.cpp), allocated by its first call: the parent and size words (4 bytes x max_points each) with the
-    // scan's block totals behind them; the block [counters][per-label table, HAF_MAX_LABELS entries][a host output image, 2 bytes x
-    // max_points] with its pinned twin; and, for labels == NULL, the engine's own image (2 bytes x max_points), which haf_segment_cells and haf_transfer_labels share
-    DevBuf<int> d_seg_words;
-    StageBuf seg_out;
+    // haf_segment_frame, haf_segment_cells and haf_transfer_labels with labels == NULL: the engine's own label image (2 bytes x max_points),
+    // allocated by the first call that asks for it.  Unlike the call's block it outlives its call: the caller reads it afterwards
     DevBuf<char> d_seg_image;
-    // haf_segment_cells (engine_cellsegment.cpp), allocated by its first call and grown when the frame or the grid grows: a cell word per
-    // pixel, then count, top, parent and size words per cell and the scan's block totals; the block [counters][per-label cells and tops]
-    // [per-label table][a host output image][the top-down label grid] with its pinned twin.  Its own image is d_seg_image above
-    DevBuf<int> d_cell_words;
-    StageBuf cell_out;
-    // haf_fit_plane (engine_plane.cpp), allocated by its first call: the points as three arrays of max_points words, one usable bit per
-    // pixel and one count per block of 1024 pixels behind them; the block [counters][moments][counts][hypothesis words][thresholds]
-    // [a host mask, max_points bytes] with its pinned twin
-    DevBuf<char> d_plane_scratch;
-    StageBuf plane_io;
-    // haf_check_grasps (engine_clearance.cpp), allocated by its first call: the points' coordinate words as three arrays of max_points
-    // words; the block [HAF_MAX_CHECK_GRASPS rows of 32 bytes][as many grasps of 64 bytes][a host mask, max_points bytes] with its
-    // pinned twin
-    DevBuf<char> d_clear_scratch;
-    StageBuf clear_io;
-    // haf_measure_labels (engine_labelshape.cpp), allocated by its first call: the block [per-label table, HAF_MAX_LABELS rows of 160 bytes]
-    // [a host label image, 2 bytes x max_points] with its pinned twin
-    StageBuf shape_io;
-    // haf_transfer_labels (engine_transfer.cpp), allocated by its first call: the z-buffer, a word per pixel of the label camera, grown to
-    // the largest camera seen; the block [counters][a host output image, 2 bytes x max_points][a host camera label image, 2 bytes x
-    // max_points] with its pinned twin.  Its own image is d_seg_image above
-    DevBuf<int> d_transfer_z;
-    StageBuf transfer_io;
 };
 
 namespace haf_host {
@@ -633,8 +607,23 @@ int upload_frame(haf_engine *e, const haf_frame &f, char *host_at, char *dev_at,
 // upload: a host frame goes up; *fd = the frame as the kernels read it
 int frame_input_prepare(haf_engine *e, const haf_frame &f, const std::string &who, StageBuf **area);
 int frame_input_upload(haf_engine *e, const haf_frame &f, StageBuf &area, hipStream_t s, FrameDev *fd);
-// a side image of frame f (f.height x f.width elements): a host one through `block` at `at`, one copy; *id = where the kernels read it
-int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, StageBuf &block, size_t at, hipStream_t s, ImageDev *id);
+// The way in and the way out of a call that runs outside the request path.  call_buffers, before the call's first stream operation:
+// hipSetDevice, then at least scratch_bytes of the shared scratch (0, nullptr: the call has none) and io_bytes of the shared block
+// (haf_engine::call_io); *out = the engine's stream and where the three lie.  Their contents are whatever the last such call left.
+// NOTHING ON THE REQUEST PATH MAY CALL IT (engine_request.cpp, engine_roi.cpp, the calibration of engine.cpp): haf_score_objects keeps
+// its label table and its staged label image in the block while its batch is scored (objects_mark_cells reads them there), and a
+// call_buffers in between could replace the block under it.
+// call_finish, behind the call's last launch: hipGetLastError, ONE copy of back_bytes at back_at from the block's device half to the
+// same place of its pinned half (none when 0), ONE synchronisation, then the testing build's guard check
+struct CallBuffers {
+    hipStream_t stream = nullptr;
+    char *dev = nullptr, *host = nullptr, *scratch = nullptr;
+};
+int call_buffers(haf_engine *e, const std::string &who, size_t io_bytes, const char *what_io, size_t scratch_bytes, const char *what_scratch,
+                 CallBuffers *out);
+int call_finish(haf_engine *e, const CallBuffers &cb, size_t back_bytes, size_t back_at = 0);
+// a side image of frame f (f.height x f.width elements): a host one through the call's block at `at`, one copy; *id = where the kernels read it
+int upload_image(haf_engine *e, const haf_frame &f, const void *data, int on_device, size_t row_stride_bytes, size_t elem_bytes, const CallBuffers &cb, size_t at, ImageDev *id);
 // the label image a call writes for frame f.  prepare, before the call's first stream operation: the engine's own image on its first use
 // when `labels` is null; *o = where the kernels write, a host image packed at packed_at inside the block the call copies back.  finish, after
 // the call's ONE copy back and ONE synchronisation: a host image's rows from host_packed_at, packed_at's pinned twin, to the caller's; *out_image (may be null) filled

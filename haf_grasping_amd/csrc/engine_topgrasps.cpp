@@ -1,6 +1,8 @@
 // engine_topgrasps.cpp -- haf_top_grasps: ranked, suppressed grasp candidates of the last scored batch (include/hafgrasp.h).  The
 // device pass (topgrasps.hip) leaves every (cloud, roll)'s first D entries of its in-roll greedy sequence; this file merges the rolls
-// of each cloud in key order with the cross-roll rule and the pose of haf_roll_pose.  Built with -ffp-contract=off.
+// of each cloud in key order with the cross-roll rule and the pose of haf_roll_pose.  The run-list scratch and the output block
+// [hdr: 4 ints per (cloud, roll)][TopCandDev x depth per (cloud, roll)] are the ones every call outside the request path shares
+// (call_scratch, call_io); a re-run with a larger depth asks for them again.  Built with -ffp-contract=off.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -82,7 +84,6 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
     // a C5 request at once: 288 x 4 MiB), the workgroups loop over the rest
     const size_t slot_words = HW;
     const int n_slots = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BR, 1024, ((size_t)2 << 30) / (2 * slot_words * 8)}));
-    if (const int rc = ensure_dev(e, e->d_top_scratch, (size_t)n_slots * 2 * slot_words, "haf_top_grasps: ", "the run-list scratch")) return rc;
     const size_t hdr_bytes = (size_t)BR * 4 * sizeof(int);      // 16-byte aligned: TopCandDev follows
     std::vector<haf_grasp_candidate> res((size_t)B * p->k);
     std::vector<int32_t> found((size_t)B, 0);
@@ -90,18 +91,18 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
     std::vector<int32_t> len;
     for (;;) {
         const size_t out_bytes = hdr_bytes + (size_t)BR * depth * sizeof(TopCandDev);
-        if (const int rc = ensure_stage(e, e->top_out, out_bytes, "haf_top_grasps: ", "the output block")) return rc;
-        int *d_hdr = reinterpret_cast<int *>(e->top_out.dev.p);
-        TopCandDev *d_cand = reinterpret_cast<TopCandDev *>(e->top_out.dev.p + hdr_bytes);
+        CallBuffers cb;
+        if (const int rc = call_buffers(e, "haf_top_grasps: ", out_bytes, "the output block", (size_t)n_slots * 2 * slot_words * sizeof(unsigned long long),
+                                        "the run-list scratch", &cb)) return rc;
+        int *d_hdr = reinterpret_cast<int *>(cb.dev);
+        TopCandDev *d_cand = reinterpret_cast<TopCandDev *>(cb.dev + hdr_bytes);
         Dims d{};
         d.H = H; d.W = W; d.R = R; d.B = B;
-        launch_top_grasps(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, e->d_top_scratch.p, slot_words, n_slots,
-                          d_hdr, d_cand, (int)depth, p->min_vote, p->cell_radius, d, e->stream);
-        HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipMemcpyAsync(e->top_out.host, e->top_out.dev.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        const int *hdr = reinterpret_cast<const int *>(e->top_out.host);
-        const TopCandDev *hc = reinterpret_cast<const TopCandDev *>(e->top_out.host + hdr_bytes);
+        launch_top_grasps(e->d_ev16.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_rec.p, reinterpret_cast<unsigned long long *>(cb.scratch), slot_words,
+                          n_slots, d_hdr, d_cand, (int)depth, p->min_vote, p->cell_radius, d, cb.stream);
+        if (const int rc = call_finish(e, cb, out_bytes)) return rc;
+        const int *hdr = reinterpret_cast<const int *>(cb.host);
+        const TopCandDev *hc = reinterpret_cast<const TopCandDev *>(cb.host + hdr_bytes);
         bool again = false;
         for (int b = 0; b < B && !again; b++) {
             found[(size_t)b] = 0;
@@ -137,7 +138,6 @@ static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_can
         if (depth >= (long)HW) return fail(e, HAF_E_INTERNAL, "haf_top_grasps: a roll's sequence outgrew its grid");
         depth = std::min<long>(2 * depth, (long)HW);
     }
-    if (const int rc = check_guards(e)) return rc;
     memcpy(out, res.data(), res.size() * sizeof(haf_grasp_candidate));
     memcpy(n_found, found.data(), found.size() * sizeof(int32_t));
     return HAF_OK;

@@ -4,8 +4,9 @@
 // image through its upload_image, the fill and the two launches of transfer.hip run on the engine's stream, ONE copy brings back the
 // counters -- and, for a host `labels`, the packed image behind them -- and ONE synchronisation ends the call.  A `zbuffer` that was
 // asked for is a debugging output and a copy of its own.  The constants are transfer_rules' (transfer_host.cpp), the function
-// haf_transfer_labels_ref forms them with.  Nothing of the last scored batch is read or written: the stage timings are not touched, and
-// the engine's own label image is the segmenters'.
+// haf_transfer_labels_ref forms them with.  Nothing of the last scored batch is read or written: the stage timings are not touched; the
+// block and the scratch, which is the z-buffer, are the ones every such call shares (call_io, call_scratch); the engine's own label
+// image is the segmenters'.
 #include "engine_state.h"
 
 namespace haf_host {
@@ -33,12 +34,12 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     if (cam_px > mp) return fail(e, HAF_E_CAPACITY, who + "more camera pixels than max_points");
     StageBuf *in = nullptr;
     if ((rc = frame_input_prepare(e, f, who, &in)) != HAF_OK) return rc;
-    if ((rc = ensure_dev(e, e->d_transfer_z, cam_px, who, "the z-buffer")) != HAF_OK) return rc;
     // the call's block, device and pinned: [counters][a host output image, packed][a host camera label image, packed]
     const size_t img_at = kTransferCounterBytes, cam_at = up16(img_at + mp * 2);
-    if ((rc = ensure_stage(e, e->transfer_io, cam_at + mp * 2, who, "the copy-back block")) != HAF_OK) return rc;
-    const hipStream_t s = e->stream;
-    char *const dev = e->transfer_io.dev.p, *const host = e->transfer_io.host;
+    CallBuffers cb;
+    if ((rc = call_buffers(e, who, cam_at + mp * 2, "the copy-back block", cam_px * sizeof(int32_t), "the z-buffer", &cb)) != HAF_OK) return rc;
+    const hipStream_t s = cb.stream;
+    char *const dev = cb.dev, *const host = cb.host;
     OutputDev o;
     if ((rc = label_output_prepare(e, f, labels, elem_bytes, row_stride_bytes, out_on_device, dev + img_at, who, &o)) != HAF_OK) return rc;
 
@@ -48,9 +49,9 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     haf_frame cam_shape{};                                // (upload_image reads a frame's width and height only)
     cam_shape.width = cam->width; cam_shape.height = cam->height;
     ImageDev ld;
-    if ((rc = upload_image(e, cam_shape, cl.data, cl.on_device, cl.row_stride_bytes, ceb, e->transfer_io, cam_at, s, &ld)) != HAF_OK) return rc;
+    if ((rc = upload_image(e, cam_shape, cl.data, cl.on_device, cl.row_stride_bytes, ceb, cb, cam_at, &ld)) != HAF_OK) return rc;
     d.r = transfer_rules(*cam, *p);
-    d.z = e->d_transfer_z.p;
+    d.z = reinterpret_cast<int *>(cb.scratch);
     d.labels = ld.src; d.label_stride = ld.row_stride;
     d.label_bytes = cl.elem_bytes;
     d.n_labels = n_labels;
@@ -60,10 +61,8 @@ int transfer_labels_impl(haf_engine *e, const haf_frame *depth, const haf_camera
     HIPCHK(e, hipMemsetAsync(d.counters, 0, kTransferCounterBytes, s));
     HIPCHK(e, launch_transfer(d, s));
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(host, dev, img_at + (host_out ? px * elem : 0), hipMemcpyDeviceToHost, s));
     if (zbuffer) HIPCHK(e, hipMemcpyAsync(zbuffer, d.z, cam_px * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    if ((rc = check_guards(e)) != HAF_OK) return rc;
+    if ((rc = call_finish(e, cb, img_at + (host_out ? px * elem : 0))) != HAF_OK) return rc;
     label_output_finish(o, f, elem_bytes, host + img_at, out_image);
     unsigned cnt[TRANSFER_CNT_WORDS];
     memcpy(cnt, host, sizeof cnt);
