@@ -146,6 +146,32 @@ assert CLEARANCE_DTYPE.itemsize == C.sizeof(GraspClearance) == 64
 MAX_CHECK_GRASPS = 4096              # HAF_MAX_CHECK_GRASPS: grasps of one haf_check_grasps call
 
 
+class OpeningParams(C.Structure):
+    """haf_opening_params: the openings and the sideways shift haf_fit_openings searches, metres, and when a placement is free"""
+    _fields_ = [("min_opening", C.c_float), ("max_opening", C.c_float), ("max_shift", C.c_float), ("max_hits", C.c_int32),
+                ("min_between", C.c_int32)]
+
+
+class GraspOpening(C.Structure):
+    """haf_grasp_opening: a grasp's placement, the counts there and what opening_finish derives from them"""
+    _fields_ = [("found", C.c_int32), ("j", C.c_int32), ("c", C.c_int32), ("sym_j", C.c_int32), ("n_between", C.c_int32),
+                ("n_finger", C.c_int32 * 2), ("n_palm", C.c_int32), ("n_finger_slab", C.c_int32), ("n_palm_slab", C.c_int32),
+                ("opening_m", C.c_double), ("shift_m", C.c_double), ("sym_opening_m", C.c_double)]
+
+
+class OpeningInfo(C.Structure):
+    """haf_opening_info: the integers of one haf_fit_openings call"""
+    _fields_ = [("shift", C.c_int32), ("half_bins", C.c_int32), ("tb", C.c_int32), ("pb", C.c_int32), ("j_min", C.c_int32),
+                ("j_max", C.c_int32), ("c_max", C.c_int32), ("reserved", C.c_int32), ("bin_m", C.c_double)]
+
+
+OPENING_DTYPE = np.dtype([("found", np.int32), ("j", np.int32), ("c", np.int32), ("sym_j", np.int32), ("n_between", np.int32),
+                          ("n_finger", np.int32, 2), ("n_palm", np.int32), ("n_finger_slab", np.int32), ("n_palm_slab", np.int32),
+                          ("opening_m", np.float64), ("shift_m", np.float64), ("sym_opening_m", np.float64)])
+assert OPENING_DTYPE.itemsize == C.sizeof(GraspOpening) == 64
+OPEN_BINS = 128                      # HAF_OPEN_BINS: words of one histogram of haf_fit_openings
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -318,6 +344,13 @@ def _bind(path, testing):
                                        C.c_void_p, C.POINTER(C.c_int32)]
     L.haf_check_grasps.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                    C.c_void_p, C.POINTER(C.c_int32)]
+    L.haf_opening_default.argtypes = [C.POINTER(OpeningParams)]
+    L.haf_opening_default.restype = None
+    L.haf_fit_openings_ref.argtypes = [C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.POINTER(OpeningParams), C.c_int32, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(OpeningInfo), C.c_void_p]
+    L.haf_fit_openings.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.POINTER(OpeningParams), C.c_int32, C.c_void_p,
+                                   C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(OpeningInfo), C.c_void_p]
+    L.haf_apply_opening.argtypes = [C.POINTER(GraspOutput), C.POINTER(GraspOpening), C.POINTER(GraspOutput)]
     L.haf_measure_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_measure_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_object_input.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_void_p, C.c_int32, C.POINTER(GraspInput), C.POINTER(C.c_int32)]
@@ -790,6 +823,55 @@ def check_grasps_ref(frame, grasps, gripper=None, mask=None):
     if rc != HAF_OK:
         raise HafError(rc, "haf_check_grasps_ref refused its arguments")
     return out, order
+
+
+def opening_params(**kw):
+    """haf_opening_params with the library's defaults (min_opening 0.01, max_opening 0.08, max_shift 0, max_hits 0, min_between 1) and
+    `kw` over them"""
+    p = OpeningParams()
+    lib().haf_opening_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_opening_params field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _fit_openings(call, frame, grasps, grip, params, mask, hist):
+    g = grip if grip is not None else gripper()
+    p = params if params is not None else opening_params()
+    roi, keep = _plane_mask(frame, mask)
+    arr, n, stride = _grasp_array(grasps)
+    out, order, nf, info = np.zeros(max(1, n), OPENING_DTYPE), np.zeros(max(1, n), np.int32), C.c_int32(0), OpeningInfo()
+    words = np.zeros((max(1, n), 2, OPEN_BINS), np.uint32) if hist else None
+    rc = call(C.byref(frame), C.byref(roi) if roi is not None else None, C.byref(g), C.byref(p), n, arr, stride, out.ctypes.data,
+              order.ctypes.data, C.byref(nf), C.byref(info), words.ctypes.data if hist else None)
+    facts = {f: getattr(info, f) for f, _ in OpeningInfo._fields_ if f != "reserved"}
+    return rc, (out[:n], order[:nf.value].copy(), facts) + ((words[:n], ) if hist else ())
+
+
+def fit_openings_ref(frame, grasps, gripper=None, params=None, mask=None, hist=False):
+    """haf_fit_openings_ref: the host definition of record of the smallest free opening at every grasp against the points of a host
+    Frame -> (OPENING_DTYPE [n_grasps], order: the indices of the found grasps in input order, info: dict of haf_opening_info's fields)
+    and, with hist=True, the histograms uint32 [n_grasps, 2, 128] as a fourth entry.  grasps, gripper and mask as check_grasps_ref's
+    (the gripper's opening is not read); params: opening_params(...), default the library's."""
+    rc, res = _fit_openings(lib().haf_fit_openings_ref, frame, grasps, gripper, params, mask, hist)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_fit_openings_ref refused its arguments")
+    return res
+
+
+def apply_opening(grasp, opening):
+    """haf_apply_opening: a grasp dict and its OPENING_DTYPE record (found == 1) -> the dict with averaged_grasp_point moved by shift_m
+    along the closing axis and the grasp points at -+ opening_m / 2 about it; every other entry is the input's"""
+    arr, _, _ = _grasp_array([grasp])
+    rec = GraspOpening.from_buffer_copy(np.asarray(opening, OPENING_DTYPE).tobytes())
+    out = GraspOutput()
+    rc = lib().haf_apply_opening(C.byref(arr[0]), C.byref(rec), C.byref(out))
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_apply_opening: a void grasp, or an opening that was not found")
+    return dict(grasp, grasp_point1=tuple(out.grasp_point1), grasp_point2=tuple(out.grasp_point2),
+                averaged_grasp_point=tuple(out.averaged_grasp_point))
 
 
 def _shape_plane(plane):
@@ -1403,6 +1485,13 @@ class Engine:
         rc, out, order = _check_grasps(lambda *a: self._L.haf_check_grasps(self._h, *a), frame, grasps, gripper, mask)
         self._check(rc)
         return out, order
+
+    def fit_openings(self, frame, grasps, gripper=None, params=None, mask=None, hist=False):
+        """haf_fit_openings: a Frame (any kind, host or device-resident) and grasps -> what fit_openings_ref gives, computed on the
+        device.  mask: a host uint8 [height, width] array or (device_ptr, row_stride_bytes); hist=True copies the histograms back."""
+        rc, res = _fit_openings(lambda *a: self._L.haf_fit_openings(self._h, *a), frame, grasps, gripper, params, mask, hist)
+        self._check(rc)
+        return res
 
     def measure_labels(self, frame, labels, n_labels=None, plane=None):
         """haf_measure_labels: a Frame (any kind, host or device-resident) and its label image (label_image(): a numpy uint8 / uint16

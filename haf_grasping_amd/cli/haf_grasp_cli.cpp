@@ -24,6 +24,11 @@
 //                                     scene's points inside the boxes of that parallel-jaw gripper (metres; the default is nominal, no
 //                                     real gripper's) placed at the candidate (haf_check_grasps).  The scene is the --depth frame, or
 //                                     the .pcd cloud as an N x 1 frame.  Without it no output line changes
+//   --fit-opening default|MIN,MAX[,SHIFT]   with --top-k: behind the "top" and "clear" lines one line per candidate,
+//                                     "open <rank> <found> opening <m> shift <m> between <n> hits <n> sym <m>": the smallest free opening
+//                                     between MIN and MAX metres of the --gripper (the default one without it; its own opening is not
+//                                     read), moved sideways by at most SHIFT, the points between the fingers and in the fingers and
+//                                     the palm there, and the smallest free opening without a shift (haf_fit_openings; same scene)
 //   --map-out PREFIX                  with --depth: the goal's votes in the pixels of the (first) depth image (haf_grasp_map), written as
 //                                     PREFIX.vote.pgm and PREFIX.roll.pgm: 16-bit binary PGMs of the image's size, sample = value + 32768
 //                                     (a pixel without a cell: vote -32768 -> 0, roll -1 -> 32767)
@@ -168,6 +173,7 @@ static void usage()
             "  --center x y z  --search-size x y  --approach x y z  --max-time s  --show-only-best  --gripper-width w\n"
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m] [--gripper default|OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H]\n"
+            "           [--fit-opening default|MIN,MAX[,SHIFT]]\n"
             "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
@@ -182,7 +188,8 @@ static void usage()
 }
 
 // --gripper: the clearance of the ranked candidates (haf_check_grasps) against `scene`
-struct ClearOptions { bool on = false; haf_gripper gripper; };
+// --fit-opening: their smallest free openings (haf_fit_openings) against the same scene
+struct ClearOptions { bool on = false; haf_gripper gripper; bool fit = false; haf_opening_params opening; };
 
 // --gripper default | OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H (metres; max_hits and min_between stay the library's)
 static bool parse_gripper(const char *arg, haf_gripper *g)
@@ -194,6 +201,19 @@ static bool parse_gripper(const char *arg, haf_gripper *g)
     if (sscanf(arg, "%f,%f,%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &tail) != 8) return false;
     g->opening = v[0]; g->finger_thickness = v[1]; g->finger_breadth = v[2]; g->tip_depth = v[3]; g->finger_length = v[4];
     g->palm_width = v[5]; g->palm_breadth = v[6]; g->palm_height = v[7];
+    return true;
+}
+
+// --fit-opening default | MIN,MAX[,SHIFT] (metres; max_hits and min_between stay the library's)
+static bool parse_opening(const char *arg, haf_opening_params *p)
+{
+    haf_opening_default(p);
+    if (strcmp(arg, "default") == 0) return true;
+    float v[3] = {0.0f, 0.0f, 0.0f};
+    char tail = 0;
+    const int n = sscanf(arg, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail);
+    if (n != 2 && n != 3) return false;
+    p->min_opening = v[0]; p->max_opening = v[1]; p->max_shift = v[2];
     return true;
 }
 
@@ -213,7 +233,7 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
         *rc = 1;
     }
     for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
-    if (!clear || !clear->on || !scene) return;
+    if (!clear || !(clear->on || clear->fit) || !scene) return;
     // the same candidates once more, as poses: "clear <rank> <free> fingers <n0> <n1> palm <n> between <n> width <w> offset <o> top <t>"
     std::vector<haf_grasp_candidate> cand((size_t)std::max(1, cfg.max_clouds) * (size_t)std::max(1, tp.k));
     std::vector<int32_t> found((size_t)std::max(1, cfg.max_clouds), 0);
@@ -221,15 +241,31 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
     const int32_t n = found[0];
     if (n < 1) return;
     std::vector<haf_grasp_clearance> rows((size_t)n);
-    if (haf_check_grasps(eng, scene, nullptr, &clear->gripper, n, cand.data(), sizeof(haf_grasp_candidate), rows.data(), nullptr, nullptr) != HAF_OK) {
+    if (clear->on && haf_check_grasps(eng, scene, nullptr, &clear->gripper, n, cand.data(), sizeof(haf_grasp_candidate), rows.data(), nullptr, nullptr) != HAF_OK) {
         fprintf(stderr, "%s: --gripper: %s\n", what, haf_last_error(eng));
         *rc = 1;
         return;
     }
-    for (int32_t t = 0; t < n; t++) {
+    for (int32_t t = 0; clear->on && t < n; t++) {
         const haf_grasp_clearance &c = rows[(size_t)t];
         printf("clear %d %d fingers %d %d palm %d between %d width %.9g offset %.9g top %.9g\n", t + 1, c.free, c.n_finger[0], c.n_finger[1], c.n_palm,
                c.n_between, c.width_m, c.offset_m, c.top_m);
+    }
+    if (!clear->fit) return;
+    // and once more: "open <rank> <found> opening <m> shift <m> between <n> hits <n> sym <m>"
+    haf_gripper gripper = clear->gripper;
+    if (!clear->on) haf_gripper_default(&gripper);
+    std::vector<haf_grasp_opening> fits((size_t)n);
+    if (haf_fit_openings(eng, scene, nullptr, &gripper, &clear->opening, n, cand.data(), sizeof(haf_grasp_candidate), fits.data(), nullptr, nullptr,
+                         nullptr, nullptr) != HAF_OK) {
+        fprintf(stderr, "%s: --fit-opening: %s\n", what, haf_last_error(eng));
+        *rc = 1;
+        return;
+    }
+    for (int32_t t = 0; t < n; t++) {
+        const haf_grasp_opening &o = fits[(size_t)t];
+        printf("open %d %d opening %.9g shift %.9g between %d hits %d sym %.9g\n", t + 1, o.found, o.opening_m, o.shift_m, o.n_between,
+               o.n_finger[0] + o.n_finger[1] + o.n_palm, o.sym_opening_m);
     }
 }
 
@@ -938,6 +974,7 @@ int main(int argc, char **argv)
         else if (a == "--hypotheses") hypotheses = true;
         else if (a == "--grid-out") { need(1); grid_out = argv[++i]; }
         else if (a == "--top-k") { need(1); top_k = atoi(argv[++i]); }
+        else if (a == "--fit-opening") { need(1); if (!parse_opening(argv[++i], &map_opt.clear.opening)) { usage(); return 2; } map_opt.clear.fit = true; }
         else if (a == "--gripper") { need(1); if (!parse_gripper(argv[++i], &map_opt.clear.gripper)) { usage(); return 2; } map_opt.clear.on = true; }
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }

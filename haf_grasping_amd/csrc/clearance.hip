@@ -16,30 +16,24 @@
 //                           workgroups, four to five waves per SIMD, and the waves hide one another's latency.  Every lane of a
 //                           wave reads the tile at the same address -- a broadcast, four points per ds_read_b128, no bank conflict
 //                           -- and nothing crosses lanes inside the loop.  The near test comes first, three subtractions and three
-//                           unsigned compares (clear_near_window below); a wave whose ballot of near lanes is zero -- for four points at once, then per point -- skips the nine multiply-adds
+//                           unsigned compares (clear_near_window of grasp_lane.h); a wave whose ballot of near lanes is zero -- for four points at once, then per point -- skips the nine multiply-adds
 //                           and the region tests: most points of a frame are far from most grasps.  At the end waves 1..3 hand their
 //                           accumulators to wave 0 through LDS, and ONE set of integer atomics goes out per (workgroup, grasp), only
 //                           where n_near > 0 and only for the words that are not empty.  The extremes travel in the zeroed rows as
 //                           label_shape.h's words (a maximum x as shape_enc(x), a minimum as shape_enc(~x)): atomicMax on unsigned
 //                           words whose zero is the empty value.  A void grasp, and a lane beyond n_grasps, carries reach_q = -1.
+// The workgroup's geometry, the staging of a tile, a lane's grasp and its near window are grasp_lane.h's, which k_grasp_slab of opening.hip
+// shares; k_clear_points is launched by that file too (launch_clear_points).
 // No kernel waits for another workgroup; the rows are integer sums, minima and maxima, which do not depend on the order of arrival.
 // Bounds: a pixel and its mask byte are loaded and its words stored only for i < n (a whole group has i0 + G <= n); the tile is staged
 // from qx / qy / qz only for i < n, a slot beyond n being the far word; the LDS tile is indexed below kClearTile and the hand-over
 // block below its 3 x 8 x 64 words; a grasp's words are loaded and its row updated only for k < n_grasps.
-#include "frame_group.h"
-#include "kernels.h"
+#include "grasp_lane.h"
 
 namespace haf {
 
 using namespace haf_clear_math;
 using haf_shape_math::shape_enc;
-
-constexpr int kClearThreads = 256;
-constexpr int kClearWaves = kClearThreads / 64;
-constexpr int kClearTile = 256;                           // points a workgroup stages
-constexpr int kClearQuarter = kClearTile / kClearWaves;   // points a wave walks
-constexpr int kClearSlots = 64;                           // grasps of a workgroup: one per lane of each wave
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 template <int KIND>
 __global__ __launch_bounds__(kFrameThreads) void k_clear_points(const ClearDev d)
@@ -78,17 +72,6 @@ __global__ __launch_bounds__(kFrameThreads) void k_clear_points(const ClearDev d
 // a lane's accumulators: the row of clearance_rules.h with the extremes as plain int32 (INT32_MAX / INT32_MIN while empty)
 struct ClearAcc { int near, f0, f1, palm, between, smin, smax, umax; };
 
-// clear_near in two instructions per axis.  With lo = o - reach_q and span = 2 reach_q: |q - o| <= reach_q  <=>  0 <= q - lo <= span,
-// and q - lo lies in (-2^18, 2^30 + 2^17) as an integer, so its unsigned word is <= span exactly when that holds (a negative one wraps
-// above 2^31 > span).  A void grasp, and a lane without one, carries lo = INT32_MAX and span = 0: q - lo is 0 only for q = INT32_MAX,
-// which no word is (|q| <= 2^30)
-struct ClearWindow { unsigned lo[3], span; };
-
-__device__ __forceinline__ bool clear_near_window(const ClearWindow &w, int x, int y, int z)
-{
-    return ((unsigned)x - w.lo[0] <= w.span) & ((unsigned)y - w.lo[1] <= w.span) & ((unsigned)z - w.lo[2] <= w.span);
-}
-
 __device__ __forceinline__ void clear_one(const ClearBounds &b, const GraspWords &g, const ClearWindow &w, int x, int y, int z, ClearAcc &a)
 {
     const bool near = clear_near_window(w, x, y, z);
@@ -112,31 +95,13 @@ __global__ __launch_bounds__(kClearThreads) void k_grasp_clear(const ClearDev d)
     __shared__ __attribute__((aligned(16))) int s_y[kClearTile];
     __shared__ __attribute__((aligned(16))) int s_z[kClearTile];
     __shared__ int s_acc[kClearWaves - 1][kClearRowWords][kClearSlots];
-    const unsigned n = (unsigned)d.f.n, base = blockIdx.x * (unsigned)kClearTile;
-#pragma unroll
-    for (int pass = 0; pass < kClearTile / kClearThreads; pass++) {
-        const unsigned t = (unsigned)pass * kClearThreads + threadIdx.x, i = base + t;
-        const bool in = i < n;
-        s_x[t] = in ? d.qx[i] : kClearFarWord; s_y[t] = in ? d.qy[i] : 0; s_z[t] = in ? d.qz[i] : 0;
-    }
+    stage_clear_tile(d, s_x, s_y, s_z);
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned k = blockIdx.y * (unsigned)kClearSlots + lane;
     const bool live = k < (unsigned)d.n_grasps;
     GraspWords g;
-    {
-        const global_ptr<const v4i> w = as_global<const v4i>(d.grasps + (size_t)(live ? k : 0u) * kClearGraspWords);
-        const v4i w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-        g.a[0] = w0.x; g.a[1] = w0.y; g.a[2] = w0.z; g.b[0] = w0.w; g.b[1] = w1.x; g.b[2] = w1.y; g.c[0] = w1.z; g.c[1] = w1.w;
-        g.c[2] = w2.x; g.o[0] = w2.y; g.o[1] = w2.z; g.o[2] = w2.w;
-        g.reach_q = live ? w3.x : -1;
-    }
     ClearWindow win;
-    {
-        const bool valid = g.reach_q >= 0;
-        win.span = valid ? 2u * (unsigned)g.reach_q : 0u;
-#pragma unroll
-        for (int j = 0; j < 3; j++) win.lo[j] = valid ? (unsigned)(g.o[j] - g.reach_q) : 0x7FFFFFFFu;
-    }
+    load_grasp_lane(d, k, live, g, win);
     __syncthreads();
     ClearAcc a = {0, 0, 0, 0, 0, INT32_MAX, INT32_MIN, INT32_MIN};
     const v4i *x4 = reinterpret_cast<const v4i *>(s_x) + wave * (kClearQuarter / 4);
@@ -181,14 +146,20 @@ __global__ __launch_bounds__(kClearThreads) void k_grasp_clear(const ClearDev d)
     }
 }
 
-void launch_clearance(const ClearDev &d, hipStream_t s)
+void launch_clear_points(const ClearDev &d, hipStream_t s)
 {
-    const unsigned n = (unsigned)d.f.n;                   // (n <= 2^28: at most 2^20 tiles)
+    const unsigned n = (unsigned)d.f.n;
     with_frame_kind(d.f.kind, [&](auto K) {
         constexpr int KIND = decltype(K)::value;
         const unsigned groups = (n + frame_group<KIND>() - 1) / frame_group<KIND>();
         hipLaunchKernelGGL(k_clear_points<KIND>, dim3((groups + kFrameThreads - 1) / kFrameThreads), dim3(kFrameThreads), 0, s, d);
     });
+}
+
+void launch_clearance(const ClearDev &d, hipStream_t s)
+{
+    const unsigned n = (unsigned)d.f.n;                   // (n <= 2^28: at most 2^20 tiles)
+    launch_clear_points(d, s);
     const unsigned tiles = (n + kClearTile - 1) / kClearTile, slots = ((unsigned)d.n_grasps + kClearSlots - 1) / kClearSlots;
     hipLaunchKernelGGL(k_grasp_clear, dim3(tiles, slots), dim3(kClearThreads), 0, s, d);
 }

@@ -1,6 +1,6 @@
 // clearance_host.cpp -- the host side of haf_check_grasps that needs neither a device nor an engine: haf_gripper_default, the checks of
 // the frame, the mask, the gripper and the grasp list (both entry points apply them), gripper_rules -- the gripper's integer bounds and
-// its reach --, grasp_frame -- THE twelve words of a grasp, in double, which both entry points call --, clearance_finish -- the derived
+// its reach --, grasp_axes and grasp_frame -- THE axes of a grasp in double and its twelve words, which both entry points call --, clearance_finish -- the derived
 // fields, order and n_free from the integer rows, which both call too -- and haf_check_grasps_ref, the definition of record of
 // clearance_rules.h's rules; the kernels of clearance.hip are tested against it word for word.  Built with -ffp-contract=off like every
 // unit (build.py: FLAGS).
@@ -72,30 +72,37 @@ int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripp
     return HAF_OK;
 }
 
+bool grasp_axes(const haf_grasp_output &g, double *a, double *b, double *c)
+{
+    const double *in[4] = {g.grasp_point1, g.grasp_point2, g.averaged_grasp_point, g.approach_vector};
+    for (const double *v : in)
+        for (int j = 0; j < 3; j++)
+            if (!std::isfinite(v[j])) return false;
+    double gv[3];
+    const double an = std::sqrt(g.approach_vector[0] * g.approach_vector[0] + g.approach_vector[1] * g.approach_vector[1] +
+                                g.approach_vector[2] * g.approach_vector[2]);
+    if (!(an >= 1e-6)) return false;
+    for (int j = 0; j < 3; j++) { a[j] = g.approach_vector[j] / an; gv[j] = g.grasp_point2[j] - g.grasp_point1[j]; }
+    const double gn = std::sqrt(gv[0] * gv[0] + gv[1] * gv[1] + gv[2] * gv[2]);
+    if (!(gn >= 1e-6)) return false;
+    const double ga = gv[0] * a[0] + gv[1] * a[1] + gv[2] * a[2];
+    for (int j = 0; j < 3; j++) c[j] = gv[j] - ga * a[j];
+    const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    if (!(cn >= 1e-3 * gn)) return false;
+    for (int j = 0; j < 3; j++) {
+        c[j] /= cn;
+        if (std::fabs(g.averaged_grasp_point[j]) > 16.0) return false;
+    }
+    b[0] = a[1] * c[2] - a[2] * c[1]; b[1] = a[2] * c[0] - a[0] * c[2]; b[2] = a[0] * c[1] - a[1] * c[0];
+    return true;
+}
+
 void grasp_frame(const haf_grasp_output &g, int32_t reach_q, GraspWords *w)
 {
     memset(w, 0, sizeof *w);
     w->reach_q = -1;                                      // void until every test has passed
-    const double *in[4] = {g.grasp_point1, g.grasp_point2, g.averaged_grasp_point, g.approach_vector};
-    for (const double *v : in)
-        for (int j = 0; j < 3; j++)
-            if (!std::isfinite(v[j])) return;
-    double a[3], gv[3], c[3];
-    const double an = std::sqrt(g.approach_vector[0] * g.approach_vector[0] + g.approach_vector[1] * g.approach_vector[1] +
-                                g.approach_vector[2] * g.approach_vector[2]);
-    if (!(an >= 1e-6)) return;
-    for (int j = 0; j < 3; j++) { a[j] = g.approach_vector[j] / an; gv[j] = g.grasp_point2[j] - g.grasp_point1[j]; }
-    const double gn = std::sqrt(gv[0] * gv[0] + gv[1] * gv[1] + gv[2] * gv[2]);
-    if (!(gn >= 1e-6)) return;
-    const double ga = gv[0] * a[0] + gv[1] * a[1] + gv[2] * a[2];
-    for (int j = 0; j < 3; j++) c[j] = gv[j] - ga * a[j];
-    const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-    if (!(cn >= 1e-3 * gn)) return;
-    for (int j = 0; j < 3; j++) {
-        c[j] /= cn;
-        if (std::fabs(g.averaged_grasp_point[j]) > 16.0) return;
-    }
-    const double b[3] = {a[1] * c[2] - a[2] * c[1], a[2] * c[0] - a[0] * c[2], a[0] * c[1] - a[1] * c[0]};
+    double a[3], b[3], c[3];
+    if (!grasp_axes(g, a, b, c)) return;
     for (int j = 0; j < 3; j++) {
         w->a[j] = (int32_t)lrint((double)kClearAxisOne * a[j]);
         w->b[j] = (int32_t)lrint((double)kClearAxisOne * b[j]);

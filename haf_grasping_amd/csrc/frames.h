@@ -10,6 +10,7 @@
 #include "cell_segment_rules.h"
 #include "transfer_rules.h"
 #include "clearance_rules.h"
+#include "opening_rules.h"
 
 #include <string>
 
@@ -89,6 +90,8 @@ haf_transfer_math::TransferRules transfer_rules(const haf_camera &cam, const haf
 int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripper *gripper, int32_t n_grasps, const void *grasps,
                     size_t grasp_stride_bytes, const haf_grasp_clearance *out, haf_clear_math::ClearBounds *bounds, std::string &err);
 bool gripper_rules(const haf_gripper &g, haf_clear_math::ClearBounds *b);
+// the unit axes of a grasp in double: a along the approach vector, c the closing axis, b = a x c; false for a void grasp
+bool grasp_axes(const haf_grasp_output &g, double *a, double *b, double *c);
 void grasp_frame(const haf_grasp_output &g, int32_t reach_q, haf_clear_math::GraspWords *w);
 void grasp_frames(const void *grasps, size_t stride, int32_t n, int32_t reach_q, haf_clear_math::GraspWords *w);
 // a grasp's row of the device table (clearance_rules.h: kClearRowWords words, as copied back) -> the plain integers of the host's row
@@ -96,5 +99,16 @@ void clearance_row_decode(const uint32_t *dev_row, int32_t *row);
 // THE derived fields of every grasp from its integer row (rows: n x kClearRowWords host words), order and n_free (either may be null)
 void clearance_finish(const haf_gripper &g, const haf_clear_math::GraspWords *w, const int32_t *rows, int32_t n, haf_grasp_clearance *out,
                       int32_t *order, int32_t *n_free);
+// opening_host.cpp, shared by haf_fit_openings_ref and haf_fit_openings: every refusal that needs no engine -- check_clearance's for the
+// gripper at max_opening, then the parameters' (*rules filled when all pass); THE integers of a call from the gripper's and the
+// parameters' doubles, false with the reason for what the call refuses; what a caller is told about them
+int check_openings(const haf_frame *frame, const haf_roi *mask, const haf_gripper *gripper, const haf_opening_params *params, int32_t n_grasps,
+                   const void *grasps, size_t grasp_stride_bytes, const haf_grasp_opening *out, haf_open_math::OpenRules *rules, std::string &err);
+bool opening_rules(const haf_gripper &g, const haf_opening_params &p, haf_open_math::OpenRules *r, std::string &why);
+void opening_info(const haf_open_math::OpenRules &r, haf_opening_info *info);
+// THE derived fields of every grasp from its integer row (rows: n x kOpenRowWords host words; a void grasp's is not read), order and
+// n_found (either may be null)
+void opening_finish(const haf_open_math::OpenRules &r, const haf_clear_math::GraspWords *w, const int32_t *rows, int32_t n,
+                    haf_grasp_opening *out, int32_t *order, int32_t *n_found);
 
 }  // namespace haf

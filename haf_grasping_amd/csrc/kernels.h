@@ -674,6 +674,20 @@ struct ClearDev {
 };
 // the two launches of one call, in stream order: the points' words, then grasps x points
 void launch_clearance(const ClearDev &d, hipStream_t s);
+// the first of them alone, k_clear_points<KIND>: f, mask and mask_stride are read, qx / qy / qz written (haf_fit_openings shares it)
+void launch_clear_points(const ClearDev &d, hipStream_t s);
+// haf_fit_openings (opening.hip).  c: the frame, the mask, the points' words and the grasps as haf_check_grasps' kernels read them (c.b
+// and c.rows are not read); r: the call's integers (opening_rules.h); hist: c.n_grasps x 2 x kOpenBins words, a grasp's finger-slab
+// histogram then its palm-slab one, zeroed by the caller; rows: c.n_grasps x kOpenRowWords words, every one written.  All of it device
+// memory
+struct OpenDev {
+    ClearDev c;
+    haf_open_math::OpenRules r;
+    unsigned *hist;
+    int *rows;
+};
+// the three launches of one call, in stream order: the points' words, grasps x points into the histograms, one wave's search per grasp
+void launch_openings(const OpenDev &d, hipStream_t s);
 // haf_measure_labels (labelshape.hip): one frame and its label image as the kernel reads them -- a kernel argument, so every field is a
 // scalar load.  f: the frame (dst and count are not read); labels: label_bytes 1 or 2 per pixel, rows label_stride bytes apart; plane:
 // read when use_plane is set; table: n_labels rows of haf_shape_math::kShapeRowWords words (label_shape.h), zeroed by the caller.  All

@@ -149,6 +149,26 @@ class CalcGraspPointsServer:
         return [(GraspOutputMsg(self.base_frame_id, cands[i]["eval"], cands[i]["grasp_point1"], cands[i]["grasp_point2"],
                                 cands[i]["averaged_grasp_point"], cands[i]["approach_vector"], cands[i]["roll"]), rows[i].copy()) for i in order]
 
+    def fitted_grasps(self, frame, k=None, gripper=None, params=None, mask=None, **top_params):
+        """The ranked candidates of the last execute*() for which SOME opening of the gripper fits (haf_fit_openings on haf_top_grasps'
+        output): per candidate the smallest free opening between params.min_opening and params.max_opening, the gripper moved sideways
+        by at most params.max_shift (capi.opening_params(...); the gripper's own opening is not read).  The found ones are returned
+        as (GraspOutputMsg, opening) pairs, best first: the message carries the APPLIED opening -- averaged_grasp_point moved by shift_m
+        along the closing axis, the grasp points opening_m apart about it (capi.apply_opening) --, opening is one capi.OPENING_DTYPE
+        record.  frame, mask and top_params as free_grasps takes them; the ranking itself is top_grasps()', unchanged."""
+        if k is not None:
+            top_params["k"] = k
+        cands = self.engine.top_grasps(**top_params)[0]
+        if not cands:
+            return []
+        rows, order, _ = self.engine.fit_openings(frame, cands, gripper, params, mask)
+        out = []
+        for i in order:
+            g = capi.apply_opening(cands[i], rows[i])
+            out.append((GraspOutputMsg(self.base_frame_id, g["eval"], g["grasp_point1"], g["grasp_point2"], g["averaged_grasp_point"],
+                                       g["approach_vector"], g["roll"]), rows[i].copy()))
+        return out
+
     def grasp_map(self, frame, want=("vote", "roll")):
         """The last execute*()'s votes in the pixels of `frame` (haf_grasp_map): any capi.depth_frame / capi.xyz_frame -- the scored
         view, another camera, the registered RGB view -- -> dict of [height, width] images: vote int16 (capi.MAP_NO_CELL where no roll

@@ -1032,9 +1032,9 @@ int  haf_transfer_labels(haf_engine *e, const haf_frame *depth, const haf_camera
  *                 rises toward the palm; all 0 without a between point.  free = 1 when n_finger[0] + n_finger[1] + n_palm <= max_hits
  *                 and n_between >= min_between, else 0.  order (may be NULL): the indices of the grasps with free = 1, in input order;
  *                 *n_free (may be NULL) their number.
- * The defaults of haf_gripper_default are NOMINAL figures, no real gripper's drawing.  Not modelled: other gripper shapes, an opening
- * per grasp, the search for the smallest free opening, the arm behind the palm.  Points are tested, not surfaces: a sparse cloud can
- * let a finger through.
+ * The defaults of haf_gripper_default are NOMINAL figures, no real gripper's drawing.  Not modelled: other gripper shapes, the arm
+ * behind the palm.  An opening per grasp and the search for the smallest free one are haf_fit_openings' (below), not this call's.
+ * Points are tested, not surfaces: a sparse cloud can let a finger through.
  *
  * grasps points at the first haf_grasp_output; grasp i is read at grasps + i * grasp_stride_bytes, so a haf_grasp_candidate[] of
  * haf_top_grasps or haf_grasp_map_labels goes in as it is with its sizeof as the stride.
@@ -1072,6 +1072,83 @@ int  haf_check_grasps_ref(const haf_frame *frame, const haf_roi *mask /* may be 
 int  haf_check_grasps(haf_engine *e, const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_gripper *gripper,
                       int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes, haf_grasp_clearance *out /* [n_grasps] */,
                       int32_t *order /* [n_grasps], may be NULL */, int32_t *n_free /* may be NULL */);
+
+/* ---- the smallest free opening at a grasp pose, and the sideways shift that goes with it (csrc/opening.hip) -------------------------
+ * haf_check_grasps tests ONE opening, centred on the grasp point.  This call answers, for each of n_grasps poses and in one pass over
+ * the scene's points, which is the smallest opening of the same gripper -- moved sideways along the closing axis by at most max_shift --
+ * at which nothing lies in the fingers or the palm and the object lies between the fingers.  Integers throughout.
+ *
+ *   inputs        haf_check_grasps': one haf_frame of any kind, an optional haf_roi, a haf_gripper whose `opening`, max_hits and
+ *                 min_between are NOT read, n_grasps in 1..HAF_MAX_CHECK_GRASPS read at a stride.  Scene points, the usable rule, a
+ *                 grasp's twelve words, void grasps, s / t / u and every bound W() are exactly that call's (above).
+ *   params        haf_opening_params: min_opening, max_opening, max_shift in metres; max_hits, min_between as haf_gripper's.
+ *   slabs         of a near point.  finger slab: U0 <= u < U1, |t| <= W(finger_breadth/2).  palm slab: U1 <= u <= U1 + W(palm_height),
+ *                 |t| <= W(palm_breadth/2).  Neither depends on the opening, and a point is in at most one.
+ *   bin width     E = max(W(max_opening/2) + W(finger_thickness), W(palm_width/2)) + W(max_shift); shift = the smallest value >= 0 with
+ *                 (E >> shift) + 2 <= 64; B = 1 << shift, in units of 2^-26 m; half_bins = (E >> shift) + 2.  (The default gripper and
+ *                 parameters: shift 16, a bin of 0.98 mm; with max_shift = 1 cm: shift 17.)
+ *   bin           bin(s) = s >= 0 ? s >> shift : ~((-s) >> shift), symmetric about 0: bin j >= 0 is [jB, (j+1)B), bin -j-1 is
+ *                 (-(j+1)B, -jB].  A point at s = -jB belongs to finger 0 and one at s = +jB to finger 1, as in haf_check_grasps.
+ *   histograms    per grasp two of HAF_OPEN_BINS = 128 uint32 words, finger slab then palm slab, word = bin + 64; only points with
+ *                 -half_bins <= bin < half_bins are counted.
+ *   near          haf_check_grasps' test with reach_q from the box es = half_bins B 2^-26 m along c, et and eu as there; a reach
+ *                 above 1 m is refused.  No counted point fails it (csrc/opening_rules.h).
+ *   placement     (j, c): a half opening of j bins, shifted by c bins.  tb = (W(finger_thickness) >> shift) + 1, pb = (W(palm_width/2)
+ *                 >> shift) + 1, c_max = W(max_shift) >> shift, j_min = max(1, (W(min_opening/2) + B - 1) >> shift), j_max =
+ *                 W(max_opening/2) >> shift.  Its bin sets: between = finger-slab bins [c-j, c+j); finger 0 = [c-j-tb, c-j); finger 1 =
+ *                 [c+j, c+j+tb); palm = palm-slab bins [c-pb, c+pb).  All of them lie inside [-63, 63) (csrc/opening_rules.h).
+ *   result        a placement is FREE when finger 0 + finger 1 + palm <= max_hits and between >= min_between.  The result is the first
+ *                 free placement in the order j ascending, |c| ascending, c ascending over j_min..j_max, -c_max..c_max; sym_j is the
+ *                 first free j with c = 0, 0 when there is none.
+ *   row           found (1, 0, or -1 for a void grasp, zeros elsewhere), j, c, sym_j, the four counts at the chosen placement (0
+ *                 without one), the two slabs' totals over the counted bins, and by ONE host function both entry points call:
+ *                 opening_m = 2 j B 2^-26, shift_m = c B 2^-26, sym_opening_m = 2 sym_j B 2^-26.
+ *   order         (may be NULL) the indices of the grasps with found = 1, in input order; *n_found (may be NULL) their number.
+ *   info          (may be NULL) shift, half_bins, tb, pb, j_min, j_max, c_max and bin_m = B 2^-26.
+ *   hist          (may be NULL) uint32 [n_grasps][2][HAF_OPEN_BINS]: the histograms, copied back only when asked for.
+ * Relation to haf_check_grasps: with opening = sym_opening_m (exact in float32), max_hits and min_between the parameters' and all else
+ * equal, that call reports the same n_between, n_finger[i] <= ours and n_palm <= ours (its finger is W(finger_thickness) thick against
+ * tb B > that, its palm W(palm_width/2) wide against pb B > that): found at c = 0 implies free = 1 there.
+ * Not modelled: a thickness or a palm per finger (one of each is shared), shapes other than boxes, surfaces (points are tested: a sparse
+ * cloud can let a finger through); the resolution of an opening and of a shift is one bin.
+ *
+ * haf_fit_openings_ref: the host definition of record -- no device, no engine, a host frame and a host mask only.
+ * haf_fit_openings: equal to it in every word of every row, of order, n_found, info and the histograms; a host or device-resident
+ * frame and mask; three launches on the engine's stream (the points' words, grasps x points into the histograms, one wave's search per
+ * grasp), ONE copy back and ONE synchronisation.  Like haf_check_grasps it neither reads nor changes last-batch state or stage
+ * timings and shares that call's block and scratch (12 bytes x max_points and 1 KiB per grasp).
+ * haf_apply_opening (host only, double): *out = *in with averaged_grasp_point moved by shift_m along the closing axis (the c of
+ * haf_check_grasps' grasp, from in's own fields) and grasp_point1 / 2 at -+ opening_m / 2 about it; everything else copied.
+ * HAF_E_ARG for a null pointer, an opening with found != 1 or a void grasp.
+ * Refusals, all before any work, nothing written -- everything haf_check_grasps refuses (the gripper's opening aside), and HAF_E_ARG
+ * for null params, a parameter that is not finite or negative, min_opening > max_opening, j_max < j_min, a reach above 1 m. */
+#define HAF_OPEN_BINS 128
+typedef struct haf_opening_params {
+    float   min_opening, max_opening;   /* between the fingers' inner faces, metres                                  */
+    float   max_shift;                  /* the gripper's centre may move this far from the grasp point, either way   */
+    int32_t max_hits, min_between;      /* as haf_gripper's                                                          */
+} haf_opening_params;
+typedef struct haf_grasp_opening {
+    int32_t found;                      /* 1 a free placement, 0 none, -1 a void grasp */
+    int32_t j, c, sym_j;                /* bins */
+    int32_t n_between, n_finger[2], n_palm;      /* at the chosen placement */
+    int32_t n_finger_slab, n_palm_slab;          /* the histograms' totals  */
+    double  opening_m, shift_m, sym_opening_m;
+} haf_grasp_opening;
+typedef struct haf_opening_info {
+    int32_t shift, half_bins, tb, pb, j_min, j_max, c_max, reserved;
+    double  bin_m;
+} haf_opening_info;
+void haf_opening_default(haf_opening_params *p);   /* 0.01f, 0.08f, 0.0f, 0, 1 */
+int  haf_fit_openings_ref(const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_gripper *gripper,
+                          const haf_opening_params *params, int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes,
+                          haf_grasp_opening *out /* [n_grasps] */, int32_t *order /* [n_grasps], may be NULL */,
+                          int32_t *n_found /* may be NULL */, haf_opening_info *info /* may be NULL */, uint32_t *hist /* may be NULL */);
+int  haf_fit_openings(haf_engine *e, const haf_frame *frame, const haf_roi *mask /* may be NULL */, const haf_gripper *gripper,
+                      const haf_opening_params *params, int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes,
+                      haf_grasp_opening *out /* [n_grasps] */, int32_t *order /* [n_grasps], may be NULL */,
+                      int32_t *n_found /* may be NULL */, haf_opening_info *info /* may be NULL */, uint32_t *hist /* host, may be NULL */);
+int  haf_apply_opening(const haf_grasp_output *in, const haf_grasp_opening *opening, haf_grasp_output *out);
 
 int haf_abi_version(void);
 

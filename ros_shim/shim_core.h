@@ -184,6 +184,32 @@ inline int top_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_t
     return HAF_OK;
 }
 
+// top_hypotheses for a parallel-jaw gripper: the same ranked candidates, each with the smallest free opening of `gripper` against the
+// scene's points in `scene` (haf_fit_openings; the gripper's own opening is not read) APPLIED -- the grasp points that opening apart about
+// a centre moved sideways by the shift found (haf_apply_opening) --, as hypothesis strings, best first; a candidate without a free
+// opening is left out.  An adapter would publish them where it publishes top_hypotheses', for a planner that commands the gripper's
+// opening from the distance of the two grasp points.  Returns the engine's status; on failure *err carries haf_last_error().
+inline int fitted_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_top_params &p, const haf_frame &scene, const haf_gripper &gripper,
+                             const haf_opening_params &opening, std::vector<std::string> *lines, std::string *err)
+{
+    const size_t clouds = (size_t)(cfg.max_clouds > 0 ? cfg.max_clouds : 1), k = (size_t)(p.k > 0 ? p.k : 1);
+    std::vector<haf_grasp_candidate> cand(clouds * k);
+    std::vector<int32_t> n(clouds, 0);
+    int rc = haf_top_grasps(engine, &p, cand.data(), n.data());
+    if (rc == HAF_OK && n[0] > 0) {
+        std::vector<haf_grasp_opening> fits((size_t)n[0]);
+        rc = haf_fit_openings(engine, &scene, nullptr, &gripper, &opening, n[0], cand.data(), sizeof(haf_grasp_candidate), fits.data(), nullptr,
+                              nullptr, nullptr, nullptr);
+        for (int32_t i = 0; rc == HAF_OK && i < n[0]; i++) {
+            haf_grasp_output applied;
+            if (fits[(size_t)i].found == 1 && haf_apply_opening(&cand[(size_t)i].grasp, &fits[(size_t)i], &applied) == HAF_OK)
+                lines->push_back(hypothesis_string(applied, cfg.roll_step_deg));
+        }
+    }
+    if (rc != HAF_OK && err) *err = haf_last_error(engine);
+    return rc;
+}
+
 // The best grasp per object of the engine's last scored goal from an instance-label image that goes with `frame` (haf_grasp_map_labels):
 // one line "<label> <u> <v> <hypothesis string>" per object that has a pixel with a vote >= min_vote, best first -- the next OBJECT for a
 // planner whose first choice fails, where top_hypotheses gives the next grasp.  An adapter with a label topic synchronised with the depth
