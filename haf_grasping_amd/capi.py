@@ -381,6 +381,8 @@ def _bind(path, testing):
         L.haf_test_scale_host.argtypes = [C.c_double] * 5
         L.haf_test_sigma_upper.restype = C.c_double
         L.haf_test_sigma_upper.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.haf_test_table_digest.argtypes = [E, C.c_char_p, C.c_int]
+        L.haf_test_host_table_digest.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
         L.haf_test_decq4_scr.restype = C.c_double
         L.haf_test_decq4_scr.argtypes = [C.c_float]
         L.haf_test_split3.restype = C.c_double

@@ -1,6 +1,8 @@
 // engine_state.h -- the engine object and what the host-side translation units of libhafgrasp.so share:
 //   engine.cpp           create / destroy, calibration of the screening pass at creation, the C-ABI entry points
-//   engine_tables.cpp    model, range and feature tables -> device tables and the constants of every guard band; buffers
+//   engine_tables.cpp    build_tables: the builder's inputs, the builder, upload_tables (the one upload of the model tables); buffers
+//   model_tables.cpp     model, range and feature tables -> the host image of every device table and the constants of every guard band,
+//                        as named stages (no device, no environment: model_tables.h)
 //   engine_request.cpp   one request: stage launches, decision tiers, host resolution of the residual cases, the batch wrapper
 //   engine_geometry.cpp  per-roll transforms, the rotated-rectangle scalars, the final grasp pose (host fp32, glibc)
 //   engine_debug.cpp     haf_get_roll_grid / haf_debug_fetch* (intermediate stages for the parity tests)
@@ -26,6 +28,7 @@
 #include "../../include/hafgrasp.h"
 #include "kernels.h"
 #include "parsers.h"
+#include "model_tables.h"
 #include "frame_stage.h"
 #include "decq.h"
 #include "engine_internal.h"
@@ -479,8 +482,6 @@ constexpr int kStrictSlots = 64;     // evaluations per pass of the strict tier'
 
 constexpr size_t kCntBytes = up16(CNT_COUNT * sizeof(int));                 // the counters' share of the output block (out_block)
 
-// contraction mode: default = screening pass + three-pass refinement; HAF_FLAG_SPLIT_F16 = three passes for everything;
-// HAF_FLAG_FP32_MFMA = one fp32 MFMA pass for everything
 // does the low-rank form serve this engine's full-size requests?  (engine_request.cpp applies it per request: whole requests of at
 // least large_evals evaluations on grids that go through the parallel integral image)
 inline bool lr_typical(const haf_engine *e)
@@ -494,13 +495,7 @@ inline double variant_cost(const haf_engine *e, int v)
     if (!lr_typical(e) || (v == SCREEN_PLAIN && !e->lr_plain_available)) return kVariantCost[v];
     return kVariantCostLr[v];
 }
-enum { MODE_SCREEN = 0, MODE_SPLIT = 1, MODE_F32 = 2 };
-inline int contraction_mode(const haf_config &c)
-{
-    if (c.flags & HAF_FLAG_FP32_MFMA) return MODE_F32;
-    if (c.flags & HAF_FLAG_SPLIT_F16) return MODE_SPLIT;
-    return MODE_SCREEN;
-}
+// (contraction_mode and its MODE_* values: model_tables.h)
 
 // ---- the routing of one decision stage (engine_request.cpp: plan_tiers) ----
 // The tier lists by name; each list's length lives in its own counter (list_counter), CNT_T1_N being the one re-count (what tier 1
@@ -575,10 +570,10 @@ inline void mark(haf_engine *e, int idx)
     if (e->cfg.flags & HAF_FLAG_PROFILE) (void)hipEventRecord(e->ev[idx], e->stream);
 }
 
-// engine_tables.cpp
-int label_grid_value(int label);
-double sigma_upper_bound(const double *M, int n, int d);
+// engine_tables.cpp (label_grid_value, header_grid_value, sigma_upper_bound: model_tables.h)
+TableSwitches table_switches();       // the testing build's environment switches of the table work
 int build_tables(haf_engine *e);
+int upload_tables(haf_engine *e, const ModelTables &t);
 int alloc_buffers(haf_engine *e);
 // engine_request.cpp
 int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, const haf_grasp_input *in, int32_t roll_first,

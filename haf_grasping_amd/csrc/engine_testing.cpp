@@ -337,6 +337,187 @@ double haf_test_scale_host(double q4, double fmin, double fmax, double lower, do
 
 // host-side pieces of the screening band (tests/test_host_cpu.py)
 double haf_test_sigma_upper(const double *M, int n, int d) { return sigma_upper_bound(M, n, d); }
+}  // extern "C"
+
+// ---- digests of the model tables (tests/test_tables_gpu.py, tests/golden/table_digests.json) ----
+// One line "name=<64-bit FNV-1a, 16 hex digits>" per device table, per parameter struct and one for the scalars and flags that the
+// table work sets.  A table's digest is that of its bytes as they lie in memory (an unallocated table: the digest of nothing).  A
+// parameter struct is hashed member by member, so that neither its device pointers nor its padding bytes count.
+namespace {
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void add(const void *p, size_t n)
+    {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; }
+    }
+    template <class T> Fnv &operator<<(const T &x) { static_assert(std::is_arithmetic_v<T>, "one member at a time"); add(&x, sizeof x); return *this; }
+};
+struct DigestText {
+    std::string text;
+    void line(const char *name, const Fnv &f)
+    {
+        char buf[96];
+        snprintf(buf, sizeof buf, "%s=%016llx\n", name, (unsigned long long)f.h);
+        text += buf;
+    }
+};
+Fnv digest_of(const ScreenParams &p)
+{
+    Fnv f;
+    f << p.c << p.v_max << p.dv_max << p.das_max << p.as_max << p.sigma_v << p.sigma_dv << p.sqrt_cmax << p.scale << p.eta_abs << p.sigma_dk
+      << p.ck_max << p.ubar2 << p.acc_rel << p.g_norm << p.hd_norm << p.fast_groups << p.extra_groups << p.cr << p.cr_poly << p.cr_nN << p.cr_nM
+      << p.cr_nHabs << p.cr_nDabs << p.cr_nHaa << p.cr_Ca << p.cr_Cq1 << p.cr_Cqq << p.cr_Babs << p.cr_qmax << p.cr_dqmax << p.cr_gnorm
+      << p.cr_mu_norm << p.cr_mu_norm_t << p.lr << p.lr_rho;
+    return f;
+}
+Fnv digest_of(const LrBand &p)
+{
+    Fnv f;
+    f << p.sigB << p.sigAbsB << p.acc10 << p.acc6 << p.qmax << p.dqmax << p.rmax << p.nN1 << p.nM1 << p.nN2 << p.nHabs << p.nDabs << p.nRabs
+      << p.sQb << p.sQtaa << p.Ca << p.Cq1 << p.Cqq << p.Babs << p.gnorm << p.mu_norm << p.mu_norm_t << p.eta_abs << p.scale << p.poly << p.pad
+      << p.sig_q << p.sig_dq << p.sig_r << p.sbq << p.sbr << p.rho_norm << p.gt_norm << p.bg_norm << p.bh_norm << p.gabsB;
+    return f;
+}
+Fnv digest_of(const CrParams &p) { Fnv f; f << p.B0 << p.rho; return f; }
+Fnv digest_of(const CrT1Params &p)
+{
+    Fnv f;
+    f << p.B0 << p.rho << p.c << p.nN << p.nM << p.nHabs << p.nDabs << p.nHaa << p.Ca << p.Cqq << p.Babs << p.qmax << p.dqmax << p.acc_rel
+      << p.dp_rel << p.dp_abs << p.sum_rel << p.scale << p.guard_abs << p.gv0 << p.gv1 << p.pad;
+    return f;
+}
+Fnv digest_of(const SvmParams &p)
+{
+    Fnv f;
+    f << p.two_gamma2 << p.neg_gamma2 << p.rho << p.guard_acc << p.guard_dot << p.guard_abs << p.as_max << p.guard_dot_p << p.guard_acc0
+      << p.guard_acc0_s << p.guard_acc_l << p.gv0 << p.gv1 << p.sqrt_cmax;
+    return f;
+}
+Fnv digest_of(const ExactParams &p)
+{
+    Fnv f;
+    f << p.gamma << p.rho << p.lower << p.upper << p.guard2 << p.as_max1 << p.gamma2 << p.n_sv << p.n_sv_pad << p.kx << p.gv0 << p.gv1
+      << p.kernel_type << p.degree << p.coef0;
+    return f;
+}
+Fnv digest_of(const I8Params &p)
+{
+    Fnv f;
+    f << p.gamma << p.rho << p.gamma2 << p.drop << p.delta << p.dq_scale << p.s_max << p.guard_scale << p.n_sv_pad << p.gv0 << p.gv1 << p.pad;
+    return f;
+}
+Fnv digest_of(const ProbParams &p) { Fnv f; f << p.A << p.B << p.gv0 << p.gv1 << p.hdr << p.host_all << p.dec_slack; return f; }
+void digest_structs(DigestText &t, const ScreenParams &screen, const ScreenParams &screen_cr, const ScreenParams &screen_lrp, const LrBand &lr_band,
+                    const CrParams &crp, const CrT1Params &crt1, const SvmParams &svm, const ExactParams &exact, const I8Params &i8,
+                    const ProbParams &prob)
+{
+    t.line("screen", digest_of(screen)); t.line("screen_cr", digest_of(screen_cr)); t.line("screen_lrp", digest_of(screen_lrp));
+    t.line("lr_band", digest_of(lr_band)); t.line("crp", digest_of(crp)); t.line("crt1", digest_of(crt1)); t.line("svm", digest_of(svm));
+    t.line("exact", digest_of(exact)); t.line("i8", digest_of(i8)); t.line("prob", digest_of(prob));
+}
+// the scalars and flags, in this order; flags as one byte each
+struct TableScalars {
+    int nf, kx, n_sv_tiles, sv_tile_neg, n_sv_pad;
+    double sum_abs_coef;
+    bool screen_active, cr_available, lr_available, lr_fused, lr_plain_available, t1_cr_available, i8_active;
+    int lr_rank, gv0, gv1;
+    bool prob_mode;
+    double host_exp_thr;
+};
+void digest_scalars(DigestText &t, const TableScalars &s)
+{
+    Fnv f;
+    f << s.nf << s.kx << s.n_sv_tiles << s.sv_tile_neg << s.n_sv_pad << s.sum_abs_coef << s.screen_active << s.cr_available << s.lr_available
+      << s.lr_fused << s.lr_plain_available << s.t1_cr_available << s.i8_active << s.lr_rank << s.gv0 << s.gv1 << s.prob_mode << s.host_exp_thr;
+    t.line("scalars", f);
+}
+int digest_hand_over(const DigestText &t, char *out, int cap)
+{
+    if (!out || cap <= 0 || t.text.size() + 1 > (size_t)cap) return HAF_E_CAPACITY;
+    memcpy(out, t.text.c_str(), t.text.size() + 1);
+    return HAF_OK;
+}
+template <class T> bool digest_device(DigestText &t, const char *name, const DevBuf<T> &b)
+{
+    Fnv f;
+    if (b.p && b.n) {
+        std::vector<char> h(b.n * sizeof(T));
+        if (hipMemcpy(h.data(), b.p, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+        f.add(h.data(), h.size());
+    }
+    t.line(name, f);
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+// the tables of a created engine as they lie on the device, its parameter structs and its scalars -> text of at most cap bytes
+int haf_test_table_digest(haf_engine *e, char *out, int cap)
+{
+    if (!e) return HAF_E_ARG;
+    if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return HAF_E_DEVICE;
+    DigestText t;
+    bool ok = true;
+#define HAF_DIGEST(name) ok = ok && digest_device(t, #name, e->name)
+    HAF_DIGEST(d_fd); HAF_DIGEST(d_svt); HAF_DIGEST(d_svt_h); HAF_DIGEST(d_sd); HAF_DIGEST(d_sd3); HAF_DIGEST(d_fd_slot); HAF_DIGEST(d_corr);
+    HAF_DIGEST(d_svt0); HAF_DIGEST(d_svt0_cr); HAF_DIGEST(d_sd_cr); HAF_DIGEST(d_sd3_cr); HAF_DIGEST(d_fd_slot_cr); HAF_DIGEST(d_corr_cr);
+    HAF_DIGEST(d_lr_btiles); HAF_DIGEST(d_lr_btiles_in); HAF_DIGEST(d_svt_lr); HAF_DIGEST(d_corr_lrp); HAF_DIGEST(d_svt_h_cr);
+    HAF_DIGEST(d_t1_tab); HAF_DIGEST(d_sv64); HAF_DIGEST(d_coef64); HAF_DIGEST(d_sv_i8);
+#undef HAF_DIGEST
+    if (!ok) return HAF_E_DEVICE;
+    digest_structs(t, e->screen, e->screen_cr, e->screen_lrp, e->lr_band, e->crp, e->crt1, e->svm, e->exact, e->i8, e->prob);
+    digest_scalars(t, TableScalars{e->nf, e->kx, e->n_sv_tiles, e->sv_tile_neg, e->n_sv_pad, e->sum_abs_coef, e->screen_active, e->cr_available,
+                                   e->lr_available, e->lr_fused, e->lr_plain_available, e->t1_cr_available, e->i8_active, e->lr_rank, e->gv0,
+                                   e->gv1, e->prob_mode, e->host_exp_thr});
+    return digest_hand_over(t, out, cap);
+}
+
+// The same digests, under the same names, of what the device-free builder makes of cfg's files and flags (model_tables.cpp): no device
+// is touched.  kappa, kappa16: haf_engine::mfma_kappa*; the environment switches are the testing build's.  A file that does not load
+// or a refusal of the builder comes back as its code, with its text in msg (msg_cap bytes).
+int haf_test_host_table_digest(const haf_config *cfg, double kappa, double kappa16, char *out, int cap, char *msg, int msg_cap)
+{
+    if (!cfg || !cfg->feature_file || !cfg->range_file || !cfg->model_file) return HAF_E_ARG;
+    std::string err;
+    auto say = [&](int code) {
+        if (msg && msg_cap > 0) { strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+        return code;
+    };
+    const int rc = guarded(&err, [&]() {
+        std::vector<FeatureRow> features;
+        RangeTable range;
+        SvmModel model;
+        if (!load_features(cfg->feature_file, features, err) || !load_range(cfg->range_file, range, err) || !load_model(cfg->model_file, model, err))
+            return say(HAF_E_IO);
+        TableInputs in;
+        in.cfg = *cfg;
+        in.features = &features; in.range = &range; in.model = &model;
+        in.mfma_kappa = kappa; in.mfma_kappa16 = kappa16;
+        in.generic_kernel = model.kernel_type != HAF_KERNEL_RBF;
+        if (in.generic_kernel) in.cfg.flags = (in.cfg.flags & ~(uint32_t)HAF_FLAG_FP32_MFMA) | HAF_FLAG_SPLIT_F16;      // (as haf_create does)
+        in.sw = table_switches();
+        ModelTables m;
+        const TableError refused = build_model_tables(in, m);
+        if (refused.code != HAF_OK) { err = refused.msg; return say(refused.code); }
+        DigestText t;
+        auto bytes = [&](const char *name, const void *p, size_t n) { Fnv f; f.add(p, n); t.line(name, f); };
+#define HAF_DIGEST(name) bytes("d_" #name, m.name.data(), m.name.size() * sizeof m.name[0])
+        HAF_DIGEST(fd); HAF_DIGEST(svt); HAF_DIGEST(svt_h); HAF_DIGEST(sd); HAF_DIGEST(sd3); HAF_DIGEST(fd_slot); HAF_DIGEST(corr);
+        HAF_DIGEST(svt0); HAF_DIGEST(svt0_cr); HAF_DIGEST(sd_cr); HAF_DIGEST(sd3_cr); HAF_DIGEST(fd_slot_cr); HAF_DIGEST(corr_cr);
+        HAF_DIGEST(lr_btiles); HAF_DIGEST(lr_btiles_in); HAF_DIGEST(svt_lr); HAF_DIGEST(corr_lrp); HAF_DIGEST(svt_h_cr);
+        HAF_DIGEST(t1_tab); HAF_DIGEST(sv64); HAF_DIGEST(coef64); HAF_DIGEST(sv_i8);
+#undef HAF_DIGEST
+        digest_structs(t, m.screen, m.screen_cr, m.screen_lrp, m.lr_band, m.crp, m.crt1, m.svm, m.exact, m.i8, m.prob);
+        digest_scalars(t, TableScalars{m.nf, m.kx, m.n_sv_tiles, m.sv_tile_neg, m.n_sv_pad, m.sum_abs_coef, m.screen_active, m.cr_available,
+                                       m.lr_available, m.lr_fused, m.lr_plain_available, m.t1_cr_available, m.i8_active, m.lr_rank, m.gv0,
+                                       m.gv1, m.prob_mode, m.host_exp_thr});
+        return digest_hand_over(t, out, cap);
+    });
+    return rc == HAF_E_INTERNAL ? say(rc) : rc;       // (an exception's text)
+}
+
 double haf_test_split3(double a, float *parts)
 {
     _Float16 h[3];

@@ -166,7 +166,7 @@ template <class Src, class FD>
 __device__ __forceinline__ float screen_attribute(const Src &src, const FD &f, const hafq::ScrTabs &st)
 {
     const float v = feature_value(src, f);
-    return fmaf((float)hafq::decq4_float_scr(v, st), (float)f.scr_mul, (float)f.scr_add);     // (the same floats ScrDesc holds: engine_tables.cpp)
+    return fmaf((float)hafq::decq4_float_scr(v, st), (float)f.scr_mul, (float)f.scr_add);     // (the same floats ScrDesc holds: model_tables.cpp, describe_slot)
 }
 
 // The same with the low-rank form's noise bound (kernels.h: kLrK; features.hip: k_features_serial, LR) for a lane of a wave that is
