@@ -385,6 +385,12 @@ def _bind(path, testing):
         L.haf_test_host_table_digest.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
         L.haf_test_decq4_scr.restype = C.c_double
         L.haf_test_decq4_scr.argtypes = [C.c_float]
+        L.haf_test_decq4_scr_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.haf_test_host_slot_table.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 8 + \
+            [C.POINTER(C.c_int), C.c_char_p, C.c_int]
+        L.haf_test_feature_thresholds.argtypes = [C.c_void_p]
+        L.haf_test_feature_form.argtypes = [E, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.haf_test_screen_finish.argtypes = [E, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.haf_test_split3.restype = C.c_double
         L.haf_test_split3.argtypes = [C.c_double, C.c_void_p]
         L.haf_test_decq_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -1196,6 +1202,35 @@ class Engine:
         out = (C.c_int * 4)()
         self._check(self._L.haf_test_prestage_forms(self._h, out))
         return dict(bin=out[0], integral=out[1], bucket_refused=bool(out[2]), n_inexact_grids=out[3])
+
+    FEATURE_FORMS = ("k_features_small", "k_features<16>", "k_features<8>", "k_features_serial", "k_features_serial<lr>")
+
+    def feature_form(self, per_roll=False):
+        """Testing build (haf_test_feature_form): which feature kernel served the last request's screening pass (index into FEATURE_FORMS;
+        -1: none ran) and which ScreenParams set it read -> dict(kernel, params: index into SCREEN_PARAMS, cr_poly).  per_roll: also
+        flags and iiabs, what the pre-stages left per (cloud, roll) for the low-rank form: the flags word (bit 1: the grid holds a
+        negative height) and the sum of |height| in units of 2^-20 m."""
+        form, n = (C.c_int * 3)(), C.c_int()
+        self._check(self._L.haf_test_feature_form(self._h, form, None, None, 0, C.byref(n)))
+        out = dict(kernel=form[0], params=form[1], cr_poly=bool(form[2]))
+        if per_roll:
+            flags, iiabs = np.zeros(max(1, n.value), np.int32), np.zeros(max(1, n.value), np.uint64)
+            self._check(self._L.haf_test_feature_form(self._h, form, flags.ctypes.data_as(C.c_void_p), iiabs.ctypes.data_as(C.c_void_p),
+                                                      len(flags), C.byref(n)))
+            out.update(flags=flags[:n.value], iiabs=iiabs[:n.value])
+        return out
+
+    SCREEN_PARAMS = ("screen", "screen_cr", "screen_lrp")
+
+    def screen_finish(self, sums):
+        """Testing build (haf_test_screen_finish): screen_finish on the host with the constants the last screening feature pass was launched
+        with, for sums [n, 5] = su2, sd2, sx2, cr, ub (fp64) -> (band [n, 8] fp32, a_x [n] fp32)."""
+        sums = np.ascontiguousarray(sums, np.float64)
+        assert sums.ndim == 2 and sums.shape[1] == 5
+        band, nax = np.zeros((len(sums), 8), np.float32), np.zeros(len(sums), np.float32)
+        self._check(self._L.haf_test_screen_finish(self._h, sums.ctypes.data_as(C.c_void_p), len(sums), band.ctypes.data_as(C.c_void_p),
+                                                   nax.ctypes.data_as(C.c_void_p)))
+        return band, nax
 
     def snapshot_screen(self, on=True):
         """Testing build: from now on every request keeps a copy of what its screening feature pass wrote (fetch_snapshot)."""

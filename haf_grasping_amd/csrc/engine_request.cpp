@@ -564,9 +564,10 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     ScreenParams sp_now = p.sp == SP_LRP ? e->screen_lrp : p.sp == SP_CR ? e->screen_cr : e->screen;
     if (p.sp != SP_LRP) sp_now.cr_poly = e->screen_variant == SCREEN_CR_POLY;
     if (p.lr) { sp_now.lr = 1; sp_now.lr_negflags = e->d_inexact.p; sp_now.lr_iiabs = e->d_iiabs.p; }
+    if (e->snap_on && !p.reuse) { e->feature_sp_kind = p.sp; e->feature_sp = sp_now; }      // (testing library only, as the snapshot below)
     if (!p.reuse)
-        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
-                        e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
+        e->feature_form = launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
+                                          e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
     if (e->snap_on && !p.reuse) {        // (testing library only: haf_test_snapshot_screen)
         const long cap = std::min<long>(evals_cap, e->max_evals_pad);
         e->snap_cap = cap;

@@ -345,6 +345,11 @@ struct haf_engine {
     DevBuf<unsigned long long> d_brslot;   // k_small_pre: per (cloud, roll) {request epoch, evaluations} in one word (ordered evaluation list)
     unsigned pre_epoch = 0;
     PrestageForms pre_forms;        // run_prestages (engine_request.cpp)
+    int feature_form = FEAT_NONE;   // the FeatureForm that served the last screening feature pass (launch_screening; FEAT_NONE: none ran yet)
+    // ... and, while the testing build's snapshot is on (snap_on), the ScreenParams set it read (SP_PLAIN / SP_CR / SP_LRP) as it was handed
+    // over.  Members of every build: graspmap_host.cpp and roi_host.cpp are compiled once for both libraries, so the layout must not differ
+    int feature_sp_kind = -1;
+    ScreenParams feature_sp{};
     struct View { int *p = nullptr; } d_counters;      // inside out_block
     DevBuf<float> d_X, d_ax, d_dec, d_svt;
     DevBuf<char> d_svt_h;            // split-fp16 SV tile images
@@ -402,7 +407,7 @@ struct haf_engine {
     long part1_stride = 0;
     // requests with at least this many evaluation slots take the thread-per-evaluation feature kernel: its floor is one thread's
     // chain of 324 attributes (~0.2 ms), the cooperative kernel costs ~1.3 us per 1000 evaluations (crossover measured at ~3e5)
-    long large_evals = 1L << 18;
+    long large_evals = kLargeEvals;
     DevBuf<ScrDesc3> d_sd3;
 
     // views into the pinned half of out_block

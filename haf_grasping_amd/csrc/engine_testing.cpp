@@ -1,5 +1,6 @@
 // engine_testing.cpp -- the haf_test_* hooks of libhafgrasp_testing.so (tests/ only; the product library does not contain this file).
 #include "engine_state.h"
+#include "screen_finish.h"
 
 #ifndef HAF_TESTING
 #error "engine_testing.cpp belongs to the testing build (-DHAF_TESTING)"
@@ -451,6 +452,27 @@ template <class T> bool digest_device(DigestText &t, const char *name, const Dev
 }
 }  // namespace
 
+// what the device-free builder (model_tables.cpp) makes of cfg's files and flags under the testing build's environment switches, as
+// haf_create would ask for it; a file that does not load or a refusal of the builder comes back as its code, with its text in err
+static int host_tables(const haf_config *cfg, double kappa, double kappa16, ModelTables &m, std::string &err)
+{
+    std::vector<FeatureRow> features;
+    RangeTable range;
+    SvmModel model;
+    if (!load_features(cfg->feature_file, features, err) || !load_range(cfg->range_file, range, err) || !load_model(cfg->model_file, model, err))
+        return HAF_E_IO;
+    TableInputs in;
+    in.cfg = *cfg;
+    in.features = &features; in.range = &range; in.model = &model;
+    in.mfma_kappa = kappa; in.mfma_kappa16 = kappa16;
+    in.generic_kernel = model.kernel_type != HAF_KERNEL_RBF;
+    if (in.generic_kernel) in.cfg.flags = (in.cfg.flags & ~(uint32_t)HAF_FLAG_FP32_MFMA) | HAF_FLAG_SPLIT_F16;      // (as haf_create does)
+    in.sw = table_switches();
+    const TableError refused = build_model_tables(in, m);
+    if (refused.code != HAF_OK) { err = refused.msg; return refused.code; }
+    return HAF_OK;
+}
+
 extern "C" {
 
 // the tables of a created engine as they lie on the device, its parameter structs and its scalars -> text of at most cap bytes
@@ -486,21 +508,9 @@ int haf_test_host_table_digest(const haf_config *cfg, double kappa, double kappa
         return code;
     };
     const int rc = guarded(&err, [&]() {
-        std::vector<FeatureRow> features;
-        RangeTable range;
-        SvmModel model;
-        if (!load_features(cfg->feature_file, features, err) || !load_range(cfg->range_file, range, err) || !load_model(cfg->model_file, model, err))
-            return say(HAF_E_IO);
-        TableInputs in;
-        in.cfg = *cfg;
-        in.features = &features; in.range = &range; in.model = &model;
-        in.mfma_kappa = kappa; in.mfma_kappa16 = kappa16;
-        in.generic_kernel = model.kernel_type != HAF_KERNEL_RBF;
-        if (in.generic_kernel) in.cfg.flags = (in.cfg.flags & ~(uint32_t)HAF_FLAG_FP32_MFMA) | HAF_FLAG_SPLIT_F16;      // (as haf_create does)
-        in.sw = table_switches();
         ModelTables m;
-        const TableError refused = build_model_tables(in, m);
-        if (refused.code != HAF_OK) { err = refused.msg; return say(refused.code); }
+        const int built = host_tables(cfg, kappa, kappa16, m, err);
+        if (built != HAF_OK) return say(built);
         DigestText t;
         auto bytes = [&](const char *name, const void *p, size_t n) { Fnv f; f.add(p, n); t.line(name, f); };
 #define HAF_DIGEST(name) bytes("d_" #name, m.name.data(), m.name.size() * sizeof m.name[0])
@@ -516,6 +526,89 @@ int haf_test_host_table_digest(const haf_config *cfg, double kappa, double kappa
         return digest_hand_over(t, out, cap);
     });
     return rc == HAF_E_INTERNAL ? say(rc) : rc;       // (an exception's text)
+}
+
+// The slot descriptors the screening feature kernels read, from the same device-free build (no device is touched): for each of the kS0K
+// slots of one ScreenParams instance -- form 0 `screen`, 1 `screen_cr`, 2 `screen_lrp` -- attr: the representative attribute (row of the
+// feature file; -1 for an unused slot), skip / shaf: as its FeatDesc holds them, desc [kS0K][4]: {scr_mul, scr_add, extra, pad} as the
+// floats ScrDesc holds, corr [kS0K][3]: the slot's ScrCorr {g, hd, ub}, mu [kS0K]: the centre the centred forms fold into scr_add (0 in
+// form 0).  scalars [7]: c, lr_rho, ubar2, eta_abs, cr (0 / 1), cr_mu_norm, cr_mu_norm_t; groups [2]: fast_groups, extra_groups.  *available = 0: the model did not get this form's tables (the arrays are left alone).
+int haf_test_host_slot_table(const haf_config *cfg, double kappa, double kappa16, int form, int *attr, int *skip, int *shaf, float *desc,
+                             float *corr, double *mu, double *scalars, unsigned long long *groups, int *available, char *msg, int msg_cap)
+{
+    if (!cfg || !cfg->feature_file || !cfg->range_file || !cfg->model_file || form < 0 || form > 2 || !attr || !skip || !shaf || !desc || !corr || !mu ||
+        !scalars || !groups || !available)
+        return HAF_E_ARG;
+    std::string err;
+    auto say = [&](int code) {
+        if (msg && msg_cap > 0) { strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+        return code;
+    };
+    const int rc = guarded(&err, [&]() {
+        ModelTables m;
+        const int built = host_tables(cfg, kappa, kappa16, m, err);
+        if (built != HAF_OK) return say(built);
+        // (as upload_tables pairs them: the low-rank form's plain epilogue reads the centred descriptors with correction vectors of its own)
+        const ScreenParams &sp = form == 0 ? m.screen : form == 1 ? m.screen_cr : m.screen_lrp;
+        const std::vector<ScrDesc> &sd = form == 0 ? m.sd : m.sd_cr;
+        const std::vector<FeatDesc> &fds = form == 0 ? m.fd_slot : m.fd_slot_cr;
+        const std::vector<ScrCorr> &sc = form == 0 ? m.corr : form == 1 ? m.corr_cr : m.corr_lrp;
+        *available = m.screen_active && (form == 0 || (form == 1 && m.cr_available) || (form == 2 && m.lr_available)) &&
+                     sd.size() >= (size_t)kS0K && fds.size() >= (size_t)kS0K && sc.size() >= (size_t)kS0K;
+        if (!*available) return (int)HAF_OK;
+        for (int s = 0; s < kS0K; s++) {
+            attr[s] = (s < (int)m.slot_rep.size() && !fds[(size_t)s].skip) ? m.slot_rep[(size_t)s] : -1;
+            skip[s] = fds[(size_t)s].skip; shaf[s] = fds[(size_t)s].shaf;
+            desc[4 * s] = sd[(size_t)s].scr_mul; desc[4 * s + 1] = sd[(size_t)s].scr_add; desc[4 * s + 2] = sd[(size_t)s].extra; desc[4 * s + 3] = sd[(size_t)s].pad;
+            mu[s] = (form != 0 && s < (int)m.slot_mu.size()) ? m.slot_mu[(size_t)s] : 0.0;
+            corr[3 * s] = sc[(size_t)s].g; corr[3 * s + 1] = sc[(size_t)s].hd; corr[3 * s + 2] = sc[(size_t)s].ub;
+        }
+        scalars[0] = sp.c; scalars[1] = sp.lr_rho; scalars[2] = sp.ubar2; scalars[3] = sp.eta_abs; scalars[4] = sp.cr;
+        scalars[5] = sp.cr_mu_norm; scalars[6] = sp.cr_mu_norm_t;
+        groups[0] = sp.fast_groups; groups[1] = sp.extra_groups;
+        return (int)HAF_OK;
+    });
+    return rc == HAF_E_INTERNAL ? say(rc) : rc;
+}
+
+// the request sizes launch_features' choice turns on (kernels.h): kSmallEvals, kWaves16Evals, kLargeEvals
+int haf_test_feature_thresholds(long long *out3)
+{
+    if (!out3) return HAF_E_ARG;
+    out3[0] = kSmallEvals; out3[1] = kWaves16Evals; out3[2] = kLargeEvals;
+    return HAF_OK;
+}
+
+// Which feature kernel served the last request's screening pass -- form [3]: the FeatureForm (kernels.h; -1: none ran), the ScreenParams
+// set it read (0 `screen`, 1 `screen_cr`, 2 `screen_lrp`; kept only while haf_test_snapshot_screen is on, else -1) and that set's cr_poly -- and, with flags / iiabs given (cap entries each), what
+// the pre-stages left per (cloud, roll) of that request for the low-rank form: the flags word (bit 1: the grid holds a negative height)
+// and the sum of |height| in units of 2^-20 m.  *n = clouds x rolls of the last request.
+int haf_test_feature_form(haf_engine *e, int *form, int *flags, unsigned long long *iiabs, int cap, int *n)
+{
+    if (!e || !form) return HAF_E_ARG;
+    form[0] = e->feature_form; form[1] = e->feature_sp_kind; form[2] = e->feature_sp.cr_poly;
+    const int br = e->last.B * e->last.R;
+    if (n) *n = br;
+    if (!flags && !iiabs) return HAF_OK;
+    if (br <= 0 || br > cap) return HAF_E_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return HAF_E_DEVICE;
+    if (flags && (!e->d_inexact.p || (size_t)br > e->d_inexact.n ||
+                  hipMemcpy(flags, e->d_inexact.p, (size_t)br * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) return HAF_E_DEVICE;
+    if (iiabs && (!e->d_iiabs.p || (size_t)br > e->d_iiabs.n ||
+                  hipMemcpy(iiabs, e->d_iiabs.p, (size_t)br * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)) return HAF_E_DEVICE;
+    return HAF_OK;
+}
+
+// screen_finish (screen_finish.h) on the host, with the very constants the last screening feature pass of this engine was launched with
+// (haf_engine::feature_sp).  sums [n][5]: su2, sd2, sx2, cr, ub -> band [n][8], nax [n].
+int haf_test_screen_finish(haf_engine *e, const double *sums, int n, float *band, float *nax)
+{
+    if (!e || e->feature_sp_kind < 0 || !sums || !band || !nax || n < 0) return HAF_E_ARG;
+    for (int i = 0; i < n; i++) {
+        const double *s = sums + (size_t)5 * i;
+        screen_finish(s[0], s[1], s[2], s[3], s[4], e->feature_sp, band + (size_t)kBandFloats * i, nax[i]);
+    }
+    return HAF_OK;
 }
 
 double haf_test_split3(double a, float *parts)
@@ -537,6 +630,13 @@ double haf_test_decq4_scr(float v)
     hafq::ScrTabs st;
     st.w = tab;
     return hafq::decq4_float_scr(v, st);
+}
+// the same for n values at once (a test that needs 10^5 of them)
+int haf_test_decq4_scr_n(const float *in, double *out, int n)
+{
+    if (!in || !out || n < 0) return HAF_E_ARG;
+    for (int i = 0; i < n; i++) out[i] = haf_test_decq4_scr(in[i]);
+    return HAF_OK;
 }
 
 // runs the screening kernel's MFMA chain on host-chosen data (testkernels.hip); a, b: fp16 bit patterns

@@ -161,7 +161,7 @@ __device__ __forceinline__ double attribute_value_rec(const Src &src, const FD &
 // path's range comes back NaN and poisons the norms: that evaluation is never trusted.
 // (round 5: + 3 u for the fp32 scaling -- fl32(q4), the product's and the sum's rounding inside the fma are one, the constants' own roundings --
 // relative to |u'|; the part relative to |scr_add| is in eta_abs)
-constexpr double kScreenEtaRel = 5.0e-6 * (1.0 + 1e-6) + 1.8e-7;
+// (the constant itself: screen_finish.h, kScreenEtaRel = 5.0e-6 * (1.0 + 1e-6) + 1.8e-7)
 template <class Src, class FD>
 __device__ __forceinline__ float screen_attribute(const Src &src, const FD &f, const hafq::ScrTabs &st)
 {

@@ -429,7 +429,21 @@ enum { XMODE_F32 = 0, XMODE_SPLIT = 1, XMODE_SCREEN = 2,
        XMODE_I8 = 4 };    // the int8 digit image of the exact-integer tier (kI8GroupBytes per 16 slots); ax = double * |xq|^2 per slot
 // idx_list == nullptr: evaluations 0..counters[CNT_EVALS]; otherwise slot j takes evaluation idx_list[j],
 // j < min(counters[list_counter], list_cap) (the screened evaluations that go on to the three-pass kernel)
-void launch_features(const float *ii, const int *evalcell, const int *counters, const FeatDesc *fd, float *X, float *ax,
+// Which feature kernel a launch_features call chose (by `large`, `sel_evals`, `sp.lr` and the list mode): the launcher says what it
+// chose, as launch_bin does (the testing build hands the screening pass's on: haf_test_feature_form).  In list mode, where two kernels
+// are launched and the list's length decides on the device which of them works, the one launched LAST.
+// the request sizes (the host's estimate of the evaluations, engine_request.cpp) the choice turns on
+constexpr long kSmallEvals = 12288;       // up to this many: k_features_small
+constexpr long kWaves16Evals = 24576;     // up to this many: k_features<., 16>, beyond: k_features<., 8>
+constexpr long kLargeEvals = 1L << 18;    // from this many on (haf_engine::large_evals): one thread per evaluation, k_features_serial
+enum FeatureForm { FEAT_NONE = -1,        // nothing launched (no evaluations)
+                   FEAT_SMALL = 0,        // k_features_small
+                   FEAT_WAVES16 = 1,      // k_features<., 16>
+                   FEAT_WAVES8 = 2,       // k_features<., 8>
+                   FEAT_SERIAL = 3,       // k_features_serial<., false>
+                   FEAT_SERIAL_LR = 4 };  // k_features_serial<XMODE_SCREEN, true>: the low-rank form's raw sums and noise bound
+// -> the FeatureForm that ran
+int  launch_features(const float *ii, const int *evalcell, const int *counters, const FeatDesc *fd, float *X, float *ax,
                      Dims d, double lower, double upper, float neg_gamma2, long max_evals, int xmode, ScreenParams sp,
                      const int *idx_list, int list_counter, int list_cap, bool large, long sel_evals, AttrRecord *dbg,
                      float *ax2, hipStream_t s,    // ax2: screening form only, -|u|^2/2 per evaluation

@@ -285,6 +285,7 @@ void screening_slots(Work &w)
         slot_of_attr[(size_t)f] = s;
     }
     w.n_slots = (int)rep.size();
+    t.slot_rep = rep;
     if (w.n_slots > kS0K) t.screen_active = false;   // more distinct attributes than the ten k-steps hold: three-pass kernel for everything
 }
 
@@ -655,6 +656,7 @@ void cr_descriptors(Work &w, CrTables &ct)
         ea2c += e32 * e32;
     }
     cp.eta_abs = std::max(std::sqrt(ea2c) * 1.01, 1e-12 * 18.0 * sp.c);
+    t.slot_mu = mu;
 }
 
 // N = Q'BQ^ and M = Q'B(Q^ - Q) (320 x 320, SIGNED: the classes cancel), the unsigned second-order matrices through

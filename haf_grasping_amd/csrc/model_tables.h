@@ -63,6 +63,10 @@ struct ModelTables {
     std::vector<ScrDesc3> sd3, sd3_cr;          // -> d_sd3, d_sd3_cr
     std::vector<FeatDesc> fd_slot, fd_slot_cr;  // -> d_fd_slot, d_fd_slot_cr
     std::vector<ScrCorr> corr, corr_cr, corr_lrp;   // -> d_corr, d_corr_cr, d_corr_lrp (kS0K per-slot entries, then the pair form)
+    // host only, for the testing build's slot-table hook (built once per engine; kept in this struct because the builder is one unit for both
+    // libraries): the representative attribute (row of the feature file) of every used slot, and the centred forms' centre per slot
+    std::vector<int> slot_rep;
+    std::vector<double> slot_mu;
     std::vector<char> svt0, svt0_cr;            // -> d_svt0, d_svt0_cr
     std::vector<char> lr_btiles, lr_btiles_in, svt_lr;   // -> d_lr_btiles, d_lr_btiles_in, d_svt_lr
     std::vector<char> svt_h_cr;                 // -> d_svt_h_cr
