@@ -19,13 +19,13 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhafgrasp.so")
 LIB_TESTING = os.path.join(HERE, "libhafgrasp_testing.so")
 # the engine's host side: every one of these is compiled twice, without and with -DHAF_TESTING (csrc/engine_state.h: test_env)
-ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp", "engine_graspmap.cpp", "engine_roi.cpp", "engine_depthfilter.cpp", "engine_segment.cpp", "engine_cellsegment.cpp", "engine_plane.cpp", "engine_clearance.cpp", "engine_opening.cpp", "engine_labelshape.cpp", "engine_objects.cpp", "engine_transfer.cpp", "engine_stage.cpp"]
+ENGINE_SOURCES = ["engine.cpp", "engine_tables.cpp", "engine_request.cpp", "engine_geometry.cpp", "engine_debug.cpp", "engine_topgrasps.cpp", "engine_graspmap.cpp", "engine_roi.cpp", "engine_depthfilter.cpp", "engine_segment.cpp", "engine_cellsegment.cpp", "engine_plane.cpp", "engine_clearance.cpp", "engine_opening.cpp", "engine_space.cpp", "engine_labelshape.cpp", "engine_objects.cpp", "engine_transfer.cpp", "engine_stage.cpp"]
 TESTING_ONLY = ["engine_testing.cpp", "testkernels.hip"]         # libhafgrasp_testing.so only
-SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip", "frames.hip", "graspmap.hip", "roi.hip", "depthfilter.hip", "segment.hip", "cellsegment.hip", "plane.hip", "clearance.hip", "opening.hip", "labelshape.hip", "transfer.hip"] + \
-          ENGINE_SOURCES + ["parsers.cpp", "model_tables.cpp", "frames_host.cpp", "frame_stage.cpp", "graspmap_host.cpp", "roi_host.cpp", "depthfilter_host.cpp", "segment_host.cpp", "cellsegment_host.cpp", "plane_host.cpp", "clearance_host.cpp", "opening_host.cpp", "labelshape_host.cpp", "transfer_host.cpp", "multi.cpp"]
+SOURCES = ["prestages.hip", "features.hip", "contraction.hip", "screen.hip", "recheck.hip", "exact8.hip", "vote.hip", "prob.hip", "topgrasps.hip", "frames.hip", "graspmap.hip", "roi.hip", "depthfilter.hip", "segment.hip", "cellsegment.hip", "plane.hip", "clearance.hip", "opening.hip", "space.hip", "labelshape.hip", "transfer.hip"] + \
+          ENGINE_SOURCES + ["parsers.cpp", "model_tables.cpp", "frames_host.cpp", "frame_stage.cpp", "graspmap_host.cpp", "roi_host.cpp", "depthfilter_host.cpp", "segment_host.cpp", "cellsegment_host.cpp", "plane_host.cpp", "clearance_host.cpp", "opening_host.cpp", "space_host.cpp", "labelshape_host.cpp", "transfer_host.cpp", "multi.cpp"]
 # per-file extra flags (screen.hip: see its header)
 EXTRA = {"screen.hip": ["-fno-slp-vectorize"]}
-HEADERS = ["kernels.h", "device_common.h", "feature_device.h", "screen_band.h", "screen_finish.h", "parsers.h", "model_tables.h", "decq.h", "engine_internal.h", "engine_state.h", "frame_points.h", "frames.h", "frame_stage.h", "frame_group.h", "object_group.h", "label_group.h", "grasp_cells.h", "pick_rules.h", "depth_filter.h", "segment_rules.h", "cell_segment_rules.h", "wave_union.h", "plane_rules.h", "clearance_rules.h", "opening_rules.h", "grasp_lane.h", "label_shape.h", "transfer_rules.h"] + TESTING_ONLY + [ os.path.join("..", "..", "include", "hafgrasp.h"),
+HEADERS = ["kernels.h", "device_common.h", "feature_device.h", "screen_band.h", "screen_finish.h", "parsers.h", "model_tables.h", "decq.h", "engine_internal.h", "engine_state.h", "frame_points.h", "frames.h", "frame_stage.h", "frame_group.h", "object_group.h", "label_group.h", "grasp_cells.h", "pick_rules.h", "depth_filter.h", "segment_rules.h", "cell_segment_rules.h", "wave_union.h", "plane_rules.h", "clearance_rules.h", "opening_rules.h", "space_rules.h", "grasp_lane.h", "label_shape.h", "transfer_rules.h"] + TESTING_ONLY + [ os.path.join("..", "..", "include", "hafgrasp.h"),
            os.path.join("..", "cli", "haf_grasp_cli.cpp"), os.path.join("..", "..", "ros_shim", "shim_core.h")]
 # -ffp-contract=off: the bit-exact stages spell out every rounding; nothing may be fused behind their back
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

@@ -172,6 +172,32 @@ assert OPENING_DTYPE.itemsize == C.sizeof(GraspOpening) == 64
 OPEN_BINS = 128                      # HAF_OPEN_BINS: words of one histogram of haf_fit_openings
 
 
+class SpaceParams(C.Structure):
+    """haf_space_params: the lattice step of haf_check_space, the projection's near plane and tolerances, and when a grasp is clear; the
+    library's defaults are nominal figures"""
+    _fields_ = [("sample_step", C.c_float), ("near_m", C.c_float), ("tol_abs", C.c_float), ("tol_rel", C.c_float), ("max_hit", C.c_int32),
+                ("max_unknown", C.c_int32), ("min_between_hit", C.c_int32)]
+
+
+class GraspSpace(C.Structure):
+    """haf_grasp_space: a grasp's counts n[region][state] and what space_finish derives from them"""
+    _fields_ = [("clear", C.c_int32), ("n", (C.c_int32 * 4) * 4), ("reserved", C.c_int32 * 3)]
+
+
+class SpaceInfo(C.Structure):
+    """haf_space_info: the lattice of one haf_check_space call"""
+    _fields_ = [("step", C.c_int32), ("n", (C.c_int32 * 3) * 4), ("n_samples", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+SPACE_DTYPE = np.dtype([("clear", np.int32), ("n", np.int32, (4, 4)), ("reserved", np.int32, 3)])
+assert SPACE_DTYPE.itemsize == C.sizeof(GraspSpace) == 80 and C.sizeof(SpaceInfo) == 64
+MAX_SPACE_VIEWS = 8                  # HAF_MAX_SPACE_VIEWS: depth views of one haf_check_space call
+MAX_SPACE_SAMPLES = 65536            # HAF_MAX_SPACE_SAMPLES: lattice points of one grasp
+MAX_SPACE_STATES = 1 << 22           # bytes of `states` haf_check_space offers
+SPACE_BETWEEN, SPACE_FINGER0, SPACE_FINGER1, SPACE_PALM = range(4)         # HAF_SPACE_*: the regions, the first index of n
+SPACE_UNSEEN, SPACE_HIDDEN, SPACE_FREE, SPACE_HIT = range(4)               # ... the states and their ranks, the second
+
+
 class Roi(C.Structure):
     """haf_roi: the pixel mask of one request of haf_score_frames_roi, of one view of haf_score_views_roi"""
     _fields_ = [("mask", C.c_void_p), ("row_stride_bytes", C.c_size_t), ("on_device", C.c_int32)]
@@ -351,6 +377,12 @@ def _bind(path, testing):
     L.haf_fit_openings.argtypes = [E, C.POINTER(Frame), C.POINTER(Roi), C.POINTER(Gripper), C.POINTER(OpeningParams), C.c_int32, C.c_void_p,
                                    C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(OpeningInfo), C.c_void_p]
     L.haf_apply_opening.argtypes = [C.POINTER(GraspOutput), C.POINTER(GraspOpening), C.POINTER(GraspOutput)]
+    L.haf_space_default.argtypes = [C.POINTER(SpaceParams)]
+    L.haf_space_default.restype = None
+    L.haf_check_space_ref.argtypes = [C.POINTER(Frame), C.c_int32, C.POINTER(Gripper), C.POINTER(SpaceParams), C.c_int32, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(SpaceInfo), C.c_void_p]
+    L.haf_check_space.argtypes = [E, C.POINTER(Frame), C.c_int32, C.POINTER(Gripper), C.POINTER(SpaceParams), C.c_int32, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(SpaceInfo), C.c_void_p]
     L.haf_measure_labels_ref.argtypes = [C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_measure_labels.argtypes = [E, C.POINTER(Frame), C.POINTER(LabelImage), C.c_int32, C.c_void_p, C.c_void_p]
     L.haf_object_input.argtypes = [C.POINTER(Config), C.POINTER(GraspInput), C.c_void_p, C.c_int32, C.POINTER(GraspInput), C.POINTER(C.c_int32)]
@@ -880,6 +912,47 @@ def apply_opening(grasp, opening):
         raise HafError(rc, "haf_apply_opening: a void grasp, or an opening that was not found")
     return dict(grasp, grasp_point1=tuple(out.grasp_point1), grasp_point2=tuple(out.grasp_point2),
                 averaged_grasp_point=tuple(out.averaged_grasp_point))
+
+
+def space_params(**kw):
+    """haf_space_params with the library's defaults (sample_step 0.004, near_m 0.05, tol_abs 0.004, tol_rel 0.002, max_hit 0, max_unknown
+    0, min_between_hit 1 -- nominal figures) and `kw` over them"""
+    p = SpaceParams()
+    lib().haf_space_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown haf_space_params field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _check_space(call, views, grasps, grip, params, states):
+    g = grip if grip is not None else gripper()
+    p = params if params is not None else space_params()
+    views = list(views) if isinstance(views, (list, tuple)) else [views]
+    arr, n, stride = _grasp_array(grasps)
+    frames = (Frame * max(1, len(views)))(*views)
+    out, order, nc, info = np.zeros(max(1, n), SPACE_DTYPE), np.zeros(max(1, n), np.int32), C.c_int32(0), SpaceInfo()
+    # (N is the call's to say: what is offered always fits min(n * MAX_SPACE_SAMPLES, MAX_SPACE_STATES) bytes)
+    st = np.zeros(min(max(1, n) * MAX_SPACE_SAMPLES, MAX_SPACE_STATES), np.uint8) if states else None
+    rc = call(frames, len(views), C.byref(g), C.byref(p), n, arr, stride, out.ctypes.data, order.ctypes.data, C.byref(nc), C.byref(info),
+              st.ctypes.data if states else None)
+    facts = dict(step=info.step, n=[list(r) for r in info.n], n_samples=info.n_samples)
+    res = (out[:n], order[:nc.value].copy(), facts)
+    if states and rc == HAF_OK:
+        res += (st[:n * info.n_samples].reshape(n, info.n_samples).copy(), )
+    return rc, res
+
+
+def check_space_ref(views, grasps, gripper=None, params=None, states=False):
+    """haf_check_space_ref: the host definition of record of what 1..8 host depth Frames have seen of the gripper's volume at every grasp
+    -> (SPACE_DTYPE [n_grasps], order: the indices of the clear grasps in input order, info: dict(step, n [4][3], n_samples)) and, with
+    states=True, every sample's final rank uint8 [n_grasps, n_samples] as a fourth entry.  views: a Frame or a list of them; grasps and
+    gripper as check_grasps_ref's; params: space_params(...), default the library's."""
+    rc, res = _check_space(lib().haf_check_space_ref, views, grasps, gripper, params, states)
+    if rc != HAF_OK:
+        raise HafError(rc, "haf_check_space_ref refused its arguments")
+    return res
 
 
 def _shape_plane(plane):
@@ -1527,6 +1600,13 @@ class Engine:
         """haf_fit_openings: a Frame (any kind, host or device-resident) and grasps -> what fit_openings_ref gives, computed on the
         device.  mask: a host uint8 [height, width] array or (device_ptr, row_stride_bytes); hist=True copies the histograms back."""
         rc, res = _fit_openings(lambda *a: self._L.haf_fit_openings(self._h, *a), frame, grasps, gripper, params, mask, hist)
+        self._check(rc)
+        return res
+
+    def check_space(self, views, grasps, gripper=None, params=None, states=False):
+        """haf_check_space: 1..8 depth Frames (each host or device-resident) and grasps -> what check_space_ref gives, computed on the
+        device: (SPACE_DTYPE rows, order, info[, states])."""
+        rc, res = _check_space(lambda *a: self._L.haf_check_space(self._h, *a), views, grasps, gripper, params, states)
         self._check(rc)
         return res
 

@@ -29,6 +29,13 @@
 //                                     between MIN and MAX metres of the --gripper (the default one without it; its own opening is not
 //                                     read), moved sideways by at most SHIFT, the points between the fingers and in the fingers and
 //                                     the palm there, and the smallest free opening without a shift (haf_fit_openings; same scene)
+//   --check-space default|STEP,TOL_ABS,TOL_REL[,MAX_HIT,MAX_UNKNOWN]   with --top-k and one or more --depth views: behind the "top", "clear"
+//                                     and "open" lines one line per candidate, "space <rank> <clear> hit <n> hidden <n> unseen <n> free
+//                                     <n> between-hit <n>": the sample points of the --gripper's volume (the default one without it) that
+//                                     the views saw a surface at, could not see behind a surface, did not see at all and saw through,
+//                                     over the fingers and the palm, and the ones between the fingers with a surface (haf_check_space,
+//                                     through hafshim::seen_free_hypotheses, whose strings of the clear candidates go to stderr as
+//                                     "<file>: seen free: <hypothesis>")
 //   --map-out PREFIX                  with --depth: the goal's votes in the pixels of the (first) depth image (haf_grasp_map), written as
 //                                     PREFIX.vote.pgm and PREFIX.roll.pgm: 16-bit binary PGMs of the image's size, sample = value + 32768
 //                                     (a pixel without a cell: vote -32768 -> 0, roll -1 -> 32767)
@@ -174,6 +181,7 @@ static void usage()
             "  --grid N  --rolls N  --roll-step deg  --device d  --per-roll  --hypotheses  --probability  --grid-out FILE\n"
             "  --top-k N [--top-radius cells] [--top-rolls steps] [--top-dist m] [--gripper default|OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H]\n"
             "           [--fit-opening default|MIN,MAX[,SHIFT]]\n"
+            "           [--check-space default|STEP,TOL_ABS,TOL_REL[,MAX_HIT,MAX_UNKNOWN]]   (with --top-k and one or more --depth views)\n"
             "  --map-out PREFIX  --mask FILE.pgm  --labels FILE.pgm [--mask-min-vote N]      (with --depth)\n"
             "  --roi-mask FILE.pgm                                         (with one --depth)\n"
             "  --stack FILE.pgm                                            (behind a --depth: a further exposure of that view)\n"
@@ -189,7 +197,8 @@ static void usage()
 
 // --gripper: the clearance of the ranked candidates (haf_check_grasps) against `scene`
 // --fit-opening: their smallest free openings (haf_fit_openings) against the same scene
-struct ClearOptions { bool on = false; haf_gripper gripper; bool fit = false; haf_opening_params opening; };
+// --check-space: what the depth views have SEEN of the gripper's volume at the candidates (haf_check_space), every --depth view a view
+struct ClearOptions { bool on = false; haf_gripper gripper; bool fit = false; haf_opening_params opening; bool space = false; haf_space_params seen; };
 
 // --gripper default | OPEN,THICK,BREADTH,TIP,LENGTH,PALM_W,PALM_B,PALM_H (metres; max_hits and min_between stay the library's)
 static bool parse_gripper(const char *arg, haf_gripper *g)
@@ -217,8 +226,24 @@ static bool parse_opening(const char *arg, haf_opening_params *p)
     return true;
 }
 
+// --check-space default | STEP,TOL_ABS,TOL_REL[,MAX_HIT,MAX_UNKNOWN] (metres; near_m and min_between_hit stay the library's)
+static bool parse_space(const char *arg, haf_space_params *p)
+{
+    haf_space_default(p);
+    if (strcmp(arg, "default") == 0) return true;
+    float v[3];
+    int m[2] = {p->max_hit, p->max_unknown};
+    char tail = 0;
+    // (three fields or five, nothing behind them: the shorter form is scanned on its own so that "a,b,c,1" and "a,b,cx" are refused)
+    if (sscanf(arg, "%f,%f,%f,%d,%d%c", &v[0], &v[1], &v[2], &m[0], &m[1], &tail) != 5 && sscanf(arg, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+    p->sample_step = v[0]; p->tol_abs = v[1]; p->tol_rel = v[2]; p->max_hit = m[0]; p->max_unknown = m[1];
+    return true;
+}
+
+static void print_openings(haf_engine *eng, const char *what, const ClearOptions &clear, const haf_frame &scene, int32_t n,
+                           const haf_grasp_candidate *cands, int *rc);
 static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, int top_k, int top_radius, int top_rolls, double top_dist, int *rc,
-                      const ClearOptions *clear = nullptr, const haf_frame *scene = nullptr)
+                      const ClearOptions *clear = nullptr, const haf_frame *scene = nullptr, int32_t n_scene_views = 1)
 {
     haf_top_params tp;
     haf_top_params_default(eng, &tp);
@@ -233,7 +258,7 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
         *rc = 1;
     }
     for (size_t t = 0; t < top.size(); t++) printf("top %zu %s\n", t + 1, top[t].c_str());
-    if (!clear || !(clear->on || clear->fit) || !scene) return;
+    if (!clear || !(clear->on || clear->fit || clear->space) || !scene) return;
     // the same candidates once more, as poses: "clear <rank> <free> fingers <n0> <n1> palm <n> between <n> width <w> offset <o> top <t>"
     std::vector<haf_grasp_candidate> cand((size_t)std::max(1, cfg.max_clouds) * (size_t)std::max(1, tp.k));
     std::vector<int32_t> found((size_t)std::max(1, cfg.max_clouds), 0);
@@ -251,12 +276,40 @@ static void print_top(haf_engine *eng, const haf_config &cfg, const char *what, 
         printf("clear %d %d fingers %d %d palm %d between %d width %.9g offset %.9g top %.9g\n", t + 1, c.free, c.n_finger[0], c.n_finger[1], c.n_palm,
                c.n_between, c.width_m, c.offset_m, c.top_m);
     }
-    if (!clear->fit) return;
-    // and once more: "open <rank> <found> opening <m> shift <m> between <n> hits <n> sym <m>"
-    haf_gripper gripper = clear->gripper;
-    if (!clear->on) haf_gripper_default(&gripper);
+    if (clear->fit) print_openings(eng, what, *clear, *scene, n, cand.data(), rc);
+    if (!clear->space || *rc) return;
+    // and once more: "space <rank> <clear> hit <n> hidden <n> unseen <n> free <n> between-hit <n>", the first four over fingers and palm
+    if (scene->kind == HAF_FRAME_XYZ_F32) { fprintf(stderr, "%s: --check-space needs --depth views\n", what); *rc = 1; return; }
+    haf_gripper grip = clear->gripper;
+    if (!clear->on) haf_gripper_default(&grip);
+    // through the shim, as an adapter would ask: every candidate's row, and the clear ones as hypothesis strings (to stderr: stdout
+    // keeps one line per candidate)
+    std::vector<haf_grasp_space> seen;
+    std::vector<std::string> seen_free;
+    if (hafshim::seen_free_hypotheses(eng, cfg, tp, scene, n_scene_views, grip, clear->seen, &seen_free, &serr, &seen) != HAF_OK || seen.size() != (size_t)n) {
+        fprintf(stderr, "%s: --check-space: %s\n", what, serr.c_str());
+        *rc = 1;
+        return;
+    }
+    for (size_t t = 0; t < seen_free.size(); t++) fprintf(stderr, "%s: seen free: %s\n", what, seen_free[t].c_str());
+    for (int32_t t = 0; t < n; t++) {
+        const haf_grasp_space &g = seen[(size_t)t];
+        int64_t st[4] = {0, 0, 0, 0};
+        for (int r = HAF_SPACE_FINGER0; r <= HAF_SPACE_PALM; r++)
+            for (int k = 0; k < 4; k++) st[k] += g.n[r][k];
+        printf("space %d %d hit %lld hidden %lld unseen %lld free %lld between-hit %d\n", t + 1, g.clear, (long long)st[HAF_SPACE_HIT],
+               (long long)st[HAF_SPACE_HIDDEN], (long long)st[HAF_SPACE_UNSEEN], (long long)st[HAF_SPACE_FREE], g.n[HAF_SPACE_BETWEEN][HAF_SPACE_HIT]);
+    }
+}
+
+// "open <rank> <found> opening <m> shift <m> between <n> hits <n> sym <m>" per candidate
+static void print_openings(haf_engine *eng, const char *what, const ClearOptions &clear, const haf_frame &scene, int32_t n, const haf_grasp_candidate *cands,
+                           int *rc)
+{
+    haf_gripper gripper = clear.gripper;
+    if (!clear.on) haf_gripper_default(&gripper);
     std::vector<haf_grasp_opening> fits((size_t)n);
-    if (haf_fit_openings(eng, scene, nullptr, &gripper, &clear->opening, n, cand.data(), sizeof(haf_grasp_candidate), fits.data(), nullptr, nullptr,
+    if (haf_fit_openings(eng, &scene, nullptr, &gripper, &clear.opening, n, cands, sizeof(haf_grasp_candidate), fits.data(), nullptr, nullptr,
                          nullptr, nullptr) != HAF_OK) {
         fprintf(stderr, "%s: --fit-opening: %s\n", what, haf_last_error(eng));
         *rc = 1;
@@ -920,7 +973,7 @@ static int run_depth(haf_engine *eng, const haf_config &cfg, const haf_grasp_inp
             if (cand[(size_t)i].grasp.best_roll < out.rolls_done) printf("hypothesis %s\n", hafshim::hypothesis_string(cand[(size_t)i].grasp, cfg.roll_step_deg).c_str());
     }
     printf("%s\n", hafshim::hypothesis_string(out, cfg.roll_step_deg).c_str());
-    if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc, &mo.clear, &frames[0]);
+    if (top_k > 0) print_top(eng, cfg, path.c_str(), top_k, top_radius, top_rolls, top_dist, &rc, &mo.clear, &frames[0], n_views);
     if (run_map(eng, cfg, frames[0], mo) != 0) rc = 1;
     char size[96];
     if (n_views == 1) snprintf(size, sizeof size, "%d x %d pixels", frames[0].width, frames[0].height);
@@ -975,6 +1028,7 @@ int main(int argc, char **argv)
         else if (a == "--grid-out") { need(1); grid_out = argv[++i]; }
         else if (a == "--top-k") { need(1); top_k = atoi(argv[++i]); }
         else if (a == "--fit-opening") { need(1); if (!parse_opening(argv[++i], &map_opt.clear.opening)) { usage(); return 2; } map_opt.clear.fit = true; }
+        else if (a == "--check-space") { need(1); if (!parse_space(argv[++i], &map_opt.clear.seen)) { usage(); return 2; } map_opt.clear.space = true; }
         else if (a == "--gripper") { need(1); if (!parse_gripper(argv[++i], &map_opt.clear.gripper)) { usage(); return 2; } map_opt.clear.on = true; }
         else if (a == "--top-radius") { need(1); top_radius = atoi(argv[++i]); }
         else if (a == "--top-rolls") { need(1); top_rolls = atoi(argv[++i]); }

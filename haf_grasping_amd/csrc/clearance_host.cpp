@@ -59,6 +59,13 @@ int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripp
         if (mask->on_device != 0 && mask->on_device != 1) { err = "the mask's on_device must be 0 (host) or 1 (device)"; return HAF_E_ARG; }
         if (mask->row_stride_bytes < (size_t)frame->width) { err = "the mask's row stride is smaller than the width"; return HAF_E_ARG; }
     }
+    if (check_grasp_list(gripper, n_grasps, grasp_stride_bytes, bounds, err) != HAF_OK) return HAF_E_ARG;
+    if ((int64_t)frame->width * (int64_t)frame->height > kClearMaxPixels) { err = "a frame of more than 2^28 pixels"; return HAF_E_CAPACITY; }
+    return HAF_OK;
+}
+
+int check_grasp_list(const haf_gripper *gripper, int32_t n_grasps, size_t grasp_stride_bytes, ClearBounds *bounds, std::string &err)
+{
     if (!gripper_rules(*gripper, bounds)) {
         err = "haf_gripper: a dimension is negative or not finite, opening is not positive, or the reach exceeds 1 m";
         return HAF_E_ARG;
@@ -68,7 +75,6 @@ int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripp
         err = "the grasp stride is below sizeof(haf_grasp_output) or not a multiple of 8";
         return HAF_E_ARG;
     }
-    if ((int64_t)frame->width * (int64_t)frame->height > kClearMaxPixels) { err = "a frame of more than 2^28 pixels"; return HAF_E_CAPACITY; }
     return HAF_OK;
 }
 

@@ -16,6 +16,7 @@
 //   engine_plane.cpp     haf_fit_plane: one frame -> its dominant plane (plane.hip)
 //   engine_clearance.cpp haf_check_grasps: one frame, one gripper, n grasp poses -> the points in the gripper's boxes (clearance.hip)
 //   engine_opening.cpp  haf_fit_openings: the same inputs -> the smallest free opening and its sideways shift per pose (opening.hip)
+//   engine_space.cpp    haf_check_space: 1..8 depth views, one gripper, n grasp poses -> what the views have seen of the gripper's volume (space.hip)
 //   engine_labelshape.cpp haf_measure_labels: one frame and its label image -> every label's box in the base frame (labelshape.hip)
 //   engine_transfer.cpp  haf_transfer_labels: another camera's label image onto a depth frame's pixels, behind a z-buffer (transfer.hip)
 //   engine_testing.cpp   haf_test_* hooks (libhafgrasp_testing.so only)
@@ -440,7 +441,7 @@ struct haf_engine {
     DevBuf<char> snap_X;
     DevBuf<float> snap_gband, snap_ax;
     // The calls that run outside the request path -- haf_segment_frame, haf_segment_cells, haf_fit_plane, haf_check_grasps,
-    // haf_fit_openings, haf_measure_labels, haf_transfer_labels, the haf_grasp_map family with haf_cell_pose, haf_score_objects and haf_top_grasps -- share
+    // haf_fit_openings, haf_check_space, haf_measure_labels, haf_transfer_labels, the haf_grasp_map family with haf_cell_pose, haf_score_objects and haf_top_grasps -- share
     // ONE block with its pinned twin and ONE device-only scratch (call_buffers, engine_stage.cpp): allocated by the first call that needs
     // them, grown to the largest need seen, laid out by the call that is running, and nobody's once it has returned.  A call writes every
     // region before it reads it (DESIGN.md 4 has the table): what it finds there is any other call's leftovers

@@ -11,6 +11,7 @@
 #include "transfer_rules.h"
 #include "clearance_rules.h"
 #include "opening_rules.h"
+#include "space_rules.h"
 
 #include <string>
 
@@ -84,11 +85,17 @@ int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_labe
                    const haf_transfer_params *p, const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device,
                    std::string &err);
 haf_transfer_math::TransferRules transfer_rules(const haf_camera &cam, const haf_transfer_params &p);
+// ... its refusals of a camera's own fields, and of near_m, tol_abs and tol_rel (name: the parameter struct's, for the text); haf_check_space
+// applies both to every view
+int check_camera(const haf_camera &cam, std::string &err);
+int check_projection_params(const char *name, float near_m, float tol_abs, float tol_rel, std::string &err);
 // clearance_host.cpp, shared by haf_check_grasps_ref and haf_check_grasps: every refusal of the frame, the mask, the gripper and the
 // grasp list that needs no engine (*bounds filled when the gripper passes); THE integer bounds and the reach of a gripper, false for one
 // the call refuses; THE twelve words of a grasp, in double (reach_q = -1 for a void one); the words of n grasps read at a stride
 int check_clearance(const haf_frame *frame, const haf_roi *mask, const haf_gripper *gripper, int32_t n_grasps, const void *grasps,
                     size_t grasp_stride_bytes, const haf_grasp_clearance *out, haf_clear_math::ClearBounds *bounds, std::string &err);
+// ... its refusals of the gripper, n_grasps and the stride alone (*bounds filled when the gripper passes); haf_check_space applies them
+int check_grasp_list(const haf_gripper *gripper, int32_t n_grasps, size_t grasp_stride_bytes, haf_clear_math::ClearBounds *bounds, std::string &err);
 bool gripper_rules(const haf_gripper &g, haf_clear_math::ClearBounds *b);
 // the unit axes of a grasp in double: a along the approach vector, c the closing axis, b = a x c; false for a void grasp
 bool grasp_axes(const haf_grasp_output &g, double *a, double *b, double *c);
@@ -110,5 +117,22 @@ void opening_info(const haf_open_math::OpenRules &r, haf_opening_info *info);
 // n_found (either may be null)
 void opening_finish(const haf_open_math::OpenRules &r, const haf_clear_math::GraspWords *w, const int32_t *rows, int32_t n,
                     haf_grasp_opening *out, int32_t *order, int32_t *n_found);
+// space_host.cpp, shared by haf_check_space_ref and haf_check_space: every refusal that needs no engine -- check_grasp_list's, the
+// parameters', then per view check_frame's, the kind, haf_invert_pose's and check_camera's, the lattice's size and the size of `states`
+// (*call filled when all pass: the gripper's bounds, the lattice and every view's rules); what a caller is told about the lattice
+struct SpaceCall {
+    haf_clear_math::ClearBounds b;
+    haf_space_math::SpaceLattice l;
+    haf_space_math::SpaceViewRules v[haf_space_math::kSpaceMaxViews];
+};
+int check_space(const haf_frame *views, int32_t n_views, const haf_gripper *gripper, const haf_space_params *params, int32_t n_grasps,
+                const void *grasps, size_t grasp_stride_bytes, const haf_grasp_space *out, const uint8_t *states, SpaceCall *call, std::string &err);
+// THE lattice of a call from the gripper's bounds and the step's word (N = l->first[4] may exceed the cap: check_space refuses it)
+void space_lattice(const haf_clear_math::ClearBounds &b, int32_t S, haf_space_math::SpaceLattice *l);
+void space_info(const haf_space_math::SpaceLattice &l, haf_space_info *info);
+// THE row of every grasp from its sixteen counts (rows: n x kSpaceRowWords host words; a void grasp's is not read), clear, order and
+// n_clear (either may be null)
+void space_finish(const haf_space_params &p, const haf_clear_math::GraspWords *w, const int32_t *rows, int32_t n, haf_grasp_space *out,
+                  int32_t *order, int32_t *n_clear);
 
 }  // namespace haf

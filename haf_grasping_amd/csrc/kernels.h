@@ -702,6 +702,24 @@ struct OpenDev {
 };
 // the three launches of one call, in stream order: the points' words, grasps x points into the histograms, one wave's search per grasp
 void launch_openings(const OpenDev &d, hipStream_t s);
+// haf_check_space (space.hip): the lattice, the views and the grasps as the kernel reads them -- a kernel argument, so every field is a
+// scalar load, a view's by its wave-uniform index.  l: the call's lattice; v[k], src[k], row_stride[k]: view k's rules (space_rules.h),
+// its first depth sample and the bytes between its rows; grasps: n_grasps x haf_clear_math::kClearGraspWords words (GraspWords); rows:
+// n_grasps x haf_space_math::kSpaceRowWords words, zeroed by the caller; states: null, or n_grasps x N bytes, every one written.  All of
+// it device memory
+struct SpaceDev {
+    haf_space_math::SpaceLattice l;
+    haf_space_math::SpaceViewRules v[haf_space_math::kSpaceMaxViews];
+    const void *src[haf_space_math::kSpaceMaxViews];
+    unsigned long long row_stride[haf_space_math::kSpaceMaxViews];
+    int n_views, n_grasps;
+    const int *grasps;
+    unsigned *rows;
+    unsigned char *states;
+};
+constexpr int kSpaceChunk = 256;                   // samples per workgroup of k_space_samples, one per lane
+// the one launch of a call: grid (chunks of the lattice, grasps); none for a lattice without a sample
+void launch_space(const SpaceDev &d, hipStream_t s);
 // haf_measure_labels (labelshape.hip): one frame and its label image as the kernel reads them -- a kernel argument, so every field is a
 // scalar load.  f: the frame (dst and count are not read); labels: label_bytes 1 or 2 per pixel, rows label_stride bytes apart; plane:
 // read when use_plane is set; table: n_labels rows of haf_shape_math::kShapeRowWords words (label_shape.h), zeroed by the caller.  All

@@ -28,6 +28,28 @@ int64_t rne(double x) { return (int64_t)std::nearbyint(x); }
 
 }  // namespace
 
+int check_camera(const haf_camera &cam, std::string &err)
+{
+    if (cam.width < 1 || cam.width > kMaxCameraSide || cam.height < 1 || cam.height > kMaxCameraSide) {
+        err = "haf_camera: width or height outside 1..32768";
+        return HAF_E_ARG;
+    }
+    if (!in_range(cam.fx, kMinFocal, kMaxFocal) || !in_range(cam.fy, kMinFocal, kMaxFocal)) { err = "haf_camera: fx or fy outside 1/256..32768"; return HAF_E_ARG; }
+    if (!in_range(cam.cx, -kMaxCentre, kMaxCentre) || !in_range(cam.cy, -kMaxCentre, kMaxCentre)) { err = "haf_camera: |cx| or |cy| above 32768"; return HAF_E_ARG; }
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(cam.base_to_camera[i])) { err = "haf_camera: base_to_camera has an entry that is not finite"; return HAF_E_ARG; }
+    return HAF_OK;
+}
+
+int check_projection_params(const char *name, float near_m, float tol_abs, float tol_rel, std::string &err)
+{
+    const std::string n = name;
+    if (!in_range(near_m, kMinNear, kMaxNear)) { err = n + ": near_m outside 0.001..16"; return HAF_E_ARG; }
+    if (!std::isfinite(tol_abs) || !(tol_abs >= 0.0f)) { err = n + ": tol_abs must be finite and not negative"; return HAF_E_ARG; }
+    if (!in_range(tol_rel, 0.0f, 1.0f)) { err = n + ": tol_rel outside 0..1"; return HAF_E_ARG; }
+    return HAF_OK;
+}
+
 int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_label_image *l, int32_t n_labels, const haf_transfer_params *p,
                    const void *labels, int32_t elem_bytes, size_t row_stride_bytes, int32_t out_on_device, std::string &err)
 {
@@ -35,17 +57,8 @@ int check_transfer(const haf_frame *depth, const haf_camera *cam, const haf_labe
     int rc = check_frame(*depth, err);
     if (rc != HAF_OK) return rc;
     if ((rc = check_label_output(*depth, labels, elem_bytes, row_stride_bytes, out_on_device, err)) != HAF_OK) return rc;
-    if (cam->width < 1 || cam->width > kMaxCameraSide || cam->height < 1 || cam->height > kMaxCameraSide) {
-        err = "haf_camera: width or height outside 1..32768";
-        return HAF_E_ARG;
-    }
-    if (!in_range(cam->fx, kMinFocal, kMaxFocal) || !in_range(cam->fy, kMinFocal, kMaxFocal)) { err = "haf_camera: fx or fy outside 1/256..32768"; return HAF_E_ARG; }
-    if (!in_range(cam->cx, -kMaxCentre, kMaxCentre) || !in_range(cam->cy, -kMaxCentre, kMaxCentre)) { err = "haf_camera: |cx| or |cy| above 32768"; return HAF_E_ARG; }
-    for (int i = 0; i < 12; i++)
-        if (!std::isfinite(cam->base_to_camera[i])) { err = "haf_camera: base_to_camera has an entry that is not finite"; return HAF_E_ARG; }
-    if (!in_range(p->near_m, kMinNear, kMaxNear)) { err = "haf_transfer_params: near_m outside 0.001..16"; return HAF_E_ARG; }
-    if (!std::isfinite(p->tol_abs) || !(p->tol_abs >= 0.0f)) { err = "haf_transfer_params: tol_abs must be finite and not negative"; return HAF_E_ARG; }
-    if (!in_range(p->tol_rel, 0.0f, 1.0f)) { err = "haf_transfer_params: tol_rel outside 0..1"; return HAF_E_ARG; }
+    if ((rc = check_camera(*cam, err)) != HAF_OK) return rc;
+    if ((rc = check_projection_params("haf_transfer_params", p->near_m, p->tol_abs, p->tol_rel, err)) != HAF_OK) return rc;
     if (p->splat < 0 || p->splat > kMaxSplat) { err = "haf_transfer_params: splat outside 0..2"; return HAF_E_ARG; }
     if ((rc = check_label_image(l, cam->width, n_labels, err)) != HAF_OK) return rc;      // (the CAMERA's width: its image is the camera's)
     if (elem_bytes == 1 && n_labels > 255) { err = "n_labels above 255 with a uint8 output"; return HAF_E_ARG; }

@@ -169,6 +169,24 @@ class CalcGraspPointsServer:
                                        g["approach_vector"], g["roll"]), rows[i].copy()))
         return out
 
+    def seen_free_grasps(self, frames, k=None, gripper=None, params=None, **top_params):
+        """The ranked candidates of the last execute*() whose gripper volume the cameras have SEEN to be empty (haf_check_space on
+        haf_top_grasps' output): a lattice of sample points inside the gripper's boxes at every candidate is classified against 1..8
+        depth views `frames` (a capi.depth_frame or a list of them: the scored view, a second camera) as unseen, hidden, free or hit,
+        and the candidates with clear == 1 -- by params (capi.space_params(...)): at most max_hit hit and max_unknown hidden or unseen
+        samples in the fingers and the palm, at least min_between_hit hit samples between the fingers -- are returned as
+        (GraspOutputMsg, space) pairs, best first; space: one capi.SPACE_DTYPE record.  Where free_grasps counts no point and says
+        "free" -- behind an object, under an overhang -- this says "not seen".  top_params as free_grasps takes them; the ranking itself
+        is top_grasps()', unchanged."""
+        if k is not None:
+            top_params["k"] = k
+        cands = self.engine.top_grasps(**top_params)[0]
+        if not cands:
+            return []
+        rows, order, _ = self.engine.check_space(frames, cands, gripper, params)
+        return [(GraspOutputMsg(self.base_frame_id, cands[i]["eval"], cands[i]["grasp_point1"], cands[i]["grasp_point2"],
+                                cands[i]["averaged_grasp_point"], cands[i]["approach_vector"], cands[i]["roll"]), rows[i].copy()) for i in order]
+
     def grasp_map(self, frame, want=("vote", "roll")):
         """The last execute*()'s votes in the pixels of `frame` (haf_grasp_map): any capi.depth_frame / capi.xyz_frame -- the scored
         view, another camera, the registered RGB view -- -> dict of [height, width] images: vote int16 (capi.MAP_NO_CELL where no roll

@@ -1150,6 +1150,94 @@ int  haf_fit_openings(haf_engine *e, const haf_frame *frame, const haf_roi *mask
                       int32_t *n_found /* may be NULL */, haf_opening_info *info /* may be NULL */, uint32_t *hist /* host, may be NULL */);
 int  haf_apply_opening(const haf_grasp_output *in, const haf_grasp_opening *opening, haf_grasp_output *out);
 
+/* ---- is the gripper's volume SEEN to be empty: sample points against depth views, on the device (csrc/space.hip) --------------------
+ * haf_check_grasps and haf_fit_openings test points, not surfaces: where a depth camera returned nothing -- behind an object, under an
+ * overhang, where it got no return -- they count zero points and report a free gripper.  This call asks the opposite question: a
+ * finger may only go where a camera has seen THROUGH the space.  A depth pixel's ray is empty up to its depth, hits a surface at its
+ * depth and is unknown behind it; a second view turns "unknown" into "seen empty".  For each of n_grasps poses the call lays a fixed
+ * lattice of sample points inside the gripper's four boxes and classifies every sample against 1..HAF_MAX_SPACE_VIEWS depth views.
+ * The rules are csrc/space_rules.h's.  Everything behind one fp32 transform per view is integer arithmetic: no result depends on an
+ * order of evaluation or on the order in which atomics arrive.
+ *
+ *   views         views[n_views], HAF_FRAME_DEPTH_U16 or HAF_FRAME_DEPTH_F32 (an XYZ frame has no rays), each with its own size,
+ *                 intrinsics, pose and residence.  View k is read as the camera haf_transfer_labels would call haf_camera{width,
+ *                 height, fx, fy, cx, cy, base_to_camera = haf_invert_pose(sensor_to_base)}: FX, FY, CX, CY as there, and NEAR, TA, TR
+ *                 from this call's near_m, tol_abs, tol_rel as there.  Pixel (u, v) has depth z by haf_frame's depth rule (depth_scale,
+ *                 min_depth, max_depth; d == 0, a d that is not finite or <= 0 invalid); its observed word is Zobs = rne(z * 65536),
+ *                 and 2^20 for a valid z above 16 m.
+ *   grasps        haf_check_grasps': the twelve words A, B, C, o of a grasp, the void rule, the bounds W() of the haf_gripper (max_hits
+ *                 and min_between are NOT read), a reach above 1 m refused.
+ *   lattice       one per call, the same for every grasp.  S = W(sample_step).  Boxes in (s, t, u), units of 2^-26 m:
+ *                   between   [-W(opening/2), W(opening/2)] x [-W(finger_breadth/2), W(finger_breadth/2)] x [U0, U1]
+ *                   finger 0  [-W(opening/2 + finger_thickness), -W(opening/2)] x the same t and u
+ *                   finger 1  [W(opening/2), W(opening/2 + finger_thickness)] x the same t and u
+ *                   palm      [-W(palm_width/2), W(palm_width/2)] x [-W(palm_breadth/2), W(palm_breadth/2)] x [U1, U1 + W(palm_height)]
+ *                 Per axis of a box [lo, hi]: n = max(1, (hi - lo) / S); sample k of n lies at lo + ((2k + 1)(hi - lo)) / (2n), int64,
+ *                 both divisions truncating.  A region with a dimension of 0 has no samples (its three n are 0).  Sample index:
+ *                 region-major in the order above, then u, then t, with s fastest.  N = all samples <= HAF_MAX_SPACE_SAMPLES.
+ *   sample point  in int64, units of 2^-40 m: P_j = o_j 2^28 + s C_j + t B_j + u A_j;  Pq_j = (P_j + 2^23) >> 24, an arithmetic
+ *                 shift: a word of 1/65536 m;  p_j = (float)Pq_j * (1.0f / 65536), exact.
+ *   per view      haf_transfer_labels' projection of p, unchanged: q = base_to_camera p in twelve rounded fp32 operations, Q = rne(q *
+ *                 65536), Qz >= NEAR, the pixel (uc, vc).  The sample is UNSEEN in the view when it does not project or the pixel is
+ *                 invalid.  Otherwise tol = TA + ((int64)TR * Zobs >> 16) and D = Qz - Zobs:  D > tol HIDDEN (behind the surface the
+ *                 ray hit);  D < -tol FREE (the ray went through it);  else HIT.
+ *   over views    rank UNSEEN 0 < HIDDEN 1 < FREE 2 < HIT 3; a sample's state is the maximum over the views: a view that sees a
+ *                 surface at the sample wins over one that sees past it, one that sees past it over one that cannot tell.
+ *   row           n[region][state], regions between, finger 0, finger 1, palm.  clear = -1 for a void grasp, with all counts 0;
+ *                 clear = 1 when, over the fingers and the palm, hit <= max_hit and hidden + unseen <= max_unknown, and
+ *                 n[between][HIT] >= min_between_hit; else 0.  By ONE host function both entry points call.
+ *   order         (may be NULL) the indices of the grasps with clear = 1, in input order; *n_clear (may be NULL) their number.
+ *   info          (may be NULL) S, the twelve n and N.
+ *   states        (may be NULL) host memory, uint8 [n_grasps][N]: every sample's final rank (0 for a void grasp's).  Offered only when
+ *                 n_grasps * N <= 2^22; a buffer of min(n_grasps * HAF_MAX_SPACE_SAMPLES, 2^22) bytes holds whatever is offered.
+ * The defaults of haf_space_default are NOMINAL figures like the gripper's.  Not modelled: a mask for the robot's own arm, lens
+ * distortion, anything between lattice points, grippers other than haf_gripper, the arm behind the palm, a free choice of which view
+ * wins (HIT beats FREE by definition).
+ *
+ * haf_check_space_ref: the host definition of record -- no device, no engine, host views only.
+ * haf_check_space: equal to it in every word of every row, of order, n_clear, info and states; every view host or device-resident, a
+ * device-resident one read where it lies; host views go up through the raw area of haf_score_frames, each at a multiple of 16 bytes;
+ * one memset, ONE launch (k_space_samples: a lane per sample, a workgroup per 256 samples of one grasp), ONE copy back and ONE
+ * synchronisation.  Like haf_check_grasps it neither reads nor changes last-batch state or stage timings, works before any request
+ * and with HAF_FLAG_PROBABILITY, and shares that call's block and scratch (128 bytes per grasp; n_grasps * N bytes with states).
+ * Refusals, all before any device work, nothing written -- everything haf_check_grasps refuses for gripper, grasps, stride and out;
+ * per view everything haf_score_frames refuses for a frame's own fields and haf_transfer_labels for a camera of the view's size and
+ * intrinsics; HAF_E_ARG: a null views or params, an XYZ view, haf_invert_pose failing, n_views outside 1..HAF_MAX_SPACE_VIEWS,
+ * sample_step not finite or outside [0.0005, 1], near_m, tol_abs or tol_rel outside haf_transfer_params' ranges, N above the cap, for
+ * the _ref form a device-resident view; HAF_E_CAPACITY: states with n_grasps * N > 2^22, a view of more pixels than max_points, the
+ * host views' pixels together above max_points. */
+#define HAF_MAX_SPACE_VIEWS 8
+#define HAF_MAX_SPACE_SAMPLES 65536
+enum { HAF_SPACE_BETWEEN = 0, HAF_SPACE_FINGER0 = 1, HAF_SPACE_FINGER1 = 2, HAF_SPACE_PALM = 3 };
+enum { HAF_SPACE_UNSEEN = 0, HAF_SPACE_HIDDEN = 1, HAF_SPACE_FREE = 2, HAF_SPACE_HIT = 3 };
+typedef struct haf_space_params {
+    float   sample_step;                /* metres between lattice points, finite, in [0.0005, 1]                              */
+    float   near_m, tol_abs, tol_rel;   /* as haf_transfer_params': [0.001, 16]; >= 0; [0, 1] per metre of the observed depth */
+    int32_t max_hit;                    /* clear: at most this many HIT samples in the fingers and the palm together          */
+    int32_t max_unknown;                /* clear: at most this many HIDDEN or UNSEEN samples there                            */
+    int32_t min_between_hit;            /* clear: at least this many HIT samples between the fingers                          */
+} haf_space_params;
+typedef struct haf_grasp_space {
+    int32_t clear;                      /* 1 clear, 0 not, -1 a void grasp */
+    int32_t n[4][4];                    /* [HAF_SPACE_BETWEEN .. PALM][HAF_SPACE_UNSEEN .. HIT] */
+    int32_t reserved[3];
+} haf_grasp_space;
+typedef struct haf_space_info {
+    int32_t step;                       /* S, units of 2^-26 m */
+    int32_t n[4][3];                    /* per region: samples along s, t, u */
+    int32_t n_samples;                  /* N */
+    int32_t reserved[2];
+} haf_space_info;
+void haf_space_default(haf_space_params *p);   /* 0.004f, 0.05f, 0.004f, 0.002f, 0, 0, 1 */
+int  haf_check_space_ref(const haf_frame *views, int32_t n_views, const haf_gripper *gripper, const haf_space_params *params,
+                         int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes, haf_grasp_space *out /* [n_grasps] */,
+                         int32_t *order /* [n_grasps], may be NULL */, int32_t *n_clear /* may be NULL */,
+                         haf_space_info *info /* may be NULL */, uint8_t *states /* [n_grasps][N], may be NULL */);
+int  haf_check_space(haf_engine *e, const haf_frame *views, int32_t n_views, const haf_gripper *gripper, const haf_space_params *params,
+                     int32_t n_grasps, const void *grasps, size_t grasp_stride_bytes, haf_grasp_space *out /* [n_grasps] */,
+                     int32_t *order /* [n_grasps], may be NULL */, int32_t *n_clear /* may be NULL */,
+                     haf_space_info *info /* may be NULL */, uint8_t *states /* host, [n_grasps][N], may be NULL */);
+
 int haf_abi_version(void);
 
 #ifdef __cplusplus

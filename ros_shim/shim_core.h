@@ -210,6 +210,31 @@ inline int fitted_hypotheses(haf_engine *engine, const haf_config &cfg, const ha
     return rc;
 }
 
+// top_hypotheses for a planner that may only go where a camera has looked: the same ranked candidates, each checked against the depth
+// views `views` (haf_check_space: the sample points of `gripper`'s volume seen free, hit, hidden or not at all), as hypothesis strings,
+// best first; a candidate whose row does not say clear == 1 is left out.  An adapter with one or more depth topics would publish them
+// where it publishes top_hypotheses'.  rows (may be null): every candidate's row, in rank order, the ones that are not clear included.
+// Returns the engine's status; on failure *err carries haf_last_error().
+inline int seen_free_hypotheses(haf_engine *engine, const haf_config &cfg, const haf_top_params &p, const haf_frame *views, int32_t n_views,
+                                const haf_gripper &gripper, const haf_space_params &space, std::vector<std::string> *lines, std::string *err,
+                                std::vector<haf_grasp_space> *rows_out = nullptr)
+{
+    const size_t clouds = (size_t)(cfg.max_clouds > 0 ? cfg.max_clouds : 1), k = (size_t)(p.k > 0 ? p.k : 1);
+    std::vector<haf_grasp_candidate> cand(clouds * k);
+    std::vector<int32_t> n(clouds, 0);
+    int rc = haf_top_grasps(engine, &p, cand.data(), n.data());
+    if (rc == HAF_OK && n[0] > 0) {
+        std::vector<haf_grasp_space> rows((size_t)n[0]);
+        rc = haf_check_space(engine, views, n_views, &gripper, &space, n[0], cand.data(), sizeof(haf_grasp_candidate), rows.data(), nullptr, nullptr,
+                             nullptr, nullptr);
+        for (int32_t i = 0; rc == HAF_OK && i < n[0]; i++)
+            if (rows[(size_t)i].clear == 1) lines->push_back(hypothesis_string(cand[(size_t)i].grasp, cfg.roll_step_deg));
+        if (rc == HAF_OK && rows_out) *rows_out = rows;
+    }
+    if (rc != HAF_OK && err) *err = haf_last_error(engine);
+    return rc;
+}
+
 // The best grasp per object of the engine's last scored goal from an instance-label image that goes with `frame` (haf_grasp_map_labels):
 // one line "<label> <u> <v> <hypothesis string>" per object that has a pixel with a vote >= min_vote, best first -- the next OBJECT for a
 // planner whose first choice fails, where top_hypotheses gives the next grasp.  An adapter with a label topic synchronised with the depth
