@@ -454,6 +454,13 @@ def _bind(path, testing):
         L.haf_test_snapshot_screen.argtypes = [E, C.c_int]
         L.haf_test_prestage_forms.argtypes = [E, C.c_void_p]
         L.haf_test_fetch_snapshot.argtypes = [E, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+        L.haf_test_sweep_form.argtypes = [E, C.c_int, C.c_void_p]
+        L.haf_test_fetch_sweep.argtypes = [E, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+        L.haf_test_host_sweep_tables.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_longlong,
+                                                 C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+        L.haf_test_host_screen_finish.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+        L.haf_test_lr_finish_band.argtypes = [C.POINTER(Config), C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_int]
         L.haf_test_tier_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.haf_test_revote.argtypes = [E, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.haf_test_last_batch.argtypes = [E, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -1320,6 +1327,32 @@ class Engine:
         if nbytes > 0:
             self._check(self._L.haf_test_fetch_snapshot(self._h, which, offset, buf.ctypes.data_as(C.c_void_p), nbytes, C.byref(avail)))
         return buf
+
+    SWEEP_PARTS = ("dec", "margin", "words", "list", "counters", "part", "in_X", "in_gband", "in_ax", "labels", "raw", "Y")
+    _SWEEP_DTYPES = (np.float32, np.float32, np.uint64, np.int32, np.int32, np.float32, np.uint8, np.float32, np.float32, np.int8, np.float32, np.uint8)
+
+    def sweep_form(self, slot=0):
+        """Testing build (haf_test_sweep_form): which sweep launch `slot` (0 the first pass, 1 tier 0b) of the last request was, as its
+        launcher reported it -> dict(variant: SCREEN_* of the kernel, -1 when there was no such launch; lr, part, fused, gather, list:
+        bool; compaction: 0 one workgroup, 1 two launches; blocks; cap: the evaluation slots the launch covered)."""
+        out = (C.c_longlong * 9)()
+        self._check(self._L.haf_test_sweep_form(self._h, slot, out))
+        return dict(variant=int(out[0]), lr=bool(out[1]), part=bool(out[2]), fused=bool(out[3]), gather=bool(out[4]), list=bool(out[5]),
+                    compaction=int(out[6]), blocks=int(out[7]), cap=int(out[8]))
+
+    def fetch_sweep(self, what, slot=0):
+        """Testing build (haf_test_fetch_sweep; snapshot_screen must be on): what sweep launch `slot` of the last request left, copied
+        right behind the launch -- `what` one of SWEEP_PARTS: dec and margin [cap] fp32, the flag words uint64, the output list int32
+        [flag0_cap], the counters int32 as they stood behind the launch, part (PART form: float32 [16, blocks * 256, 4]) and, for tier
+        0b's list-image form, its list-indexed operand images (uint8), bands and a_x; labels: the label grids int8 (every cell of the
+        engine's grids); raw: the raw sums a low-rank sweep read; Y: the 6-step images k_project wrote (uint8, two-launch form)."""
+        which = self.SWEEP_PARTS.index(what)
+        avail = C.c_longlong()
+        self._check(self._L.haf_test_fetch_sweep(self._h, slot, which, 0, None, 0, C.byref(avail)))
+        buf = np.empty(max(0, avail.value), dtype=np.uint8)
+        if avail.value > 0:
+            self._check(self._L.haf_test_fetch_sweep(self._h, slot, which, 0, buf.ctypes.data_as(C.c_void_p), avail.value, C.byref(avail)))
+        return buf.view(self._SWEEP_DTYPES[which])
 
     def revote(self, labels=None, gridf=None, heights=None, roi_words=None):
         """Testing build (haf_test_revote): replaces the last scored batch's B x R grids by `labels` (int8 [B, R, H, W]; a plain engine)

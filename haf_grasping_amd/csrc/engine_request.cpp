@@ -254,6 +254,11 @@ static int *list_buf(haf_engine *e, int l)
     int *const buf[] = {e->d_flag0_list.p, e->d_flag0b_list.p, e->d_flag_list.p, e->d_flagi_list.p, e->d_flag2_list.p};
     return l == L_NONE ? nullptr : buf[l];
 }
+static size_t list_len(const haf_engine *e, int l)
+{
+    const size_t n[] = {e->d_flag0_list.n, e->d_flag0b_list.n, e->d_flag_list.n, e->d_flagi_list.n, e->d_flag2_list.n};
+    return l == L_NONE ? 0 : n[l];
+}
 // a pass that writes the exact tiers' input list publishes its length in that list's counter too (screen.hip: also_counter)
 static int handover_counter(int l) { return l == L_FLAG ? CNT_FLAGGED : -1; }
 
@@ -555,6 +560,48 @@ static TierFacts tier_facts(const haf_engine *e, const Request &q, int mode, boo
                      q.fused_pre, (long)q.d.H * q.d.W, q.evals_cap};
 }
 
+// Testing library only (haf_test_snapshot_screen): what sweep launch `slot` (0 the first pass, 1 tier 0b) of this request left, copied
+// aside on the request's stream right behind the launch -- dec, margin, the flag words, the output list, the counters and, in the PART
+// form, the partial sums.  The buffers are sized by haf_test_snapshot_screen; nothing happens while the snapshot is off.
+static void snapshot_sweep(haf_engine *e, int slot, const SweepForm &form, long cap, long evals_cap, int out_l, hipStream_t s)
+{
+    haf_engine::SweepSnap &sn = e->snap_sweep[slot];
+    sn.form = form;
+    sn.cap = sn.dec_cap = sn.list_cap = sn.part_bytes = sn.raw_cap = sn.y_bytes = 0;
+    if (!e->snap_on || form.variant < 0 || !sn.dec.p) return;
+    cap = std::min<long>(std::min<long>(cap, e->max_evals_pad), (long)sn.dec.n);
+    const long pad = std::min<long>((cap + kS0BlockEvals - 1) / kS0BlockEvals * kS0BlockEvals, (long)sn.dec.n);
+    sn.cap = cap;
+    // (dec and margin go by evaluation id in every launch, a list launch's too: the request's evaluation slots, not the list's)
+    sn.dec_cap = std::min<long>(std::min<long>(evals_cap, e->max_evals_pad), (long)std::min(sn.dec.n, e->d_dec.n));
+    (void)hipMemcpyAsync(sn.dec.p, e->d_dec.p, (size_t)sn.dec_cap * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e->d_margin.p && sn.margin.p)
+        (void)hipMemcpyAsync(sn.margin.p, e->d_margin.p, std::min<size_t>((size_t)sn.dec_cap, std::min(sn.margin.n, e->d_margin.n)) * sizeof(float), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sn.words.p, e->d_flag0_words.p, std::min<size_t>(std::min(sn.words.n, e->d_flag0_words.n), (size_t)(pad / 64)) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sn.counters.p, e->d_counters.p, CNT_COUNT * sizeof(int), hipMemcpyDeviceToDevice, s);
+    if (sn.labels.p) (void)hipMemcpyAsync(sn.labels.p, e->d_labels.p, std::min(sn.labels.n, e->d_labels.n), hipMemcpyDeviceToDevice, s);
+    if (form.lr && sn.raw.p) {
+        sn.raw_cap = std::min<long>(sn.dec_cap, (long)std::min(sn.raw.n, e->d_gband.n) / kBandFloats);
+        (void)hipMemcpyAsync(sn.raw.p, e->d_gband.p, (size_t)sn.raw_cap * kBandFloats * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (!form.fused && sn.Y.p) {
+            // (k_project's images lie behind the 10-step images of the engine's largest request: launch_screening's y_img)
+            const size_t off = (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes, have = e->d_X.n * sizeof(float);
+            const size_t want = (size_t)((sn.dec_cap + kTile - 1) / kTile) * (size_t)kLrMatBytes;
+            sn.y_bytes = (long)std::min(std::min(want, sn.Y.n), have > off ? have - off : 0);
+            (void)hipMemcpyAsync(sn.Y.p, reinterpret_cast<const char *>(e->d_X.p) + off, (size_t)sn.y_bytes, hipMemcpyDeviceToDevice, s);
+        }
+    }
+    if (const int *out_list = list_buf(e, out_l)) {
+        sn.list_cap = std::min<long>(e->flag0_cap, (long)std::min(sn.list.n, list_len(e, out_l)));
+        (void)hipMemcpyAsync(sn.list.p, out_list, (size_t)sn.list_cap * sizeof(int), hipMemcpyDeviceToDevice, s);
+    }
+    if (form.part && e->d_screen_part.p && sn.part.p) {
+        // (slice k of the launch lies at float4 index k * blocks * 256: the first kS0MaxParts slices of `blocks` workgroups are contiguous)
+        sn.part_bytes = (long)std::min<size_t>(sn.part.n, std::min<size_t>(e->d_screen_part.n, (size_t)16 * form.blocks * kS0BlockEvals * 16));
+        (void)hipMemcpyAsync(sn.part.p, e->d_screen_part.p, (size_t)sn.part_bytes, hipMemcpyDeviceToDevice, s);
+    }
+}
+
 // the screening pass (tier 0), tier 0b, the short-list gate and tier 1 of a PATH_SCREEN plan
 static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
 {
@@ -577,20 +624,22 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     }
     char *y_img = reinterpret_cast<char *>(e->d_X.p) + (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes;   // behind the 10-step images (the buffer holds the 42 KiB three-pass form)
     mark(e, HAF_ST_SVM);
+    SweepForm form0, form1;
     if (p.lr && !e->lr_fused) launch_project(e->d_X.p, e->d_lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)
     if (p.lr)
-        launch_svm_screen_lr(e->lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        form0 = launch_svm_screen_lr(e->lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
                              e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d,
                              evals_cap, e->d_margin.p, e->screen_variant, e->crp, e->lr_band, s, handover_counter(p.pass0_out),
                              e->lr_fused ? e->d_lr_btiles_in.p : nullptr);
     else
-        launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, p.cr ? e->d_svt0_cr.p : e->d_svt0.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        form0 = launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, p.cr ? e->d_svt0_cr.p : e->d_svt0.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
                           e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d, evals_cap, e->d_margin.p,
                           e->screen_variant, e->crp, s, handover_counter(p.pass0_out), nullptr, CNT_EVALS, CNT_FLAGGED0, e->d_screen_part.p, e->screen_parts);
+    snapshot_sweep(e, 0, form0, evals_cap, evals_cap, p.pass0_out, s);
     mark(e, HAF_ST_REFINE);
     const long list_cap = std::min<long>(e->flag0_cap, evals_cap);
     if (p.t0b == T0B_GATHER) {
-        launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p,
+        form1 = launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p,
                              e->d_labels.p, e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap,
                              e->d_counters.p, d, list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, e->lr_band, s, handover_counter(p.t0b_out),
                              e->d_lr_btiles_in.p, list_buf(e, p.t0b_in), list_counter(p.t0b_in), CNT_FLAGGED0B);
@@ -605,11 +654,20 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
         launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_gband.p, d, e->range.lower,
                         e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SCREEN, sp_b, list_buf(e, p.t0b_in), list_counter(p.t0b_in), e->flag0_cap,
                         false, list_cap, nullptr, e->d_ax.p, s);
-        launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->d_svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        if (e->snap_on && e->snap_sweep[1].in_X.p) {         // (testing library only: tier 0b's own, list-indexed feature output)
+            haf_engine::SweepSnap &sn = e->snap_sweep[1];
+            const size_t tiles = std::min<size_t>((size_t)((list_cap + kTile - 1) / kTile), sn.in_X.n / (size_t)kS0MatBytes);
+            const size_t slots = std::min<size_t>((size_t)list_cap, sn.in_ax.n);
+            (void)hipMemcpyAsync(sn.in_X.p, e->d_X1.p, tiles * (size_t)kS0MatBytes, hipMemcpyDeviceToDevice, s);
+            (void)hipMemcpyAsync(sn.in_gband.p, e->d_gband.p, slots * kBandFloats * sizeof(float), hipMemcpyDeviceToDevice, s);
+            (void)hipMemcpyAsync(sn.in_ax.p, e->d_ax.p, slots * sizeof(float), hipMemcpyDeviceToDevice, s);
+        }
+        form1 = launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->d_svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
                           e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap, e->d_counters.p, d,
                           list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, s, handover_counter(p.t0b_out), list_buf(e, p.t0b_in), list_counter(p.t0b_in),
                           CNT_FLAGGED0B, e->d_screen_part.p, e->screen_parts);
     }
+    snapshot_sweep(e, 1, form1, list_cap, evals_cap, p.t0b_out, s);
     // (the gate's count goes to CNT_FLAGGEDI only when it writes the exact-integer tier's output list)
     if (p.gate)
         launch_short_list_gate(e->d_counters.p, list_counter(p.gate_in), list_buf(e, p.gate_in), e->flag0_cap, list_buf(e, p.gate_out),

@@ -440,6 +440,25 @@ struct haf_engine {
     long snap_cap = 0;              // evaluation slots the last snapshot covers
     DevBuf<char> snap_X;
     DevBuf<float> snap_gband, snap_ax;
+    // ... and of what every SWEEP launch of a request left (launch_screening: [0] the first pass, [1] tier 0b), taken right behind the
+    // launch, before a later tier writes dec, margin, the flag words or the lists again; `form` is what the launcher said it launched
+    // (kept whether or not the snapshot is on).  in_*: tier 0b's list-indexed operand images, bands and a_x (its feature kernel's output)
+    struct SweepSnap {
+        SweepForm form{};
+        long cap = 0;               // evaluation slots the launch covered (its max_evals); 0: the launch did not run in the last request
+        long dec_cap = 0;           // entries of dec and margin that were copied (they go by evaluation id: the request's slots)
+        long list_cap = 0;          // entries of the output list that were copied
+        long part_bytes = 0;        // bytes of part_buf that were copied (PART form only)
+        DevBuf<float> dec, margin;
+        DevBuf<unsigned long long> words;
+        DevBuf<int> list, counters;
+        DevBuf<char> part, in_X;
+        DevBuf<float> in_gband, in_ax;
+        DevBuf<int8_t> labels;      // the label grids right behind the launch (every cell of the engine's grids)
+        DevBuf<float> raw;          // low-rank form: the raw sums as the sweep read them (behind k_project in the two-launch form)
+        DevBuf<char> Y;             // low-rank form, two launches: the projected 6-step operand images k_project wrote
+        long raw_cap = 0, y_bytes = 0;
+    } snap_sweep[2];
     // The calls that run outside the request path -- haf_segment_frame, haf_segment_cells, haf_fit_plane, haf_check_grasps,
     // haf_fit_openings, haf_check_space, haf_measure_labels, haf_transfer_labels, the haf_grasp_map family with haf_cell_pose, haf_score_objects and haf_top_grasps -- share
     // ONE block with its pinned twin and ONE device-only scratch (call_buffers, engine_stage.cpp): allocated by the first call that needs

@@ -1,6 +1,7 @@
 // engine_testing.cpp -- the haf_test_* hooks of libhafgrasp_testing.so (tests/ only; the product library does not contain this file).
 #include "engine_state.h"
 #include "screen_finish.h"
+#include "screen_band.h"
 
 #ifndef HAF_TESTING
 #error "engine_testing.cpp belongs to the testing build (-DHAF_TESTING)"
@@ -136,6 +137,21 @@ int haf_test_snapshot_screen(haf_engine *e, int on)
             e->snap_gband.alloc((size_t)e->max_evals_pad * kBandFloats) != hipSuccess || e->snap_ax.alloc((size_t)e->max_evals_pad) != hipSuccess)
             return HAF_E_DEVICE;
     }
+    // ... and of what the sweep launches leave (engine_request.cpp: snapshot_sweep): [0] the first pass, [1] tier 0b with its list-indexed input
+    for (int k = 0; on && k < 2; k++) {
+        haf_engine::SweepSnap &sn = e->snap_sweep[k];
+        if (sn.dec.p) continue;
+        const size_t pad = (size_t)e->max_evals_pad, part = std::min<size_t>(e->d_screen_part.n, (size_t)16 * pad * 16);
+        if (sn.dec.alloc(pad) != hipSuccess || sn.margin.alloc(pad) != hipSuccess || sn.words.alloc(pad / 64 + 1) != hipSuccess ||
+            sn.list.alloc((size_t)std::max(e->flag0_cap, 1)) != hipSuccess || sn.counters.alloc(CNT_COUNT) != hipSuccess || sn.part.alloc(part) != hipSuccess)
+            return HAF_E_DEVICE;
+        if (sn.labels.alloc(e->d_labels.n) != hipSuccess || sn.raw.alloc(pad * kBandFloats) != hipSuccess ||
+            (k == 0 && e->lr_available && sn.Y.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kLrMatBytes) != hipSuccess))
+            return HAF_E_DEVICE;
+        if (k == 1 && (sn.in_X.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes) != hipSuccess ||
+                       sn.in_gband.alloc(pad * kBandFloats) != hipSuccess || sn.in_ax.alloc(pad) != hipSuccess))
+            return HAF_E_DEVICE;
+    }
     e->snap_on = on != 0;
     if (!on) e->snap_cap = 0;
     return HAF_OK;
@@ -147,6 +163,50 @@ int haf_test_fetch_snapshot(haf_engine *e, int which, long long offset, void *ou
     const char *src = which == 0 ? e->snap_X.p : which == 1 ? reinterpret_cast<const char *>(e->snap_gband.p) : reinterpret_cast<const char *>(e->snap_ax.p);
     const long long have = which == 0 ? (long long)((e->snap_cap + kTile - 1) / kTile) * kS0MatBytes
                                       : (long long)e->snap_cap * (which == 1 ? kBandFloats : 1) * (long long)sizeof(float);
+    *avail = src ? have : 0;
+    if (!bytes) return HAF_OK;
+    if (!src || !out || offset + bytes > have) return HAF_E_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return HAF_E_DEVICE;
+    return hipMemcpy(out, src + offset, (size_t)bytes, hipMemcpyDeviceToHost) == hipSuccess ? HAF_OK : HAF_E_DEVICE;
+}
+// Which sweep launch `slot` (0 the first pass, 1 tier 0b) of the last request was, as its launcher reported it (kernels.h: SweepForm):
+// out [9] = variant (-1: no such launch), lr, part, fused, gather, list, compaction (0 one workgroup, 1 two launches), blocks, and the
+// evaluation slots the launch covered.
+int haf_test_sweep_form(haf_engine *e, int slot, long long *out9)
+{
+    if (!e || !out9 || slot < 0 || slot > 1) return HAF_E_ARG;
+    const haf_engine::SweepSnap &sn = e->snap_sweep[slot];
+    const SweepForm &f = sn.form;
+    const long long v[9] = {f.variant, f.lr, f.part, f.fused, f.gather, f.list, f.compaction, f.blocks, sn.cap};
+    memcpy(out9, v, sizeof v);
+    return HAF_OK;
+}
+// bytes [offset, offset + bytes) of what sweep launch `slot` of the last request left while the snapshot was on: which = 0 dec, 1 margin
+// (HAF_FLAG_KEEP_DEBUG), 2 the flag words, 3 the output list (flag0_cap entries, whatever the counter says), 4 the counters right behind
+// the launch, 5 part_buf (PART form: slice k at float4 index k * blocks * 256), 6 / 7 / 8 tier 0b's list-indexed operand images, bands
+// and a_x (slot 1, list-image form), 9 the label grids (int8, every cell of the engine's grids), 10 the raw sums as a low-rank sweep read
+// them, 11 the projected 6-step images k_project wrote (low-rank form in two launches).  *avail = bytes held.
+int haf_test_fetch_sweep(haf_engine *e, int slot, int which, long long offset, void *out, long long bytes, long long *avail)
+{
+    if (!e || !avail || slot < 0 || slot > 1 || offset < 0 || bytes < 0 || which < 0 || which > 11) return HAF_E_ARG;
+    const haf_engine::SweepSnap &sn = e->snap_sweep[slot];
+    const long pad = (sn.cap + kS0BlockEvals - 1) / kS0BlockEvals * kS0BlockEvals;
+    const char *src = nullptr;
+    long long have = 0;
+    switch (which) {
+        case 0: src = (const char *)sn.dec.p; have = sn.dec_cap * 4; break;
+        case 1: src = (const char *)sn.margin.p; have = e->d_margin.p ? sn.dec_cap * 4 : 0; break;
+        case 2: src = (const char *)sn.words.p; have = std::min<long long>(pad / 64, (long long)sn.words.n) * 8; break;
+        case 3: src = (const char *)sn.list.p; have = sn.list_cap * 4; break;
+        case 4: src = (const char *)sn.counters.p; have = sn.cap ? CNT_COUNT * 4 : 0; break;
+        case 5: src = sn.part.p; have = sn.part_bytes; break;
+        case 6: src = sn.in_X.p; have = sn.in_X.p ? std::min<long long>((sn.cap + kTile - 1) / kTile * (long long)kS0MatBytes, (long long)sn.in_X.n) : 0; break;
+        case 7: src = (const char *)sn.in_gband.p; have = sn.in_gband.p ? sn.cap * kBandFloats * 4 : 0; break;
+        case 8: src = (const char *)sn.in_ax.p; have = sn.in_ax.p ? sn.cap * 4 : 0; break;
+        case 9: src = (const char *)sn.labels.p; have = sn.cap ? (long long)sn.labels.n : 0; break;
+        case 10: src = (const char *)sn.raw.p; have = sn.raw_cap * kBandFloats * 4; break;
+        default: src = sn.Y.p; have = sn.y_bytes; break;
+    }
     *avail = src ? have : 0;
     if (!bytes) return HAF_OK;
     if (!src || !out || offset + bytes > have) return HAF_E_ARG;
@@ -566,6 +626,101 @@ int haf_test_host_slot_table(const haf_config *cfg, double kappa, double kappa16
         scalars[0] = sp.c; scalars[1] = sp.lr_rho; scalars[2] = sp.ubar2; scalars[3] = sp.eta_abs; scalars[4] = sp.cr;
         scalars[5] = sp.cr_mu_norm; scalars[6] = sp.cr_mu_norm_t;
         groups[0] = sp.fast_groups; groups[1] = sp.extra_groups;
+        return (int)HAF_OK;
+    });
+    return rc == HAF_E_INTERNAL ? say(rc) : rc;
+}
+
+// The tables the sweep kernels read, from the same device-free build (no device is touched).  which = 0 svt0, 1 svt0_cr, 2 svt_lr,
+// 3 lr_btiles: its bytes into out (cap bytes; *bytes = its size, 0 when the model did not get it).  ints [4]:
+// n_sv_tiles, sv_tile_neg, gv0, gv1.  scalars [12]: SvmParams rho, guard_acc0, guard_acc0_s, guard_abs, sqrt_cmax; CrParams B0, rho;
+// acc_rel of `screen` and of `screen_cr`; LrBand acc6, acc10; the flag words up to which the one-workgroup list compaction serves.
+int haf_test_host_sweep_tables(const haf_config *cfg, double kappa, double kappa16, int which, void *out, long long cap, long long *bytes,
+                               int *ints, double *scalars, char *msg, int msg_cap)
+{
+    if (!cfg || !cfg->feature_file || !cfg->range_file || !cfg->model_file || which < 0 || which > 3 || !bytes || !ints || !scalars || cap < 0) return HAF_E_ARG;
+    std::string err;
+    auto say = [&](int code) {
+        if (msg && msg_cap > 0) { strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+        return code;
+    };
+    const int rc = guarded(&err, [&]() {
+        ModelTables m;
+        const int built = host_tables(cfg, kappa, kappa16, m, err);
+        if (built != HAF_OK) return say(built);
+        const std::vector<char> *tab[4] = {&m.svt0, &m.svt0_cr, &m.svt_lr, &m.lr_btiles};
+        const bool have = which == 0 ? m.screen_active : which == 1 ? m.screen_active && m.cr_available : m.screen_active && m.lr_available;
+        const void *src = tab[which]->data();
+        const size_t n = have ? tab[which]->size() : 0;
+        *bytes = (long long)n;
+        if (out && n && (long long)n <= cap) memcpy(out, src, n);
+        else if (out && n) { err = "haf_test_host_sweep_tables: the table is larger than the caller's buffer"; return say(HAF_E_CAPACITY); }
+        ints[0] = m.n_sv_tiles; ints[1] = m.sv_tile_neg; ints[2] = m.svm.gv0; ints[3] = m.svm.gv1;
+        const double sc[12] = {m.svm.rho, m.svm.guard_acc0, m.svm.guard_acc0_s, m.svm.guard_abs, m.svm.sqrt_cmax, m.crp.B0, m.crp.rho,
+                               m.screen.acc_rel, m.screen_cr.acc_rel, m.lr_band.acc6, m.lr_band.acc10, (double)haf::screen_compact_small_words()};
+        memcpy(scalars, sc, sizeof sc);
+        return (int)HAF_OK;
+    });
+    return rc == HAF_E_INTERNAL ? say(rc) : rc;
+}
+
+// screen_finish (screen_finish.h) with the constants of the same device-free build: form 0 `screen`, 1 `screen_cr` (cr_poly as given),
+// as launch_screening hands them to the ten-step feature pass.  sums [n][5]: su2, sd2, sx2, cr, ub -> band [n][8], nax [n].  No device.
+int haf_test_host_screen_finish(const haf_config *cfg, double kappa, double kappa16, int form, int cr_poly, const double *sums, int n,
+                                float *band, float *nax, char *msg, int msg_cap)
+{
+    if (!cfg || !cfg->feature_file || !cfg->range_file || !cfg->model_file || form < 0 || form > 1 || !sums || !band || !nax || n < 0) return HAF_E_ARG;
+    std::string err;
+    auto say = [&](int code) {
+        if (msg && msg_cap > 0) { strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+        return code;
+    };
+    const int rc = guarded(&err, [&]() {
+        ModelTables m;
+        const int built = host_tables(cfg, kappa, kappa16, m, err);
+        if (built != HAF_OK) return say(built);
+        if (!m.screen_active || (form == 1 && !m.cr_available)) { err = "haf_test_host_screen_finish: the model did not get this form"; return say(HAF_E_ARG); }
+        ScreenParams sp = form == 1 ? m.screen_cr : m.screen;
+        sp.cr_poly = form == 1 && cr_poly;
+        for (int i = 0; i < n; i++) {
+            const double *s = sums + (size_t)5 * i;
+            screen_finish(s[0], s[1], s[2], s[3], s[4], sp, band + (size_t)kBandFloats * i, nax[i]);
+        }
+        return (int)HAF_OK;
+    });
+    return rc == HAF_E_INTERNAL ? say(rc) : rc;
+}
+
+// lr_finish_band / lr_finish_band_plain (screen_band.h) on the host with the LrBand of the same device-free build: raw [n][8] as the
+// low-rank sweep reads them -> out [n][8]: form 0 the plain epilogue's {gA, gB, gC, cm, corr, abs_c, 0, 0}, 1 / 2 the centred-remainder
+// form's {L, c_abs, k_psi, cm, 0, 0, 0, 0} with the exp / the polynomial epilogue.  No device.
+int haf_test_lr_finish_band(const haf_config *cfg, double kappa, double kappa16, const float *raw, int n, int form, float *out, char *msg, int msg_cap)
+{
+    if (!cfg || !cfg->feature_file || !cfg->range_file || !cfg->model_file || form < 0 || form > 2 || !raw || !out || n < 0) return HAF_E_ARG;
+    std::string err;
+    auto say = [&](int code) {
+        if (msg && msg_cap > 0) { strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+        return code;
+    };
+    const int rc = guarded(&err, [&]() {
+        ModelTables m;
+        const int built = host_tables(cfg, kappa, kappa16, m, err);
+        if (built != HAF_OK) return say(built);
+        if (!m.screen_active || !m.lr_available || (form == 0 && !m.lr_plain_available)) { err = "haf_test_lr_finish_band: the model did not get this form"; return say(HAF_E_ARG); }
+        LrBand lb = m.lr_band;
+        lb.poly = form == 2;
+        for (int i = 0; i < n; i++) {
+            const float *r = raw + (size_t)kBandFloats * i;
+            float *o = out + (size_t)kBandFloats * i;
+            for (int k = 0; k < kBandFloats; k++) o[k] = 0.0f;
+            if (form == 0) {
+                float4 g, g2;
+                lr_finish_band_plain(r, lb, g, g2);
+                o[0] = g.x; o[1] = g.y; o[2] = g.z; o[3] = g.w; o[4] = g2.x; o[5] = g2.y;
+            } else {
+                lr_finish_band(r, lb, o[0], o[1], o[2], o[3]);
+            }
+        }
         return (int)HAF_OK;
     });
     return rc == HAF_E_INTERNAL ? say(rc) : rc;

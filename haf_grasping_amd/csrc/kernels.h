@@ -452,7 +452,18 @@ double probe_mfma_rounding(hipStream_t s, double *worst16);  // largest error of
 int probe_f16_subnormal_mfma(hipStream_t s);   // 1: the MFMA takes fp16 subnormal operands at their value, 0: it flushes, -1: HIP error
 // low-rank form: Y = fp16(B^' X) per evaluation (X: 10-step operand images, Y: 6-step images), |y^ - y|^2 into raw[kBandFloats e + 5]
 void launch_project(const void *X0, const void *btiles, void *Y, float *raw, const int *counters, long max_evals, hipStream_t s);
-void launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const void *svt_lr, const int *evalcell, const int *counters,
+// Which sweep a launch_svm_screen / launch_svm_screen_lr call launched: the launchers choose by the request's size, the model's tiles and
+// their arguments and say what they chose, as launch_bin and launch_features do (the testing build hands it on: haf_test_sweep_form)
+struct SweepForm {
+    int variant = -1;        // SCREEN_* of the kernel's template argument; -1: nothing launched (no evaluation slots)
+    int lr = 0;              // 1: k_svm_screen_lr, 0: k_svm_screen
+    int part = 0;            // k_svm_screen<., true> + k_screen_combine (the number of SV ranges is the device's: screen_parts())
+    int fused = 0, gather = 0;   // k_svm_screen_lr's FUSED and GATHER
+    int list = 0;            // k_svm_screen's list mode (idx_list != nullptr)
+    int compaction = 0;      // 0: k_screen_compact_small, 1: k_screen_count + k_screen_compact
+    long blocks = 0;         // workgroups of 256 evaluation slots
+};
+SweepForm launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const void *svt_lr, const int *evalcell, const int *counters,
                           SvmParams p, float *dec, int8_t *labels, unsigned long long *flag0_words, int *wgcount, int *flag0_list,
                           int flag0_cap, int *counters_rw, Dims d, long max_evals, float *margin, int variant, CrParams cr, LrBand lb,
                           hipStream_t s, int also_counter = -1,
@@ -461,13 +472,14 @@ void launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const voi
                           // (counters[count_slot] entries, at most flag0_cap) straight from the first pass's images and raw sums; the
                           // compacted output list's length goes to counters[out_slot]
                           const int *idx_list = nullptr, int count_slot = CNT_EVALS, int out_slot = CNT_FLAGGED0);   // != nullptr: the FUSED form -- Y holds the 10-step images, ptiles the projection tiles by input k-step (no launch_project)
-void launch_svm_screen(const void *X0, const float *gband, const float *nax, const void *svt0, const int *evalcell, const int *counters,
+SweepForm launch_svm_screen(const void *X0, const float *gband, const float *nax, const void *svt0, const int *evalcell, const int *counters,
                        SvmParams p, float *dec, int8_t *labels, unsigned long long *flag0_words, int *wgcount, int *flag0_list,
                        int flag0_cap, int *counters_rw, Dims d, long max_evals, float *margin, int variant, CrParams cr, hipStream_t s,
                        int also_counter = -1,    // >= 0: the compacted list's length is published in this counter too (capped at flag0_cap)
                        const int *idx_list = nullptr, int count_slot = CNT_EVALS,   // list mode: slot j of X0 / gband / nax holds evaluation idx_list[j], counters[count_slot] of them
                        int out_slot = CNT_FLAGGED0,
                        void *part_buf = nullptr, int parts = 0);   // SV-range split of requests that do not fill the chip (screen.hip: PART form): a buffer of screen_part_bytes(); parts 0 = by the live count, 1 = never, n = forced (tests)
+int screen_compact_small_words();                         // flag words up to which the one-workgroup compaction serves (kListCompactThreads)
 size_t screen_part_bytes();                               // the counter that receives the length of the compacted list
 void launch_svm(const float *X, const float *ax, const float *svt, const int *evalcell, const int *counters,
                 SvmParams p, float *dec, int8_t *labels, int *flag_list, int flag_cap, int *counters_rw, Dims d,

@@ -659,7 +659,7 @@ __global__ __launch_bounds__(kListCompactThreads) void k_screen_compact_small(co
 }
 
 // the flag words of every workgroup that can hold evaluations (the kernels clip to the live ones) -> the ordered list
-static void launch_screen_compaction(const unsigned long long *flag0_words, int *wgcount, long blocks, int *flag0_list, int flag0_cap,
+static int launch_screen_compaction(const unsigned long long *flag0_words, int *wgcount, long blocks, int *flag0_list, int flag0_cap,
                                      int *counters_rw, int also_counter, const int *idx_list, int count_slot, int out_slot, int in_cap,
                                      hipStream_t s)
 {
@@ -667,13 +667,15 @@ static void launch_screen_compaction(const unsigned long long *flag0_words, int 
     if (words <= kListCompactThreads) {
         hipLaunchKernelGGL(k_screen_compact_small, dim3(1), dim3(kListCompactThreads), 0, s, flag0_words, flag0_list, flag0_cap, counters_rw,
                            also_counter, idx_list, count_slot, out_slot, in_cap);
-        return;
+        return 0;
     }
     const int n_wg = (int)((words + kCompactWords - 1) / kCompactWords);
     hipLaunchKernelGGL(k_screen_count, dim3(n_wg), dim3(kCompactWords), 0, s, flag0_words, wgcount, counters_rw, count_slot, in_cap);
     hipLaunchKernelGGL(k_screen_compact, dim3(n_wg), dim3(kCompactWords), 0, s, flag0_words, wgcount, n_wg, flag0_list, flag0_cap,
                        counters_rw, also_counter, idx_list, count_slot, out_slot, in_cap);
+    return 1;
 }
+int screen_compact_small_words() { return kListCompactThreads; }
 
 // Does the matrix core take fp16 subnormal A operands at their value?  The screening feature kernel stores u^ = fp16(u') without
 // flushing small magnitudes (two vector instructions per attribute saved) and counts |u^ - u'| from the stored value; that is
@@ -1287,13 +1289,14 @@ __global__ __launch_bounds__(kS0Waves * 64, HAF_LR_WGS) void k_svm_screen_lr(con
     if (lane == 0) flag0_words[(base >> 6) + wave] = bal;
 }
 
-void launch_svm_screen(const void *X0, const float *gband, const float *nax, const void *svt0, const int *evalcell, const int *counters,
+SweepForm launch_svm_screen(const void *X0, const float *gband, const float *nax, const void *svt0, const int *evalcell, const int *counters,
                        SvmParams p, float *dec, int8_t *labels, unsigned long long *flag0_words, int *wgcount, int *flag0_list,
                        int flag0_cap, int *counters_rw, Dims d, long max_evals, float *margin, int variant, CrParams cr, hipStream_t s,
                        int also_counter, const int *idx_list, int count_slot, int out_slot, void *part_buf, int parts)
 {
     long blocks = (max_evals + kS0BlockEvals - 1) / kS0BlockEvals;
-    if (blocks <= 0) return;
+    SweepForm form;
+    if (blocks <= 0) return form;
     // list mode: what the INPUT list holds (it is the same size as the output list; whole requests: everything the launch covers)
     const int in_cap = idx_list ? (int)std::min<long>(flag0_cap, max_evals) : 0x7fffffff;
     // parts: 0 = the engine's rule (requests of up to kS0PartBlocks workgroups are split over SV ranges, as many as the live count asks
@@ -1318,16 +1321,20 @@ void launch_svm_screen(const void *X0, const float *gband, const float *nax, con
         default: HAF_SCREEN_LAUNCH(SCREEN_PLAIN); break;
     }
 #undef HAF_SCREEN_LAUNCH
-    launch_screen_compaction(flag0_words, wgcount, blocks, flag0_list, flag0_cap, counters_rw, also_counter, idx_list, count_slot, out_slot, in_cap, s);
+    form.variant = (variant == SCREEN_SUMSQ || variant == SCREEN_CR_EXP || variant == SCREEN_CR_POLY) ? variant : SCREEN_PLAIN;
+    form.part = split; form.list = idx_list != nullptr; form.blocks = blocks;
+    form.compaction = launch_screen_compaction(flag0_words, wgcount, blocks, flag0_list, flag0_cap, counters_rw, also_counter, idx_list, count_slot, out_slot, in_cap, s);
+    return form;
 }
 
-void launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const void *svt_lr, const int *evalcell, const int *counters,
+SweepForm launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const void *svt_lr, const int *evalcell, const int *counters,
                           SvmParams p, float *dec, int8_t *labels, unsigned long long *flag0_words, int *wgcount, int *flag0_list,
                           int flag0_cap, int *counters_rw, Dims d, long max_evals, float *margin, int variant, CrParams cr, LrBand lb,
                           hipStream_t s, int also_counter, const void *ptiles, const int *idx_list, int count_slot, int out_slot)
 {
     const long blocks = (max_evals + kS0BlockEvals - 1) / kS0BlockEvals;
-    if (blocks <= 0) return;
+    SweepForm form;
+    if (blocks <= 0) return form;
     lb.poly = variant == SCREEN_CR_POLY;
     // gather form (idx_list != nullptr; CR_EXP on the fused kernel only): what the INPUT list holds, as in launch_svm_screen
     const int in_cap = idx_list ? (int)std::min<long>(flag0_cap, max_evals) : 0x7fffffff;
@@ -1341,8 +1348,11 @@ void launch_svm_screen_lr(const void *Y, float *raw, const float *nax, const voi
     else { if (ptiles) HAF_LR_LAUNCH(SCREEN_CR_EXP, true, false); else HAF_LR_LAUNCH(SCREEN_CR_EXP, false, false); }
 #undef HAF_LR_LAUNCH
     const int cs = idx_list ? count_slot : CNT_EVALS;
-    launch_screen_compaction(flag0_words, wgcount, blocks, flag0_list, flag0_cap, counters_rw, also_counter, idx_list, cs,
-                             idx_list ? out_slot : CNT_FLAGGED0, in_cap, s);
+    form.lr = 1; form.blocks = blocks; form.gather = idx_list != nullptr; form.fused = idx_list || ptiles;
+    form.variant = idx_list ? SCREEN_CR_EXP : (variant == SCREEN_CR_POLY || variant == SCREEN_PLAIN) ? variant : SCREEN_CR_EXP;
+    form.compaction = launch_screen_compaction(flag0_words, wgcount, blocks, flag0_list, flag0_cap, counters_rw, also_counter, idx_list, cs,
+                                               idx_list ? out_slot : CNT_FLAGGED0, in_cap, s);
+    return form;
 }
 
 size_t screen_part_bytes() { return (size_t)kS0MaxParts * kS0PartBlocks * kS0BlockEvals * sizeof(float4); }

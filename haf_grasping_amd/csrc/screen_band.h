@@ -12,14 +12,19 @@
 //   quadratic part, first order:  ln2^2 [p'N1 dy + p'(M1 B^')p + sum b_n z_n a_n + p'N2 p_perp],  N1 = Q'bQ~^, M1 = Q'b dQ~, N2 = Q'bR (signed)
 //   second order:                 ln2^2/2 sum|b_n| eps_n^2 <= 2 ln2^2 (|H~abs||dy|^2 + |D~abs||y_e|^2 + acc6^2 |y^|^2 C~qq + |Rabs| nun^2)
 //   psi3 and the exp / polynomial terms: through eps = sup|eps_n| and zmax as before.
+// Host and device, as screen_finish.h: the sweep's tail calls it per evaluation; the testing build evaluates it on a reference's raw
+// sums (haf_test_lr_finish_band, tests/test_sweep_gpu.py).
 #pragma once
+#include "screen_finish.h"
+#if defined(__HIPCC__)
 #include "device_common.h"
 #include "feature_device.h"
+#endif
 
 namespace haf {
 
 // returns false when the evaluation must never be trusted (outside the range the bounds were derived for)
-__device__ __forceinline__ void lr_finish_band(const float *raw, const LrBand &lb, float &L, float &c_abs_out, float &k_psi_out, float &cm_out)
+HAF_FRAME_HD void lr_finish_band(const float *raw, const LrBand &lb, float &L, float &c_abs_out, float &k_psi_out, float &cm_out)
 {
     constexpr double kF32Acc = 326.0 * 5.9604644775390625e-08 * 1.01;
     const double ln2 = 0.69314718056;
@@ -78,7 +83,7 @@ __device__ __forceinline__ void lr_finish_band(const float *raw, const LrBand &l
 //     accumulation, p' against p, the fp32 accumulation of the sum itself, |p_perp||rho~| (abs_c); sum b_n a_n stays with gB.
 //     Second part: |sum b_n (2^(z_n) - 1) e_n| <= |b (2^z - 1)|_2 e2 <= ln2 2^zmax (sbq |y_e| + sbr |p_perp|) e2.
 // Output as screen_finish: g = {gA, gB, gC, cm}, g2 = {corr, abs_c}.
-__device__ __forceinline__ void lr_finish_band_plain(const float *raw, const LrBand &lb, float4 &g, float4 &g2)
+HAF_FRAME_HD void lr_finish_band_plain(const float *raw, const LrBand &lb, float4 &g, float4 &g2)
 {
     constexpr double kF32Acc = 326.0 * 5.9604644775390625e-08 * 1.01;
     const double ln2 = 0.69314718056;

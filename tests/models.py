@@ -4,7 +4,7 @@ import os
 import numpy as np
 
 
-def write_random_model(path, nsv, D=323, seed=0, gamma=None, rho=0.1, density=1.0, balanced=False, labels=(1, -1)):
+def write_random_model(path, nsv, D=323, seed=0, gamma=None, rho=0.1, density=1.0, balanced=False, labels=(1, -1), n_pos=None):
     """C-SVC / RBF model in libsvm's text format (svm.cpp:2599-2691 writer layout).
 
     SURVEY.md §8(d): SV values U(-1,1) printed %.8g, coef ~ U(0,2) with the class sign (printed %.16g),
@@ -12,10 +12,13 @@ def write_random_model(path, nsv, D=323, seed=0, gamma=None, rho=0.1, density=1.
     balanced=True rescales the negative class so that sum(coef) = 0 (as in every real C-SVC solution) and uses
     rho = 0.01: decision values then straddle zero and both labels occur.
     labels=(a, b): the header's "label a b" (integers); the first half of the SVs belongs to a.
+    n_pos: how many of the nsv SVs carry a coefficient >= 0 (the first class); None = the first half, as ever -- the random draws do not
+    depend on it, so every file written without it is byte for byte what it was.
     """
     rng = np.random.RandomState(seed)
     gamma = 1.0 / D if gamma is None else gamma
-    n0 = nsv // 2
+    n0 = nsv // 2 if n_pos is None else int(n_pos)
+    assert 0 < n0 < nsv
     n1 = nsv - n0
     sv = rng.uniform(-1.0, 1.0, size=(nsv, D))
     keep = rng.uniform(size=(nsv, D)) < density
