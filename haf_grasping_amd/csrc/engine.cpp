@@ -77,7 +77,7 @@ void haf_destroy(haf_engine *e)
 static int calibrate(haf_engine *e)
 {
     const haf_config &c = e->cfg;
-    if (contraction_mode(c) != MODE_SCREEN || !e->screen_active || e->prob_mode) return HAF_OK;
+    if (contraction_mode(c) != MODE_SCREEN || !e->screen_active || e->mdl.prob_mode) return HAF_OK;
     const int G = c.grid_h;
     const long cells = (long)G * G;
     const long stride = std::max<long>(1, (cells + c.max_points - 1) / c.max_points);
@@ -146,7 +146,7 @@ static int calibrate(haf_engine *e)
         e->variant_forced = true;
         for (int oi = 0; oi < SCREEN_VARIANTS && rc == HAF_OK; oi++) {
             const int v = order[oi];
-            if (v >= SCREEN_CR_EXP && !e->cr_available) continue;
+            if (v >= SCREEN_CR_EXP && !e->mdl.cr_available) continue;
             e->screen_variant = v;
             e->screen_active = true;
             rc = score_rolls_impl(e, 1, &cl, &in, 0, R, rec.data());
@@ -165,7 +165,7 @@ static int calibrate(haf_engine *e)
             if (share < 0.0) continue;
             double cost = variant_cost(e, v) + kUndecidedCost * share;
             const double s_cr = e->variant_share[SCREEN_CR_EXP];
-            if ((v == SCREEN_PLAIN || v == SCREEN_SUMSQ) && e->cr_available && s_cr >= 0.0 && s_cr < share)
+            if ((v == SCREEN_PLAIN || v == SCREEN_SUMSQ) && e->mdl.cr_available && s_cr >= 0.0 && s_cr < share)
                 cost = std::min(cost, variant_cost(e, v) + 1.6 * share + kUndecidedCost * s_cr);
             if (cost < best_cost) { best_cost = cost; best = v; }
         }
@@ -183,9 +183,9 @@ static int calibrate(haf_engine *e)
         const char *f0b = test_env("HAF_T0B"), *fsk = test_env("HAF_T1_SKIP");
         // (the scene is small and tame -- the C5 bench leaves five times the share of the 56 x 56 scene undecided -- so the rule is
         // "whenever it decided more there", not a threshold)
-        e->use_t0b = e->cr_available && (v == SCREEN_PLAIN || v == SCREEN_SUMSQ) && e->variant_share[SCREEN_CR_EXP] >= 0.0 &&
+        e->use_t0b = e->mdl.cr_available && (v == SCREEN_PLAIN || v == SCREEN_SUMSQ) && e->variant_share[SCREEN_CR_EXP] >= 0.0 &&
                      e->variant_share[SCREEN_CR_EXP] < e->variant_share[v];
-        if (f0b) e->use_t0b = atoi(f0b) != 0 && e->cr_available;
+        if (f0b) e->use_t0b = atoi(f0b) != 0 && e->mdl.cr_available;
         // is tier 1 of use behind the screening passes of this model?  One request in the final configuration: how much of what they
         // left did the three-pass kernel decide
         const bool forced1 = e->variant_forced;
@@ -313,7 +313,7 @@ static int create_impl(const haf_config *cfg, haf_engine **out)
     if (const char *v = test_env("HAF_SCREEN_VARIANT")) { e->screen_variant = std::max(0, std::min(SCREEN_VARIANTS - 1, atoi(v))); e->variant_forced = true; e->direct_work = 0; }
     int rc = build_tables(e);
     if (rc != HAF_OK) return bail(rc);
-    if (e->screen_variant >= SCREEN_CR_EXP && !e->cr_available) e->screen_variant = SCREEN_PLAIN;   // (a pinned form the model has no tables for)
+    if (e->screen_variant >= SCREEN_CR_EXP && !e->mdl.cr_available) e->screen_variant = SCREEN_PLAIN;   // (a pinned form the model has no tables for)
     rc = alloc_buffers(e);
     if (rc != HAF_OK) return bail(rc);
     // (a test that scales the screening band wants the tiers and the adaptive rule as they are, not a model classified under that band)
@@ -331,7 +331,7 @@ int haf_model_info(const haf_engine *e, int32_t *n_sv, int32_t *dim, int32_t *n_
     if (!e) return HAF_E_ARG;
     if (n_sv) *n_sv = e->model.n_sv;
     if (dim) *dim = e->model.dim;
-    if (n_features) *n_features = e->nf;
+    if (n_features) *n_features = e->mdl.nf;
     return HAF_OK;
 }
 
@@ -362,7 +362,7 @@ int haf_unregister_host_cloud(haf_engine *e, const void *ptr)
 int haf_screen_form(const haf_engine *e, int32_t *form, int32_t *active)
 {
     if (!e) return HAF_E_ARG;
-    const bool on = contraction_mode(e->cfg) == MODE_SCREEN && e->screen_active && !e->prob_mode;
+    const bool on = contraction_mode(e->cfg) == MODE_SCREEN && e->screen_active && !e->mdl.prob_mode;
     if (form) *form = e->screen_variant;
     if (active) *active = on ? 1 : 0;
     return HAF_OK;
@@ -371,8 +371,8 @@ int haf_screen_form(const haf_engine *e, int32_t *form, int32_t *active)
 int haf_screen_low_rank(const haf_engine *e, int32_t *available, int32_t *rank, int32_t *last_used)
 {
     if (!e) return HAF_E_ARG;
-    if (available) *available = (e->lr_available && e->lr_enabled) ? 1 : 0;
-    if (rank) *rank = e->lr_rank;
+    if (available) *available = (e->mdl.lr_available && e->lr_enabled) ? 1 : 0;
+    if (rank) *rank = e->mdl.lr_rank;
     if (last_used) *last_used = e->last.lr ? 1 : 0;
     return HAF_OK;
 }

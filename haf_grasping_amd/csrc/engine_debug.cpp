@@ -10,7 +10,7 @@ static int get_roll_grid_impl(haf_engine *e, int32_t cloud, int32_t roll, float 
     const int rl = roll - e->last.roll_first;
     if (cloud < 0 || cloud >= e->last.B || rl < 0 || rl >= e->last.R) return fail(e, HAF_E_ARG, "haf_get_roll_grid: (cloud, roll) not in the last scored batch");
     const size_t HW = (size_t)e->cfg.grid_h * e->cfg.grid_w, base = ((size_t)cloud * e->last.R + rl) * HW;
-    if (eval_grid && e->prob_mode) {
+    if (eval_grid && e->mdl.prob_mode) {
         HIPCHK(e, hipMemcpy(eval_grid, e->d_evf.p + base, HW * sizeof(float), hipMemcpyDeviceToHost));
     } else if (eval_grid) {
         std::vector<short> tmp(HW);
@@ -111,12 +111,12 @@ static int debug_fetch_impl(haf_engine *e, int32_t what, int32_t cloud, int32_t 
             return HAF_OK;
         }
         case HAF_DBG_GRASPSGRID:
-            if (!e->prob_mode) return fail(e, HAF_E_ARG, "haf_debug_fetch: HAF_DBG_GRASPSGRID needs HAF_FLAG_PROBABILITY");
+            if (!e->mdl.prob_mode) return fail(e, HAF_E_ARG, "haf_debug_fetch: HAF_DBG_GRASPSGRID needs HAF_FLAG_PROBABILITY");
             if (!need(HW * 4)) break;
             HIPCHK(e, hipMemcpy(dst, e->d_gridf.p + br * HW, HW * 4, hipMemcpyDeviceToHost));
             return HAF_OK;
         case HAF_DBG_PROBABILITY: {
-            if (!e->prob_mode) return fail(e, HAF_E_ARG, "haf_debug_fetch: HAF_DBG_PROBABILITY needs HAF_FLAG_PROBABILITY");
+            if (!e->mdl.prob_mode) return fail(e, HAF_E_ARG, "haf_debug_fetch: HAF_DBG_PROBABILITY needs HAF_FLAG_PROBABILITY");
             if (!need(HW * 16)) break;
             double *g = (double *)dst;
             for (size_t i = 0; i < 2 * HW; i++) g[i] = NAN;

@@ -43,7 +43,7 @@ MapLayout map_layout(const haf_engine *e, size_t n_img, size_t n_mask, size_t ra
 int check_last(haf_engine *e, const char *who, int32_t request, int *rolls)
 {
     const std::string name(who);
-    if (e->prob_mode) return fail(e, HAF_E_ARG, name + ": not available with HAF_FLAG_PROBABILITY (fp32 votes)");
+    if (e->mdl.prob_mode) return fail(e, HAF_E_ARG, name + ": not available with HAF_FLAG_PROBABILITY (fp32 votes)");
     const LastCall &last = e->last;
     if (last.B < 1 || last.R < 1 || (int)last.inputs.size() < last.B) return fail(e, HAF_E_ARG, name + ": no scored batch");
     if (request < 0 || request >= last.B) return fail(e, HAF_E_ARG, name + ": request not in the last scored batch");

@@ -74,7 +74,7 @@ int score_objects_impl(haf_engine *e, const haf_frame *frame, const haf_label_im
     if (!e) return HAF_E_ARG;
     const std::string who = "haf_score_objects: ";
     if (!frame || !object_labels || !in || !out || n_objects < 1) return fail(e, HAF_E_ARG, who + "null or empty argument");
-    if (e->prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
+    if (e->mdl.prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
     if (n_objects > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, who + "more objects than max_clouds");
     if (e->cfg.n_rolls > e->max_rolls) return fail(e, HAF_E_CAPACITY, who + "more rolls in one call than max_rolls_per_call");
     // the frame counts ONCE against max_points, whatever n_objects is

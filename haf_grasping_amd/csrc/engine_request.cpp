@@ -43,7 +43,7 @@ static double host_decision(const SvmModel &m, const double *xg, int kx)
 // the feature kernel, then to the host: column i of x64 (attr_column) holds entry off + i
 static int fetch_attributes64(haf_engine *e, const Dims &d, hipStream_t s, const int *list, int cnt, int off, int n, std::vector<double> &x64)
 {
-    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, reinterpret_cast<float *>(e->d_x64.p), nullptr, d, e->range.lower,
+    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, reinterpret_cast<float *>(e->d_x64.p), nullptr, d, e->range.lower,
                     e->range.upper, 0.0f, n, XMODE_F64, ScreenParams{}, list + off, cnt, n, false, n, nullptr, nullptr, s, off);
     x64.assign(((size_t)n + 15) / 16 * kKP * 16, 0.0);
     HIPCHK(e, hipMemcpyAsync(x64.data(), e->d_x64.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -63,7 +63,7 @@ static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool
     *changed = false;
     *resolved = 0;
     const int n2 = std::min(e->h_counters[CNT_FLAGGED2], e->list_cap);
-    if (n2 <= 0 || e->prob_mode) return HAF_OK;
+    if (n2 <= 0 || e->mdl.prob_mode) return HAF_OK;
     std::vector<double> dec((size_t)n2);
     std::vector<int> ev((size_t)n2);
     HIPCHK(e, hipMemcpyAsync(dec.data(), e->d_dec_exact2.p, (size_t)n2 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -73,13 +73,13 @@ static int host_resolve_strict(haf_engine *e, const Dims &d, hipStream_t s, bool
     for (int off = 0; off < n2; off += e->flag_cap) {            // (the attribute image holds one window of the list at a time)
         const int nw = std::min(e->flag_cap, n2 - off);
         std::vector<int> cand;
-        for (int i = off; i < off + nw; i++) if (!(std::fabs(dec[(size_t)i]) > e->host_exp_thr)) cand.push_back(i);
+        for (int i = off; i < off + nw; i++) if (!(std::fabs(dec[(size_t)i]) > e->mdl.host_exp_thr)) cand.push_back(i);
         if (cand.empty()) continue;
         const int rc = fetch_attributes64(e, d, s, e->d_flag2_list.p, CNT_FLAGGED2, off, nw, x64);
         if (rc != HAF_OK) return rc;
         for (int i : cand) {
-            const double dv = host_decision(e->model, attr_column(x64, i - off), e->kx);
-            const int8_t lab = (int8_t)(dv > 0.0 ? e->gv0 : e->gv1);
+            const double dv = host_decision(e->model, attr_column(x64, i - off), e->mdl.kx);
+            const int8_t lab = (int8_t)(dv > 0.0 ? e->mdl.gv0 : e->mdl.gv1);
             int cell = 0;
             int8_t old = 0;
             HIPCHK(e, hipMemcpy(&cell, e->d_evalcell.p + ev[(size_t)i], sizeof(int), hipMemcpyDeviceToHost));
@@ -148,11 +148,11 @@ static int host_resolve_probability(haf_engine *e, const Dims &d, hipStream_t s,
         const int rc = fetch_attributes64(e, d, s, e->d_flag_list.p, CNT_FLAGGED, off, nw, x64);
         if (rc != HAF_OK) return rc;
         for (int i = 0; i < nw; i++) {
-            const double dv = host_decision(e->model, attr_column(x64, i), e->kx);
+            const double dv = host_decision(e->model, attr_column(x64, i), e->mdl.kx);
             double p[2];
-            const int idx = host_probability(dv, e->prob.A, e->prob.B, p);
+            const int idx = host_probability(dv, e->mdl.prob.A, e->mdl.prob.B, p);
             const double q[2] = {hafq::decq(p[0], 6), hafq::decq(p[1], 6)};
-            const int res = idx ? e->prob.gv1 : e->prob.gv0;
+            const int res = idx ? e->mdl.prob.gv1 : e->mdl.prob.gv0;
             const float own = (float)res * (float)(res > 0 ? q[1] : q[0]);
             const int8_t lab = (int8_t)res;
             const int evi = ev[(size_t)(off + i)];
@@ -468,7 +468,7 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
 {
     const int B = q.B, R = q.R, H = e->cfg.grid_h, W = e->cfg.grid_w;
     Dims &d = q.d;
-    d.H = H; d.W = W; d.R = R; d.B = B; d.nf = e->nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->n_sv_tiles; d.sv_tile_neg = e->sv_tile_neg;
+    d.H = H; d.W = W; d.R = R; d.B = B; d.nf = e->mdl.nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->mdl.n_sv_tiles; d.sv_tile_neg = e->mdl.sv_tile_neg;
     haf_pick_math::cell_reach(H, W, &q.r_row, &q.r_col);
     q.evals_cap = (long)B * R * (H - 14) * (W - 14);
     // For choosing between the feature kernels only: the masked cells of a roll lie inside the rotated search rectangle of
@@ -482,11 +482,11 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
         if (q.from.roi && q.from.roi->masked[(size_t)b] >= 0) sel = std::min<long>(sel, 29 * q.from.roi->masked[(size_t)b]);
         q.evals_sel += (long)R * sel;
     }
-    const long work = q.evals_sel * (long)e->n_sv_pad;
+    const long work = q.evals_sel * (long)e->mdl.n_sv_pad;
     // A request whose whole SVM work is tiny goes straight to the fp64 MFMA tier (every evaluation enters its list): same
     // labels by construction -- the tier decides outside its own band and hands the rest to the strict tier -- and three
     // launches instead of a feature kernel, a contraction kernel and the rechecks behind them.
-    q.direct = !e->prob_mode && !e->generic_kernel && e->direct_work > 0 && work <= e->direct_work;
+    q.direct = !e->mdl.prob_mode && !e->generic_kernel && e->direct_work > 0 && work <= e->direct_work;
     q.short_request = work <= (1L << 26) && q.total_n <= (1L << 20);
     // A small engine with a small model behind one of the fast contractions: what that contraction flags goes through the SAME one-launch
     // kernel in list mode (exact attributes + fp64 MFMA decision, tier 2's arithmetic) instead of tier 2a's three launches and tier 2's
@@ -494,7 +494,7 @@ static void classify_request(const haf_engine *e, const haf_grasp_input *in, Req
     // exact work (C3: 81 -> 30 us; the kernel costs ~9 ns per listed evaluation at 192 SVs, so it wins up to ~8 000 of them: a request
     // of up to 2^25 evaluation x SV pairs, of which a trained model flags around a tenth).  Decided from the request's search areas and
     // the model's size, so identical calls take identical paths.
-    q.small_exact = !q.direct && !e->prob_mode && e->direct_work > 0 && work <= 16 * e->direct_work;
+    q.small_exact = !q.direct && !e->mdl.prob_mode && e->direct_work > 0 && work <= 16 * e->direct_work;
     q.large = q.evals_sel >= e->large_evals;              // enough evaluations to fill the chip with one thread each
 }
 
@@ -511,7 +511,7 @@ static int run_prestages(haf_engine *e, Request &q)
     // small grids: a1 (tail) + a2 + a3 + a4 in ONE launch (k_small_pre); the probability branch needs k_scan's row-major order
     // (an ROI request, of frames or of views, takes the general pre-stage kernels, which serve small grids too: k_small_pre stays what it is)
     int fused_bin = -1;
-    if (!e->prob_mode && !e->no_fused_pre && !q.from.roi)
+    if (!e->mdl.prob_mode && !e->no_fused_pre && !q.from.roi)
         fused_bin = launch_small_pre(q.d_clouds, q.d_geo, q.max_n, e->d_heights.p, e->d_ii.p, e->d_mask.p, e->d_rowcount.p, e->d_brcount.p,
                                      e->d_labels.p, e->d_evalcell.p, e->d_counters.p, e->d_flag_list.p, q.direct, d, q.r_row, q.r_col, s,
                                      e->d_brslot.p, ++e->pre_epoch);
@@ -531,7 +531,7 @@ static int run_prestages(haf_engine *e, Request &q)
     const BinChoice bin = launch_bin(q.d_clouds, q.h_clouds, q.max_n, q.total_n, q.d_geo, e->d_heights.p, d, q.r_row, q.r_col,
                                      q.bucket_ok && !e->no_bucket_sort, bs, e->d_counters.p, s);
     mark(e, HAF_ST_INTEGRAL);
-    const int integral = launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->lr_available ? e->d_iiabs.p : nullptr);
+    const int integral = launch_integral(e->d_heights.p, e->d_rowsum.p, e->d_ii.p, e->d_inexact.p, e->d_counters.p, d, s, e->mdl.lr_available ? e->d_iiabs.p : nullptr);
     e->pre_forms = PrestageForms{bin.form, integral, bin.bucket_refused};
     mark(e, HAF_ST_MASK);
     if (q.from.objects) {
@@ -554,8 +554,8 @@ static int run_prestages(haf_engine *e, Request &q)
 
 static TierFacts tier_facts(const haf_engine *e, const Request &q, int mode, bool reuse_operands)
 {
-    return TierFacts{e->screen_variant, e->cr_available, e->lr_available, e->lr_enabled, e->lr_plain_available, e->lr_fused,
-                     e->use_t0b, e->t1_skip, e->t1_cr_available, e->i8_active, e->calibrated, e->short_gate, e->generic_kernel,
+    return TierFacts{e->screen_variant, e->mdl.cr_available, e->mdl.lr_available, e->lr_enabled, e->mdl.lr_plain_available, e->mdl.lr_fused,
+                     e->use_t0b, e->t1_skip, e->mdl.t1_cr_available, e->mdl.i8_active, e->calibrated, e->short_gate, e->generic_kernel,
                      e->model.n_sv, test_env("HAF_T0B_NO_GATHER") != nullptr, mode, reuse_operands, q.direct, q.small_exact, q.large,
                      q.fused_pre, (long)q.d.H * q.d.W, q.evals_cap};
 }
@@ -608,13 +608,13 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     const hipStream_t s = q.s;
     const Dims &d = q.d;
     const long evals_cap = q.evals_cap;
-    ScreenParams sp_now = p.sp == SP_LRP ? e->screen_lrp : p.sp == SP_CR ? e->screen_cr : e->screen;
+    ScreenParams sp_now = p.sp == SP_LRP ? e->mdl.screen_lrp : p.sp == SP_CR ? e->mdl.screen_cr : e->mdl.screen;
     if (p.sp != SP_LRP) sp_now.cr_poly = e->screen_variant == SCREEN_CR_POLY;
     if (p.lr) { sp_now.lr = 1; sp_now.lr_negflags = e->d_inexact.p; sp_now.lr_iiabs = e->d_iiabs.p; }
     if (e->snap_on && !p.reuse) { e->feature_sp_kind = p.sp; e->feature_sp = sp_now; }      // (testing library only, as the snapshot below)
     if (!p.reuse)
-        e->feature_form = launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
-                                          e->range.upper, e->svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
+        e->feature_form = launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->d_X.p, e->d_gband.p, d, e->range.lower,
+                                          e->range.upper, e->mdl.svm.neg_gamma2, evals_cap, XMODE_SCREEN, sp_now, nullptr, 0, 0, q.large, q.evals_sel, nullptr, e->d_ax.p, s);
     if (e->snap_on && !p.reuse) {        // (testing library only: haf_test_snapshot_screen)
         const long cap = std::min<long>(evals_cap, e->max_evals_pad);
         e->snap_cap = cap;
@@ -625,34 +625,34 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     char *y_img = reinterpret_cast<char *>(e->d_X.p) + (size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes;   // behind the 10-step images (the buffer holds the 42 KiB three-pass form)
     mark(e, HAF_ST_SVM);
     SweepForm form0, form1;
-    if (p.lr && !e->lr_fused) launch_project(e->d_X.p, e->d_lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)
+    if (p.lr && !e->mdl.lr_fused) launch_project(e->d_X.p, e->mdl.lr_btiles.p, y_img, e->d_gband.p, e->d_counters.p, evals_cap, s);   // (counted with the sweep it feeds)
     if (p.lr)
-        form0 = launch_svm_screen_lr(e->lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        form0 = launch_svm_screen_lr(e->mdl.lr_fused ? reinterpret_cast<char *>(e->d_X.p) : y_img, e->d_gband.p, e->d_ax.p, e->mdl.svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                              e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d,
-                             evals_cap, e->d_margin.p, e->screen_variant, e->crp, e->lr_band, s, handover_counter(p.pass0_out),
-                             e->lr_fused ? e->d_lr_btiles_in.p : nullptr);
+                             evals_cap, e->d_margin.p, e->screen_variant, e->mdl.crp, e->mdl.lr_band, s, handover_counter(p.pass0_out),
+                             e->mdl.lr_fused ? e->mdl.lr_btiles_in.p : nullptr);
     else
-        form0 = launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, p.cr ? e->d_svt0_cr.p : e->d_svt0.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        form0 = launch_svm_screen(e->d_X.p, e->d_gband.p, e->d_ax.p, p.cr ? e->mdl.svt0_cr.p : e->mdl.svt0.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                           e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.pass0_out), e->flag0_cap, e->d_counters.p, d, evals_cap, e->d_margin.p,
-                          e->screen_variant, e->crp, s, handover_counter(p.pass0_out), nullptr, CNT_EVALS, CNT_FLAGGED0, e->d_screen_part.p, e->screen_parts);
+                          e->screen_variant, e->mdl.crp, s, handover_counter(p.pass0_out), nullptr, CNT_EVALS, CNT_FLAGGED0, e->d_screen_part.p, e->screen_parts);
     snapshot_sweep(e, 0, form0, evals_cap, evals_cap, p.pass0_out, s);
     mark(e, HAF_ST_REFINE);
     const long list_cap = std::min<long>(e->flag0_cap, evals_cap);
     if (p.t0b == T0B_GATHER) {
-        form1 = launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->d_svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p,
+        form1 = launch_svm_screen_lr(reinterpret_cast<char *>(e->d_X.p), e->d_gband.p, e->d_ax.p, e->mdl.svt_lr.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p,
                              e->d_labels.p, e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap,
-                             e->d_counters.p, d, list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, e->lr_band, s, handover_counter(p.t0b_out),
-                             e->d_lr_btiles_in.p, list_buf(e, p.t0b_in), list_counter(p.t0b_in), CNT_FLAGGED0B);
+                             e->d_counters.p, d, list_cap, e->d_margin.p, SCREEN_CR_EXP, e->mdl.crp, e->mdl.lr_band, s, handover_counter(p.t0b_out),
+                             e->mdl.lr_btiles_in.p, list_buf(e, p.t0b_in), list_counter(p.t0b_in), CNT_FLAGGED0B);
     } else if (p.t0b == T0B_FEATURES) {
         // tier 0b: the centred-remainder form on the LIST of the first pass (its own operand images: translated attributes,
         // centred support vectors; band, common factor and images indexed by list slot)
-        ScreenParams sp_b = e->screen_cr;
+        ScreenParams sp_b = e->mdl.screen_cr;
         sp_b.cr_poly = 0;
         // (the group-parallel feature kernel even for lists of 10^5: one evaluation per lane on SCATTERED cells -- k_features_serial in
         // list mode -- was measured at 7.7 ns per evaluation against 2.1 ns, its 2 400 corner loads per lane being 64 separate
         // L1 accesses each)
-        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_gband.p, d, e->range.lower,
-                        e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SCREEN, sp_b, list_buf(e, p.t0b_in), list_counter(p.t0b_in), e->flag0_cap,
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->d_X1.p, e->d_gband.p, d, e->range.lower,
+                        e->range.upper, e->mdl.svm.neg_gamma2, list_cap, XMODE_SCREEN, sp_b, list_buf(e, p.t0b_in), list_counter(p.t0b_in), e->flag0_cap,
                         false, list_cap, nullptr, e->d_ax.p, s);
         if (e->snap_on && e->snap_sweep[1].in_X.p) {         // (testing library only: tier 0b's own, list-indexed feature output)
             haf_engine::SweepSnap &sn = e->snap_sweep[1];
@@ -662,9 +662,9 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
             (void)hipMemcpyAsync(sn.in_gband.p, e->d_gband.p, slots * kBandFloats * sizeof(float), hipMemcpyDeviceToDevice, s);
             (void)hipMemcpyAsync(sn.in_ax.p, e->d_ax.p, slots * sizeof(float), hipMemcpyDeviceToDevice, s);
         }
-        form1 = launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->d_svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        form1 = launch_svm_screen(e->d_X1.p, e->d_gband.p, e->d_ax.p, e->mdl.svt0_cr.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                           e->d_flag0_words.p, e->d_flag0_wgcount.p, list_buf(e, p.t0b_out), e->flag0_cap, e->d_counters.p, d,
-                          list_cap, e->d_margin.p, SCREEN_CR_EXP, e->crp, s, handover_counter(p.t0b_out), list_buf(e, p.t0b_in), list_counter(p.t0b_in),
+                          list_cap, e->d_margin.p, SCREEN_CR_EXP, e->mdl.crp, s, handover_counter(p.t0b_out), list_buf(e, p.t0b_in), list_counter(p.t0b_in),
                           CNT_FLAGGED0B, e->d_screen_part.p, e->screen_parts);
     }
     snapshot_sweep(e, 1, form1, list_cap, evals_cap, p.t0b_out, s);
@@ -675,14 +675,14 @@ static void launch_screening(haf_engine *e, const Request &q, const TierPlan &p)
     if (!p.t1) return;
     // (the list is short whenever screening is worth its while: always the group-parallel feature kernel, whose
     // workgroups beyond the list's end exit at once)
-    ScreenParams sp_t1 = e->screen;
-    if (p.t1cr) { sp_t1.cr_t1_tab = e->d_t1_tab.p; sp_t1.cr_t1_L = e->d_t1_L.p; }
-    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X1.p, e->d_ax1.p, d, e->range.lower,
-                    e->range.upper, e->svm.neg_gamma2, list_cap, XMODE_SPLIT, sp_t1, list_buf(e, p.t1_in), p.t1_cnt,
+    ScreenParams sp_t1 = e->mdl.screen;
+    if (p.t1cr) { sp_t1.cr_t1_tab = e->mdl.t1_tab.p; sp_t1.cr_t1_L = e->d_t1_L.p; }
+    launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->d_X1.p, e->d_ax1.p, d, e->range.lower,
+                    e->range.upper, e->mdl.svm.neg_gamma2, list_cap, XMODE_SPLIT, sp_t1, list_buf(e, p.t1_in), p.t1_cnt,
                     e->flag0_cap, false, list_cap, e->d_attr.p, nullptr, s);
-    launch_svm_h(e->d_X1.p, e->d_ax1.p, p.t1cr ? e->d_svt_h_cr.p : e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+    launch_svm_h(e->d_X1.p, e->d_ax1.p, p.t1cr ? e->mdl.svt_h_cr.p : e->mdl.svt_h.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                  list_buf(e, p.t1_out), e->list_cap, e->d_counters.p, d, list_cap, list_buf(e, p.t1_in), p.t1_cnt, e->flag0_cap,
-                 e->d_part1.p, e->part1_stride, s, p.t1cr ? &e->crt1 : nullptr, p.t1cr ? e->d_t1_L.p : nullptr, e->d_t1_flags.p);
+                 e->d_part1.p, e->part1_stride, s, p.t1cr ? &e->mdl.crt1 : nullptr, p.t1cr ? e->d_t1_L.p : nullptr, e->d_t1_flags.p);
 }
 
 // the first pass of every other path: the generic / direct tier, or a contraction over every evaluation
@@ -692,25 +692,25 @@ static void launch_first_pass(haf_engine *e, const Request &q, const TierPlan &p
     const Dims &d = q.d;
     if (p.path == PATH_GENERIC) {
         launch_prob_list(e->d_counters.p, list_counter(p.pass0_out), list_buf(e, p.pass0_out), e->list_cap, s);
-        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in), e->list_cap,
+        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.coef64.p, e->mdl.exact, list_buf(e, p.strict_in), e->list_cap,
                        e->d_counters.p, list_counter(p.strict_in), e->d_dec_exact2.p, e->d_labels.p, d, s);
         mark(e, HAF_ST_SVM);
     } else if (p.path == PATH_DIRECT) {
         // every evaluation counts as rechecked (k_small_pre / k_prob_list have put them on the exact tier's list)
-        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, d, std::min<long>(q.evals_cap, e->list_cap),
+        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.exact, d, std::min<long>(q.evals_cap, e->list_cap),
                             e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.pass0_out), e->list_cap, e->d_attr.p, s);
         mark(e, HAF_ST_SVM);
     } else if (p.path == PATH_SPLIT) {
-        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
-                        e->range.upper, e->svm.neg_gamma2, q.evals_cap, XMODE_SPLIT, e->screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
+                        e->range.upper, e->mdl.svm.neg_gamma2, q.evals_cap, XMODE_SPLIT, e->mdl.screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
         mark(e, HAF_ST_SVM);
-        launch_svm_h(e->d_X.p, e->d_ax.p, e->d_svt_h.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        launch_svm_h(e->d_X.p, e->d_ax.p, e->mdl.svt_h.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                      list_buf(e, p.pass0_out), e->list_cap, e->d_counters.p, d, q.evals_cap, nullptr, 0, 0, nullptr, 0, s, nullptr, nullptr, e->d_t1_flags.p);
     } else {
-        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
-                        e->range.upper, e->svm.neg_gamma2, q.evals_cap, XMODE_F32, e->screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
+        launch_features(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->d_X.p, e->d_ax.p, d, e->range.lower,
+                        e->range.upper, e->mdl.svm.neg_gamma2, q.evals_cap, XMODE_F32, e->mdl.screen, nullptr, 0, 0, q.large, q.evals_sel, e->d_attr.p, nullptr, s);
         mark(e, HAF_ST_SVM);
-        launch_svm(e->d_X.p, e->d_ax.p, e->d_svt.p, e->d_evalcell.p, e->d_counters.p, e->svm, e->d_dec.p, e->d_labels.p,
+        launch_svm(e->d_X.p, e->d_ax.p, e->mdl.svt.p, e->d_evalcell.p, e->d_counters.p, e->mdl.svm, e->d_dec.p, e->d_labels.p,
                    list_buf(e, p.pass0_out), e->list_cap, e->d_counters.p, d, q.evals_cap, s, e->d_t1_flags.p);
     }
     mark(e, HAF_ST_REFINE);
@@ -721,16 +721,16 @@ static void launch_first_pass(haf_engine *e, const Request &q, const TierPlan &p
 static void fp64_window(haf_engine *e, const Request &q, const TierPlan &p, int off)
 {
     if (p.fp64 == FP64_SMALL)
-        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->d_fd.p, e->d_sv64.p, e->exact, q.d, e->flag_cap, e->d_dec_exact.p,
+        launch_small_direct(e->d_ii.p, e->d_evalcell.p, e->d_counters.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.exact, q.d, e->flag_cap, e->d_dec_exact.p,
                             e->d_labels.p, list_buf(e, p.fp64_out), e->list_cap, nullptr, q.s, list_buf(e, p.fp64_in), list_counter(p.fp64_in), off);
     else
-        launch_recheck_mfma(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->exact, list_buf(e, p.fp64_in), e->flag_cap, off, e->d_counters.p,
+        launch_recheck_mfma(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.exact, list_buf(e, p.fp64_in), e->flag_cap, off, e->d_counters.p,
                             e->d_x64.p, e->d_part64.p, p.i8 ? e->d_dec_exacti.p : e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.fp64_out), e->list_cap,
                             q.d, q.s, nullptr, false, list_counter(p.fp64_in), e->d_tier_words.p);
 }
 static void i8_window(haf_engine *e, const Request &q, const TierPlan &p, int off)
 {
-    launch_recheck_i8(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv_i8.p, e->i8, e->range.lower, e->range.upper, list_buf(e, p.i8_in), e->flag_cap,
+    launch_recheck_i8(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv_i8.p, e->mdl.i8, e->range.lower, e->range.upper, list_buf(e, p.i8_in), e->flag_cap,
                       off, e->d_counters.p, e->d_x64.p, e->d_part64.p, e->d_dec_exact.p, e->d_labels.p, list_buf(e, p.i8_out), e->list_cap, q.d, q.s,
                       e->d_tier_words.p);
 }
@@ -789,7 +789,7 @@ static int finish_exact_tiers(haf_engine *e, Request &q, const TierPlan &p)
         }
         const int n_fp64 = e->h_counters[list_counter(p.fp64_in)];
         for (int off = done_fp64; off < n_fp64; off += e->flag_cap) { fp64_window(e, q, p, off); e->stat_extra_windows++; }
-        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in), e->list_cap,
+        launch_recheck(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.coef64.p, e->mdl.exact, list_buf(e, p.strict_in), e->list_cap,
                        e->d_counters.p, list_counter(p.strict_in), e->d_dec_exact2.p, e->d_labels.p, q.d, s);
         if ((rc = vote_and_wait(e, q)) != HAF_OK) return rc;
         strict_ran = e->h_counters[list_counter(p.strict_in)] > 0;
@@ -797,7 +797,7 @@ static int finish_exact_tiers(haf_engine *e, Request &q, const TierPlan &p)
         strict_ran = true;                            // (it has run, on everything; what is left is the C library's tanh near zero)
     } else if (e->h_counters[list_counter(p.strict_in)] > 0) {
         // (the host knows the list's length here: the spread form of the tier, recheck.hip)
-        launch_recheck_known(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, list_buf(e, p.strict_in),
+        launch_recheck_known(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.coef64.p, e->mdl.exact, list_buf(e, p.strict_in),
                              std::min(e->h_counters[list_counter(p.strict_in)], e->list_cap), e->d_strict_terms.p, kStrictSlots, e->d_dec_exact2.p,
                              e->d_labels.p, q.d, s);
         if ((rc = vote_and_wait(e, q)) != HAF_OK) return rc;
@@ -845,17 +845,17 @@ static int decide_probability(haf_engine *e, Request &q)
     const Dims &d = q.d;
     mark(e, HAF_ST_FEATURES); mark(e, HAF_ST_SVM); mark(e, HAF_ST_REFINE); mark(e, HAF_ST_RECHECK);
     launch_prob_list(e->d_counters.p, CNT_FLAGGED2, e->d_flag2_list.p, e->list_cap, s);
-    launch_recheck(e->d_ii.p, e->d_evalcell.p, e->d_fd.p, e->d_sv64.p, e->d_coef64.p, e->exact, e->d_flag2_list.p, e->list_cap,
+    launch_recheck(e->d_ii.p, e->d_evalcell.p, e->mdl.fd.p, e->mdl.sv64.p, e->mdl.coef64.p, e->mdl.exact, e->d_flag2_list.p, e->list_cap,
                    e->d_counters.p, CNT_FLAGGED2, e->d_dec_exact2.p, e->d_labels.p, d, s);
     // the estimates; those a last-bit exp difference could move come back as a list and are finished on the host (round 4)
-    launch_probability_eval(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_own.p, e->d_ptext.p,
+    launch_probability_eval(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->mdl.prob, e->d_labels.p, e->d_own.p, e->d_ptext.p,
                             e->d_flag_list.p, e->list_cap, e->d_counters.p, q.evals_cap, s);
     HIPCHK(e, hipMemcpyAsync(e->out_block.host, e->out_block.dev.p, kCntBytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     const int rc = host_resolve_probability(e, d, s, &q.host_resolved);
     if (rc != HAF_OK) return rc;
     mark(e, HAF_ST_VOTE);
-    launch_probability(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->prob, e->d_labels.p, e->d_mask.p, e->d_rowcount.p,
+    launch_probability(e->d_dec_exact2.p, e->d_evalcell.p, e->d_counters.p, e->mdl.prob, e->d_labels.p, e->d_mask.p, e->d_rowcount.p,
                        e->d_brcount.p, reinterpret_cast<const float *>(e->d_heights.p), e->d_own.p, e->d_ptext.p, e->d_gridf.p,
                        e->d_evf.p, e->d_rec.p, q.evals_cap, d, s);
     mark(e, HAF_ST_DOWNLOAD);
@@ -871,7 +871,7 @@ static int decide_probability(haf_engine *e, Request &q)
 static int next_variant(const haf_engine *e, int v)
 {
     if (v == SCREEN_PLAIN) return SCREEN_SUMSQ;
-    if (v == SCREEN_SUMSQ && e->cr_available) return SCREEN_CR_EXP;
+    if (v == SCREEN_SUMSQ && e->mdl.cr_available) return SCREEN_CR_EXP;
     if (v == SCREEN_CR_EXP) return SCREEN_CR_POLY;
     return -1;
 }
@@ -952,14 +952,14 @@ static int record_outcome(haf_engine *e, const Request &q, int mode, int inexact
     LastCall &l = e->last;
     l.B = q.B; l.R = q.R; l.roll_first = roll_first;
     l.evals = h[CNT_EVALS];
-    l.flagged = e->prob_mode ? 0 : h[CNT_FLAGGED];      // (probability mode: the counter holds the estimates the host finished)
+    l.flagged = e->mdl.prob_mode ? 0 : h[CNT_FLAGGED];      // (probability mode: the counter holds the estimates the host finished)
     l.flagged2 = h[CNT_FLAGGED2];
     l.lr = q.lr_used;
     l.flagged0 = q.t0b_used ? std::min(h[CNT_FLAGGED0B], h[CNT_FLAGGED0]) : h[CNT_FLAGGED0];   // what leaves the screening passes
     l.flaggedi = q.i8_used ? h[CNT_FLAGGEDI] : h[CNT_FLAGGED];
     l.bypass = h[CNT_BYPASS];                            // (the short-list gate: entries that went around tier 1 and the exact-integer tier)
     l.inexact = inexact_grids;
-    l.screened = (mode == MODE_SCREEN) && !e->prob_mode && !q.direct && h[CNT_FLAGGED0] <= e->flag0_cap;
+    l.screened = (mode == MODE_SCREEN) && !e->mdl.prob_mode && !q.direct && h[CNT_FLAGGED0] <= e->flag0_cap;
     l.host_resolved = q.host_resolved;
     l.i8 = q.i8_used;
     l.inputs.assign(in, in + q.B);
@@ -1002,14 +1002,14 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
     if (mode == MODE_SCREEN && !e->screen_active) {
         // (the switch-off used to be for the engine's lifetime) every reprobe_every-th request that is large enough to judge by
         // runs the screening pass again; it costs that request one wasted pass at worst
-        if (!roi && !e->variant_forced && !e->prob_mode && !q.direct && q.evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
+        if (!roi && !e->variant_forced && !e->mdl.prob_mode && !q.direct && q.evals_sel >= 4096 && ++e->inactive_calls >= e->reprobe_every) {
             e->inactive_calls = 0;
             reprobe = true;
         } else {
             mode = MODE_SPLIT;
         }
     }
-    rc = e->prob_mode ? decide_probability(e, q) : decide(e, q, mode, false);
+    rc = e->mdl.prob_mode ? decide_probability(e, q) : decide(e, q, mode, false);
     if (rc != HAF_OK) return rc;
     if (e->h_counters[CNT_ERROR] != 0 && !e->no_bucket_sort) {
         // a tile of k_bin_tiles had more candidate buckets than its list holds (never observed; the bound is geometric): the
@@ -1019,7 +1019,7 @@ int score_rolls_impl(haf_engine *e, int32_t n_clouds, const haf_cloud *clouds, c
         return score_rolls_impl(e, n_clouds, clouds, in, roll_first, roll_count, records, from);
     }
     const int inexact_grids = e->h_counters[CNT_INEXACT];     // (a redo of the decision stage below resets the counters)
-    if (mode == MODE_SCREEN && !e->prob_mode && !q.direct &&
+    if (mode == MODE_SCREEN && !e->mdl.prob_mode && !q.direct &&
         (rc = roi ? roi_screen_overflow(e, q, &mode) : adapt_screen_form(e, q, &mode, reprobe)) != HAF_OK) return rc;
     return record_outcome(e, q, mode, inexact_grids, roll_first, in, records);
 }

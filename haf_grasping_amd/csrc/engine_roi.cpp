@@ -102,7 +102,7 @@ int score_frames_roi_impl(haf_engine *e, int32_t n, const haf_frame *frames, con
     if (!e) return HAF_E_ARG;
     const std::string who = "haf_score_frames_roi: ";
     if (!frames || !rois || !in || !out || n < 1) return fail(e, HAF_E_ARG, who + "null or empty argument");
-    if (e->prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
+    if (e->mdl.prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
     if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, who + "more frames than max_clouds");
     if (e->cfg.n_rolls > e->max_rolls) return fail(e, HAF_E_CAPACITY, who + "more rolls in one call than max_rolls_per_call");
     // request after request, its frame's refusals before its mask's: the masks of the requests in front of a refused frame come first
@@ -132,7 +132,7 @@ int score_views_roi_impl(haf_engine *e, int32_t n, const int32_t *views_per_requ
     if (!e) return HAF_E_ARG;
     const std::string who = "haf_score_views_roi: ";
     if (!views_per_request || !frames || !rois || !in || !out || n < 1) return fail(e, HAF_E_ARG, who + "null or empty argument");
-    if (e->prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
+    if (e->mdl.prob_mode) return fail(e, HAF_E_ARG, who + "not available with HAF_FLAG_PROBABILITY");
     if (n > e->cfg.max_clouds) return fail(e, HAF_E_CAPACITY, who + "more requests than max_clouds");
     if (e->cfg.n_rolls > e->max_rolls) return fail(e, HAF_E_CAPACITY, who + "more rolls in one call than max_rolls_per_call");
     std::vector<int> first((size_t)n + 1, 0);

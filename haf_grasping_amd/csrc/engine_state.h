@@ -121,7 +121,7 @@ inline int check_guards(haf_engine *) { return HAF_OK; }
 
 // A device array that frees itself: the engine's are released by `delete e` (haf_destroy), in no list of names.  A failed alloc() leaves
 // it empty (p == nullptr, n == 0), so n tells whether it can be used.  Move-only.  (file, line: the allocating source line, which the
-// testing build's guard report names; ensure_dev passes its caller's on)
+// testing build's guard report names; ensure_dev passes its caller's on, upload_tables the table's name in the file's place)
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
@@ -164,6 +164,9 @@ template <typename T> struct DevBuf {
 #endif
 };
 static_assert(!std::is_copy_constructible_v<DevBuf<char>> && !std::is_copy_assignable_v<DevBuf<char>>, "a DevBuf has one owner");
+
+// The model on the device: the tables as device arrays and the constants that go with them (model_tables.h)
+struct DeviceModel : TableSet<DevBuf>, ModelConsts {};
 
 // A device block and its pinned host twin of the same size, freed with the object.  ensure() gets both halves or neither: when either
 // allocation fails the pair it had stays in place and usable (the engine left as it was); growing replaces the pair, not its
@@ -259,11 +262,9 @@ struct haf_engine {
     std::vector<FeatureRow> features;
     RangeTable range;
     SvmModel model;
-    int nf = 0, kx = 0, n_sv_tiles = 0, n_sv_pad = 0, sv_tile_neg = 0;
-    int gv0 = 0, gv1 = 0;
-    double sum_abs_coef = 0;
-    SvmParams svm{};
-    ExactParams exact{};
+    // the model as haf_create made it: every device table (model_tables.h: TableSet, for_each_table), every parameter struct, every scalar
+    // and flag of the table work.  upload_tables fills it; nothing writes to it afterwards
+    DeviceModel mdl;
     std::string error;
 
     // stream: the CURRENT stream, on which every operation of every call is enqueued (haf_set_stream; null is HIP's default stream).
@@ -282,7 +283,7 @@ struct haf_engine {
     int flag_cap = 0;
     int flag0_cap = 0;      // screening pass: evaluations that go on to the three-pass kernel
     bool generic_kernel = false; // the model's kernel is not RBF: every evaluation through the libsvm-order tier (engine.cpp, engine_request.cpp)
-    bool screen_active = true;   // default mode only: cleared once more than 60 % of a call's evaluations fell inside the band of every
+    bool screen_active = true;   // starts as mdl.screen_active.  Default mode only: cleared once more than 60 % of a call's evaluations fell inside the band of every
                                  // form of the screening pass -- for such a model the single pass is wasted work.  Not for good: every
                                  // reprobe_every-th full-size request afterwards tries the pass again (the judgement may have come from
                                  // the synthetic calibration scene or from one unusual cloud) and switches it back on when it pays
@@ -293,7 +294,6 @@ struct haf_engine {
     // (ill-conditioned models: large coefficients whose kernel values are small); CR_EXP / CR_POLY: the centred-remainder
     // form (round 4: trained models with a large C, whose decisions are 1e-5..1e-8 of sum|coef|K)
     int screen_variant = SCREEN_PLAIN;
-    bool cr_available = false;   // the centred-remainder tables exist (screen_cr, d_svt0_cr, ...)
     bool variant_forced = false; // testing build: HAF_SCREEN_VARIANT pins the variant (no adaptive rule)
     bool variant_settled = false;   // every form has been seen (at calibration or on requests) and the engine has chosen: no more switching
     // "tier 0b": behind the PLAIN / SUMSQ form, the centred-remainder form (SCREEN_CR_EXP) runs once more on the first pass's LIST --
@@ -306,15 +306,7 @@ struct haf_engine {
     DevBuf<char> d_screen_part;
     int screen_parts = 0;        // 0: by the live evaluation count; testing build (HAF_SCREEN_PARTS): 1 = never, n = forced
     double variant_share[SCREEN_VARIANTS] = {-1.0, -1.0, -1.0, -1.0};   // undecided share of each variant on the calibration scene (-1: not tried)
-    ScreenParams screen{};
-    ScreenParams screen_cr{};    // the centred-remainder form's constants and descriptor tables
-    CrParams crp{};
-    // tier 1 (three-pass list kernel) in the centred-remainder form, behind SCREEN_CR_POLY: its own SV images (s - m), the centre /
-    // linear-term table of the exact-form feature kernel, L per list slot
-    bool t1_cr_available = false;
-    CrT1Params crt1{};
-    DevBuf<char> d_svt_h_cr;
-    DevBuf<double> d_t1_tab, d_t1_L;
+    DevBuf<double> d_t1_L;       // tier 1 in the centred-remainder form (mdl.svt_h_cr, mdl.t1_tab): L per list slot
     size_t cells_cap = 0;   // B*R*H*W
 
     // ONE input block per request: [CloudDev x B][RollGeo x B*R][host clouds' points], packed at call time so that a single
@@ -352,42 +344,22 @@ struct haf_engine {
     int feature_sp_kind = -1;
     ScreenParams feature_sp{};
     struct View { int *p = nullptr; } d_counters;      // inside out_block
-    DevBuf<float> d_X, d_ax, d_dec, d_svt;
-    DevBuf<char> d_svt_h;            // split-fp16 SV tile images
-    DevBuf<char> d_svt0;             // screening-pass SV tile images
-    DevBuf<char> d_svt0_cr;          // the same for the centred-remainder form: fp16(w_n - mu), t_n = 0, coefficient b_n
-    // low-rank form of the centred-remainder pass (kernels.h: kLrK; large requests only): projection tiles (rows of B^'), 6-step SV
-    // tile images of q~_n, the band's constants, per (cloud, roll) "a height is negative" flags (prestages.hip)
-    bool lr_available = false;
+    DevBuf<float> d_X, d_ax, d_dec;
+    // low-rank form of the centred-remainder pass (mdl.lr_available; kernels.h: kLrK; large requests only)
     bool lr_enabled = true;          // testing build: HAF_NO_LR switches it off; HAF_LR_ALWAYS lifts the request-size rule
     bool lr_always = false;
-    int lr_rank = 0;                 // dimension of the HAF slots' linear span (158 for the reference's Features.txt)
-    DevBuf<char> d_lr_btiles, d_svt_lr;
-    ScreenParams screen_lrp{};       // the feature kernel's constants for the PLAIN epilogue in the low-rank form (centred descriptors, own correction vectors)
-    DevBuf<ScrCorr> d_corr_lrp;
-    bool lr_plain_available = false;
-    DevBuf<char> d_lr_btiles_in;     // the projection matrix by input k-step (fused form: the projection is the sweep's prologue)
-    bool lr_fused = true;            // testing build: HAF_LR_UNFUSED = k_project + sweep as two launches
     DevBuf<unsigned long long> d_iiabs;   // per (cloud, roll): sum of |height| in units of 2^-20 m (k_integral_totals)
-    LrBand lr_band{};
-    DevBuf<FeatDesc> d_fd_slot_cr;
-    DevBuf<ScrDesc> d_sd_cr;
-    DevBuf<ScrDesc3> d_sd3_cr;
-    DevBuf<ScrCorr> d_corr_cr;
     DevBuf<float> d_X1, d_ax1, d_gband;   // three-pass operand images / a_x of the screened-out rest; per-evaluation guard band
     DevBuf<int> d_flag0_list;
     DevBuf<unsigned long long> d_flag0_words;   // one bit per evaluation: undecided by the screening pass
     DevBuf<int> d_flag0_wgcount;                // popcounts per 256 words, for the ordered compaction
     DevBuf<int8_t> d_labels;
-    DevBuf<double> d_dec_exact, d_dec_exact2, d_sv64, d_coef64, d_x64, d_part64;
+    DevBuf<double> d_dec_exact, d_dec_exact2, d_x64, d_part64;
     DevBuf<double> d_strict_terms;   // strict tier, spread form: kStrictSlots x n_sv_pad products coef K (launch_recheck_known)
-    // tier 2a, the exact-integer tier (exact8.hip): int8 digit images of the support vectors, its hand-over list to the fp64 MFMA
-    // tier and that tier's decision values for it (d_dec_exact then holds tier 2a's values, in the order of d_flag_list)
-    DevBuf<char> d_sv_i8;
+    // tier 2a, the exact-integer tier (exact8.hip; mdl.i8_active): its hand-over list to the fp64 MFMA tier and that tier's decision
+    // values for it (d_dec_exact then holds tier 2a's values, in the order of d_flag_list)
     DevBuf<int> d_flagi_list;
     DevBuf<double> d_dec_exacti;
-    I8Params i8{};
-    bool i8_active = false;
     bool short_gate = true;         // testing build: HAF_NO_SHORT_GATE switches the gate off
     DevBuf<short> d_ev16;
     DevBuf<float> d_margin;         // HAF_FLAG_KEEP_DEBUG, default mode: |dec^| / band of every evaluation the screening tier decided
@@ -399,17 +371,11 @@ struct haf_engine {
     // show_predicted_gps builds from them, the fp32 votes, and the two "%g" probabilities per evaluation
     DevBuf<float> d_own, d_gridf, d_evf;
     DevBuf<double> d_ptext;
-    ProbParams prob{};
-    bool prob_mode = false;
-    DevBuf<FeatDesc> d_fd, d_fd_slot;
-    DevBuf<ScrDesc> d_sd;
-    DevBuf<ScrCorr> d_corr;         // per-slot constants of the centred screening band
     DevBuf<double> d_part1;
     long part1_stride = 0;
     // requests with at least this many evaluation slots take the thread-per-evaluation feature kernel: its floor is one thread's
     // chain of 324 attributes (~0.2 ms), the cooperative kernel costs ~1.3 us per 1000 evaluations (crossover measured at ~3e5)
     long large_evals = kLargeEvals;
-    DevBuf<ScrDesc3> d_sd3;
 
     // views into the pinned half of out_block
     RollRecordDev *h_rec = nullptr;
@@ -418,9 +384,6 @@ struct haf_engine {
     // launch (k_small_direct): cheaper than a feature kernel, a fast contraction and the rechecks behind it (C2: 3 760 x 172 in
     // 36 us against 21 + 30 + 30 us; measured the other way round at C3's 31 093 x 172: 203 us against 186)
     long direct_work = 1L << 21;
-    // strict tier: an evaluation whose libsvm-order decision value is within this of zero is decided on the HOST with glibc's exp
-    // (the device's exp may differ from it in the last bit: 2^-52 per kernel value, i.e. at most 2^-52 sum|coef| in the sum)
-    double host_exp_thr = 0.0;
     bool calibrated = false;        // the screening variant was chosen at creation (calibrate())
     double mfma_kappa = 12.0;       // error of one v_mfma_f32_16x16x32_f16 in units of 2^-24 (|c| + sum|a b|): max(12, 1.5 x probe_mfma_rounding())
     double mfma_kappa16 = 12.0;     // the same for v_mfma_f32_16x16x16f16 (the K tail of the three-pass kernel)
@@ -512,12 +475,12 @@ constexpr size_t kCntBytes = up16(CNT_COUNT * sizeof(int));                 // t
 inline bool lr_typical(const haf_engine *e)
 {
     const haf_config &c = e->cfg;
-    return e->lr_available && e->lr_enabled && (long)c.grid_h * c.grid_w > 8192 &&
+    return e->mdl.lr_available && e->lr_enabled && (long)c.grid_h * c.grid_w > 8192 &&
            (long)(c.grid_h - 14) * (c.grid_w - 14) * e->max_rolls >= e->large_evals;
 }
 inline double variant_cost(const haf_engine *e, int v)
 {
-    if (!lr_typical(e) || (v == SCREEN_PLAIN && !e->lr_plain_available)) return kVariantCost[v];
+    if (!lr_typical(e) || (v == SCREEN_PLAIN && !e->mdl.lr_plain_available)) return kVariantCost[v];
     return kVariantCostLr[v];
 }
 // (contraction_mode and its MODE_* values: model_tables.h)

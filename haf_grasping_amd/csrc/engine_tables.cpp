@@ -51,91 +51,38 @@ template <class T> static hipError_t copy_up(const DevBuf<T> &d, const std::vect
 // parameter struct or a flag of the model.  (A table the model does not get is empty and stays unallocated: DevBuf::alloc(0).)
 int upload_tables(haf_engine *e, const ModelTables &t)
 {
+    DeviceModel &m = e->mdl;
     bool ok = true;
-    ok = ok && hipSuccess == e->d_fd.alloc(t.fd.size());
-    ok = ok && hipSuccess == e->d_svt.alloc(t.svt.size());
-    ok = ok && hipSuccess == e->d_svt_h.alloc(t.svt_h.size());
-    ok = ok && hipSuccess == e->d_sd.alloc(t.sd.size());
-    ok = ok && hipSuccess == e->d_sd3.alloc(t.sd3.size());
-    ok = ok && hipSuccess == e->d_fd_slot.alloc(t.fd_slot.size());
-    ok = ok && hipSuccess == e->d_corr.alloc(t.corr.size());
-    ok = ok && hipSuccess == e->d_svt0.alloc(t.svt0.size());
-    ok = ok && hipSuccess == e->d_svt0_cr.alloc(t.svt0_cr.size());
-    ok = ok && hipSuccess == e->d_sd_cr.alloc(t.sd_cr.size());
-    ok = ok && hipSuccess == e->d_sd3_cr.alloc(t.sd3_cr.size());
-    ok = ok && hipSuccess == e->d_fd_slot_cr.alloc(t.fd_slot_cr.size());
-    ok = ok && hipSuccess == e->d_corr_cr.alloc(t.corr_cr.size());
-    ok = ok && hipSuccess == e->d_lr_btiles.alloc(t.lr_btiles.size());
-    ok = ok && hipSuccess == e->d_lr_btiles_in.alloc(t.lr_btiles_in.size());
-    ok = ok && hipSuccess == e->d_svt_lr.alloc(t.svt_lr.size());
-    ok = ok && hipSuccess == e->d_corr_lrp.alloc(t.corr_lrp.size());
-    ok = ok && hipSuccess == e->d_svt_h_cr.alloc(t.svt_h_cr.size());
-    ok = ok && hipSuccess == e->d_t1_tab.alloc(t.t1_tab.size());
-    ok = ok && hipSuccess == e->d_sv64.alloc(t.sv64.size());
-    ok = ok && hipSuccess == e->d_coef64.alloc(t.coef64.size());
-    ok = ok && hipSuccess == e->d_sv_i8.alloc(t.sv_i8.size());
+    // (the table's name where alloc takes the allocating file: the testing build's guard report says which table a damaged zone belongs to)
+    for_each_table([&](const char *name, auto &d, const auto &h) { ok = ok && hipSuccess == d.alloc(h.size(), name); }, m, t);
     if (!ok) return fail(e, HAF_E_DEVICE, std::string("hipMalloc of the model tables failed: ") + hipGetErrorString(hipGetLastError()));
 
-    HIPCHK(e, copy_up(e->d_fd, t.fd));
-    HIPCHK(e, copy_up(e->d_svt, t.svt));
-    HIPCHK(e, copy_up(e->d_svt_h, t.svt_h));
-    HIPCHK(e, copy_up(e->d_sd, t.sd));
-    HIPCHK(e, copy_up(e->d_sd3, t.sd3));
-    HIPCHK(e, copy_up(e->d_fd_slot, t.fd_slot));
-    HIPCHK(e, copy_up(e->d_corr, t.corr));
-    HIPCHK(e, copy_up(e->d_svt0, t.svt0));
-    HIPCHK(e, copy_up(e->d_svt0_cr, t.svt0_cr));
-    HIPCHK(e, copy_up(e->d_sd_cr, t.sd_cr));
-    HIPCHK(e, copy_up(e->d_sd3_cr, t.sd3_cr));
-    HIPCHK(e, copy_up(e->d_fd_slot_cr, t.fd_slot_cr));
-    HIPCHK(e, copy_up(e->d_corr_cr, t.corr_cr));
-    HIPCHK(e, copy_up(e->d_lr_btiles, t.lr_btiles));
-    HIPCHK(e, copy_up(e->d_lr_btiles_in, t.lr_btiles_in));
-    HIPCHK(e, copy_up(e->d_svt_lr, t.svt_lr));
-    HIPCHK(e, copy_up(e->d_corr_lrp, t.corr_lrp));
-    HIPCHK(e, copy_up(e->d_svt_h_cr, t.svt_h_cr));
-    HIPCHK(e, copy_up(e->d_t1_tab, t.t1_tab));
-    HIPCHK(e, copy_up(e->d_sv64, t.sv64));
-    HIPCHK(e, copy_up(e->d_coef64, t.coef64));
-    HIPCHK(e, copy_up(e->d_sv_i8, t.sv_i8));
+    hipError_t rc = hipSuccess;
+    const char *failed = "";
+    for_each_table([&](const char *name, auto &d, const auto &h) { if (rc == hipSuccess && (rc = copy_up(d, h)) != hipSuccess) failed = name; }, m, t);
+    if (rc != hipSuccess) return fail(e, HAF_E_DEVICE, std::string("upload of the model table ") + failed + ": " + hipGetErrorString(rc));
 
-    // the parameter structs, with the device pointers the builder left null
+    static_cast<ModelConsts &>(m) = t;
+    e->screen_active = m.screen_active;
+
+    // the parameter structs' device pointers, which the builder left null
     auto pairs = [](const ScrCorr *p) { return p ? reinterpret_cast<const ScrCorr2 *>(p + kS0K) : nullptr; };
-    e->screen = t.screen;
-    e->screen.sd = e->d_sd.p; e->screen.sd3 = e->d_sd3.p; e->screen.fd_slot = e->d_fd_slot.p;
-    e->screen.corr = e->d_corr.p; e->screen.corr2 = pairs(e->d_corr.p);
+    m.screen.sd = m.sd.p; m.screen.sd3 = m.sd3.p; m.screen.fd_slot = m.fd_slot.p;
+    m.screen.corr = m.corr.p; m.screen.corr2 = pairs(m.corr.p);
     // screen_cr began as a copy of screen (model_tables.cpp: cr_centre) and keeps the plain form's tables where the model did not
     // get the centred ones; screen_lrp is a copy of screen_cr with correction vectors of its own (lr_commit)
-    e->screen_cr = t.screen_cr;
     if (t.screen_cr.cr) {
-        e->screen_cr.sd = e->screen.sd; e->screen_cr.sd3 = e->screen.sd3; e->screen_cr.fd_slot = e->screen.fd_slot;
-        e->screen_cr.corr = e->screen.corr; e->screen_cr.corr2 = e->screen.corr2;
+        m.screen_cr.sd = m.screen.sd; m.screen_cr.sd3 = m.screen.sd3; m.screen_cr.fd_slot = m.screen.fd_slot;
+        m.screen_cr.corr = m.screen.corr; m.screen_cr.corr2 = m.screen.corr2;
     }
     if (t.cr_available) {
-        e->screen_cr.sd = e->d_sd_cr.p; e->screen_cr.sd3 = e->d_sd3_cr.p; e->screen_cr.fd_slot = e->d_fd_slot_cr.p;
-        e->screen_cr.corr = e->d_corr_cr.p; e->screen_cr.corr2 = pairs(e->d_corr_cr.p);
+        m.screen_cr.sd = m.sd_cr.p; m.screen_cr.sd3 = m.sd3_cr.p; m.screen_cr.fd_slot = m.fd_slot_cr.p;
+        m.screen_cr.corr = m.corr_cr.p; m.screen_cr.corr2 = pairs(m.corr_cr.p);
     }
-    e->screen_lrp = t.screen_lrp;
     if (t.lr_available) {
-        e->screen_lrp.sd = e->screen_cr.sd; e->screen_lrp.sd3 = e->screen_cr.sd3; e->screen_lrp.fd_slot = e->screen_cr.fd_slot;
-        e->screen_lrp.corr = e->d_corr_lrp.p; e->screen_lrp.corr2 = pairs(e->d_corr_lrp.p);
+        m.screen_lrp.sd = m.screen_cr.sd; m.screen_lrp.sd3 = m.screen_cr.sd3; m.screen_lrp.fd_slot = m.screen_cr.fd_slot;
+        m.screen_lrp.corr = m.corr_lrp.p; m.screen_lrp.corr2 = pairs(m.corr_lrp.p);
     }
-    e->lr_band = t.lr_band;
-    e->crp = t.crp;
-    e->crt1 = t.crt1;
-    e->svm = t.svm;
-    e->exact = t.exact;
-    e->i8 = t.i8;
-    e->prob = t.prob;
-
-    e->nf = t.nf; e->kx = t.kx; e->n_sv_tiles = t.n_sv_tiles; e->sv_tile_neg = t.sv_tile_neg; e->n_sv_pad = t.n_sv_pad;
-    e->sum_abs_coef = t.sum_abs_coef;
-    e->screen_active = t.screen_active; e->cr_available = t.cr_available; e->lr_available = t.lr_available; e->lr_fused = t.lr_fused;
-    e->lr_plain_available = t.lr_plain_available; e->t1_cr_available = t.t1_cr_available; e->i8_active = t.i8_active;
-    e->lr_rank = t.lr_rank;
-    e->gv0 = t.gv0; e->gv1 = t.gv1;
-    e->prob_mode = t.prob_mode;
-    e->host_exp_thr = t.host_exp_thr;
     return HAF_OK;
 }
 
@@ -213,10 +160,10 @@ int alloc_buffers(haf_engine *e)
         ok &= hipSuccess == e->d_ax1.alloc(slots);
         e->part1_stride = (long)slots;
         ok &= hipSuccess == e->d_part1.alloc(slots * 2 * kHListParts);      // class sums per SV tile range (k_svm_h_combine)
-        if (e->t1_cr_available) ok &= hipSuccess == e->d_t1_L.alloc(slots);
+        if (e->mdl.t1_cr_available) ok &= hipSuccess == e->d_t1_L.alloc(slots);
         ok &= hipSuccess == e->d_gband.alloc((size_t)e->max_evals_pad * kBandFloats);
         ok &= hipSuccess == e->d_flag0_list.alloc((size_t)e->flag0_cap);
-        if (e->cr_available) ok &= hipSuccess == e->d_flag0b_list.alloc((size_t)e->flag0_cap);
+        if (e->mdl.cr_available) ok &= hipSuccess == e->d_flag0b_list.alloc((size_t)e->flag0_cap);
         ok &= hipSuccess == e->d_screen_part.alloc(screen_part_bytes());
         ok &= hipSuccess == e->d_flag0_words.alloc((size_t)e->max_evals_pad / 64);
         ok &= hipSuccess == e->d_flag0_wgcount.alloc((size_t)e->max_evals_pad / 64 / 256 + 1);
@@ -233,12 +180,12 @@ int alloc_buffers(haf_engine *e)
     // k_recheck_mfma reads whole workgroups of 64 evaluations (4 groups of 16): round the image up accordingly
     ok &= hipSuccess == e->d_x64.alloc(((size_t)e->flag_cap + 63) / 64 * 64 * kKP);
     ok &= hipSuccess == e->d_flag2_list.alloc((size_t)e->list_cap);
-    if (e->i8_active) {
+    if (e->mdl.i8_active) {
         ok &= hipSuccess == e->d_flagi_list.alloc((size_t)e->list_cap);
         ok &= hipSuccess == e->d_dec_exacti.alloc((size_t)e->list_cap);
     }
     ok &= hipSuccess == e->d_dec_exact2.alloc((size_t)e->list_cap);
-    if (!e->prob_mode) ok &= hipSuccess == e->d_strict_terms.alloc((size_t)kStrictSlots * e->n_sv_pad);
+    if (!e->mdl.prob_mode) ok &= hipSuccess == e->d_strict_terms.alloc((size_t)kStrictSlots * e->mdl.n_sv_pad);
     if ((c.flags & HAF_FLAG_KEEP_DEBUG) && mode == MODE_SCREEN) ok &= hipSuccess == e->d_margin.alloc((size_t)e->max_evals_pad);
     if (c.flags & HAF_FLAG_KEEP_DEBUG) {
         // attribute records of the exact-form feature kernels (haf_debug_fetch_attr): 7.6 KB per evaluation, so only for
@@ -247,7 +194,7 @@ int alloc_buffers(haf_engine *e)
         if (bytes <= (2ull << 30)) ok &= hipSuccess == e->d_attr.alloc((size_t)e->max_evals * kKP);
     }
     ok &= hipSuccess == e->d_ev16.alloc(e->cells_cap);
-    if (e->prob_mode) {
+    if (e->mdl.prob_mode) {
         ok &= hipSuccess == e->d_own.alloc(e->cells_cap);
         ok &= hipSuccess == e->d_gridf.alloc(e->cells_cap);
         ok &= hipSuccess == e->d_evf.alloc(e->cells_cap);

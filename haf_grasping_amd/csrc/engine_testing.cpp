@@ -146,7 +146,7 @@ int haf_test_snapshot_screen(haf_engine *e, int on)
             sn.list.alloc((size_t)std::max(e->flag0_cap, 1)) != hipSuccess || sn.counters.alloc(CNT_COUNT) != hipSuccess || sn.part.alloc(part) != hipSuccess)
             return HAF_E_DEVICE;
         if (sn.labels.alloc(e->d_labels.n) != hipSuccess || sn.raw.alloc(pad * kBandFloats) != hipSuccess ||
-            (k == 0 && e->lr_available && sn.Y.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kLrMatBytes) != hipSuccess))
+            (k == 0 && e->mdl.lr_available && sn.Y.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kLrMatBytes) != hipSuccess))
             return HAF_E_DEVICE;
         if (k == 1 && (sn.in_X.alloc((size_t)(e->max_evals_pad / kTile) * (size_t)kS0MatBytes) != hipSuccess ||
                        sn.in_gband.alloc(pad * kBandFloats) != hipSuccess || sn.in_ax.alloc(pad) != hipSuccess))
@@ -241,7 +241,7 @@ static int revote_impl(haf_engine *e, const int8_t *labels, const float *gridf, 
                        haf_roll_record *records_out)
 {
     if (!records_out || (labels != nullptr) == (gridf != nullptr)) return fail(e, HAF_E_ARG, "haf_test_revote: exactly one of labels and gridf, and records_out");
-    if ((gridf != nullptr) != e->prob_mode) return fail(e, HAF_E_ARG, "haf_test_revote: labels go with a plain engine, gridf with HAF_FLAG_PROBABILITY");
+    if ((gridf != nullptr) != e->mdl.prob_mode) return fail(e, HAF_E_ARG, "haf_test_revote: labels go with a plain engine, gridf with HAF_FLAG_PROBABILITY");
     if (roi_words && !labels) return fail(e, HAF_E_ARG, "haf_test_revote: roi_words go with labels");
     const LastCall &last = e->last;
     if (last.B < 1 || last.R < 1 || last.B > e->cfg.max_clouds || last.R > e->max_rolls) return fail(e, HAF_E_ARG, "haf_test_revote: no scored batch");
@@ -259,7 +259,7 @@ static int revote_impl(haf_engine *e, const int8_t *labels, const float *gridf, 
     if (heights) HIPCHK(e, hipMemcpyAsync(e->d_heights.p, heights, cells * sizeof(float), hipMemcpyHostToDevice, s));
     if (roi_words) HIPCHK(e, hipMemcpyAsync(e->d_roi_cells.p, roi_words, words * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     Dims d{};
-    d.H = H; d.W = W; d.R = last.R; d.B = last.B; d.nf = e->nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->n_sv_tiles; d.sv_tile_neg = e->sv_tile_neg;
+    d.H = H; d.W = W; d.R = last.R; d.B = last.B; d.nf = e->mdl.nf; d.n_sv = e->model.n_sv; d.n_sv_tiles = e->mdl.n_sv_tiles; d.sv_tile_neg = e->mdl.sv_tile_neg;
     const float *hts = reinterpret_cast<const float *>(e->d_heights.p);
     if (gridf)
         launch_probability_vote(e->d_gridf.p, hts, e->d_brcount.p, e->d_evf.p, e->d_rec.p, d, s);
@@ -469,28 +469,15 @@ Fnv digest_of(const I8Params &p)
     return f;
 }
 Fnv digest_of(const ProbParams &p) { Fnv f; f << p.A << p.B << p.gv0 << p.gv1 << p.hdr << p.host_all << p.dec_slack; return f; }
-void digest_structs(DigestText &t, const ScreenParams &screen, const ScreenParams &screen_cr, const ScreenParams &screen_lrp, const LrBand &lr_band,
-                    const CrParams &crp, const CrT1Params &crt1, const SvmParams &svm, const ExactParams &exact, const I8Params &i8,
-                    const ProbParams &prob)
+// the parameter structs, then the scalars and flags in ModelConsts' order, flags as one byte each
+void digest_consts(DigestText &t, const ModelConsts &c)
 {
-    t.line("screen", digest_of(screen)); t.line("screen_cr", digest_of(screen_cr)); t.line("screen_lrp", digest_of(screen_lrp));
-    t.line("lr_band", digest_of(lr_band)); t.line("crp", digest_of(crp)); t.line("crt1", digest_of(crt1)); t.line("svm", digest_of(svm));
-    t.line("exact", digest_of(exact)); t.line("i8", digest_of(i8)); t.line("prob", digest_of(prob));
-}
-// the scalars and flags, in this order; flags as one byte each
-struct TableScalars {
-    int nf, kx, n_sv_tiles, sv_tile_neg, n_sv_pad;
-    double sum_abs_coef;
-    bool screen_active, cr_available, lr_available, lr_fused, lr_plain_available, t1_cr_available, i8_active;
-    int lr_rank, gv0, gv1;
-    bool prob_mode;
-    double host_exp_thr;
-};
-void digest_scalars(DigestText &t, const TableScalars &s)
-{
+    t.line("screen", digest_of(c.screen)); t.line("screen_cr", digest_of(c.screen_cr)); t.line("screen_lrp", digest_of(c.screen_lrp));
+    t.line("lr_band", digest_of(c.lr_band)); t.line("crp", digest_of(c.crp)); t.line("crt1", digest_of(c.crt1)); t.line("svm", digest_of(c.svm));
+    t.line("exact", digest_of(c.exact)); t.line("i8", digest_of(c.i8)); t.line("prob", digest_of(c.prob));
     Fnv f;
-    f << s.nf << s.kx << s.n_sv_tiles << s.sv_tile_neg << s.n_sv_pad << s.sum_abs_coef << s.screen_active << s.cr_available << s.lr_available
-      << s.lr_fused << s.lr_plain_available << s.t1_cr_available << s.i8_active << s.lr_rank << s.gv0 << s.gv1 << s.prob_mode << s.host_exp_thr;
+    f << c.nf << c.kx << c.n_sv_tiles << c.sv_tile_neg << c.n_sv_pad << c.sum_abs_coef << c.screen_active << c.cr_available << c.lr_available
+      << c.lr_fused << c.lr_plain_available << c.t1_cr_available << c.i8_active << c.lr_rank << c.gv0 << c.gv1 << c.prob_mode << c.host_exp_thr;
     t.line("scalars", f);
 }
 int digest_hand_over(const DigestText &t, char *out, int cap)
@@ -499,16 +486,26 @@ int digest_hand_over(const DigestText &t, char *out, int cap)
     memcpy(out, t.text.c_str(), t.text.size() + 1);
     return HAF_OK;
 }
-template <class T> bool digest_device(DigestText &t, const char *name, const DevBuf<T> &b)
+// a table's bytes as they lie in memory, on the device or on the host, into f; false: they could not be read
+template <class T> bool add_table(Fnv &f, const DevBuf<T> &b)
 {
-    Fnv f;
-    if (b.p && b.n) {
-        std::vector<char> h(b.n * sizeof(T));
-        if (hipMemcpy(h.data(), b.p, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
-        f.add(h.data(), h.size());
-    }
-    t.line(name, f);
+    std::vector<char> h(b.p ? b.n * sizeof(T) : 0);
+    if (!h.empty() && hipMemcpy(h.data(), b.p, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    f.add(h.data(), h.size());
     return true;
+}
+template <class T> bool add_table(Fnv &f, const std::vector<T> &v) { f.add(v.data(), v.size() * sizeof(T)); return true; }
+// the digest text of a model, DeviceModel or ModelTables: one line "d_<name>" per table, then the constants'
+template <class Model> bool digest_model(DigestText &t, const Model &m)
+{
+    bool ok = true;
+    for_each_table([&](const char *name, const auto &b) {
+        Fnv f;
+        ok = ok && add_table(f, b);
+        t.line((std::string("d_") + name).c_str(), f);
+    }, m);
+    digest_consts(t, m);
+    return ok;
 }
 }  // namespace
 
@@ -541,18 +538,7 @@ int haf_test_table_digest(haf_engine *e, char *out, int cap)
     if (!e) return HAF_E_ARG;
     if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return HAF_E_DEVICE;
     DigestText t;
-    bool ok = true;
-#define HAF_DIGEST(name) ok = ok && digest_device(t, #name, e->name)
-    HAF_DIGEST(d_fd); HAF_DIGEST(d_svt); HAF_DIGEST(d_svt_h); HAF_DIGEST(d_sd); HAF_DIGEST(d_sd3); HAF_DIGEST(d_fd_slot); HAF_DIGEST(d_corr);
-    HAF_DIGEST(d_svt0); HAF_DIGEST(d_svt0_cr); HAF_DIGEST(d_sd_cr); HAF_DIGEST(d_sd3_cr); HAF_DIGEST(d_fd_slot_cr); HAF_DIGEST(d_corr_cr);
-    HAF_DIGEST(d_lr_btiles); HAF_DIGEST(d_lr_btiles_in); HAF_DIGEST(d_svt_lr); HAF_DIGEST(d_corr_lrp); HAF_DIGEST(d_svt_h_cr);
-    HAF_DIGEST(d_t1_tab); HAF_DIGEST(d_sv64); HAF_DIGEST(d_coef64); HAF_DIGEST(d_sv_i8);
-#undef HAF_DIGEST
-    if (!ok) return HAF_E_DEVICE;
-    digest_structs(t, e->screen, e->screen_cr, e->screen_lrp, e->lr_band, e->crp, e->crt1, e->svm, e->exact, e->i8, e->prob);
-    digest_scalars(t, TableScalars{e->nf, e->kx, e->n_sv_tiles, e->sv_tile_neg, e->n_sv_pad, e->sum_abs_coef, e->screen_active, e->cr_available,
-                                   e->lr_available, e->lr_fused, e->lr_plain_available, e->t1_cr_available, e->i8_active, e->lr_rank, e->gv0,
-                                   e->gv1, e->prob_mode, e->host_exp_thr});
+    if (!digest_model(t, e->mdl)) return HAF_E_DEVICE;
     return digest_hand_over(t, out, cap);
 }
 
@@ -572,17 +558,7 @@ int haf_test_host_table_digest(const haf_config *cfg, double kappa, double kappa
         const int built = host_tables(cfg, kappa, kappa16, m, err);
         if (built != HAF_OK) return say(built);
         DigestText t;
-        auto bytes = [&](const char *name, const void *p, size_t n) { Fnv f; f.add(p, n); t.line(name, f); };
-#define HAF_DIGEST(name) bytes("d_" #name, m.name.data(), m.name.size() * sizeof m.name[0])
-        HAF_DIGEST(fd); HAF_DIGEST(svt); HAF_DIGEST(svt_h); HAF_DIGEST(sd); HAF_DIGEST(sd3); HAF_DIGEST(fd_slot); HAF_DIGEST(corr);
-        HAF_DIGEST(svt0); HAF_DIGEST(svt0_cr); HAF_DIGEST(sd_cr); HAF_DIGEST(sd3_cr); HAF_DIGEST(fd_slot_cr); HAF_DIGEST(corr_cr);
-        HAF_DIGEST(lr_btiles); HAF_DIGEST(lr_btiles_in); HAF_DIGEST(svt_lr); HAF_DIGEST(corr_lrp); HAF_DIGEST(svt_h_cr);
-        HAF_DIGEST(t1_tab); HAF_DIGEST(sv64); HAF_DIGEST(coef64); HAF_DIGEST(sv_i8);
-#undef HAF_DIGEST
-        digest_structs(t, m.screen, m.screen_cr, m.screen_lrp, m.lr_band, m.crp, m.crt1, m.svm, m.exact, m.i8, m.prob);
-        digest_scalars(t, TableScalars{m.nf, m.kx, m.n_sv_tiles, m.sv_tile_neg, m.n_sv_pad, m.sum_abs_coef, m.screen_active, m.cr_available,
-                                       m.lr_available, m.lr_fused, m.lr_plain_available, m.t1_cr_available, m.i8_active, m.lr_rank, m.gv0,
-                                       m.gv1, m.prob_mode, m.host_exp_thr});
+        digest_model(t, m);
         return digest_hand_over(t, out, cap);
     });
     return rc == HAF_E_INTERNAL ? say(rc) : rc;       // (an exception's text)

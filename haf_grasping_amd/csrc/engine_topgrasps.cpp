@@ -64,7 +64,7 @@ int top_merge(const haf_config &c, const haf_grasp_input *in, const std::vector<
 static int top_grasps_impl(haf_engine *e, const haf_top_params *p, haf_grasp_candidate *out, int32_t *n_found)
 {
     if (!p || !out || !n_found) return fail(e, HAF_E_ARG, "haf_top_grasps: null argument");
-    if (e->prob_mode) return fail(e, HAF_E_ARG, "haf_top_grasps: not available with HAF_FLAG_PROBABILITY (fp32 votes)");
+    if (e->mdl.prob_mode) return fail(e, HAF_E_ARG, "haf_top_grasps: not available with HAF_FLAG_PROBABILITY (fp32 votes)");
     const LastCall &last = e->last;
     if (last.B < 1 || last.R < 1 || (int)last.inputs.size() < last.B) return fail(e, HAF_E_ARG, "haf_top_grasps: no scored batch");
     if (p->k < 1 || p->k > 1024) return fail(e, HAF_E_ARG, "haf_top_grasps: k must be in [1, 1024]");

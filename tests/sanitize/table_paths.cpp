@@ -80,11 +80,7 @@ static int run_line(const std::string &line, bool sweep)
     ModelTables t;
     const TableError e = build_model_tables(in, t);
     unsigned long long s = 0;
-    if (e.code == HAF_OK)
-        s = sum_bytes(t.fd) + sum_bytes(t.svt) + sum_bytes(t.svt_h) + sum_bytes(t.sd) + sum_bytes(t.sd_cr) + sum_bytes(t.sd3) + sum_bytes(t.sd3_cr) +
-            sum_bytes(t.fd_slot) + sum_bytes(t.fd_slot_cr) + sum_bytes(t.corr) + sum_bytes(t.corr_cr) + sum_bytes(t.corr_lrp) + sum_bytes(t.svt0) +
-            sum_bytes(t.svt0_cr) + sum_bytes(t.lr_btiles) + sum_bytes(t.lr_btiles_in) + sum_bytes(t.svt_lr) + sum_bytes(t.svt_h_cr) +
-            sum_bytes(t.t1_tab) + sum_bytes(t.sv64) + sum_bytes(t.coef64) + sum_bytes(t.sv_i8);
+    if (e.code == HAF_OK) for_each_table([&s](const char *, const auto &v) { s += sum_bytes(v); }, t);
     printf("%s flags %u grid %d: code %d (%s) cr %d lr %d t1 %d i8 %d bytes %llu\n", mf.c_str(), flags, grid, e.code, e.msg.c_str(),
            (int)t.cr_available, (int)t.lr_available, (int)t.t1_cr_available, (int)t.i8_active, s);
     if (e.code != want) { fprintf(stderr, "expected code %d, got %d: %s\n", want, e.code, e.msg.c_str()); return 1; }
